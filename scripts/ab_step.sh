@@ -5,5 +5,5 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 for v in "$@"; do
   echo "== $v"
-  env $v python bench.py --no-cpu-baseline --steps 20 --min-seconds 3 2>/dev/null | python -c "import sys,json; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('bench', round(r['value'],2), 'scans/s', r['blocks_ms_per_step'])"
+  env $v python bench.py --no-cpu-baseline --steps 60 2>/dev/null | python -c "import sys,json; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('bench', round(r['value'],2), 'scans/s', round(r['ms_per_step'],3), 'ms/step')"
 done

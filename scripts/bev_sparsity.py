@@ -1,5 +1,5 @@
-import sys, numpy as np
-sys.path.insert(0, '/root/repo')
+import os, sys, numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lidog_amd import synth
 from lidog_amd.bev import pixel_luts
 b = synth.make_batch([0], "kitti120k", device="cpu")

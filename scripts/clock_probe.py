@@ -46,8 +46,8 @@ def main():
 
     th = threading.Thread(target=sampler, daemon=True)
     th.start()
-    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--no-cpu-baseline", "--no-kernel-timing", "--steps", "300",
-                        "--max-blocks", "1"] + sys.argv[1:], capture_output=True, text=True)
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--no-cpu-baseline", "--no-kernel-timing", "--steps", "300"]
+                       + sys.argv[1:], capture_output=True, text=True)
     t_end = time.time()
     stop.set()
     th.join()

@@ -314,7 +314,7 @@ def test_two_rank_bench_keeps_replicas_identical():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--min-seconds", "0.1", "--batch", "2"]
+           "--batch", "2"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=REPO)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -347,7 +347,7 @@ def test_ranks_started_by_a_foreign_launcher_run_the_probe_themselves():
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-           "--min-seconds", "0.1", "--batch", "1", "--config", "source8k"]
+           "--batch", "1", "--config", "source8k"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=REPO)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -375,7 +375,7 @@ def test_a_hung_two_rank_run_still_produces_a_fallback_line():
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-           "--min-seconds", "0.1", "--batch", "1", "--config", "source8k"]
+           "--batch", "1", "--config", "source8k"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=REPO)
     assert out.returncode != 0
     assert "injected fault" in out.stderr and "was killed" in out.stderr, out.stderr[-3000:]

@@ -588,6 +588,63 @@ int lidog_trunk_gemm_timing_read(double *out /*[4]*/);
  * convolution); reading resets the counters */
 int lidog_trunk_work_read(double *out /*[6]*/);
 
+/* ------------------------------------------------------------------ instance norm (IBN-Net blocks)
+ * Replaces ME.MinkowskiInstanceNorm (ME 0.5.4) and the IBN block's normalisation + ME.cat + ReLU,
+ * utils/models/minkunet_ibn.py:26 (in_norm1) and :38-40 (bn_norm1 | in_norm1 -> ME.cat -> ReLU).
+ * Every channel is normalised per scan: mean / invstd [B, C] over the rows of batch index b (biased variance,
+ * invstd = 1 / sqrt(var + eps)); y = (x - mean[b]) * invstd[b] * w + bias with w, bias [C].  All sums in double,
+ * finished in a fixed order (no float atomics: the same bits on every run).  [rows, C] with C % 4 == 0, C <= 1024 and
+ * 2 B C <= 4096 take float4 kernels; any other shape plain scalar ones. */
+
+/* bytes of workspace lidog_in_segments needs for a map of n rows */
+int64_t lidog_in_segments_ws(int64_t n);
+/* The segments of a coordinate map (minkunet_ibn.py:26): perm [n] = the rows in stable batch order (radix sort of the
+ * batch column), seg_off [B + 1] = where each batch index starts in perm (empty scans: empty ranges), bid [n] = the batch
+ * index of every row.  B = largest batch index + 1 (<= 4096).  Rows may be in any order; build once per map. */
+int lidog_in_segments(const int32_t *coords, int64_t n, int32_t B, int32_t *perm, int32_t *seg_off, int32_t *bid,
+                      void *ws, int64_t ws_bytes, void *stream);
+/* doubles of workspace the per-(b, c) reductions below need (minkunet_ibn.py:26,38-40) */
+int64_t lidog_in_reduce_ws(int32_t B, int32_t C);
+/* forward statistics (minkunet_ibn.py:26,38-40): mean / invstd [B, C] of x [n, C]; a scan without rows gets mean 0,
+ * invstd 1 / sqrt(eps).  perm / seg_off from lidog_in_segments; ws: lidog_in_reduce_ws(B, C) doubles. */
+int lidog_in_stats(const float *x, int64_t n, int32_t C, int32_t B, const int32_t *perm, const int32_t *seg_off,
+                   float eps, float *mean, float *invstd, double *ws, void *stream);
+/* y = (x - mean[bid[row]]) * invstd[bid[row]] * w + b (minkunet_ibn.py:26,38-40) */
+int lidog_in_apply(const float *x, int64_t n, int32_t C, int32_t B, const int32_t *bid, const float *mean,
+                   const float *invstd, const float *w, const float *b, float *y, void *stream);
+/* backward reduction (minkunet_ibn.py:26,38-40): per (b, c) sum dy and sum dy * xhat, xhat = (x - mean) * invstd;
+ * coef [2, B, C] = (sum dy / n_b, sum dy xhat / n_b); dw [C] = sum dy * xhat, db [C] = sum dy (sums over b ascending) */
+int lidog_in_bwd_reduce(const float *dy, const float *x, int64_t n, int32_t C, int32_t B, const int32_t *perm,
+                        const int32_t *seg_off, const float *mean, const float *invstd, double *ws, float *coef,
+                        float *dw, float *db, void *stream);
+/* dx = (dy - m0 - xhat * m1) * invstd * w with (m0, m1) = coef of the row's scan (minkunet_ibn.py:26,38-40) */
+int lidog_in_bwd_apply(const float *dy, const float *x, int64_t n, int32_t C, int32_t B, const int32_t *bid,
+                       const float *mean, const float *invstd, const float *w, const float *coef, float *dx,
+                       void *stream);
+/* The IBN block's forward pass after conv1 (minkunet_ibn.py:38-40): y [n, 2C] = ReLU(BN(x)) | ReLU(IN(x)) in one pass
+ * over x [n, C], BatchNorm with mean / invstd [C] (lidog_bn_stats), instance norm with mean / invstd [B, C]
+ * (lidog_in_stats), and the ReLU bit mask of y in relu_bits [lidog_relu_bits_words(n, 2 C)] (lidog_bn_apply_bits'
+ * layout).  Equals lidog_bn_apply + lidog_in_apply + lidog_cat2 + lidog_relu_fwd bit for bit.  C % 4 == 0, n > 0. */
+int lidog_ibn_apply(const float *x, int64_t n, int32_t C, int32_t B, const float *bn_mean, const float *bn_invstd,
+                    const float *bn_w, const float *bn_b, const int32_t *bid, const float *in_mean,
+                    const float *in_invstd, const float *in_w, const float *in_b, float *y, uint32_t *relu_bits,
+                    void *stream);
+/* Its backward reductions (minkunet_ibn.py:38-40) from dy [n, 2C] and the bit mask: the BatchNorm half's
+ * (bn_sums [2C + 1], bn_dw / bn_db [C]; workspace lidog_bn_reduce_ws(C, 1) doubles) equal lidog_bn_bwd_reduce on the
+ * ReLU-masked first half bit for bit; the instance-norm half's (in_coef, in_dw, in_db; in_ws lidog_in_reduce_ws(B, C))
+ * equal lidog_in_bwd_reduce on the masked second half. */
+int lidog_ibn_bwd_reduce(const float *dy, const uint32_t *relu_bits, const float *x, int64_t n, int32_t C, int32_t B,
+                         const float *bn_mean, const float *bn_invstd, double *bn_sums, double *bn_ws, float *bn_dw,
+                         float *bn_db, const int32_t *perm, const int32_t *seg_off, const float *in_mean,
+                         const float *in_invstd, double *in_ws, float *in_coef, float *in_dw, float *in_db,
+                         void *stream);
+/* dx [n, C] = dx_BN + dx_IN in one pass (minkunet_ibn.py:38-40): lidog_bn_bwd_apply's and lidog_in_bwd_apply's
+ * expressions on the masked halves of dy, added; bn_count = rows of the BatchNorm statistics */
+int lidog_ibn_bwd_apply(const float *dy, const uint32_t *relu_bits, const float *x, int64_t n, int32_t C, int32_t B,
+                        const float *bn_mean, const float *bn_invstd, const float *bn_w, const double *bn_sums,
+                        double bn_count, const int32_t *bid, const float *in_mean, const float *in_invstd,
+                        const float *in_w, const float *in_coef, float *dx, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

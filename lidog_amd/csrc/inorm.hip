@@ -1,0 +1,648 @@
+// Instance normalisation of sparse feature matrices (MinkowskiInstanceNorm, ME 0.5.4) and the IBN block's fused
+// BatchNorm | InstanceNorm + ReLU pass.  Reference call sites: utils/models/minkunet_ibn.py:26 (in_norm1) and :38-40
+// (bn_out = bn_norm1(out); in_out = in_norm1(out); ME.cat(bn_out, in_out) -> ReLU).
+//
+// Instance norm normalises every channel PER SCAN: for batch index b and channel c,
+//   mean[b, c] = sum_{rows of b} x / n_b,  var[b, c] = sum (x - mean)^2 / n_b (biased),
+//   y = (x - mean[b, c]) * (var + eps)^-1/2 * w[c] + bias[c].
+// The statistics are segmented sums keyed on the batch column of the coordinate map:
+//   segments   a stable ordering of the map's rows by batch id (the radix sort of sconv_os.hip) + seg_off[B + 1];
+//              built once per coordinate map by the caller and kept with it
+//   reduce     per-(b, c) sums in double over each segment; workgroup w owns a contiguous range of SORTED rows and
+//              writes one partial row of 2 B C columns (zeros for the scans it does not touch); the two-level
+//              last-workgroup tail of stats_tail.h adds the rows in a fixed order and finalises per (b, c): no float
+//              atomics, the same bits on every run
+//   apply      y = (x - mean[b]) * invstd[b] * w + bias, b read from the per-row batch ids
+// The backward pass is the standard normalisation gradient per (b, c): a reduce pass (sum dy, sum dy * xhat) that also
+// writes dweight / dbias [C] (sums over b in ascending order) and per-(b, c) coefficients m0 = sum dy / n_b,
+// m1 = sum dy xhat / n_b; then dx = (dy - m0 - xhat * m1) * (invstd * w).
+//
+// [rows, C] with C % 4 == 0 streams float4 rows as bn.hip does; any other C takes plain scalar kernels (the module is
+// public; no performance target there).
+#include "common.h"
+#include "stats_tail.h"
+
+#define IN_MAX_BLOCKS 256       // workgroups (= partial rows) of a segmented reduction
+#define IN_LDS_DOUBLES 4096     // LDS of a reduction workgroup: the row reduction, then the final per-(b, c) sums
+#define IN_RS_BITS 9            // key bits per radix pass (RS_BITS of sconv_os.hip)
+
+// the float4 path: C4 <= 256 lanes per row, and the final 2 B C sums of the backward reduction fit in LDS
+static bool in_vector_path(int C, int B) { return C % 4 == 0 && C / 4 <= 256 && 2 * (int64_t)B * C <= IN_LDS_DOUBLES; }
+
+// ------------------------------------------------------------------ segments
+__global__ __launch_bounds__(256) void k_in_keys(const int32_t *__restrict__ coords, int64_t n, int32_t *__restrict__ bid,
+                                                 uint32_t *__restrict__ keys, int32_t *__restrict__ rows) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= n) return;
+    const int32_t b = coords[r * 4];
+    bid[r] = b;
+    keys[r] = (uint32_t)b;
+    rows[r] = (int32_t)r;
+}
+
+// seg_off[b] = first sorted position whose batch id is >= b (b = 0 .. B): empty scans get empty ranges
+__global__ __launch_bounds__(256) void k_in_seg_off(const uint32_t *__restrict__ sorted, int64_t n, int B,
+                                                    int32_t *__restrict__ seg_off) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b > B) return;
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (sorted[mid] < (uint32_t)b) lo = mid + 1;
+        else hi = mid;
+    }
+    seg_off[b] = (int32_t)lo;
+}
+
+static int64_t in_align(int64_t bytes) { return (bytes + 255) / 256 * 256; }
+
+extern "C" int64_t lidog_in_segments_ws(int64_t n) {
+    if (n <= 0) return 256;
+    return 3 * in_align(4 * n) + in_align(4 * lidog_radix_sort_hist_ints(n, 2));
+}
+
+extern "C" int lidog_in_segments(const int32_t *coords, int64_t n, int32_t B, int32_t *perm, int32_t *seg_off,
+                                 int32_t *bid, void *ws, int64_t ws_bytes, void *stream) {
+    hipStream_t st = (hipStream_t)stream;
+    LIDOG_REQUIRE(B >= 0 && B <= 4096 && n >= 0 && n < ((int64_t)1 << 31), "in_segments: 0 <= B <= 4096, n < 2^31");
+    LIDOG_REQUIRE(seg_off != nullptr, "in_segments: seg_off [B + 1] required");
+    if (n == 0) {
+        LIDOG_CHECK_HIP(hipMemsetAsync(seg_off, 0, sizeof(int32_t) * (B + 1), st));
+        return 0;
+    }
+    LIDOG_REQUIRE(coords && perm && bid && ws, "in_segments: coords, perm, bid and the workspace are required");
+    LIDOG_REQUIRE(ws_bytes >= lidog_in_segments_ws(n), "in_segments: workspace too small");
+    char *p = (char *)ws;
+    uint32_t *ka = (uint32_t *)p;  p += in_align(4 * n);
+    uint32_t *kb = (uint32_t *)p;  p += in_align(4 * n);
+    int32_t *tmp = (int32_t *)p;   p += in_align(4 * n);
+    int32_t *hist = (int32_t *)p;
+    // batch ids < 4096 are 12 bits: two passes of 9; one when every id fits in the first digit
+    const int passes = B <= (1 << IN_RS_BITS) ? 1 : 2;
+    int32_t *va = (passes & 1) ? tmp : perm, *vb = (passes & 1) ? perm : tmp;   // the row ids end in perm
+    k_in_keys<<<(unsigned)cdiv64(n, 256), 256, 0, st>>>(coords, n, bid, ka, va);
+    if (lidog_radix_sort_pairs(ka, va, kb, vb, n, passes, hist, st)) return 1;
+    k_in_seg_off<<<(unsigned)cdiv64(B + 1, 256), 256, 0, st>>>((passes & 1) ? kb : ka, n, B, seg_off);
+    LIDOG_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------ segmented reductions
+// What the last workgroup does with the per-(b, c) sums.  MODE 0 (x, x^2): mean / invstd.  MODE 1 (dy, dy * xhat):
+// coef [2][B][C] = (sum dy / n_b, sum dy xhat / n_b) and dw / db [C] = sums over b, ascending.
+struct InFinish {
+    const int32_t *seg_off;
+    int B, C;
+    float eps;
+    float *mean, *invstd;    // MODE 0
+    float *coef, *dw, *db;   // MODE 1
+};
+
+__device__ __forceinline__ void in_finalize(int mode, const InFinish &f, int j, double s0, double s1) {
+    const int b = j / f.C;
+    const double cnt = (double)(f.seg_off[b + 1] - f.seg_off[b]);
+    if (mode == 0) {
+        double m = 0.0, var = 0.0;
+        if (cnt > 0) {   // a scan with no rows in this map: finite placeholders, no row reads them
+            m = s0 / cnt;
+            var = s1 / cnt - m * m;
+            if (var < 0) var = 0;
+        }
+        f.mean[j] = (float)m;
+        f.invstd[j] = (float)(1.0 / sqrt(var + (double)f.eps));
+    } else {
+        const int BC = f.B * f.C;
+        f.coef[j] = cnt > 0 ? (float)(s0 / cnt) : 0.f;
+        f.coef[BC + j] = cnt > 0 ? (float)(s1 / cnt) : 0.f;
+    }
+}
+
+// largest b in [0, B) with seg_off[b] <= v (the scan that holds sorted row v)
+__device__ __forceinline__ int in_seg_of(const int32_t *__restrict__ seg_off, int B, int64_t v) {
+    int lo = 0, hi = B - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (seg_off[mid] <= v) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// MODE 0: (x, x * x).  MODE 1: (g, g * xhat), g = dy masked by the ReLU bits when given.  dy is read at row * dy_s4 + c4
+// (float4 units) and the mask bit at float4 number row * bits_s4 + bits_o4 + c4 of the bit layout of lidog_bn_apply_bits:
+// the same kernel serves the stand-alone instance norm (dy [n, C]) and the IN half of the IBN block (dy [n, 2C]).
+template <int MODE>
+__global__ __launch_bounds__(256) void k_in_reduce4(const float4 *__restrict__ x, const float4 *__restrict__ dy, int dy_s4,
+                                                    const uint32_t *__restrict__ bits, int bits_s4, int bits_o4,
+                                                    int64_t n, int C4, const int32_t *__restrict__ perm,
+                                                    const float *__restrict__ mean, const float *__restrict__ invstd,
+                                                    int64_t per_wg, StatsTail tail, InFinish fin) {
+    __shared__ double red[IN_LDS_DOUBLES];
+    const int C = C4 * 4, B = fin.B, BC = B * C;
+    const int RB = 256 / C4;
+    const int tid = threadIdx.x;
+    const int r = tid / C4, c4 = tid % C4;
+    const bool active = r < RB;
+    const int32_t *seg_off = fin.seg_off;
+    const int64_t lo = (int64_t)blockIdx.x * per_wg, hi = lo + per_wg < n ? lo + per_wg : n;
+    const int b0 = in_seg_of(seg_off, B, lo), b1 = in_seg_of(seg_off, B, hi - 1);
+    double *prow = tail.partial + (size_t)blockIdx.x * 2 * BC;
+    for (int j = tid; j < 2 * BC; j += 256) {   // the scans this workgroup has no rows of
+        const int bj = (j < BC ? j : j - BC) / C;
+        if (bj < b0 || bj > b1) lidog_store_sc1(prow + j, 0.0);
+    }
+    for (int b = b0; b <= b1; ++b) {
+        const int64_t s = seg_off[b] > lo ? seg_off[b] : lo, e = seg_off[b + 1] < hi ? seg_off[b + 1] : hi;
+        double a[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        float m[4] = {0, 0, 0, 0}, is[4] = {1, 1, 1, 1};
+        if (MODE == 1 && active) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { m[j] = mean[b * C + c4 * 4 + j]; is[j] = invstd[b * C + c4 * 4 + j]; }
+        }
+        if (active) {
+            // 4 rows in flight per lane; the last row of the range stands in for rows past it (masked afterwards)
+            for (int64_t row0 = s + r; row0 < e; row0 += 4 * RB) {
+                float4 v[4], g[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    int64_t row = row0 + u * RB;
+                    row = row < e ? row : e - 1;
+                    const int64_t pr = perm[row];
+                    v[u] = x[pr * C4 + c4];
+                    g[u] = MODE == 1 ? dy[pr * dy_s4 + c4] : make_float4(0, 0, 0, 0);
+                    if (MODE == 1 && bits) {
+                        const float4 k = lidog_relu_bits_as_float4(bits, pr * bits_s4 + bits_o4 + c4);
+                        g[u].x = k.x > 0.f ? g[u].x : 0.f; g[u].y = k.y > 0.f ? g[u].y : 0.f;
+                        g[u].z = k.z > 0.f ? g[u].z : 0.f; g[u].w = k.w > 0.f ? g[u].w : 0.f;
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    if (row0 + u * RB >= e) continue;
+                    const float vv[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+                    const float gg[4] = {g[u].x, g[u].y, g[u].z, g[u].w};
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        if (MODE == 0) {
+                            a[j] += (double)vv[j];
+                            a[4 + j] += (double)vv[j] * (double)vv[j];
+                        } else {
+                            const float xh = (vv[j] - m[j]) * is[j];
+                            a[j] += (double)gg[j];
+                            a[4 + j] += (double)gg[j] * (double)xh;
+                        }
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) red[tid * 8 + j] = a[j];
+        __syncthreads();
+        if (active && r == 0) {
+            for (int rr = 1; rr < RB; ++rr)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) a[j] += red[(rr * C4 + c4) * 8 + j];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                lidog_store_sc1(prow + b * C + c4 * 4 + j, a[j]);
+                lidog_store_sc1(prow + BC + b * C + c4 * 4 + j, a[4 + j]);
+            }
+        }
+        __syncthreads();   // red is rewritten by the next scan
+    }
+    lidog_stats_tail_rows_with(tail, (int)blockIdx.x, (int)gridDim.x, 1, [&](const double *grows, int ng) {
+        for (int j = tid; j < BC; j += 256) {
+            const double s0 = lidog_rows_sum_sc1(grows, 0, ng, 2 * BC, j);
+            const double s1 = lidog_rows_sum_sc1(grows, 0, ng, 2 * BC, BC + j);
+            in_finalize(MODE, fin, j, s0, s1);
+            if (MODE == 1) { red[j] = s0; red[BC + j] = s1; }
+        }
+        if (MODE == 1) {
+            __syncthreads();
+            for (int c = tid; c < C; c += 256) {
+                double s0 = 0.0, s1 = 0.0;
+                for (int b = 0; b < B; ++b) { s0 += red[b * C + c]; s1 += red[BC + b * C + c]; }
+                fin.db[c] = (float)s0;
+                fin.dw[c] = (float)s1;
+            }
+        }
+    });
+}
+
+// C % 4 != 0 (or sums that do not fit the LDS of the float4 path): one workgroup per (b, c), strided rows
+template <int MODE>
+__global__ __launch_bounds__(256) void k_in_reduce_scalar(const float *__restrict__ x, const float *__restrict__ dy,
+                                                          int C, const int32_t *__restrict__ perm,
+                                                          const float *__restrict__ mean,
+                                                          const float *__restrict__ invstd, double *__restrict__ sums,
+                                                          InFinish fin) {
+    __shared__ double s_red[2][4];
+    const int j = blockIdx.x, b = j / C, c = j % C;
+    const int64_t s = fin.seg_off[b], e = fin.seg_off[b + 1];
+    const float m = MODE ? mean[j] : 0.f, is = MODE ? invstd[j] : 1.f;
+    double t0 = 0, t1 = 0;
+    for (int64_t i = s + threadIdx.x; i < e; i += 256) {
+        const int64_t pr = perm[i];
+        const float v = x[pr * C + c];
+        if (MODE == 0) {
+            t0 += (double)v;
+            t1 += (double)v * (double)v;
+        } else {
+            const float g = dy[pr * C + c], xh = (v - m) * is;
+            t0 += (double)g;
+            t1 += (double)g * (double)xh;
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        t0 += __shfl_down(t0, d);
+        t1 += __shfl_down(t1, d);
+    }
+    if ((threadIdx.x & 63) == 0) { s_red[0][threadIdx.x >> 6] = t0; s_red[1][threadIdx.x >> 6] = t1; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double s0 = s_red[0][0] + s_red[0][1] + s_red[0][2] + s_red[0][3];
+        const double s1 = s_red[1][0] + s_red[1][1] + s_red[1][2] + s_red[1][3];
+        in_finalize(MODE, fin, j, s0, s1);
+        if (MODE == 1) { sums[j] = s0; sums[(int64_t)fin.B * C + j] = s1; }
+    }
+}
+
+__global__ void k_in_param_grads(const double *__restrict__ sums, int B, int C, float *__restrict__ dw,
+                                 float *__restrict__ db) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    double s0 = 0.0, s1 = 0.0;
+    for (int b = 0; b < B; ++b) { s0 += sums[b * C + c]; s1 += sums[(int64_t)B * C + b * C + c]; }
+    db[c] = (float)s0;
+    dw[c] = (float)s1;
+}
+
+static int64_t in_per_wg(int64_t n, int C4) {
+    const int64_t RB = 256 / C4;
+    int64_t per = cdiv64(n, IN_MAX_BLOCKS);
+    return per < 4 * RB ? 4 * RB : per;
+}
+
+extern "C" int64_t lidog_in_reduce_ws(int32_t B, int32_t C) {
+    const int64_t wide = (int64_t)2 * B * C;
+    if (in_vector_path(C, B)) return (IN_MAX_BLOCKS + cdiv64(IN_MAX_BLOCKS, STATS_GROUP)) * wide;
+    return wide;
+}
+
+template <int MODE>
+static int in_reduce(const float *x, const float *dy, int dy_s4, const uint32_t *bits, int bits_s4, int bits_o4,
+                     int64_t n, int C, int B, const int32_t *perm, const float *mean, const float *invstd, double *ws,
+                     const InFinish &fin, hipStream_t st) {
+    if (B == 0 || C == 0) return 0;
+    LIDOG_REQUIRE(ws != nullptr && fin.seg_off != nullptr && (n == 0 || perm != nullptr),
+                  "instance norm reduce: seg_off, perm and a workspace of lidog_in_reduce_ws(B, C) doubles required");
+    if (n > 0 && in_vector_path(C, B)) {
+        const int C4 = C / 4;
+        const int64_t per = in_per_wg(n, C4);
+        const int nb = (int)cdiv64(n, per);
+        unsigned *tickets = lidog_stats_tickets(st);
+        if (!tickets) return 1;
+        StatsTail tail{ws, tickets, nullptr, 0.0, B * C, BnFinish{}};
+        k_in_reduce4<MODE><<<(unsigned)nb, 256, 0, st>>>((const float4 *)x, (const float4 *)dy, dy_s4, bits, bits_s4,
+                                                          bits_o4, n, C4, perm, mean, invstd, per, tail, fin);
+        if (hipPeekAtLastError() != hipSuccess) lidog_stats_tickets_reset(st);
+    } else {
+        LIDOG_REQUIRE(bits == nullptr && (MODE == 0 || dy_s4 == C / 4 || C % 4 != 0),
+                      "instance norm reduce: strided / masked dy only on the float4 path");
+        k_in_reduce_scalar<MODE><<<(unsigned)(B * C), 256, 0, st>>>(x, dy, C, perm, mean, invstd, ws, fin);
+        if (MODE == 1) k_in_param_grads<<<(C + 127) / 128, 128, 0, st>>>(ws, B, C, fin.dw, fin.db);
+    }
+    LIDOG_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int lidog_in_stats(const float *x, int64_t n, int32_t C, int32_t B, const int32_t *perm,
+                              const int32_t *seg_off, float eps, float *mean, float *invstd, double *ws, void *stream) {
+    LIDOG_REQUIRE(mean && invstd, "in_stats: mean / invstd [B, C] required");
+    InFinish fin{seg_off, B, C, eps, mean, invstd, nullptr, nullptr, nullptr};
+    return in_reduce<0>(x, nullptr, 0, nullptr, 0, 0, n, C, B, perm, nullptr, nullptr, ws, fin, (hipStream_t)stream);
+}
+
+extern "C" int lidog_in_bwd_reduce(const float *dy, const float *x, int64_t n, int32_t C, int32_t B,
+                                   const int32_t *perm, const int32_t *seg_off, const float *mean, const float *invstd,
+                                   double *ws, float *coef, float *dw, float *db, void *stream) {
+    LIDOG_REQUIRE(coef && dw && db, "in_bwd_reduce: coef [2, B, C], dw [C] and db [C] required");
+    InFinish fin{seg_off, B, C, 0.f, nullptr, nullptr, coef, dw, db};
+    return in_reduce<1>(x, dy, C / 4, nullptr, 0, 0, n, C, B, perm, mean, invstd, ws, fin, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------ elementwise passes
+static unsigned in_grid(int64_t n) {
+    const int64_t g = cdiv64(n, 256);
+    return (unsigned)(g > 4096 ? 4096 : (g < 1 ? 1 : g));
+}
+
+// the normalisation gradient of one element: k_bn_bwd_apply4's expression and operation order (bn.hip), so that the
+// BatchNorm half of the IBN backward pass below equals lidog_bn_bwd_apply bit for bit
+__device__ __forceinline__ float norm_dx(float g, float x, float mu, float is, float sc, float m0, float m1) {
+    return (g - m0 - (x - mu) * is * m1) * sc;
+}
+
+__device__ __forceinline__ float4 in_affine4(float4 v, float4 m, float4 s, float4 w, float4 b) {
+    v.x = (v.x - m.x) * s.x * w.x + b.x;
+    v.y = (v.y - m.y) * s.y * w.y + b.y;
+    v.z = (v.z - m.z) * s.z * w.z + b.z;
+    v.w = (v.w - m.w) * s.w * w.w + b.w;
+    return v;
+}
+
+__global__ __launch_bounds__(256) void k_in_apply4(const float4 *__restrict__ x, int64_t total4, int C4,
+                                                   const int32_t *__restrict__ bid, const float4 *__restrict__ mean,
+                                                   const float4 *__restrict__ invstd, const float4 *__restrict__ w,
+                                                   const float4 *__restrict__ b, float4 *__restrict__ y) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (int64_t)gridDim.x * 256) {
+        const int64_t row = i / C4;
+        const int c4 = (int)(i - row * C4);
+        const int64_t k = (int64_t)bid[row] * C4 + c4;
+        y[i] = in_affine4(x[i], mean[k], invstd[k], w[c4], b[c4]);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_in_apply(const float *__restrict__ x, int64_t total, int C,
+                                                  const int32_t *__restrict__ bid, const float *__restrict__ mean,
+                                                  const float *__restrict__ invstd, const float *__restrict__ w,
+                                                  const float *__restrict__ b, float *__restrict__ y) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t row = i / C;
+        const int c = (int)(i - row * C);
+        const int64_t k = (int64_t)bid[row] * C + c;
+        y[i] = (x[i] - mean[k]) * invstd[k] * w[c] + b[c];
+    }
+}
+
+__global__ __launch_bounds__(256) void k_in_bwd_apply4(const float4 *__restrict__ dy, const float4 *__restrict__ x,
+                                                       int64_t total4, int C4, int B, const int32_t *__restrict__ bid,
+                                                       const float4 *__restrict__ mean, const float4 *__restrict__ invstd,
+                                                       const float4 *__restrict__ w, const float4 *__restrict__ coef,
+                                                       float4 *__restrict__ dx) {
+    const int64_t BC4 = (int64_t)B * C4;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (int64_t)gridDim.x * 256) {
+        const int64_t row = i / C4;
+        const int c4 = (int)(i - row * C4);
+        const int64_t k = (int64_t)bid[row] * C4 + c4;
+        const float4 g = dy[i], xv = x[i], mu = mean[k], is = invstd[k], ww = w[c4], m0 = coef[k], m1 = coef[BC4 + k];
+        float4 o;
+        o.x = norm_dx(g.x, xv.x, mu.x, is.x, is.x * ww.x, m0.x, m1.x);
+        o.y = norm_dx(g.y, xv.y, mu.y, is.y, is.y * ww.y, m0.y, m1.y);
+        o.z = norm_dx(g.z, xv.z, mu.z, is.z, is.z * ww.z, m0.z, m1.z);
+        o.w = norm_dx(g.w, xv.w, mu.w, is.w, is.w * ww.w, m0.w, m1.w);
+        dx[i] = o;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_in_bwd_apply(const float *__restrict__ dy, const float *__restrict__ x,
+                                                      int64_t total, int C, int B, const int32_t *__restrict__ bid,
+                                                      const float *__restrict__ mean, const float *__restrict__ invstd,
+                                                      const float *__restrict__ w, const float *__restrict__ coef,
+                                                      float *__restrict__ dx) {
+    const int64_t BC = (int64_t)B * C;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t row = i / C;
+        const int c = (int)(i - row * C);
+        const int64_t k = (int64_t)bid[row] * C + c;
+        dx[i] = norm_dx(dy[i], x[i], mean[k], invstd[k], invstd[k] * w[c], coef[k], coef[BC + k]);
+    }
+}
+
+extern "C" int lidog_in_apply(const float *x, int64_t n, int32_t C, int32_t B, const int32_t *bid, const float *mean,
+                              const float *invstd, const float *w, const float *b, float *y, void *stream) {
+    hipStream_t st = (hipStream_t)stream;
+    (void)B;
+    const int64_t total = n * C;
+    if (total == 0) return 0;
+    if (C % 4 == 0)
+        k_in_apply4<<<in_grid(total / 4), 256, 0, st>>>((const float4 *)x, total / 4, C / 4, bid, (const float4 *)mean,
+                                                        (const float4 *)invstd, (const float4 *)w, (const float4 *)b,
+                                                        (float4 *)y);
+    else
+        k_in_apply<<<in_grid(total), 256, 0, st>>>(x, total, C, bid, mean, invstd, w, b, y);
+    LIDOG_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int lidog_in_bwd_apply(const float *dy, const float *x, int64_t n, int32_t C, int32_t B, const int32_t *bid,
+                                  const float *mean, const float *invstd, const float *w, const float *coef, float *dx,
+                                  void *stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t total = n * C;
+    if (total == 0) return 0;
+    if (C % 4 == 0)
+        k_in_bwd_apply4<<<in_grid(total / 4), 256, 0, st>>>((const float4 *)dy, (const float4 *)x, total / 4, C / 4, B,
+                                                            bid, (const float4 *)mean, (const float4 *)invstd,
+                                                            (const float4 *)w, (const float4 *)coef, (float4 *)dx);
+    else
+        k_in_bwd_apply<<<in_grid(total), 256, 0, st>>>(dy, x, total, C, B, bid, mean, invstd, w, coef, dx);
+    LIDOG_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------ the IBN block: ReLU(BN(x)) | ReLU(IN(x))
+// y [n, 2C]: float4 q = row * 2 C4 + c of y is BatchNorm (c < C4) or instance norm (c >= C4) of x's float4 row * C4 +
+// c mod C4, then max(., 0); bits: lidog_bn_apply_bits' layout over y.  Both halves use the expression of their own
+// apply pass (bn.hip:k_bn_apply4, k_in_apply4): the result equals lidog_bn_apply + lidog_in_apply + lidog_cat2 +
+// lidog_relu_fwd bit for bit.  The two halves of a row are read by neighbouring lanes: x comes from HBM once.
+__global__ __launch_bounds__(256) void k_ibn_apply4(const float4 *__restrict__ x, int64_t total4, int C4,
+                                                    const float4 *__restrict__ bn_mean,
+                                                    const float4 *__restrict__ bn_invstd, const float4 *__restrict__ bn_w,
+                                                    const float4 *__restrict__ bn_b, const int32_t *__restrict__ bid,
+                                                    const float4 *__restrict__ in_mean,
+                                                    const float4 *__restrict__ in_invstd,
+                                                    const float4 *__restrict__ in_w, const float4 *__restrict__ in_b,
+                                                    float4 *__restrict__ y, uint32_t *__restrict__ bits) {
+    const int C8 = 2 * C4;
+    for (int64_t base = (int64_t)blockIdx.x * 256; base < total4; base += (int64_t)gridDim.x * 256) {
+        const int64_t i = base + threadIdx.x;
+        const bool ok = i < total4;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (ok) {
+            const int64_t row = i / C8;
+            const int c = (int)(i - row * C8);
+            if (c < C4) {
+                v = in_affine4(x[row * C4 + c], bn_mean[c], bn_invstd[c], bn_w[c], bn_b[c]);
+            } else {
+                const int c4 = c - C4;
+                const int64_t k = (int64_t)bid[row] * C4 + c4;
+                v = in_affine4(x[row * C4 + c4], in_mean[k], in_invstd[k], in_w[c4], in_b[c4]);
+            }
+            v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+            y[i] = v;
+        }
+        uint32_t nib = (v.x > 0.f ? 1u : 0u) | (v.y > 0.f ? 2u : 0u) | (v.z > 0.f ? 4u : 0u) | (v.w > 0.f ? 8u : 0u);
+        uint32_t wv = nib << (4 * (threadIdx.x & 7));
+        wv |= __shfl_xor(wv, 1);
+        wv |= __shfl_xor(wv, 2);
+        wv |= __shfl_xor(wv, 4);
+        if (ok && (threadIdx.x & 7) == 0) bits[i >> 3] = wv;
+    }
+}
+
+// The BatchNorm half's backward reduction, k_colreduce_nc4<1> of bn.hip (no ReLU operand) over the masked BN half of
+// dy [n, 2C]: the same grid (lidog_bn_bwd_reduce_blocks), the same rows per lane in the same order, the same LDS
+// reduction and tail -- the sums lidog_bn_bwd_reduce computes from ReLU-backward + split2 output, bit for bit.
+__global__ __launch_bounds__(256) void k_ibn_bn_reduce4(const float4 *__restrict__ x, const float4 *__restrict__ dy,
+                                                        const uint32_t *__restrict__ bits, int64_t n, int C4,
+                                                        const float *__restrict__ mean, const float *__restrict__ invstd,
+                                                        StatsTail tail) {
+    __shared__ double red[256 * 8];
+    const int RB = 256 / C4;
+    const int tid = threadIdx.x;
+    const int r = tid / C4, c4 = tid % C4;
+    const bool active = r < RB;
+    double a[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    float m[4] = {0, 0, 0, 0}, is[4] = {1, 1, 1, 1};
+    if (active) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { m[j] = mean[c4 * 4 + j]; is[j] = invstd[c4 * 4 + j]; }
+        const int64_t step = (int64_t)gridDim.x * RB;
+        for (int64_t row0 = (int64_t)blockIdx.x * RB + r; row0 < n; row0 += 4 * step) {
+            float4 v[4], g[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                int64_t row = row0 + u * step;
+                row = row < n ? row : n - 1;
+                v[u] = x[row * C4 + c4];
+                g[u] = dy[row * 2 * C4 + c4];
+                const float4 k = lidog_relu_bits_as_float4(bits, row * 2 * C4 + c4);
+                g[u].x = k.x > 0.f ? g[u].x : 0.f; g[u].y = k.y > 0.f ? g[u].y : 0.f;
+                g[u].z = k.z > 0.f ? g[u].z : 0.f; g[u].w = k.w > 0.f ? g[u].w : 0.f;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const bool ok = row0 + u * step < n;
+                const float4 z = make_float4(0, 0, 0, 0);
+                const float4 vv = v[u], gg = ok ? g[u] : z;
+                const float vx[4] = {vv.x, vv.y, vv.z, vv.w}, gx[4] = {gg.x, gg.y, gg.z, gg.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float xh = (vx[j] - m[j]) * is[j];
+                    a[j] += (double)gx[j];
+                    a[4 + j] += (double)gx[j] * (double)xh;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) red[tid * 8 + j] = a[j];
+    __syncthreads();
+    if (active && r == 0) {
+        for (int rr = 1; rr < RB; ++rr)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) a[j] += red[(rr * C4 + c4) * 8 + j];
+    }
+    lidog_stats_tail(tail, active && r == 0, c4, a);
+}
+
+// dx = dx_BN + dx_IN from dy [n, 2C] and the mask bits of the forward pass: each half is k_bn_bwd_apply4's /
+// k_in_bwd_apply4's expression, and their sum is what autograd adds for the two readers of x
+__global__ __launch_bounds__(256) void k_ibn_bwd_apply4(const float4 *__restrict__ dy, const uint32_t *__restrict__ bits,
+                                                        const float4 *__restrict__ x, int64_t total4, int C4, int B,
+                                                        const float *__restrict__ bn_mean,
+                                                        const float *__restrict__ bn_invstd,
+                                                        const float *__restrict__ bn_w, const double *__restrict__ bn_sums,
+                                                        double bn_ic, const int32_t *__restrict__ bid,
+                                                        const float4 *__restrict__ in_mean,
+                                                        const float4 *__restrict__ in_invstd,
+                                                        const float4 *__restrict__ in_w, const float4 *__restrict__ coef,
+                                                        float4 *__restrict__ dx) {
+    __shared__ float4 s_bn[5][256];   // per channel quad: mean, invstd, invstd * w, m0, m1 of the BatchNorm half
+    const int C = 4 * C4;
+    for (int q = threadIdx.x; q < C4; q += 256) {
+        float t[5][4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c = 4 * q + j;
+            t[0][j] = bn_mean[c];
+            t[1][j] = bn_invstd[c];
+            t[2][j] = bn_invstd[c] * bn_w[c];
+            t[3][j] = (float)(bn_sums[c] * bn_ic);
+            t[4][j] = (float)(bn_sums[C + c] * bn_ic);
+        }
+#pragma unroll
+        for (int k = 0; k < 5; ++k) s_bn[k][q] = make_float4(t[k][0], t[k][1], t[k][2], t[k][3]);
+    }
+    __syncthreads();
+    const int64_t BC4 = (int64_t)B * C4;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (int64_t)gridDim.x * 256) {
+        const int64_t row = i / C4;
+        const int c4 = (int)(i - row * C4);
+        const int64_t qb = row * 2 * C4 + c4, qi = qb + C4;
+        float4 gb = dy[qb], gi = dy[qi];
+        const float4 xv = x[i];
+        const float4 kb = lidog_relu_bits_as_float4(bits, qb), ki = lidog_relu_bits_as_float4(bits, qi);
+        gb.x = kb.x > 0.f ? gb.x : 0.f; gb.y = kb.y > 0.f ? gb.y : 0.f; gb.z = kb.z > 0.f ? gb.z : 0.f;
+        gb.w = kb.w > 0.f ? gb.w : 0.f;
+        gi.x = ki.x > 0.f ? gi.x : 0.f; gi.y = ki.y > 0.f ? gi.y : 0.f; gi.z = ki.z > 0.f ? gi.z : 0.f;
+        gi.w = ki.w > 0.f ? gi.w : 0.f;
+        const float4 mu = s_bn[0][c4], is = s_bn[1][c4], sc = s_bn[2][c4], m0 = s_bn[3][c4], m1 = s_bn[4][c4];
+        const int64_t k = (int64_t)bid[row] * C4 + c4;
+        const float4 imu = in_mean[k], iis = in_invstd[k], iw = in_w[c4], im0 = coef[k], im1 = coef[BC4 + k];
+        float4 o;
+        o.x = norm_dx(gb.x, xv.x, mu.x, is.x, sc.x, m0.x, m1.x) + norm_dx(gi.x, xv.x, imu.x, iis.x, iis.x * iw.x, im0.x, im1.x);
+        o.y = norm_dx(gb.y, xv.y, mu.y, is.y, sc.y, m0.y, m1.y) + norm_dx(gi.y, xv.y, imu.y, iis.y, iis.y * iw.y, im0.y, im1.y);
+        o.z = norm_dx(gb.z, xv.z, mu.z, is.z, sc.z, m0.z, m1.z) + norm_dx(gi.z, xv.z, imu.z, iis.z, iis.z * iw.z, im0.z, im1.z);
+        o.w = norm_dx(gb.w, xv.w, mu.w, is.w, sc.w, m0.w, m1.w) + norm_dx(gi.w, xv.w, imu.w, iis.w, iis.w * iw.w, im0.w, im1.w);
+        dx[i] = o;
+    }
+}
+
+static bool ibn_shape_ok(int64_t n, int C, int B) { return n > 0 && in_vector_path(C, B) && C >= 4; }
+
+extern "C" int lidog_ibn_apply(const float *x, int64_t n, int32_t C, int32_t B, const float *bn_mean,
+                               const float *bn_invstd, const float *bn_w, const float *bn_b, const int32_t *bid,
+                               const float *in_mean, const float *in_invstd, const float *in_w, const float *in_b,
+                               float *y, uint32_t *relu_bits, void *stream) {
+    LIDOG_REQUIRE(ibn_shape_ok(n, C, B), "ibn_apply: n > 0, C %% 4 == 0, C <= 1024, 2 B C <= %d", IN_LDS_DOUBLES);
+    LIDOG_REQUIRE(relu_bits != nullptr, "ibn_apply: relu_bits [lidog_relu_bits_words(n, 2 C)] required");
+    const int64_t total4 = n * (2 * C / 4);
+    k_ibn_apply4<<<in_grid(total4), 256, 0, (hipStream_t)stream>>>(
+        (const float4 *)x, total4, C / 4, (const float4 *)bn_mean, (const float4 *)bn_invstd, (const float4 *)bn_w,
+        (const float4 *)bn_b, bid, (const float4 *)in_mean, (const float4 *)in_invstd, (const float4 *)in_w,
+        (const float4 *)in_b, (float4 *)y, relu_bits);
+    LIDOG_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int lidog_ibn_bwd_reduce(const float *dy, const uint32_t *relu_bits, const float *x, int64_t n, int32_t C,
+                                    int32_t B, const float *bn_mean, const float *bn_invstd, double *bn_sums,
+                                    double *bn_ws, float *bn_dw, float *bn_db, const int32_t *perm,
+                                    const int32_t *seg_off, const float *in_mean, const float *in_invstd, double *in_ws,
+                                    float *in_coef, float *in_dw, float *in_db, void *stream) {
+    hipStream_t st = (hipStream_t)stream;
+    LIDOG_REQUIRE(ibn_shape_ok(n, C, B), "ibn_bwd_reduce: n > 0, C %% 4 == 0, C <= 1024, 2 B C <= %d", IN_LDS_DOUBLES);
+    LIDOG_REQUIRE(dy && relu_bits && x && bn_sums && bn_ws && bn_dw && bn_db && in_coef && in_dw && in_db,
+                  "ibn_bwd_reduce: missing argument");
+    // BatchNorm half: lidog_bn_bwd_reduce's launch (grid, workspace, tail, row count behind the sums)
+    const int64_t nb = lidog_bn_bwd_reduce_blocks(n, C);
+    BnFinish bfin = {0.f, 0.f, nullptr, nullptr, nullptr, nullptr, bn_dw, bn_db};
+    StatsTail tail;
+    if (lidog_stats_tail_make(&tail, bn_ws, bn_sums, (double)n, C, bfin, st)) return 1;
+    k_ibn_bn_reduce4<<<(unsigned)nb, 256, 0, st>>>((const float4 *)x, (const float4 *)dy, relu_bits, n, C / 4, bn_mean,
+                                                    bn_invstd, tail);
+    lidog_stats_tail_finish(tail, (int)nb, st);
+    LIDOG_LAUNCH_CHECK();
+    // instance-norm half: the stand-alone reduction, reading dy's second half through the mask
+    InFinish fin{seg_off, B, C, 0.f, nullptr, nullptr, in_coef, in_dw, in_db};
+    return in_reduce<1>(x, dy + C, 2 * C / 4, relu_bits, 2 * C / 4, C / 4, n, C, B, perm, in_mean, in_invstd, in_ws,
+                        fin, st);
+}
+
+extern "C" int lidog_ibn_bwd_apply(const float *dy, const uint32_t *relu_bits, const float *x, int64_t n, int32_t C,
+                                   int32_t B, const float *bn_mean, const float *bn_invstd, const float *bn_w,
+                                   const double *bn_sums, double bn_count, const int32_t *bid, const float *in_mean,
+                                   const float *in_invstd, const float *in_w, const float *in_coef, float *dx,
+                                   void *stream) {
+    LIDOG_REQUIRE(ibn_shape_ok(n, C, B) && bn_count > 0, "ibn_bwd_apply: n > 0, bn_count > 0, C %% 4 == 0, C <= 1024");
+    const int64_t total4 = n * (C / 4);
+    k_ibn_bwd_apply4<<<in_grid(total4), 256, 0, (hipStream_t)stream>>>(
+        (const float4 *)dy, relu_bits, (const float4 *)x, total4, C / 4, B, bn_mean, bn_invstd, bn_w, bn_sums,
+        1.0 / bn_count, bid, (const float4 *)in_mean, (const float4 *)in_invstd, (const float4 *)in_w,
+        (const float4 *)in_coef, (float4 *)dx);
+    LIDOG_LAUNCH_CHECK();
+    return 0;
+}

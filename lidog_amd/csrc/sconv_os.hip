@@ -238,6 +238,28 @@ static int64_t os_pad(int64_t n) { return (n + OS_TM - 1) / OS_TM * OS_TM; }
 
 static int64_t rs_chunks(int64_t n) { return cdiv64(n, RS_CHUNK); }
 
+// Stable LSD radix sort of n (key, val) pairs by the low passes * RS_BITS bits of the keys (declared in common.h): the
+// pairs ping-pong between (ka, va) and (kb, vb), so they end in (ka, va) after an even number of passes and in (kb, vb)
+// after an odd one.  hist: lidog_radix_sort_hist_ints(n, passes) int32.
+int64_t lidog_radix_sort_hist_ints(int64_t n, int passes) { return (int64_t)RS_BINS * (rs_chunks(n) + passes); }
+
+int lidog_radix_sort_pairs(uint32_t *ka, int32_t *va, uint32_t *kb, int32_t *vb, int64_t n, int passes, int32_t *hist,
+                           hipStream_t st) {
+    const int chunks = (int)rs_chunks(n);
+    int32_t *totals = hist + (int64_t)RS_BINS * chunks;      // [passes][RS_BINS], one row per pass (zeroed once)
+    LIDOG_CHECK_HIP(hipMemsetAsync(totals, 0, sizeof(int32_t) * RS_BINS * passes, st));
+    for (int pass = 0; pass < passes; ++pass) {
+        const int shift = pass * RS_BITS;
+        int32_t *tot = totals + pass * RS_BINS;
+        k_rs_hist<<<chunks, 64, 0, st>>>(ka, n, shift, chunks, hist, tot);
+        k_rs_scan<<<RS_BINS, 64, 0, st>>>(hist, tot, chunks);
+        k_rs_scatter<<<chunks, 64, 0, st>>>(ka, va, n, shift, chunks, hist, kb, vb);
+        uint32_t *tk = ka; ka = kb; kb = tk;
+        int32_t *tv = va; va = vb; vb = tv;
+    }
+    return 0;
+}
+
 // bytes of workspace lidog_kernel_map_sorted needs for a map of n rows
 extern "C" int64_t lidog_kernel_map_sorted_ws(int64_t n) {
     if (n <= 0) return 256;
@@ -263,25 +285,13 @@ extern "C" int lidog_kernel_map_sorted(const int32_t *nbr, int64_t n, int32_t K,
     int32_t *rows = (int32_t *)p;                 p += 4 * n;
     uint32_t *masks = (uint32_t *)p;              p += 4 * n;
     int32_t *hist = (int32_t *)p;
-    const int chunks = (int)rs_chunks(n);
-    int32_t *totals = hist + (int64_t)RS_BINS * chunks;      // [3][RS_BINS], one row per pass (zeroed once)
     const int passes = (K + RS_BITS - 1) / RS_BITS;
     // the pairs ping-pong between (keys, a) and (keys_out, b); the row ids start where an odd / even number of passes
     // leaves them in `perm`
     int32_t *va = (passes & 1) ? rows : perm, *vb = (passes & 1) ? perm : rows;
     k_os_bitpos<<<1, 32, 0, st>>>(k_off, K, pos);
     k_os_keys<<<(unsigned)cdiv64(n, 256), 256, 0, st>>>(nbr, n, K, pos, keys, va, masks);
-    uint32_t *ka = keys, *kb = keys_out;
-    LIDOG_CHECK_HIP(hipMemsetAsync(totals, 0, sizeof(int32_t) * RS_BINS * passes, st));
-    for (int pass = 0; pass < passes; ++pass) {
-        const int shift = pass * RS_BITS;
-        int32_t *tot = totals + pass * RS_BINS;
-        k_rs_hist<<<chunks, 64, 0, st>>>(ka, n, shift, chunks, hist, tot);
-        k_rs_scan<<<RS_BINS, 64, 0, st>>>(hist, tot, chunks);
-        k_rs_scatter<<<chunks, 64, 0, st>>>(ka, va, n, shift, chunks, hist, kb, vb);
-        uint32_t *tk = ka; ka = kb; kb = tk;
-        int32_t *tv = va; va = vb; vb = tv;
-    }
+    if (lidog_radix_sort_pairs(keys, va, keys_out, vb, n, passes, hist, st)) return 1;
     const int64_t n_pad = os_pad(n);
     k_os_wave_masks<<<(unsigned)cdiv64(n_pad, 256), 256, 0, st>>>(masks, perm, n, n_pad, wave_masks);
     k_os_tile_order<<<1, 64, 0, st>>>(wave_masks, (int)(n_pad / OS_TM), tile_order);

@@ -73,8 +73,12 @@ __device__ __forceinline__ double lidog_rows_sum_sc1(const double *base, int r0,
 
 // Second half of the tail, for a workgroup whose slice of partial row `b` (of `nb` rows) has been stored with
 // lidog_store_sc1 by its threads: `per_row` workgroups contribute to a row (column tiles of a 2-D grid; 1 otherwise).
-// Called by EVERY thread of EVERY workgroup of the launch.
-__device__ __forceinline__ void lidog_stats_tail_rows(const StatsTail &t, int b, int nb, int per_row) {
+// Called by EVERY thread of EVERY workgroup of the launch.  `finish(grows, ng)` is what the last group finisher does
+// with the ng group rows (ascending, 2C columns each): lidog_stats_tail_rows below writes the sums and finalises per
+// channel; the instance norm (inorm.hip) finalises per (scan, channel) from the same rows.
+template <class Finish>
+__device__ __forceinline__ void lidog_stats_tail_rows_with(const StatsTail &t, int b, int nb, int per_row,
+                                                           Finish &&finish) {
     __shared__ int s_last;
     const int C = t.C, C2 = 2 * C;
     const int ng = (nb + STATS_GROUP - 1) / STATS_GROUP;
@@ -112,20 +116,26 @@ __device__ __forceinline__ void lidog_stats_tail_rows(const StatsTail &t, int b,
     __syncthreads();
     if (!s_last) return;
     // ---- last group finisher: the group rows, ascending; then what follows the reduction
-    const double *grows = t.partial + (size_t)nb * C2;
-    for (int c = threadIdx.x; c < C; c += blockDim.x) {
-        const double s0 = lidog_rows_sum_sc1(grows, 0, ng, C2, c);
-        const double s1 = lidog_rows_sum_sc1(grows, 0, ng, C2, C + c);
-        t.sums[c] = s0;
-        t.sums[C + c] = s1;
-        if (t.fin.db) t.fin.db[c] = (float)s0;
-        if (t.fin.dw) t.fin.dw[c] = (float)s1;
-        if (t.fin.mean) lidog_bn_finalize_channel(s0, s1, t.count, c, t.fin);
-    }
-    if (threadIdx.x == 0 && t.count > 0) t.sums[C2] = t.count;
+    finish((const double *)(t.partial + (size_t)nb * C2), ng);
     // ticket words back to zero for the next launch on this stream (every add of this launch has returned by now)
     for (int i = threadIdx.x; i < 1 + ng; i += blockDim.x)
         __hip_atomic_store((lidog_gu32 *)(t.tickets + i), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__device__ __forceinline__ void lidog_stats_tail_rows(const StatsTail &t, int b, int nb, int per_row) {
+    lidog_stats_tail_rows_with(t, b, nb, per_row, [&](const double *grows, int ng) {
+        const int C = t.C, C2 = 2 * C;
+        for (int c = threadIdx.x; c < C; c += blockDim.x) {
+            const double s0 = lidog_rows_sum_sc1(grows, 0, ng, C2, c);
+            const double s1 = lidog_rows_sum_sc1(grows, 0, ng, C2, C + c);
+            t.sums[c] = s0;
+            t.sums[C + c] = s1;
+            if (t.fin.db) t.fin.db[c] = (float)s0;
+            if (t.fin.dw) t.fin.dw[c] = (float)s1;
+            if (t.fin.mean) lidog_bn_finalize_channel(s0, s1, t.count, c, t.fin);
+        }
+        if (threadIdx.x == 0 && t.count > 0) t.sums[C2] = t.count;
+    });
 }
 
 // Called by EVERY thread of EVERY workgroup (256 threads, 1-D grid) at the end of the kernel.  `writer`: this thread

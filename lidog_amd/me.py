@@ -6,6 +6,7 @@ Mirrors the surface of MinkowskiEngine 0.5.4 that LiDOG's models and pipelines u
   MinkowskiConvolution / ...Transpose                utils/models/minkunet_bev.py:57-123
   MinkowskiBatchNorm(.bn) / MinkowskiSyncBatchNorm   minkunet_bev.py:60,406-408; train_lidog.py:228
   MinkowskiReLU(inplace=True), cat, +=               minkunet_bev.py:124,337; resnet_block.py:52
+  MinkowskiInstanceNorm                              utils/models/minkunet_ibn.py:26,38-40
   utils.kaiming_normal_                              minkunet_bev.py:404
   modules.resnet_block.BasicBlock                    minkunet_bev.py:4,425-439
 
@@ -83,11 +84,12 @@ class _Arena:
 
 
 class _CoordMap:
-    __slots__ = ("coords", "keys", "vals", "cap", "n", "bits", "box")
+    __slots__ = ("coords", "keys", "vals", "cap", "n", "bits", "box", "segs")
 
     def __init__(self, coords, keys, vals, cap):
         self.coords, self.keys, self.vals, self.cap, self.n = coords, keys, vals, cap, coords.shape[0]
         self.bits = self.box = None    # occupancy bitmap over the bounding box (CoordinateManager._bitmap)
+        self.segs = None               # (perm, seg_off, bid, B): rows per scan (CoordinateManager.segments)
 
 
 class KernelMap:
@@ -538,6 +540,22 @@ class CoordinateManager:
         elif K == 8:
             self._own(*m.rows("out"))
         return m
+
+    def segments(self, key):
+        """(perm, seg_off, bid, B) of coordinate map `key`: its rows in stable batch order, where each batch index
+        starts in that order [B + 1], the batch index of every row, and B = largest batch index + 1 of the manager.
+        Built once per map (instance norm statistics are per scan); any row order is accepted."""
+        cmap = self.maps[key]
+        if cmap.segs is None:
+            n, B = cmap.n, int(self.batch_size or 0)
+            perm = torch.empty(n, dtype=torch.int32, device=self.device)
+            seg_off = torch.empty(B + 1, dtype=torch.int32, device=self.device)
+            bid = torch.empty(n, dtype=torch.int32, device=self.device)
+            nbytes = _lib.load().lidog_in_segments_ws(n)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            call("lidog_in_segments", ptr(cmap.coords), n, B, ptr(perm), ptr(seg_off), ptr(bid), ptr(ws), nbytes)
+            cmap.segs = self._own(perm, seg_off, bid) + (B,)
+        return cmap.segs
 
     def identity_map(self, n):
         if n not in self.identity:
@@ -1298,6 +1316,155 @@ class MinkowskiSyncBatchNorm(MinkowskiBatchNorm):
             if out is module or name != "bn":
                 out.add_module(name, cls.convert_sync_batchnorm(child, process_group))
         return out
+
+
+# ------------------------------------------------------------------ instance norm
+# [ME-mem] MinkowskiInstanceNorm of MinkowskiEngine 0.5.4, restated from memory (unpinned like every ME convention here,
+# SURVEY.md 8(c)): parameters weight (ones) / bias (zeros) of shape [1, C]; per scan b and channel c the biased variance
+# over the rows of b; y = (x - mean) * (var + IN_EPS)^-1/2 * weight + bias; no running statistics (train = eval).
+IN_EPS = 1e-8
+
+
+def _in_param_shape(C):
+    return (1, C)
+
+
+def _in_vector_path(C, B):
+    """the shapes csrc/inorm.hip runs on float4 kernels (and the fused IBN passes accept); others take scalar kernels"""
+    return C % 4 == 0 and 4 <= C <= 1024 and 2 * B * C <= 4096
+
+
+class _InstanceNormFn(torch.autograd.Function):
+    """MinkowskiInstanceNorm over the segments of a coordinate map (csrc/inorm.hip, minkunet_ibn.py:26)"""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, segs, eps):
+        x = x.contiguous()
+        n, C = x.shape
+        perm, seg_off, bid, B = segs
+        dev = x.device
+        mean = torch.empty(B * C, dtype=torch.float32, device=dev)
+        invstd = torch.empty(B * C, dtype=torch.float32, device=dev)
+        ws = torch.empty(_lib.load().lidog_in_reduce_ws(B, C), dtype=torch.float64, device=dev)
+        call("lidog_in_stats", ptr(x), n, C, B, ptr(perm), ptr(seg_off), float(eps), ptr(mean), ptr(invstd), ptr(ws))
+        y = torch.empty_like(x)
+        call("lidog_in_apply", ptr(x), n, C, B, ptr(bid), ptr(mean), ptr(invstd), ptr(weight), ptr(bias), ptr(y))
+        ctx.save_for_backward(x, weight, mean, invstd)
+        ctx.segs = segs
+        ctx.params = (weight, bias)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight, mean, invstd = ctx.saved_tensors
+        perm, seg_off, bid, B = ctx.segs
+        n, C = x.shape
+        dev = x.device
+        dy = dy.contiguous()
+        dw = _grad_out(ctx.params[0], _in_param_shape(C))
+        db = _grad_out(ctx.params[1], _in_param_shape(C))
+        dw = dw if dw is not None else torch.empty(_in_param_shape(C), dtype=torch.float32, device=dev)
+        db = db if db is not None else torch.empty(_in_param_shape(C), dtype=torch.float32, device=dev)
+        coef = torch.empty(2 * B * C, dtype=torch.float32, device=dev)
+        ws = torch.empty(_lib.load().lidog_in_reduce_ws(B, C), dtype=torch.float64, device=dev)
+        call("lidog_in_bwd_reduce", ptr(dy), ptr(x), n, C, B, ptr(perm), ptr(seg_off), ptr(mean), ptr(invstd), ptr(ws),
+             ptr(coef), ptr(dw), ptr(db))
+        dx = torch.empty_like(x)
+        call("lidog_in_bwd_apply", ptr(dy), ptr(x), n, C, B, ptr(bid), ptr(mean), ptr(invstd), ptr(weight), ptr(coef),
+             ptr(dx))
+        return dx, dw, db, None, None
+
+
+class MinkowskiInstanceNorm(nn.Module):
+    """ME.MinkowskiInstanceNorm (utils/models/minkunet_ibn.py:26): every channel normalised per scan ([ME-mem] above)"""
+
+    def __init__(self, num_features):
+        super().__init__()
+        self.num_features = num_features
+        self.weight = nn.Parameter(torch.ones(_in_param_shape(num_features)))
+        self.bias = nn.Parameter(torch.zeros(_in_param_shape(num_features)))
+
+    def forward(self, x):
+        segs = x.coordinate_manager.segments(x.coordinate_map_key)
+        return x._like(_InstanceNormFn.apply(x.F, self.weight, self.bias, segs, IN_EPS))
+
+    def extra_repr(self):
+        return f"{self.num_features}"
+
+
+class _IBNReluFn(torch.autograd.Function):
+    """ReLU(BN(x)) | ReLU(IN(x)) of the IBN block (minkunet_ibn.py:38-40) as one pass each way: BatchNorm statistics by
+    lidog_bn_stats (the literal path's kernel), instance-norm statistics by lidog_in_stats, then lidog_ibn_apply; backward
+    lidog_ibn_bwd_reduce + lidog_ibn_bwd_apply.  Forward and every gradient equal the literal
+    relu(cat(bn(x), in(x))) through this module's operators bit for bit."""
+
+    @staticmethod
+    def forward(ctx, x, bn_w, bn_b, in_w, in_b, running_mean, running_var, momentum, bn_eps, segs, in_eps):
+        x = x.contiguous()
+        n, C = x.shape
+        perm, seg_off, bid, B = segs
+        dev = x.device
+        rows = float(n)
+        sums = torch.empty(2 * C + 1, dtype=torch.float64, device=dev)
+        bn_mean = torch.empty(C, dtype=torch.float32, device=dev)
+        bn_invstd = torch.empty(C, dtype=torch.float32, device=dev)
+        call("lidog_bn_stats", ptr(x), n, C, 1, ptr(sums), ptr(_bn_ws(C, 1, dev)), rows, float(bn_eps), float(momentum),
+             ptr(bn_mean), ptr(bn_invstd), ptr(running_mean), ptr(running_var))
+        in_mean = torch.empty(B * C, dtype=torch.float32, device=dev)
+        in_invstd = torch.empty(B * C, dtype=torch.float32, device=dev)
+        ws = torch.empty(_lib.load().lidog_in_reduce_ws(B, C), dtype=torch.float64, device=dev)
+        call("lidog_in_stats", ptr(x), n, C, B, ptr(perm), ptr(seg_off), float(in_eps), ptr(in_mean), ptr(in_invstd),
+             ptr(ws))
+        y = torch.empty((n, 2 * C), dtype=torch.float32, device=dev)
+        bits = torch.empty(_lib.load().lidog_relu_bits_words(n, 2 * C), dtype=torch.int32, device=dev)
+        call("lidog_ibn_apply", ptr(x), n, C, B, ptr(bn_mean), ptr(bn_invstd), ptr(bn_w), ptr(bn_b), ptr(bid),
+             ptr(in_mean), ptr(in_invstd), ptr(in_w), ptr(in_b), ptr(y), ptr(bits))
+        ctx.save_for_backward(x, bn_w, bn_mean, bn_invstd, in_w, in_mean, in_invstd, bits)
+        ctx.segs = segs
+        ctx.params = (bn_w, bn_b, in_w, in_b)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, bn_w, bn_mean, bn_invstd, in_w, in_mean, in_invstd, bits = ctx.saved_tensors
+        perm, seg_off, bid, B = ctx.segs
+        n, C = x.shape
+        dev = x.device
+        dy = dy.contiguous()
+        shapes = ((C,), (C,), _in_param_shape(C), _in_param_shape(C))
+        grads = []
+        for p, shape in zip(ctx.params, shapes):
+            g = _grad_out(p, shape)
+            grads.append(g if g is not None else torch.empty(shape, dtype=torch.float32, device=dev))
+        bn_dw, bn_db, in_dw, in_db = grads
+        sums = torch.empty(2 * C + 1, dtype=torch.float64, device=dev)
+        coef = torch.empty(2 * B * C, dtype=torch.float32, device=dev)
+        ws = torch.empty(_lib.load().lidog_in_reduce_ws(B, C), dtype=torch.float64, device=dev)
+        call("lidog_ibn_bwd_reduce", ptr(dy), ptr(bits), ptr(x), n, C, B, ptr(bn_mean), ptr(bn_invstd), ptr(sums),
+             ptr(_bn_ws(C, 1, dev)), ptr(bn_dw), ptr(bn_db), ptr(perm), ptr(seg_off), ptr(in_mean), ptr(in_invstd),
+             ptr(ws), ptr(coef), ptr(in_dw), ptr(in_db))
+        dx = torch.empty_like(x)
+        call("lidog_ibn_bwd_apply", ptr(dy), ptr(bits), ptr(x), n, C, B, ptr(bn_mean), ptr(bn_invstd), ptr(bn_w),
+             ptr(sums), float(n), ptr(bid), ptr(in_mean), ptr(in_invstd), ptr(in_w), ptr(coef), ptr(dx))
+        return dx, bn_dw, bn_db, in_dw, in_db, None, None, None, None, None, None
+
+
+def ibn_relu(bn_module, in_module, x):
+    """relu(cat(bn_module(x), in_module(x))) of the IBN block (minkunet_ibn.py:38-40; used by lidog_amd.minkunet when the
+    backend offers it): one fused pass each way for a training-mode, unsynchronised BatchNorm; every other case (eval
+    mode, SyncBatchNorm across ranks, shapes outside the float4 kernels) runs the literal composition of the operators"""
+    bn = bn_module.bn
+    f = x.F
+    n, C = f.shape
+    segs = x.coordinate_manager.segments(x.coordinate_map_key)
+    fused = (bn.training or not bn.track_running_stats) and bn.affine and bn_module._sync_group() is None and n > 0 \
+        and _in_vector_path(C, segs[3])
+    if not fused:
+        out = cat(bn_module(x), in_module(x))
+        return out._like(_ReLUFn.apply(out.F, True))
+    momentum = _training_momentum(bn)
+    return x._like(_IBNReluFn.apply(f, bn.weight, bn.bias, in_module.weight, in_module.bias, bn.running_mean,
+                                    bn.running_var, momentum, bn.eps, segs, IN_EPS))
 
 
 class MinkowskiReLU(nn.Module):

@@ -5,6 +5,8 @@ the reference models so reference checkpoints load unchanged:
 
   MinkUNet34BEV  utils/models/minkunet_bev.py:9-156 (layers), :302-399 (forward), :445-447
   MinkUNet34     utils/models/minkunet.py:23-95 (layers), :97-158 (forward), :171-174
+  MinkUNet34IBN  utils/models/minkunet_ibn.py:9-50 (IBNBlock), :53-206, :209-211; _make_layer and
+                 weight_initialization of utils/models/resnet_old.py:57-97
   BasicBlock     MinkowskiEngine.modules.resnet_block (evidence: utils/models/resnet_block.py:8-56)
 
 ``make_models(ME, Encoder2D, sparse2super)`` binds the wiring to an operator
@@ -32,10 +34,50 @@ def make_models(ME, Encoder2D=None, sparse2super=None):
     _fused = getattr(ME, "bn_relu", None)  # optional backend fast path: BN + ReLU in one kernel
     _conv_bn = getattr(ME, "conv_bn", None)
     _trunk_exec = getattr(ME, "trunk_forward", None)  # optional: the whole trunk as one launch sequence
+    _ibn = getattr(ME, "ibn_relu", None)  # optional: ReLU(BN(x)) | ReLU(IN(x)) in one pass each way
+
+    class IBNBlock(nn.Module):
+        """minkunet_ibn.py:9-50: conv1 -> (BatchNorm | InstanceNorm of the same output) -> cat -> ReLU -> conv2 (2 planes
+        -> planes) -> norm2 -> += downsample(x) -> ReLU"""
+        expansion = 1
+
+        def __init__(self, inplanes, planes, stride=1, dilation=1, downsample=None, bn_momentum=0.1, dimension=-1):
+            super().__init__()
+            assert dimension > 0
+            self.conv1 = ME.MinkowskiConvolution(inplanes, planes, kernel_size=3, stride=stride, dilation=dilation,
+                                                 dimension=dimension)
+            self.bn_norm1 = ME.MinkowskiBatchNorm(planes, momentum=bn_momentum)
+            self.in_norm1 = ME.MinkowskiInstanceNorm(planes)
+            self.conv2 = ME.MinkowskiConvolution(planes * 2, planes, kernel_size=3, stride=1, dilation=dilation,
+                                                 dimension=dimension)
+            self.norm2 = ME.MinkowskiBatchNorm(planes, momentum=bn_momentum)
+            self.relu = ME.MinkowskiReLU(inplace=True)
+            self.downsample = downsample
+
+        def forward(self, x):
+            residual = x
+            out = self.conv1(x)
+            if _ibn is not None:
+                out = _ibn(self.bn_norm1, self.in_norm1, out)
+            else:
+                out = self.relu(ME.cat(self.bn_norm1(out), self.in_norm1(out)))
+            if _conv_bn is not None:   # norm2 + residual + ReLU as one fused pass behind conv2 (as in BasicBlock)
+                if self.downsample is not None:
+                    residual = self.downsample(x)
+                return _conv_bn(self.conv2, self.norm2, out, relu=True, residual=residual)
+            out = self.norm2(self.conv2(out))
+            if self.downsample is not None:
+                residual = self.downsample(x)
+            out += residual
+            return self.relu(out)
 
     class _Trunk(nn.Module):
         BLOCK = BasicBlock
         LAYERS = LAYERS34
+        EXECUTOR = True     # the training-mode trunk may go to the executor (it knows BasicBlocks only)
+
+        def _stage_block(self, stage):
+            return self.BLOCK
 
         def _build_trunk(self, in_channels, out_channels, D, initial_kernel_size):
             self.D = D
@@ -47,7 +89,7 @@ def make_models(ME, Encoder2D=None, sparse2super=None):
                 setattr(self, f"conv{i}p{s}s2", ME.MinkowskiConvolution(self.inplanes, self.inplanes, kernel_size=2,
                                                                        stride=2, dimension=D))
                 setattr(self, f"bn{i}", ME.MinkowskiBatchNorm(self.inplanes))
-                setattr(self, f"block{i}", self._make_layer(PLANES[i - 1], self.LAYERS[i - 1]))
+                setattr(self, f"block{i}", self._make_layer(PLANES[i - 1], self.LAYERS[i - 1], self._stage_block(i)))
             skips = [PLANES[2], PLANES[1], PLANES[0], INIT_DIM]
             for (j, s), skip in zip(_DEC, skips):
                 setattr(self, f"convtr{j}p{s}s2", ME.MinkowskiConvolutionTranspose(self.inplanes, PLANES[j],
@@ -55,22 +97,21 @@ def make_models(ME, Encoder2D=None, sparse2super=None):
                                                                                   dimension=D))
                 setattr(self, f"bntr{j}", ME.MinkowskiBatchNorm(PLANES[j]))
                 self.inplanes = PLANES[j] + skip
-                setattr(self, f"block{j + 1}", self._make_layer(PLANES[j], self.LAYERS[j]))
+                setattr(self, f"block{j + 1}", self._make_layer(PLANES[j], self.LAYERS[j], self._stage_block(j + 1)))
             self.final = ME.MinkowskiConvolution(PLANES[7], out_channels, kernel_size=1, bias=True, dimension=D)
             self.relu = ME.MinkowskiReLU(inplace=True)
             self.dropout = ME.MinkowskiDropout(p=0.5)  # constructed, never called (minkunet_bev.py:126)
 
-        def _make_layer(self, planes, blocks):
+        def _make_layer(self, planes, blocks, block):
             downsample = None
             if self.inplanes != planes:
                 downsample = nn.Sequential(
                     ME.MinkowskiConvolution(self.inplanes, planes, kernel_size=1, stride=1, dimension=self.D),
                     ME.MinkowskiBatchNorm(planes))
-            layers = [self.BLOCK(self.inplanes, planes, stride=1, dilation=1, downsample=downsample,
-                                 dimension=self.D)]
+            layers = [block(self.inplanes, planes, stride=1, dilation=1, downsample=downsample, dimension=self.D)]
             self.inplanes = planes
             for _ in range(1, blocks):
-                layers.append(self.BLOCK(self.inplanes, planes, stride=1, dilation=1, dimension=self.D))
+                layers.append(block(self.inplanes, planes, stride=1, dilation=1, dimension=self.D))
             return nn.Sequential(*layers)
 
         def weight_initialization(self):
@@ -92,7 +133,7 @@ def make_models(ME, Encoder2D=None, sparse2super=None):
 
         def _trunk_forward(self, x):
             """returns (out_block8, out_bottle, {level: tensor}, classifier output or None = not computed yet)"""
-            if _trunk_exec is not None:
+            if _trunk_exec is not None and self.EXECUTOR:
                 done = _trunk_exec(self, x)
                 if done is not None:
                     return done
@@ -151,4 +192,24 @@ def make_models(ME, Encoder2D=None, sparse2super=None):
                 return seg, img_pred
             return seg, img_pred, bottle, None
 
-    return types.SimpleNamespace(MinkUNet34=MinkUNet34, MinkUNet34BEV=MinkUNet34BEV)
+    class MinkUNet34IBN(_Trunk):
+        """IBN-Net baseline (minkunet_ibn.py:209-211): IBN blocks in block1-3, BasicBlocks in block4-8.  The operator
+        path runs it (the trunk executor knows BasicBlocks only).  ResNetBase.__init__ drops initial_kernel_size, so
+        conv0p1s1 is always 5^3 (resnet_old.py via minkunet_ibn.py:68-69)."""
+        EXECUTOR = False
+
+        def __init__(self, in_channels, out_channels, D=3, initial_kernel_size=5):
+            super().__init__()
+            self._build_trunk(in_channels, out_channels, D, 5)
+            self.weight_initialization()
+
+        def _stage_block(self, stage):
+            return IBNBlock if stage <= 3 else BasicBlock
+
+        def forward(self, x, is_seg=True):
+            out, bottle, _, _ = self._trunk_forward(x)
+            seg = self.final(out)
+            return seg if is_seg else (seg, bottle)
+
+    return types.SimpleNamespace(MinkUNet34=MinkUNet34, MinkUNet34BEV=MinkUNet34BEV, MinkUNet34IBN=MinkUNet34IBN,
+                                 IBNBlock=IBNBlock)

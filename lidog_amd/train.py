@@ -56,7 +56,7 @@ def bev_image_size(bound_2d, voxel=0.05, pool=(5, 3, 1)):
 
 def build_model(kind="MinkUNet34BEV", bound_2d=50.0, in_channels=1, out_channels=7, conv1_kernel_size=5,
                 decoder_2d_levels=("block8",), device="cuda"):
-    """get_model of train_lidog.py:42-75 (MinkUNet34BEV) / train_source.py:43-58 (MinkUNet34)"""
+    """get_model of train_lidog.py:42-75 (MinkUNet34BEV) / train_source.py:43-58 (MinkUNet34, MinkUNet34IBN)"""
     import lidog_amd
     if kind == "MinkUNet34BEV":
         m = lidog_amd.MinkUNet34BEV(in_channels=in_channels, out_channels=out_channels, D=3,
@@ -65,6 +65,8 @@ def build_model(kind="MinkUNet34BEV", bound_2d=50.0, in_channels=1, out_channels
     elif kind == "MinkUNet34":
         m = lidog_amd.MinkUNet34(in_channels=in_channels, out_channels=out_channels, D=3,
                                  initial_kernel_size=conv1_kernel_size)
+    elif kind == "MinkUNet34IBN":   # train_source.py:49-53; ResNetBase drops the kernel size: conv0p1s1 is 5^3
+        m = lidog_amd.MinkUNet34IBN(in_channels=in_channels, out_channels=out_channels, D=3)
     else:
         raise NotImplementedError(kind)
     return m.to(device)
@@ -223,7 +225,7 @@ class Fit:
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--model", default="MinkUNet34BEV", choices=["MinkUNet34BEV", "MinkUNet34"])
+    ap.add_argument("--model", default="MinkUNet34BEV", choices=["MinkUNet34BEV", "MinkUNet34", "MinkUNet34IBN"])
     ap.add_argument("--bound", type=float, default=50.0)
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--optimizer", default="Adam", choices=["Adam", "SGD"])

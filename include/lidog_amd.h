@@ -645,6 +645,24 @@ int lidog_ibn_bwd_apply(const float *dy, const uint32_t *relu_bits, const float 
                         double bn_count, const int32_t *bid, const float *in_mean, const float *in_invstd,
                         const float *in_w, const float *in_coef, float *dx, void *stream);
 
+/* ------------------------------------------------------------------ instance-whitening loss (RobustNet)
+ * IWLoss (utils/losses/losses.py:464-485) of PLTRobustNet.training_step (trainer_lighting_robustnet.py) in closed form.
+ * For a map x [n, C] (float32, row-major; n >= 2): S = sum_i sum_k |x_ik| P_ik with P_ik = sum_{j<k} |x_ij|, and the
+ * reference's loss is L = S / (n (n - 1)) (pass w = 1 / (n (n - 1))).  Up to 8 maps per launch, any C; C % 4 == 0 and
+ * C <= 128 take the float4 kernels (16-byte aligned maps).  Sums in double, finished in a fixed order: no float
+ * atomics, the same bits on every run. */
+
+/* doubles of workspace lidog_iw_fwd needs (any M) */
+int64_t lidog_iw_ws(void);
+/* per_map [M] and total [1] (device, float32): per_map[m] = w[m] * S(x[m]), total = scale * sum_m per_map[m] (ascending m,
+ * in double).  x, n, C, w are HOST arrays of M entries; x[m] device pointers. */
+int lidog_iw_fwd(const float *const *x, const int64_t *n, const int32_t *C, const double *w, int32_t M, double scale,
+                 double *ws, float *total, float *per_map, void *stream);
+/* gx[m] [n_m, C_m] = sign(x) (P + Q) * gout[0] * scale * w[m], Q_ik = sum_{j>k} |x_ij| (reverse scan); gout is a
+ * device scalar (the gradient of total); gx HOST array of M device pointers. */
+int lidog_iw_bwd(const float *const *x, const int64_t *n, const int32_t *C, const double *w, int32_t M, double scale,
+                 const float *gout, float *const *gx, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,7 @@
 Public surface:
   lidog_amd.me            MinkowskiEngine-compatible operator API (HIP kernels via the C ABI)
   lidog_amd.bev           sparse2super + Encoder2D (fused BEV projection, MFMA 2-D head)
-  lidog_amd.MinkUNet34 / MinkUNet34BEV / MinkUNet34IBN    the reference models wired to those operators
+  lidog_amd.MinkUNet34 / MinkUNet34BEV / MinkUNet34IBN / MinkUNet34Robust   the reference models wired to those operators
   lidog_amd.losses        SoftDICELoss / DICELoss on the device
   lidog_amd.trainer       training step, Adam, RCCL data parallelism
   lidog_amd.trunk         the whole encoder-decoder as one launch sequence per pass (csrc/trunk.hip)
@@ -67,3 +67,4 @@ _models = make_models(me, bev.Encoder2D, bev.sparse2super)
 MinkUNet34 = _models.MinkUNet34
 MinkUNet34BEV = _models.MinkUNet34BEV
 MinkUNet34IBN = _models.MinkUNet34IBN
+MinkUNet34Robust = _models.MinkUNet34Robust

@@ -2,11 +2,15 @@
 
   SoftDICELoss  utils/losses/losses.py:100-109,129-187  (powerize, present-class mask, eps = 0.05)
   DICELoss      utils/losses/losses.py:56-97            (hard one-hot, no mask)
+  IWLoss        utils/losses/losses.py:464-485          (RobustNet's instance-whitening loss, csrc/iwloss.hip)
+  CovMatrix_IRW utils/models/cov_settings.py:4-25        (its eye / mask helper)
 Same formulas as the reference, as HIP kernels (csrc/losses.hip; there is no torch formula behind them: CPU tensors and
 unsupported class counts raise); the `.cpu()` round trips (losses.py:72-73,148-149) are gone, and rows carrying the
 ignore label are skipped in place instead of being compacted away with boolean indexing: the compaction needs the
 number of valid rows on the host, i.e. a device synchronisation in the middle of every step.
 """
+import ctypes
+
 import torch
 import torch.nn as nn
 
@@ -76,3 +80,98 @@ class DICELoss(nn.Module):
     def forward(self, output, target):
         _check(output)
         return _DiceFn.apply(output, target, self.ignore_label, 0.0, False, self.powerize, self.use_tmask, 0.0)
+
+
+# ------------------------------------------------------------------ instance-whitening loss (RobustNet)
+# IWLoss views a map [n, C] as [n, C, 1]: its "covariance" is one C x C outer product per ROW, over all rows of all scans
+# together, masked to the strict upper triangle, |.|-summed and divided by n (n - 1) (csrc/iwloss.hip has the closed
+# form).  n < 2 divides by zero in the reference; here it raises ValueError before any launch.  `margin` and
+# `num_remove_cov` of CovMatrix_IRW are unused, as in the reference.
+IW_MAX_MAPS = 8
+
+
+def _iw_args(maps):
+    M = len(maps)
+    xs = (ctypes.c_void_p * M)(*[m.data_ptr() for m in maps])
+    ns = (ctypes.c_int64 * M)(*[m.shape[0] for m in maps])
+    cs = (ctypes.c_int32 * M)(*[m.shape[1] for m in maps])
+    ws = (ctypes.c_double * M)(*[1.0 / (m.shape[0] * (m.shape[0] - 1.0)) for m in maps])
+    return xs, ns, cs, ws, M
+
+
+class _IWFn(torch.autograd.Function):
+    """csrc/iwloss.hip: every map in one launch each way; total = scale * sum_m L(map m), per-map L undifferentiated"""
+
+    @staticmethod
+    def forward(ctx, scale, *maps):
+        dev = maps[0].device
+        xs, ns, cs, ws, M = _iw_args(maps)
+        total = torch.empty((), dtype=torch.float32, device=dev)
+        per_map = torch.empty(M, dtype=torch.float32, device=dev)
+        wsp = torch.empty(_lib.load().lidog_iw_ws(), dtype=torch.float64, device=dev)
+        call("lidog_iw_fwd", xs, ns, cs, ws, M, float(scale), ptr(wsp), ptr(total), ptr(per_map))
+        ctx.save_for_backward(*maps)
+        ctx.scale = scale
+        ctx.mark_non_differentiable(per_map)
+        return total, per_map
+
+    @staticmethod
+    def backward(ctx, gout, _unused):
+        maps = ctx.saved_tensors
+        xs, ns, cs, ws, M = _iw_args(maps)
+        grads = [torch.empty_like(m) for m in maps]
+        gx = (ctypes.c_void_p * M)(*[g.data_ptr() for g in grads])
+        call("lidog_iw_bwd", xs, ns, cs, ws, M, float(ctx.scale), ptr(gout.contiguous()), gx)
+        return (None, *grads)
+
+
+def _iw_check(f_map):
+    _lib.require_gpu(f_map, "IWLoss feature map")
+    if f_map.dim() != 2 or f_map.dtype != torch.float32:
+        raise NotImplementedError(f"IWLoss takes float32 feature maps [n, C], got {tuple(f_map.shape)} {f_map.dtype}")
+    if f_map.shape[0] < 2:
+        raise ValueError(f"IWLoss needs n >= 2 rows (the reference divides by n - 1), got n = {f_map.shape[0]}")
+    if f_map.shape[1] < 1:
+        raise ValueError("IWLoss needs C >= 1 channels")
+    return f_map.contiguous()
+
+
+def iw_loss(maps, scale=None):
+    """(scale * sum_m IWLoss(maps[m]), per-map IWLoss values [M]) with one launch each way; scale defaults to 1 / M
+    (the mean of PLTRobustNet.training_step's aux loss).  Only the first output carries a gradient."""
+    maps = [_iw_check(m) for m in maps]
+    if not 1 <= len(maps) <= IW_MAX_MAPS:
+        raise ValueError(f"iw_loss takes 1 to {IW_MAX_MAPS} maps per launch, got {len(maps)}")
+    scale = 1.0 / len(maps) if scale is None else float(scale)
+    return _IWFn.apply(scale, *maps)
+
+
+class IWLoss(nn.Module):
+    """IWLoss (utils/losses/losses.py:464-485), reference call signature.  eye / mask_matrix must be what CovMatrix_IRW
+    gives (the identity -- or None -- and ones(C, C).triu(1)): any other mask raises.  margin and num_remove_cov are
+    unused, as in the reference."""
+
+    def forward(self, f_map, eye, mask_matrix, margin=None, num_remove_cov=None):
+        f = _iw_check(f_map)
+        C = f.shape[1]
+        want = torch.ones((C, C), dtype=mask_matrix.dtype, device=mask_matrix.device).triu(1)
+        if tuple(mask_matrix.shape) != (C, C) or not torch.equal(mask_matrix, want):
+            raise ValueError("IWLoss: the closed form needs mask_matrix = ones(C, C).triu(1) (CovMatrix_IRW's mask)")
+        return iw_loss([f], scale=1.0)[0]
+
+
+class CovMatrix_IRW:
+    """utils/models/cov_settings.py: (eye, strict upper-triangle mask, margin, number of off-diagonal entries) of a
+    feature map's channel count, on the map's device"""
+
+    def __init__(self, relax_denom=2.0):
+        self.relax_denom = relax_denom
+
+    def __call__(self, feats):
+        dim = feats.shape[1]
+        self.dim = dim
+        self.i = torch.eye(dim, dim, device=feats.device)
+        self.reversal_i = torch.ones((dim, dim), device=feats.device).triu(diagonal=1)
+        self.num_off_diagonal = torch.sum(self.reversal_i)
+        self.margin = 0 if self.relax_denom == 0 else self.num_off_diagonal // self.relax_denom
+        return self.i, self.reversal_i, self.margin, self.num_off_diagonal

@@ -1323,6 +1323,10 @@ class MinkowskiSyncBatchNorm(MinkowskiBatchNorm):
 # SURVEY.md 8(c)): parameters weight (ones) / bias (zeros) of shape [1, C]; per scan b and channel c the biased variance
 # over the rows of b; y = (x - mean) * (var + IN_EPS)^-1/2 * weight + bias; no running statistics (train = eval).
 IN_EPS = 1e-8
+# [ME-mem] MinkowskiReLU(inplace=True) of ME 0.5.4 applies torch.nn.ReLU(inplace=True) to input.F: a SparseTensor the
+# caller still holds sees the ReLU'd features.  RobustNet's aux maps depend on it (minkunet_robustnet.py:160-176):
+# out_in0 and the outputs of block1-3 reach the instance-whitening loss ReLU'd; out_in1 does not (that ReLU acts on
+# conv1p1s2's output).  MinkowskiReLU below honours `inplace` the same way (_ReLUFn, mark_dirty).
 
 
 def _in_param_shape(C):

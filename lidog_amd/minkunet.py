@@ -7,6 +7,7 @@ the reference models so reference checkpoints load unchanged:
   MinkUNet34     utils/models/minkunet.py:23-95 (layers), :97-158 (forward), :171-174
   MinkUNet34IBN  utils/models/minkunet_ibn.py:9-50 (IBNBlock), :53-206, :209-211; _make_layer and
                  weight_initialization of utils/models/resnet_old.py:57-97
+  MinkUNet34Robust  utils/models/minkunet_robustnet.py:9-53 (RobustBlock), :56-224 (layers, forward), :227-230
   BasicBlock     MinkowskiEngine.modules.resnet_block (evidence: utils/models/resnet_block.py:8-56)
 
 ``make_models(ME, Encoder2D, sparse2super)`` binds the wiring to an operator
@@ -70,6 +71,39 @@ def make_models(ME, Encoder2D=None, sparse2super=None):
                 residual = self.downsample(x)
             out += residual
             return self.relu(out)
+
+    class RobustBlock(nn.Module):
+        """minkunet_robustnet.py:9-53: conv1 -> norm1 (BN) -> ReLU -> conv2 -> norm2 -> += downsample(x) or x ->
+        in_norm1 (InstanceNorm); no ReLU at the end of the block (the caller applies one, in place)"""
+        expansion = 1
+
+        def __init__(self, inplanes, planes, stride=1, dilation=1, downsample=None, bn_momentum=0.1, dimension=-1):
+            super().__init__()
+            assert dimension > 0
+            self.conv1 = ME.MinkowskiConvolution(inplanes, planes, kernel_size=3, stride=stride, dilation=dilation,
+                                                 dimension=dimension)
+            self.in_norm1 = ME.MinkowskiInstanceNorm(planes)
+            self.norm1 = ME.MinkowskiBatchNorm(planes, momentum=bn_momentum)
+            self.conv2 = ME.MinkowskiConvolution(planes, planes, kernel_size=3, stride=1, dilation=dilation,
+                                                 dimension=dimension)
+            self.norm2 = ME.MinkowskiBatchNorm(planes, momentum=bn_momentum)
+            self.relu = ME.MinkowskiReLU(inplace=True)
+            self.downsample = downsample
+
+        def forward(self, x):
+            residual = x if self.downsample is None else None
+            if _conv_bn is not None:   # BN statistics from the convolutions' epilogues; norm2 + residual in one pass
+                out = _conv_bn(self.conv1, self.norm1, x, relu=True)
+                if self.downsample is not None:
+                    residual = self.downsample(x)
+                out = _conv_bn(self.conv2, self.norm2, out, relu=False, residual=residual)
+            else:
+                out = self.relu(self.norm1(self.conv1(x)))
+                out = self.norm2(self.conv2(out))
+                if self.downsample is not None:
+                    residual = self.downsample(x)
+                out += residual
+            return self.in_norm1(out)
 
     class _Trunk(nn.Module):
         BLOCK = BasicBlock
@@ -211,5 +245,75 @@ def make_models(ME, Encoder2D=None, sparse2super=None):
             seg = self.final(out)
             return seg if is_seg else (seg, bottle)
 
+    class MinkUNet34Robust(_Trunk):
+        """RobustNet baseline (minkunet_robustnet.py:227-230): instance norms in0 / in1 after conv0p1s1 / conv1p1s2,
+        RobustBlocks in block1-3, BasicBlocks in block4-8, the MinkUNet34 decoder.  The operator path runs it (the trunk
+        executor knows BasicBlocks only).  ResNetBase.__init__ drops initial_kernel_size, so conv0p1s1 is always 5^3.
+
+        forward(x, is_seg=False) returns (logits, (out_in0, out_in1, out_in1p2, out_in2p4, out_in3p8)), the maps of the
+        instance-whitening loss.  The reference passes out_in0 and the three block outputs to MinkowskiReLU(inplace=True)
+        afterwards, so the tuple holds them ReLU'd; its second ReLU acts on conv1p1s2's output, not on out_in1, which
+        therefore stays un-ReLU'd (the [ME-mem] convention next to lidog_amd.me.IN_EPS)."""
+        EXECUTOR = False
+
+        def __init__(self, in_channels, out_channels, D=3, initial_kernel_size=5):
+            super().__init__()
+            self.D = D
+            # minkunet_robustnet.py:68-158, in registration order (state_dict keys)
+            self.inplanes = INIT_DIM
+            self.conv0p1s1 = ME.MinkowskiConvolution(in_channels, INIT_DIM, kernel_size=5, dimension=D)
+            self.in0 = ME.MinkowskiInstanceNorm(INIT_DIM)
+            self.conv1p1s2 = ME.MinkowskiConvolution(INIT_DIM, INIT_DIM, kernel_size=2, stride=2, dimension=D)
+            self.in1 = ME.MinkowskiInstanceNorm(INIT_DIM)
+            self.block1 = self._make_layer(PLANES[0], self.LAYERS[0], RobustBlock)
+            for i, s in _ENC[1:]:
+                setattr(self, f"conv{i}p{s}s2", ME.MinkowskiConvolution(self.inplanes, self.inplanes, kernel_size=2,
+                                                                       stride=2, dimension=D))
+                setattr(self, f"bn{i}", ME.MinkowskiBatchNorm(self.inplanes))
+                setattr(self, f"block{i}", self._make_layer(PLANES[i - 1], self.LAYERS[i - 1],
+                                                            RobustBlock if i <= 3 else BasicBlock))
+            skips = [PLANES[2], PLANES[1], PLANES[0], INIT_DIM]
+            for (j, s), skip in zip(_DEC, skips):
+                setattr(self, f"convtr{j}p{s}s2", ME.MinkowskiConvolutionTranspose(self.inplanes, PLANES[j],
+                                                                                  kernel_size=2, stride=2,
+                                                                                  dimension=D))
+                setattr(self, f"bntr{j}", ME.MinkowskiBatchNorm(PLANES[j]))
+                self.inplanes = PLANES[j] + skip
+                setattr(self, f"block{j + 1}", self._make_layer(PLANES[j], self.LAYERS[j], BasicBlock))
+            self.final = ME.MinkowskiConvolution(PLANES[7], out_channels, kernel_size=1, bias=True, dimension=D)
+            self.relu = ME.MinkowskiReLU(inplace=True)
+            self.dropout = ME.MinkowskiDropout(p=0.5)  # constructed, never called
+            self.weight_initialization()
+
+        def forward(self, x, is_seg=True):
+            # minkunet_robustnet.py:160-224
+            out = self.conv0p1s1(x)
+            out_in0 = self.in0(out)
+            out_p1 = self.relu(out_in0)            # in place: out_in0 holds the ReLU'd features from here on
+            out = self.conv1p1s2(out_p1)
+            out_in1 = self.in1(out)
+            # the reference's in-place ReLU of conv1p1s2's output: out of place here, because in1 keeps that output
+            # for its backward pass (same values; out_in1 is not ReLU'd either way)
+            out = ME.MinkowskiReLU()(out)
+            out_in1p2 = self.block1(out)
+            out_b1p2 = self.relu(out_in1p2)
+            out = self._conv_bn_relu(self.conv2p2s2, self.bn2, out_b1p2)
+            out_in2p4 = self.block2(out)
+            out_b2p4 = self.relu(out_in2p4)
+            out = self._conv_bn_relu(self.conv3p4s2, self.bn3, out_b2p4)
+            out_in3p8 = self.block3(out)
+            out_b3p8 = self.relu(out_in3p8)
+            out = self._conv_bn_relu(self.conv4p8s2, self.bn4, out_b3p8)
+            out = self.block4(out)
+            skips = [out_p1, out_b1p2, out_b2p4, out_b3p8]
+            for j, s in _DEC:
+                out = self._conv_bn_relu(getattr(self, f"convtr{j}p{s}s2"), getattr(self, f"bntr{j}"), out)
+                out = ME.cat(out, skips.pop())
+                out = getattr(self, f"block{j + 1}")(out)
+            seg = self.final(out)
+            if is_seg:
+                return seg
+            return seg, (out_in0, out_in1, out_in1p2, out_in2p4, out_in3p8)
+
     return types.SimpleNamespace(MinkUNet34=MinkUNet34, MinkUNet34BEV=MinkUNet34BEV, MinkUNet34IBN=MinkUNet34IBN,
-                                 IBNBlock=IBNBlock)
+                                 IBNBlock=IBNBlock, MinkUNet34Robust=MinkUNet34Robust, RobustBlock=RobustBlock)

@@ -27,7 +27,7 @@ from . import synth
 from .checkpoint import load_training_checkpoint, save_lightning_checkpoint
 from .evaluate import per_class_iou
 from .optim import make_optimizer, make_scheduler, shard_indices
-from .trainer import LiDOGStep, SourceStep, setup_data_parallel
+from .trainer import LiDOGStep, RobustStep, SourceStep, setup_data_parallel
 
 
 class SynthScans:
@@ -56,7 +56,8 @@ def bev_image_size(bound_2d, voxel=0.05, pool=(5, 3, 1)):
 
 def build_model(kind="MinkUNet34BEV", bound_2d=50.0, in_channels=1, out_channels=7, conv1_kernel_size=5,
                 decoder_2d_levels=("block8",), device="cuda"):
-    """get_model of train_lidog.py:42-75 (MinkUNet34BEV) / train_source.py:43-58 (MinkUNet34, MinkUNet34IBN)"""
+    """get_model of train_lidog.py:42-75 (MinkUNet34BEV) / train_source.py:43-58 (MinkUNet34, MinkUNet34IBN,
+    MinkUNet34Robust)"""
     import lidog_amd
     if kind == "MinkUNet34BEV":
         m = lidog_amd.MinkUNet34BEV(in_channels=in_channels, out_channels=out_channels, D=3,
@@ -67,6 +68,8 @@ def build_model(kind="MinkUNet34BEV", bound_2d=50.0, in_channels=1, out_channels
                                  initial_kernel_size=conv1_kernel_size)
     elif kind == "MinkUNet34IBN":   # train_source.py:49-53; ResNetBase drops the kernel size: conv0p1s1 is 5^3
         m = lidog_amd.MinkUNet34IBN(in_channels=in_channels, out_channels=out_channels, D=3)
+    elif kind == "MinkUNet34Robust":   # the same: conv0p1s1 is 5^3
+        m = lidog_amd.MinkUNet34Robust(in_channels=in_channels, out_channels=out_channels, D=3)
     else:
         raise NotImplementedError(kind)
     return m.to(device)
@@ -75,7 +78,7 @@ def build_model(kind="MinkUNet34BEV", bound_2d=50.0, in_channels=1, out_channels
 def build_step(model, kind="MinkUNet34BEV", optimizer="Adam", lr=1e-3, scheduler=None, weight_decay=1e-4,
                momentum=0.98, warmup_epochs=0, source_weights=(0.5, 0.5), num_classes=7, ignore_label=-1):
     """SyncBN conversion when data-parallel (train_lidog.py:227-231), optimiser + scheduler
-    (trainer_lighting_2d.py:349-394), step object (PLTTrainer2D / PLTTrainer).  Returns (model, step, scheduler)."""
+    (trainer_lighting_2d.py:349-394), step object (PLTTrainer2D / PLTRobustNet / PLTTrainer).  Returns (model, step, scheduler)."""
     model = setup_data_parallel(model)
     model.train()
     opt = make_optimizer(optimizer, model, lr, weight_decay=weight_decay, momentum=momentum)
@@ -83,6 +86,8 @@ def build_step(model, kind="MinkUNet34BEV", optimizer="Adam", lr=1e-3, scheduler
     if kind == "MinkUNet34BEV":
         step = LiDOGStep(model, opt, source_weights=source_weights, warmup_epochs=warmup_epochs,
                          num_classes=num_classes, ignore_label=ignore_label)
+    elif kind == "MinkUNet34Robust":
+        step = RobustStep(model, opt, source_weights=source_weights, ignore_label=ignore_label)
     else:
         step = SourceStep(model, opt, ignore_label=ignore_label)
     return model, step, sched
@@ -225,7 +230,8 @@ class Fit:
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--model", default="MinkUNet34BEV", choices=["MinkUNet34BEV", "MinkUNet34", "MinkUNet34IBN"])
+    ap.add_argument("--model", default="MinkUNet34BEV", choices=["MinkUNet34BEV", "MinkUNet34", "MinkUNet34IBN",
+                                                                    "MinkUNet34Robust"])
     ap.add_argument("--bound", type=float, default=50.0)
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--optimizer", default="Adam", choices=["Adam", "SGD"])

@@ -4,9 +4,13 @@ import os, re
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P = os.path.join(R, "profiles")
 
-ROUND = {"r01": "round 1", "r02": "round 2", "r03": "round 3", "r04": "round 4", "r05": "round 5", "r06": "round 6"}
+ROUND = {"r01": "round 1", "r02": "round 2", "r03": "round 3", "r04": "round 4", "r05": "round 5", "r06": "round 6", "r07": "round 7"}
 # (regex on the name without the round / build prefix, what, DESIGN.md place)
 RULES = [
+    (r"ibn_bench\.jsonl$", "MinkUNet34 against MinkUNet34IBN training steps, same box, alternating (`scripts/bench_ibn.py`)", "§3i"),
+    (r"ibn_kernel_stats\.txt$", "per-kernel totals of the IBN step, `rocprofv3 --kernel-trace --stats`", "§3i"),
+    (r"robust_bench\.jsonl$", "instance-whitening loss fused against the literal bmm path (device time), MinkUNet34 against MinkUNet34Robust steps at epoch 5, alternating (`scripts/bench_robust.py`)", "§3j"),
+    (r"(ibn|robust)_bench_ab\.txt$", "`python bench.py` of the parent commit and this tree, same box, alternating", "§3i / §3j"),
     (r"kernel_stats_(train|bench)_bs\d(_one_stream|_dp1)?\.csv$", "per-kernel totals of 8 training steps, `rocprofv3 --kernel-trace --stats` over `scripts/prof_train.py` (`_one_stream`: weight gradients in line, `LIDOG_BACKWARD_OVERLAP=0`)", "§5, §8"),
     (r"kernel_breakdown_train_bs\d(_one_stream|_dp1)?\.txt$", "the same trace summed per kernel family (`scripts/kernel_breakdown.py`)", "§8"),
     (r"step_timeline(_one_stream|_dp1)?\.txt$", "dispatch timeline of the last profiled step, per stream (`scripts/step_timeline.py`)", "§8"),

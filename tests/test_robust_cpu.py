@@ -1,0 +1,171 @@
+"""MinkUNet34Robust and its instance-whitening loss without a GPU: the Robust wiring of lidog_amd.minkunet bound to the
+CPU oracle (+ the instance norm of tests/ibn_ref.py and the in-place ReLU of tests/robust_ref.py) reproduces G10; the
+product model's keys, shapes and size; the closed form of csrc/iwloss.hip against the literal bmm IWLoss in float64;
+the in-place ReLU convention; the driver's --model choices; the C ABI."""
+import ctypes
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from helpers import REPO, seeded_state_dict
+from ibn_ref import attach
+from robust_ref import G10, inplace_relu, iw_literal, step_losses
+
+
+def _oracle_robust():
+    import oracle.me_cpu as OME
+    from lidog_amd.minkunet import make_models
+    from oracle.ref_torch import Encoder2DRef
+    attach(OME)
+    OME.set_mode("exact")
+    return OME, make_models(OME, Encoder2DRef, None).MinkUNet34Robust
+
+
+def test_g10_was_recorded_with_the_inplace_relu_substitution():
+    g10 = np.load(G10)
+    assert bool(g10["inplace_relu"])
+    # out_in0 and the block1-3 outputs reach the loss ReLU'd; out_in1 does not (its ReLU acts on conv1p1s2's output)
+    mins = g10["aux_min"]
+    assert mins[0] == 0 and mins[2] == 0 and mins[3] == 0 and mins[4] == 0 and mins[1] < 0
+    # the per-map values of the reference's own IWLoss equal the literal restatement of tests/robust_ref.py
+    assert np.allclose(g10["iw"], g10["iw_ref"], rtol=1e-6, atol=0)
+    assert abs(float(g10["aux"]) - float(np.mean(g10["iw"]))) <= 1e-6 * float(g10["aux"])
+    assert abs(float(g10["total"]) - 0.5 * float(g10["sem"]) - 0.5 * float(g10["aux"])) <= 1e-6
+
+
+def test_robust_wiring_on_the_oracle_reproduces_g10():
+    g10 = np.load(G10)
+    OME, cls = _oracle_robust()
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)   # the fixture was recorded on one thread (BatchNorm sums follow the thread split)
+    try:
+        with inplace_relu(OME):
+            model = cls(1, 7, 3)
+            assert list(model.state_dict().keys()) == list(g10["keys"])
+            model.load_state_dict(seeded_state_dict(model, seed=7))
+            model.train()
+            coords = torch.from_numpy(g10["coords"])
+            with torch.no_grad():
+                out, maps = model(OME.SparseTensor(coordinates=coords, features=torch.ones((coords.shape[0], 1))),
+                                  is_seg=False)
+                sem, per, aux, total = step_losses(out, maps, torch.from_numpy(g10["labels"]))
+    finally:
+        torch.set_num_threads(threads)
+    d = (out.F - torch.from_numpy(g10["logits"])).abs().max().item()
+    assert d <= 5e-5, d
+    assert abs(float(sem) - float(g10["sem"])) <= 1e-5
+    assert np.allclose([float(p) for p in per], g10["iw"], rtol=1e-4, atol=0)
+    assert abs(float(total) - float(g10["total"])) <= 1e-5
+    assert [float(m.F.min()) >= 0 for m in maps] == [True, False, True, True, True]
+
+
+def test_product_model_has_the_reference_keys_shapes_and_size():
+    import lidog_amd
+    g10 = np.load(G10)
+    m = lidog_amd.MinkUNet34Robust(1, 7, 3)
+    sd = m.state_dict()
+    assert list(sd) == list(g10["keys"])
+    for t, s in zip(sd.values(), g10["shapes"]):
+        assert list(t.shape) == [int(v) for v in s[:t.dim()]] and not any(s[t.dim():])
+    assert sum(p.numel() for p in m.parameters()) == 37848327 == int(g10["n_params"])
+    assert len(sd) == 386 and sd["in0.weight"].shape == (1, 32) and sd["block3.0.in_norm1.weight"].shape == (1, 128)
+    assert m.conv0p1s1.kernel.shape[0] == 125     # initial_kernel_size is dropped (ResNetBase): always 5^3
+    assert not m.EXECUTOR
+
+
+def _closed_form(x):
+    """csrc/iwloss.hip's formulas in float64: (L, dL/dx), P an exclusive prefix, Q an exclusive reverse scan of |x|"""
+    n = x.shape[0]
+    a = x.abs()
+    P = torch.cat([torch.zeros_like(a[:, :1]), torch.cumsum(a, 1)[:, :-1]], 1)
+    Q = torch.cat([torch.flip(torch.cumsum(torch.flip(a, [1]), 1), [1])[:, 1:], torch.zeros_like(a[:, :1])], 1)
+    w = 1.0 / (n * (n - 1.0))
+    return (a * P).sum() * w, torch.sign(x) * (P + Q) * w
+
+
+def _rows(kind, n, C, g):
+    x = torch.randn((n, C), generator=g, dtype=torch.float64)
+    if kind == "sparse":
+        x[torch.rand((n, C), generator=g) < 0.6] = 0
+        x[::3] = 0
+    elif kind == "negative":
+        x = -x.abs() - 0.1
+    elif kind == "dominant":
+        x *= 1e-3
+        x[:, C // 2] = 1e4
+    return x
+
+
+@pytest.mark.parametrize("kind", ["random", "sparse", "negative", "dominant"])
+@pytest.mark.parametrize("n,C", [(2, 3), (7, 7), (50, 32), (33, 12)])
+def test_closed_form_equals_the_literal_bmm_iwloss_in_float64(kind, n, C):
+    g = torch.Generator().manual_seed(n * 131 + C)
+    x = _rows(kind, n, C, g)
+    xl = x.clone().requires_grad_(True)
+    lit = iw_literal(xl)
+    lit.backward()
+    L, dx = _closed_form(x)
+    lit = float(lit.detach())
+    assert abs(float(L) - lit) <= 1e-12 * max(lit, 1e-300)
+    assert torch.allclose(dx, xl.grad, rtol=1e-10, atol=1e-300)
+
+
+def test_inplace_relu_convention():
+    """MinkowskiReLU(inplace=True) modifies the features a caller still holds: on the product operators (which need no
+    GPU to construct) by contract, and on the oracle only inside robust_ref.inplace_relu"""
+    import lidog_amd.me as ME
+    import oracle.me_cpu as OME
+    assert ME.MinkowskiReLU(inplace=True).inplace
+    src = open(os.path.join(REPO, "lidog_amd", "me.py")).read()
+    assert "IN_EPS" in src and "torch.nn.ReLU(inplace=True)" in src
+    own = OME.MinkowskiReLU
+    f = torch.tensor([[-1.0, 2.0], [3.0, -4.0]])
+    with inplace_relu(OME):
+        x = OME.SparseTensor(coordinates=torch.tensor([[0, 0, 0, 0], [0, 1, 0, 0]], dtype=torch.int32), features=f)
+        OME.MinkowskiReLU(inplace=True)(x)
+        assert float(x.F.min()) == 0.0
+    assert OME.MinkowskiReLU is own
+    x = OME.SparseTensor(coordinates=torch.tensor([[0, 0, 0, 0], [0, 1, 0, 0]], dtype=torch.int32),
+                         features=torch.tensor([[-1.0, 2.0], [3.0, -4.0]]))
+    OME.MinkowskiReLU(inplace=True)(x)
+    assert float(x.F.min()) == -4.0     # the oracle's own ReLU never works in place
+
+
+def test_convert_sync_batchnorm_leaves_instance_norms_alone():
+    import lidog_amd
+    import lidog_amd.me as ME
+    m = ME.MinkowskiSyncBatchNorm.convert_sync_batchnorm(lidog_amd.MinkUNet34Robust(1, 7, 3))
+    mods = list(m.modules())
+    ins = [x for x in mods if isinstance(x, ME.MinkowskiInstanceNorm)]
+    assert len(ins) == 2 + 2 + 3 + 4 and not any(isinstance(x, ME.MinkowskiBatchNorm) for x in ins)
+    assert not any(type(x) is ME.MinkowskiBatchNorm for x in mods)
+
+
+def test_cov_matrix_irw_gives_the_reference_eye_and_mask():
+    from lidog_amd.losses import CovMatrix_IRW
+    eye, mask, margin, num = CovMatrix_IRW(relax_denom=2.0)(torch.zeros((5, 4)))
+    assert torch.equal(eye, torch.eye(4)) and torch.equal(mask, torch.ones(4, 4).triu(1))
+    assert float(num) == 6 and float(margin) == 3
+
+
+def test_train_help_lists_the_robust_model():
+    out = subprocess.run([sys.executable, "-B", "-m", "lidog_amd.train", "--help"], capture_output=True, text=True,
+                         cwd=REPO, env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"))
+    assert out.returncode == 0 and "MinkUNet34Robust" in out.stdout, out.stderr[-2000:]
+
+
+def test_iw_entries_in_header_binding_and_exports():
+    from lidog_amd import _lib, build
+    lib = ctypes.CDLL(build.build())
+    header = open(os.path.join(REPO, "include", "lidog_amd.h")).read()
+    mine = set(re.findall(r"\b(lidog_iw_[a-z0-9_]+)\s*\(", header))
+    assert mine == {"lidog_iw_ws", "lidog_iw_fwd", "lidog_iw_bwd"}
+    for name in mine:
+        assert hasattr(lib, name) and name in _lib.SIGNATURES
+    assert lib.lidog_abi_version() == _lib.ABI_VERSION == 8
+    assert "iwloss.hip" in build.SOURCES

@@ -384,6 +384,11 @@ int lidog_adam_step(float *param, const float *grad, float *exp_avg, float *exp_
                     void *stream);
 /* torch.optim.SGD(lr, momentum=0.98, weight_decay, nesterov=True) of trainer_lighting_2d.py:351-355 (and
  * trainer_lighting.py:337-341) on a slice of the flat buffers; momentum_buf starts at zero. */
+/* dst[i] = dst[i] + src[i] (plain fp32 adds) over n_segs segments; segs [n_segs][3] HOST int64: dst, src (device
+ * addresses), element count.  Up to 8 segments per launch; float4 where dst and src share their alignment mod 16, scalar
+ * elsewhere.  The trunk executor's accumulate mode (convolution table column 19) adds its second pass's parameter
+ * gradients into the optimiser's flat buffer with it. */
+int lidog_grad_accumulate(const int64_t *segs, int32_t n_segs, void *stream);
 int lidog_sgd_step(float *param, const float *grad, float *momentum_buf, int64_t n, float lr, float momentum,
                    float weight_decay, int32_t nesterov, float grad_scale, void *stream);
 
@@ -517,7 +522,10 @@ int64_t lidog_wgrad_items_host(const int64_t *k_off_host, int32_t K, int64_t chu
  *         stem through the neighbour table), map row, C_in, C_out, K, W [K,C_in,C_out], Wt [K,C_out,C_in] or 0
  *         (transposed here), gW, bias or 0, g_bias or 0, BatchNorm weight, bias, running_mean, running_var, g_weight,
  *         g_bias (0 for a convolution without BatchNorm), weight-gradient work items, their count, item_off
- *         (lidog_sconv_wgrad), 0;   conv_f [n_convs][2]: BatchNorm eps, momentum
+ *         (lidog_sconv_wgrad), accumulate (0: the parameter gradients are WRITTEN to gW / g_bias / g_weight / g_bias;
+ *         1: they are computed into garena and ADDED to those slices by lidog_grad_accumulate -- the kernel gradient on
+ *         the stream of its weight-gradient kernel, the others on `stream` -- before the convolution's parameters are
+ *         counted down; backward only);   conv_f [n_convs][2]: BatchNorm eps, momentum
  *   maps  [n_maps][16]: K, n_in, n_out, pairs, pair_in, pair_out, row_ptr / row_list of the output rows, of the input
  *         rows (lidog_kernel_map_rows; 0 where unused), tile descriptors [3][n_tiles], n_tiles, neighbour table
  *         (stem) or 0, identity rows 0..n-1 (1x1) or 0

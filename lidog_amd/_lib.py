@@ -142,6 +142,7 @@ SIGNATURES = {
     "lidog_iw_ws": [],
     "lidog_iw_fwd": [_p, _p, _p, _p, _i32, _d, _p, _p, _p, _p],
     "lidog_iw_bwd": [_p, _p, _p, _p, _i32, _d, _p, _p, _p],
+    "lidog_grad_accumulate": [_p, _i32, _p],
 }
 _RESTYPES = {"lidog_hash_capacity": _i64, "lidog_sconv_reduce_stats_ws": _i64, "lidog_bn_reduce_ws": _i64,
              "lidog_dice_ws": _i64, "lidog_colsum_ws": _i64, "lidog_conv2d_support_ws": _i64, "lidog_conv2d_wgrad_sparse_ws": _i64,

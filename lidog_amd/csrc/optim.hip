@@ -30,3 +30,76 @@ extern "C" int lidog_sgd_step(float *param, const float *grad, float *momentum_b
     LIDOG_LAUNCH_CHECK();
     return 0;
 }
+
+// Gradient accumulation of the trunk executor's second pass over one model in one step (lidog_amd/trunk.py, csrc/
+// trunk.hip accumulate mode): dst[i] = dst[i] + src[i] over up to ACC_SEGS (dst, src, n) segments per launch.  Plain fp32
+// adds, so the result has the bits of autograd's `grad += new` whichever of the two passes wrote dst.  A segment is
+// walked as a scalar head up to dst's first 16-byte boundary, float4 body, scalar tail (a bias of 7); a src whose
+// alignment differs from dst's takes the scalar loop throughout.
+namespace {
+constexpr int ACC_SEGS = 8;
+struct AccSegs {
+    float *dst[ACC_SEGS];
+    const float *src[ACC_SEGS];
+    int64_t n[ACC_SEGS];
+    int64_t block0[ACC_SEGS + 1];   // first workgroup of every segment; block0[nseg] = grid size
+    int32_t nseg;
+};
+}  // namespace
+
+__global__ __launch_bounds__(256) void k_grad_accumulate(AccSegs a) {
+    int s = 0;
+    while (s + 1 < a.nseg && (int64_t)blockIdx.x >= a.block0[s + 1]) ++s;
+    float *__restrict__ dst = a.dst[s];
+    const float *__restrict__ src = a.src[s];
+    const int64_t n = a.n[s];
+    const int64_t t = ((int64_t)blockIdx.x - a.block0[s]) * 256 + threadIdx.x;
+    const int64_t stride = (a.block0[s + 1] - a.block0[s]) * 256;
+    if ((((uintptr_t)dst ^ (uintptr_t)src) & 15) != 0) {
+        for (int64_t i = t; i < n; i += stride) dst[i] = dst[i] + src[i];
+        return;
+    }
+    int64_t head = (int64_t)(((16 - ((uintptr_t)dst & 15)) & 15) >> 2);
+    if (head > n) head = n;
+    const int64_t body = (n - head) >> 2, tail0 = head + 4 * body;
+    if (t < head) dst[t] = dst[t] + src[t];
+    float4 *__restrict__ d4 = (float4 *)(dst + head);
+    const float4 *__restrict__ s4 = (const float4 *)(src + head);
+    for (int64_t i = t; i < body; i += stride) {
+        float4 x = d4[i];
+        const float4 y = s4[i];
+        x.x = x.x + y.x;
+        x.y = x.y + y.y;
+        x.z = x.z + y.z;
+        x.w = x.w + y.w;
+        d4[i] = x;
+    }
+    if (t < n - tail0) dst[tail0 + t] = dst[tail0 + t] + src[tail0 + t];
+}
+
+extern "C" int lidog_grad_accumulate(const int64_t *segs, int32_t n_segs, void *stream) {
+    LIDOG_REQUIRE(n_segs >= 0 && (segs || n_segs == 0), "grad_accumulate: bad segment table");
+    for (int32_t s0 = 0; s0 < n_segs; s0 += ACC_SEGS) {
+        AccSegs a;
+        a.nseg = 0;
+        int64_t blocks = 0;
+        for (int32_t s = s0; s < n_segs && s < s0 + ACC_SEGS; ++s) {
+            const int64_t *g = segs + 3 * (int64_t)s;
+            LIDOG_REQUIRE(g[2] >= 0 && ((g[0] && g[1]) || g[2] == 0), "grad_accumulate: segment %d is malformed", s);
+            if (g[2] == 0) continue;
+            int64_t nb = cdiv64(g[2], 1024);     // one float4 per thread
+            if (nb > 4096) nb = 4096;
+            a.dst[a.nseg] = (float *)(uintptr_t)g[0];
+            a.src[a.nseg] = (const float *)(uintptr_t)g[1];
+            a.n[a.nseg] = g[2];
+            a.block0[a.nseg] = blocks;
+            blocks += nb;
+            ++a.nseg;
+        }
+        if (a.nseg == 0) continue;
+        a.block0[a.nseg] = blocks;
+        k_grad_accumulate<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(a);
+        LIDOG_LAUNCH_CHECK();
+    }
+    return 0;
+}

@@ -24,7 +24,7 @@ namespace {
 
 // ---- table layouts (int64 rows; python fills them as numpy arrays, lidog_amd/trunk.py)
 enum { TC_KIND, TC_MAP, TC_CIN, TC_COUT, TC_K, TC_W, TC_WT, TC_GW, TC_BIAS, TC_GBIAS, TC_BNW, TC_BNB, TC_BNRM, TC_BNRV,
-       TC_GBNW, TC_GBNB, TC_ITEMS, TC_NITEMS, TC_ITEMOFF, TC_COLS = 20 };
+       TC_GBNW, TC_GBNB, TC_ITEMS, TC_NITEMS, TC_ITEMOFF, TC_ACC, TC_COLS = 20 };
 enum { TM_K, TM_NIN, TM_NOUT, TM_P, TM_PAIR_IN, TM_PAIR_OUT, TM_RP_OUT, TM_RL_OUT, TM_RP_IN, TM_RL_IN, TM_TILES,
        TM_NTILES, TM_NBR, TM_IDENT, TM_PERM, TM_WMASK, TM_ORDER, TM_COLS = 20 };
 enum { TO_TYPE, TO_CONV, TO_IN, TO_OUT, TO_RELU, TO_RES, TO_FOLD, TO_B, TO_COLS = 8 };
@@ -780,7 +780,41 @@ extern "C" int lidog_trunk_backward(const int64_t *convs, const double *conv_f, 
     // Gradient buckets watch the launch stream and the lane only; that covers a side op's parameter gradients when the
     // launch stream has waited for its reduction (SyncBatchNorm), not otherwise (local BatchNorm + buckets: in line).
     // Same kernels, same arguments: same bits.
-    const bool side_on = g_side_backward && lane && (sync || !dp.buckets());
+    // Accumulate mode (TC_ACC, the second backward pass over a model called twice before one backward: the optimiser's
+    // slices already hold the first pass's gradients): this pass's parameter gradients go to garena and one
+    // lidog_grad_accumulate per convolution and stream adds them into the slices -- the kernel gradient behind its
+    // weight-gradient kernel on the lane (which, in stream order, also holds whatever the first pass still writes there),
+    // bias and BatchNorm gradients on the launch stream -- before param_done counts the convolution down.  No side
+    // branch then: its BatchNorm gradients would be added on a third stream the buckets do not watch.
+    bool accumulate = false;
+    for (int i = 0; i < n_convs; ++i) accumulate = accumulate || convs[(int64_t)i * TC_COLS + TC_ACC] != 0;
+    std::vector<float *> acc_src((size_t)n_convs * 4, nullptr);
+    auto grad_out = [&](int64_t conv, int slot, int col, int64_t count) -> float * {
+        const int64_t *cc = convs + conv * TC_COLS;
+        if (!cc[TC_ACC]) return P<float>(cc[col]);
+        float *&p = acc_src[conv * 4 + slot];
+        if (!p) {   // the same alignment mod 16 as the destination: the float4 path of the add applies to both
+            char *b = (char *)ga.take(count * 4 + 16);
+            p = (float *)(b + (((uintptr_t)cc[col] - (uintptr_t)b) & 15));
+        }
+        return p;
+    };
+    std::vector<int64_t> acc_segs;
+    auto add_seg = [&](int64_t conv, int slot, int col, int64_t count) {
+        const int64_t *cc = convs + conv * TC_COLS;
+        const float *src = acc_src[conv * 4 + slot];
+        if (!src) return;
+        acc_segs.push_back(cc[col]);
+        acc_segs.push_back((int64_t)(uintptr_t)src);
+        acc_segs.push_back(count);
+    };
+    auto flush_segs = [&](void *st) -> int {
+        if (acc_segs.empty() || ctx.dry) { acc_segs.clear(); return 0; }
+        const int rc = lidog_grad_accumulate(acc_segs.data(), (int32_t)(acc_segs.size() / 3), st);
+        acc_segs.clear();
+        return rc;
+    };
+    const bool side_on = g_side_backward && lane && (sync || !dp.buckets()) && !accumulate;
     hipStream_t side_st = nullptr;
     hipEvent_t *side_ev = nullptr;
     int n_side = 0;
@@ -854,8 +888,9 @@ extern "C" int lidog_trunk_backward(const int64_t *convs, const double *conv_f, 
                 sums = (double *)scp->take((2 * Cout + 1) * 8);
                 int64_t wsn = lidog_bn_reduce_ws(Cout, 1);
                 double *ws = wsn ? (double *)scp->take(wsn * 8) : nullptr;
+                float *g_w = grad_out(op[TO_CONV], 2, TC_GBNW, Cout), *g_b = grad_out(op[TO_CONV], 3, TC_GBNB, Cout);
                 TRY(lidog_bn_bwd_reduce_bits(gout, pre, ymask, mbits, n, Cout, 1, mean, invstd, sums, ws, (double)n,
-                                                 P<float>(c[TC_GBNW]), P<float>(c[TC_GBNB]), mask_from_x ? bnw : nullptr,
+                                                 g_w, g_b, mask_from_x ? bnw : nullptr,
                                                  mask_from_x ? bnb : nullptr, cur));
             }
             float *dx = (float *)ga.take(n * Cout * 4);
@@ -920,6 +955,7 @@ extern "C" int lidog_trunk_backward(const int64_t *convs, const double *conv_f, 
             g_out = P<const int32_t>(m[TM_PAIR_OUT]);
         }
         bool wgrad_done = false;
+        void *wgrad_st = cur;
         auto queue_wgrad = [&]() -> int {
             wgrad_done = true;
             const int n_items = (int)c[TC_NITEMS];
@@ -940,13 +976,15 @@ extern "C" int lidog_trunk_backward(const int64_t *convs, const double *conv_f, 
             } else {
                 partial = (float *)scp->take(pbytes);
             }
+            float *gw_out = grad_out(op[TO_CONV], 0, TC_GW, (int64_t)K * Cin * Cout);
+            wgrad_st = st;
             if (in_bn.pre)
                 TRY(lidog_sconv_wgrad_in_bn(in_bn.pre, g_in, gout, g_out, P<const int32_t>(c[TC_ITEMS]), n_items,
-                                            P<const int32_t>(c[TC_ITEMOFF]), K, Cin, Cout, partial, P<float>(c[TC_GW]),
+                                            P<const int32_t>(c[TC_ITEMOFF]), K, Cin, Cout, partial, gw_out,
                                             in_bn.mean, in_bn.invstd, in_bn.w, in_bn.b, 1, st));
             else
             TRY(lidog_sconv_wgrad(x, g_in, gout, g_out, P<const int32_t>(c[TC_ITEMS]), n_items,
-                                  P<const int32_t>(c[TC_ITEMOFF]), K, Cin, Cout, partial, P<float>(c[TC_GW]), st));
+                                  P<const int32_t>(c[TC_ITEMOFF]), K, Cin, Cout, partial, gw_out, st));
             if (g_timing && !ctx.dry && Cin % 32 == 0 && Cout % 32 == 0) {
                 g_work[0] += 1;
                 g_work[1] += 4.0 * (double)m[TM_P] * (Cin + Cout) + 4.0 * (double)Cin * Cout * (K + 2.0 * (slabs > 1 ? slabs : 1));
@@ -1038,11 +1076,12 @@ extern "C" int lidog_trunk_backward(const int64_t *convs, const double *conv_f, 
                     const float *p_y = (p_relu && !p_from_x && !pr[REC_BITS]) ? bp[in_b] : nullptr;
                     double *sums = (double *)ga.take((2 * Cin + 1) * 8);   // lives until the producer's turn
                     double *ws = (double *)sc.take(lidog_bn_reduce_ws(Cin, 1) * 8);
+                    float *pg_w = grad_out(pop[TO_CONV], 2, TC_GBNW, Cin), *pg_b = grad_out(pop[TO_CONV], 3, TC_GBNB, Cin);
                     TRY(lidog_sconv_reduce_rows_bwdstats(T, rp, rl, n_in, Cin, folds ? gp[in_b] : nullptr, gx, p_pre,
                                                               p_y, p_bits, p_mean, p_invstd,
                                                               p_from_x ? P<const float>(pc[TC_BNW]) : nullptr,
                                                               p_from_x ? P<const float>(pc[TC_BNB]) : nullptr, sums, ws,
-                                                              (double)n_in, P<float>(pc[TC_GBNW]), P<float>(pc[TC_GBNB]),
+                                                              (double)n_in, pg_w, pg_b,
                                                               stream));
                     bwd_sums[po] = sums;
                     gp[in_b] = gx;
@@ -1067,7 +1106,8 @@ extern "C" int lidog_trunk_backward(const int64_t *convs, const double *conv_f, 
             if (int rc = queue_wgrad()) return rc;
         if (c[TC_BIAS] && c[TC_GBIAS]) {
             double *ws = (double *)scp->take(lidog_colsum_ws(Cout) * 8);
-            TRY(lidog_colsum(gout, n, Cout, P<float>(c[TC_GBIAS]), ws, cur));
+            float *g_bias = grad_out(op[TO_CONV], 1, TC_GBIAS, Cout);
+            TRY(lidog_colsum(gout, n, Cout, g_bias, ws, cur));
         }
         if (side_op) {
             if (!ctx.dry && !join_evt[in_b]) {   // no data gradient was asked for: still order the parameter gradients
@@ -1075,6 +1115,17 @@ extern "C" int lidog_trunk_backward(const int64_t *convs, const double *conv_f, 
                 LIDOG_CHECK_HIP(hipEventRecord(side_last, side_st));
             }
             ++n_side;
+        }
+        if (c[TC_ACC]) {   // accumulate mode: add this convolution's gradients into the optimiser's slices
+            add_seg(op[TO_CONV], 0, TC_GW, (int64_t)K * Cin * Cout);
+            if (wgrad_st != cur)
+                if (int rc = flush_segs(wgrad_st)) return rc;
+            if (c[TC_BIAS] && c[TC_GBIAS]) add_seg(op[TO_CONV], 1, TC_GBIAS, Cout);
+            if (op[TO_TYPE] == OP_CONVBN) {
+                add_seg(op[TO_CONV], 2, TC_GBNW, Cout);
+                add_seg(op[TO_CONV], 3, TC_GBNB, Cout);
+            }
+            if (int rc = flush_segs(cur)) return rc;
         }
         // every parameter gradient of this convolution is queued now (kernel: lane or launch stream; bias and BatchNorm
         // gains / biases: launch stream)

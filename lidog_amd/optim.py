@@ -96,7 +96,12 @@ class GradientBuckets:
     one layer.  `own_communicator=True` gives the buckets a communicator of their own (`dist.new_group`) and removes
     that coupling; it is not the default because two communicators in flight at once could not be exercised on more
     than one rank in this build's environment, and a same-communicator schedule is identical on every rank by
-    construction."""
+    construction.
+
+    Uses per step: a model called on two sources before one backward pass (trainer_lighting_2d_multi.py:166-167) uses
+    every parameter twice.  `set_uses(2)` (the two-source step objects) makes a bucket wait for 2 x its parameters: the
+    trunk executor counts a parameter down once per backward pass over it (in C), autograd's post-accumulate hook fires
+    once per parameter after every use has been summed and counts what the executor did not (`c_uses`)."""
 
     single_rank = False   # test hook: bucket and all-reduce even in a one-rank process group
 
@@ -111,6 +116,7 @@ class GradientBuckets:
         self.pending0 = []
         self.slices = []
         self.issued_early = 0     # buckets reduced while backward was still being queued (hook or trunk executor)
+        self.uses = 1             # uses of every parameter per step (set_uses)
         self.transport = None
         # LIDOG_DP_SAFE=1 (bench.py's fallback after a hung N > 1 run): no bucket leaves before backward has ended; finish()
         # reduces them one after the other on the compute stream through torch.distributed -- no bucket stream, no
@@ -138,6 +144,8 @@ class GradientBuckets:
         # countdown per bucket, shared with the trunk executor (csrc/trunk.hip counts the trunk's parameters down in C
         # and reduces a bucket itself when it reaches 0): a host int32 array, not a list
         self.pending = np.array(self.pending0, dtype=np.int32)
+        # per parameter: backward passes of this step that the trunk executor counted down in C
+        self.c_uses = np.zeros(len(flat.params), dtype=np.int32)
         self.slice_table = np.array(self.slices, dtype=np.int64).reshape(-1, 2)
         for p in flat.params:
             p.register_post_accumulate_grad_hook(self._hook)
@@ -151,14 +159,29 @@ class GradientBuckets:
         for p in members:
             self.bucket_of[id(p)] = b
 
+    def set_uses(self, uses):
+        """how many times the model uses each parameter before one backward pass (1 or 2); call between steps"""
+        if uses not in (1, 2):
+            raise NotImplementedError(f"{uses} uses per step")
+        if uses == self.uses:
+            return
+        self.uses = uses
+        if self.active:
+            self.pending[:] = np.array(self.pending0, dtype=np.int32) * uses
+            self.c_uses[:] = 0
+
     def _hook(self, p):
-        off = self.flat.offsets[self.index_of[id(p)]]
+        i = self.index_of[id(p)]
+        off = self.flat.offsets[i]
         if not self.flat.in_place(p, off):   # stray gradient: bring it into the flat buffer before it is reduced
             view = self.flat.grad[off:off + p.numel()].view(p.shape)
             view.copy_(p.grad)
             p.grad = view
         b = self.bucket_of[id(p)]
-        self.pending[b] -= 1
+        left = self.uses - int(self.c_uses[i])     # autograd summed every use it saw before this hook
+        if left <= 0:
+            return
+        self.pending[b] -= left
         if self.pending[b] == 0:
             self.issued_early += 1
             self._reduce(b)
@@ -195,7 +218,7 @@ class GradientBuckets:
             # the current stream
             for lo, hi in self.slices:
                 dist.all_reduce(self.flat.grad[lo:hi], group=self.group)
-            self.pending[:] = self.pending0
+            self._reset()
             return
         for b, left in enumerate(self.pending.tolist()):
             if left > 0:
@@ -205,7 +228,11 @@ class GradientBuckets:
         self.handles = []
         if self.transport.bucket_kind == "native":
             torch.cuda.current_stream(self.flat.grad.device).wait_stream(self.transport.stream)
-        self.pending[:] = self.pending0
+        self._reset()
+
+    def _reset(self):
+        self.pending[:] = np.array(self.pending0, dtype=np.int32) * self.uses
+        self.c_uses[:] = 0
 
     def executor_tables(self, params_by_slot):
         """int32 [n, 4] bucket of each (kernel, bias, BatchNorm weight, BatchNorm bias) of the trunk's convolutions,

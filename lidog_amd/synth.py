@@ -83,8 +83,27 @@ def mix3d_voxels(seed, config="nusc35k"):
     return vox[first], lab[first]
 
 
-def make_batch(seeds, config="kitti120k", device="cpu", bev_size=167, mix3d=False):
-    """Collated batch with the keys of CollateFNSingleSourceBEVMultiLevel (collation.py:318-325)."""
+# scan seeds of a batch's second source start here (make_batch(seeds1=...)): the same configuration on both sources, as
+# in the reference's single-dataset configs (['Synth4D-kitti', 'Synth4D-kitti']), still gives two different sets of scans
+SOURCE1_SEED = 1 << 20
+
+
+def make_batch(seeds, config="kitti120k", device="cpu", bev_size=167, mix3d=False, seeds1=None, config1=None):
+    """Collated batch with the keys of CollateFNSingleSourceBEVMultiLevel (collation.py:318-325).
+    `seeds1`: scan indices of a second source (configuration `config1`, default `config`; scan seed SOURCE1_SEED +
+    index): adds the `source_*1` keys of CollateFNMultiSourceBEVMultiLevel (collation.py:328-418) and `coords_int1`."""
+    coords, labels, bev, feats = _collate(seeds, config, device, bev_size, mix3d)
+    batch = {"source_coordinates0": coords.float(), "source_features0": feats, "source_sem_labels0": labels,
+             "source_bev_labels0": {"block8": bev}, "coords_int": coords}
+    if seeds1 is not None:
+        coords, labels, bev, feats = _collate([SOURCE1_SEED + int(s) for s in seeds1], config1 or config, device,
+                                              bev_size, mix3d)
+        batch.update({"source_coordinates1": coords.float(), "source_features1": feats, "source_sem_labels1": labels,
+                      "source_bev_labels1": {"block8": bev}, "coords_int1": coords})
+    return batch
+
+
+def _collate(seeds, config, device, bev_size, mix3d):
     coords, labels = [], []
     for b, s in enumerate(seeds):
         v, l = (mix3d_voxels if mix3d else scan_voxels)(s, config)
@@ -96,5 +115,4 @@ def make_batch(seeds, config="kitti120k", device="cpu", bev_size=167, mix3d=Fals
     rng = np.random.default_rng(1000003 + int(seeds[0]))
     bev = torch.from_numpy(rng.integers(-1, 7, (len(seeds), bev_size, bev_size))).long().to(device)
     feats = torch.ones((coords.shape[0], 1), dtype=torch.float32, device=device)
-    return {"source_coordinates0": coords.float(), "source_features0": feats, "source_sem_labels0": labels,
-            "source_bev_labels0": {"block8": bev}, "coords_int": coords}
+    return coords, labels, bev, feats

@@ -10,6 +10,7 @@ What the reference's entry scripts do through pytorch-lightning, as plain argume
 
     python -m lidog_amd.train --model MinkUNet34BEV --epochs 2 --scans 16 --batch 4 --save-dir /tmp/run
     python -m torch.distributed.run --nproc-per-node N -m lidog_amd.train ...        (one process per GPU, RCCL)
+    python -m lidog_amd.train --sources kitti120k nusc35k --source-weights 0.5 0.5 ...   (two sources, */multi/*.yaml)
 
 Scans are synthetic (lidog_amd.synth; there are no datasets on the box); anything with `__len__` and
 `batch(indices, device) -> dict` (keys of CollateFNSingleSourceBEVMultiLevel, collation.py:318-325) can be passed as
@@ -19,6 +20,7 @@ import argparse
 import os
 import re
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -27,7 +29,8 @@ from . import synth
 from .checkpoint import load_training_checkpoint, save_lightning_checkpoint
 from .evaluate import per_class_iou
 from .optim import make_optimizer, make_scheduler, shard_indices
-from .trainer import LiDOGStep, RobustStep, SourceStep, setup_data_parallel
+from .trainer import (LiDOGMultiStep, LiDOGStep, RobustMultiStep, RobustStep, SourceMultiStep, SourceStep,
+                      setup_data_parallel)
 
 
 class SynthScans:
@@ -42,6 +45,44 @@ class SynthScans:
     def batch(self, indices, device):
         return synth.make_batch([self.first + i for i in indices], self.config, device, bev_size=self.bev_size,
                                 mix3d=self.mix3d)
+
+
+class MultiSynthScans:
+    """Two sources paired as MultiBEVSourceDataset (utils/datasets/synth4d_bev.py:682-772): the length is the larger of
+    the two; item i takes scan i of source 0 and scan perm[i] of source 1 (perm: a permutation of source 1 shuffled once
+    at construction); an index past a source's end takes a random scan of that source.  The permutation and the random
+    draws come from `seed` (the run's seed): the same seed gives the same pairs in the same order.  Source 1's scans
+    have their own seed range (synth.SOURCE1_SEED), so one configuration on both sources gives two sets of scans."""
+
+    num_sources = 2
+
+    def __init__(self, n0, n1, configs=("kitti120k", "nusc35k"), seed=1234, first=0, mix3d=False, bev_size=167):
+        if len(configs) != 2:
+            raise NotImplementedError(f"{len(configs)} sources (the reference takes one or two)")
+        self.n = (int(n0), int(n1))
+        self.configs, self.first, self.mix3d, self.bev_size = tuple(configs), first, mix3d, bev_size
+        rng = np.random.default_rng([int(seed), 2])
+        self.perm1 = rng.permutation(self.n[1])
+        self._draws = np.random.default_rng([int(seed), 3])
+
+    def __len__(self):
+        return max(self.n)
+
+    def pair(self, i):
+        """(index into source 0, index into source 1) of item i"""
+        j0 = i if i < self.n[0] else int(self._draws.integers(0, self.n[0]))
+        j1 = int(self.perm1[i]) if i < self.n[1] else int(self._draws.integers(0, self.n[1]))
+        return j0, j1
+
+    def batch(self, indices, device):
+        pairs = [self.pair(i) for i in indices]
+        return synth.make_batch([self.first + a for a, _ in pairs], self.configs[0], device, bev_size=self.bev_size,
+                                mix3d=self.mix3d, seeds1=[self.first + b for _, b in pairs], config1=self.configs[1])
+
+
+def source_names(configs):
+    """keys of the per-source validation results: the configuration names, made unique by their position"""
+    return [c if list(configs).count(c) == 1 else f"{c}:{i}" for i, c in enumerate(configs)]
 
 
 def bev_image_size(bound_2d, voxel=0.05, pool=(5, 3, 1)):
@@ -76,14 +117,25 @@ def build_model(kind="MinkUNet34BEV", bound_2d=50.0, in_channels=1, out_channels
 
 
 def build_step(model, kind="MinkUNet34BEV", optimizer="Adam", lr=1e-3, scheduler=None, weight_decay=1e-4,
-               momentum=0.98, warmup_epochs=0, source_weights=(0.5, 0.5), num_classes=7, ignore_label=-1):
+               momentum=0.98, warmup_epochs=0, source_weights=(0.5, 0.5), num_classes=7, ignore_label=-1, num_sources=1):
     """SyncBN conversion when data-parallel (train_lidog.py:227-231), optimiser + scheduler
-    (trainer_lighting_2d.py:349-394), step object (PLTTrainer2D / PLTRobustNet / PLTTrainer).  Returns (model, step, scheduler)."""
+    (trainer_lighting_2d.py:349-394), step object (PLTTrainer2D / PLTRobustNet / PLTTrainer, or their two-source
+    versions for num_sources=2).  Returns (model, step, scheduler)."""
+    if num_sources not in (1, 2):
+        raise NotImplementedError(f"{num_sources} sources (the reference takes one or two)")
     model = setup_data_parallel(model)
     model.train()
     opt = make_optimizer(optimizer, model, lr, weight_decay=weight_decay, momentum=momentum)
     sched = make_scheduler(scheduler, opt)
-    if kind == "MinkUNet34BEV":
+    if num_sources == 2:
+        if kind == "MinkUNet34BEV":
+            step = LiDOGMultiStep(model, opt, source_weights=source_weights, warmup_epochs=warmup_epochs,
+                                  num_classes=num_classes, ignore_label=ignore_label)
+        elif kind == "MinkUNet34Robust":
+            step = RobustMultiStep(model, opt, source_weights=source_weights, ignore_label=ignore_label)
+        else:
+            step = SourceMultiStep(model, opt, source_weights=source_weights, ignore_label=ignore_label)
+    elif kind == "MinkUNet34BEV":
         step = LiDOGStep(model, opt, source_weights=source_weights, warmup_epochs=warmup_epochs,
                          num_classes=num_classes, ignore_label=ignore_label)
     elif kind == "MinkUNet34Robust":
@@ -118,7 +170,10 @@ class Fit:
                  scheduler=None, epochs=25, warmup_epochs=0, source_weights=(0.5, 0.5), weight_decay=1e-4,
                  momentum=0.98, check_val_every_n_epoch=5, num_sanity_val_steps=2, save_dir=None, seed=1234,
                  train_data=None, val_data=None, shuffle=True, resume=None, auto_resume=False, prefetch=True,
-                 device="cuda", log=None, state_dict=None):
+                 device="cuda", log=None, state_dict=None, num_sources=None):
+        """`train_data` with `num_sources = 2` (MultiSynthScans) trains on two sources; `val_data` may then be a dict
+        {source name: dataset}: every source is validated on its own (the list of loaders of train_lidog.py:186-190),
+        the results keyed by name"""
         self.rank, self.world = _rank_world()
         self.kind, self.batch_size, self.epochs = model_kind, batch_size, epochs
         self.check_val, self.sanity = check_val_every_n_epoch, num_sanity_val_steps
@@ -131,8 +186,11 @@ class Fit:
         model = build_model(model_kind, bound_2d, device=device)
         if state_dict is not None:
             model.load_state_dict(state_dict)
+        if num_sources is None:
+            num_sources = getattr(self.train_data, "num_sources", 1)
         self.model, self.step, self.sched = build_step(
-            model, model_kind, optimizer, lr, scheduler, weight_decay, momentum, warmup_epochs, source_weights)
+            model, model_kind, optimizer, lr, scheduler, weight_decay, momentum, warmup_epochs, source_weights,
+            num_sources=num_sources)
         self.opt = self.step.opt
         self.epoch, self.global_step = 0, 0
         self.history = []
@@ -168,9 +226,14 @@ class Fit:
     def validate(self, epoch, limit=None):
         if self.val_data is None:
             return None
+        if isinstance(self.val_data, dict):    # one validation set per source (validation_step's dataloader_idx)
+            return {name: self._validate(data, epoch, limit) for name, data in self.val_data.items()}
+        return self._validate(self.val_data, epoch, limit)
+
+    def _validate(self, data, epoch, limit=None):
         res = []
-        for ids in self._epoch_batches(self.val_data, 0, False)[:limit]:
-            res.append(self.validation_step(self.val_data.batch(ids, self.device)))
+        for ids in self._epoch_batches(data, 0, False)[:limit]:
+            res.append(self.validation_step(data.batch(ids, self.device)))
         if not res:
             return None
         out = {"epoch": epoch, "sem_loss": sum(r["sem_loss"] for r in res) / len(res),
@@ -228,7 +291,7 @@ class Fit:
         return self.history
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--model", default="MinkUNet34BEV", choices=["MinkUNet34BEV", "MinkUNet34", "MinkUNet34IBN",
                                                                     "MinkUNet34Robust"])
@@ -242,13 +305,28 @@ def main(argv=None):
     ap.add_argument("--scans", type=int, default=16, help="synthetic training scans per epoch (all ranks together)")
     ap.add_argument("--val-scans", type=int, default=0)
     ap.add_argument("--config", default="kitti120k", choices=sorted(synth.CONFIGS))
+    ap.add_argument("--sources", nargs=2, default=None, choices=sorted(synth.CONFIGS), metavar="CONFIG",
+                    help="train on two sources (configs/*/multi/*.yaml): --scans scans of each, paired as "
+                         "MultiBEVSourceDataset; each source is validated on its own")
+    ap.add_argument("--source-weights", nargs=2, type=float, default=(0.5, 0.5))
     ap.add_argument("--mix3d", action="store_true")
     ap.add_argument("--check-val-every-n-epoch", type=int, default=5)
     ap.add_argument("--save-dir", default=None)
     ap.add_argument("--resume", default=None)
     ap.add_argument("--auto-resume", action="store_true")
     ap.add_argument("--seed", type=int, default=1234)
-    a = ap.parse_args(argv)
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    fit = _fit_from_args(a)
+    fit.run()
+    _finish_distributed()
+
+
+def _fit_from_args(a):
+    """the Fit of parsed command-line arguments (process group set up when launched as several ranks)"""
     world = int(os.environ.get("WORLD_SIZE", 1))
     local = int(os.environ.get("LOCAL_RANK", 0))
     torch.cuda.set_device(local)
@@ -256,12 +334,21 @@ def main(argv=None):
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))
     bev = bev_image_size(a.bound)
-    fit = Fit(a.model, a.bound, a.batch, a.optimizer, a.lr, a.scheduler, a.epochs, a.warmup_epochs,
-              check_val_every_n_epoch=a.check_val_every_n_epoch, save_dir=a.save_dir, seed=a.seed,
-              train_data=SynthScans(a.scans, a.config, mix3d=a.mix3d, bev_size=bev),
-              val_data=SynthScans(a.val_scans, a.config, first=10 ** 6, mix3d=a.mix3d, bev_size=bev) if a.val_scans else None,
-              resume=a.resume, auto_resume=a.auto_resume)
-    fit.run()
+    if a.sources:
+        train = MultiSynthScans(a.scans, a.scans, a.sources, seed=a.seed, mix3d=a.mix3d, bev_size=bev)
+        val = {name: SynthScans(a.val_scans, c, first=10 ** 6 + i * synth.SOURCE1_SEED, mix3d=a.mix3d, bev_size=bev)
+               for i, (name, c) in enumerate(zip(source_names(a.sources), a.sources))} if a.val_scans else None
+    else:
+        train = SynthScans(a.scans, a.config, mix3d=a.mix3d, bev_size=bev)
+        val = SynthScans(a.val_scans, a.config, first=10 ** 6, mix3d=a.mix3d, bev_size=bev) if a.val_scans else None
+    return Fit(a.model, a.bound, a.batch, a.optimizer, a.lr, a.scheduler, a.epochs, a.warmup_epochs,
+               source_weights=tuple(a.source_weights), check_val_every_n_epoch=a.check_val_every_n_epoch,
+               save_dir=a.save_dir, seed=a.seed, train_data=train, val_data=val, resume=a.resume,
+               auto_resume=a.auto_resume)
+
+
+def _finish_distributed():
+    world = int(os.environ.get("WORLD_SIZE", 1))
     if world > 1:
         dist.barrier()
         torch.cuda.synchronize()

@@ -5,6 +5,8 @@ box never receives):
   training_step        utils/pipelines/trainer_lighting_2d.py:141-201  (PLTTrainer2D)
                        utils/pipelines/trainer_lighting.py:92-104      (PLTTrainer, source-only)
                        utils/pipelines/trainer_lighting_robustnet.py    (PLTRobustNet, one source)
+  two sources          utils/pipelines/trainer_lighting_2d_multi.py:135-215 (PLTTrainer2DMulti), trainer_lighting.py:92-116,
+                       trainer_lighting_robustnet.py:96-150: the *MultiStep classes below
   configure_optimizers utils/pipelines/trainer_lighting_2d.py:349-394  (Adam lr, weight_decay 1e-4)
   DDP + SyncBN         train_lidog.py:227-231,286-289                   (strategy='ddp')
 
@@ -51,6 +53,55 @@ class _CoordinatePrefetch:
             coords = prefetch["coords_int"]
             self.__dict__.setdefault("_prepared", {})[id(coords)] = \
                 (coords, ME.CoordinateManager.prepare(coords, self._trace, prefetch_ready))
+
+
+class _TwoSourcePrefetch(_CoordinatePrefetch):
+    """_CoordinatePrefetch for batches with a second source (`source_*1`, `coords_int1`): the model is called on source 0
+    and then on source 1; the trace recorded by the first call prepares the coordinate maps of BOTH inputs of the next
+    batch.  The optimiser's gradient buckets expect two uses of every parameter (GradientBuckets.set_uses)."""
+
+    def _sparse_input_of(self, batch, s):
+        key = "coords_int" if s == 0 else "coords_int1"
+        coords = batch[key] if key in batch else batch[f"source_coordinates{s}"].int()
+        hit = self.__dict__.setdefault("_prepared", {}).pop(id(coords), None)
+        feats = batch[f"source_features{s}"]
+        if hit is not None and hit[0] is coords:
+            st = ME.SparseTensor(features=feats, coordinates=coords, coordinate_manager=hit[1])
+        else:
+            st = ME.SparseTensor(coordinates=coords, features=feats)
+        if s == 0:
+            self._last_manager = st.coordinate_manager
+        return st
+
+    def _after_step_two(self, prefetch, prefetch_ready):
+        self._trace = self._last_manager.trace
+        if prefetch is None:
+            return
+        for key in ("coords_int", "coords_int1"):
+            if key in prefetch:
+                coords = prefetch[key]
+                self.__dict__.setdefault("_prepared", {})[id(coords)] = \
+                    (coords, ME.CoordinateManager.prepare(coords, self._trace, prefetch_ready))
+
+    def _two_uses(self):
+        buckets = getattr(self.opt, "buckets", None)
+        if buckets is not None:
+            buckets.set_uses(2)
+
+    def training_step(self, batch, epoch=0, prefetch=None, prefetch_ready=None):
+        """one optimiser step on both sources: the two forward passes (BatchNorm statistics move twice, source 0 first),
+        ONE backward pass, one step.  Returns the detached total and per-source losses."""
+        self._two_uses()
+        out = self.forward_loss(batch, epoch)
+        total = out["loss"]
+        self.opt.zero_grad()
+        total.backward()
+        self.opt.step()
+        self._after_step_two(prefetch, prefetch_ready)
+        _check_transport(self)
+        return {k: (v.detach() if torch.is_tensor(v) else v) for k, v in out.items() if k not in self._not_returned}
+
+    _not_returned = ("outputs",)
 
 
 _PEER_CHECK_EVERY = int(_os.environ.get("LIDOG_PEER_CHECK_EVERY", "200"))
@@ -164,3 +215,64 @@ def setup_data_parallel(model):
     if dist.is_initialized() and (dist.get_world_size() > 1 or ME.MinkowskiSyncBatchNorm.single_rank):
         model = ME.MinkowskiSyncBatchNorm.convert_sync_batchnorm(model)
     return model
+
+
+class LiDOGMultiStep(_TwoSourcePrefetch, LiDOGStep):
+    """PLTTrainer2DMulti.training_step (trainer_lighting_2d_multi.py:135-215): the model on source 0, then on source 1;
+    per source the BEV loss is the mean over levels of DICE on .view(-1, C) (:176-189);
+    after warm-up  total = w0 * (sem0 + bev0) + w1 * (sem1 + bev1)   (:191-197),
+    during warm-up total = w0 * bev0 + w1 * bev1                     (:198-205)."""
+
+    def forward_loss(self, batch, epoch=0):
+        outs = [self.model(self._sparse_input_of(batch, s), is_train=True) for s in (0, 1)]
+        bev_l, sem_l = [], []
+        for s, (sem, bev) in enumerate(outs):
+            loss = 0.0
+            for key, lab in batch[f"source_bev_labels{s}"].items():
+                loss = loss + self.bev_criterion(bev[key].view(-1, self.nc), lab.view(-1)) / len(bev)
+            bev_l.append(loss)
+        if epoch >= self.warmup:
+            sem_l = [self.sem_criterion(outs[s][0].F, batch[f"source_sem_labels{s}"].long()) for s in (0, 1)]
+            total = self.w[0] * (sem_l[0] + bev_l[0]) + self.w[1] * (sem_l[1] + bev_l[1])
+        else:
+            sem_l = [torch.zeros((), device=outs[s][0].F.device) for s in (0, 1)]
+            total = self.w[0] * bev_l[0] + self.w[1] * bev_l[1]
+        self.last_paths = tuple(type(o[0].F.grad_fn).__name__ for o in outs)
+        self.last_path = self.last_paths[0]
+        return {"loss": total, "sem_loss0": sem_l[0], "bev_loss0": bev_l[0], "sem_loss1": sem_l[1],
+                "bev_loss1": bev_l[1], "outputs": [o[0] for o in outs]}
+
+
+class SourceMultiStep(_TwoSourcePrefetch, SourceStep):
+    """PLTTrainer.training_step with two sources (trainer_lighting.py:92-116; MinkUNet34 and MinkUNet34IBN):
+    total = w0 * sem0 + w1 * sem1."""
+
+    def __init__(self, model, optimizer, source_weights=(0.5, 0.5), ignore_label=-1):
+        super().__init__(model, optimizer, ignore_label=ignore_label)
+        self.w = source_weights
+
+    def forward_loss(self, batch, epoch=0):
+        outs = [self.model(self._sparse_input_of(batch, s), is_seg=True) for s in (0, 1)]
+        sem_l = [self.criterion(outs[s].F, batch[f"source_sem_labels{s}"].long()) for s in (0, 1)]
+        total = self.w[0] * sem_l[0] + self.w[1] * sem_l[1]
+        self.last_paths = tuple(type(o.F.grad_fn).__name__ for o in outs)
+        return {"loss": total, "sem_loss0": sem_l[0], "sem_loss1": sem_l[1], "outputs": outs}
+
+
+class RobustMultiStep(_TwoSourcePrefetch, RobustStep):
+    """PLTRobustNet.training_step with two sources (trainer_lighting_robustnet.py:96-150):
+    total = w0 * sem0 + w1 * sem1 + 0.5 * (aux0 + aux1), aux_s the mean IWLoss of source s's five aux maps from epoch
+    `aux_epoch` (5) on -- one iw_loss launch per source and direction (at most 8 maps per launch) -- else zero."""
+
+    def forward_loss(self, batch, epoch=0):
+        outs = [self.model(self._sparse_input_of(batch, s), is_seg=False) for s in (0, 1)]
+        sem_l = [self.criterion(outs[s][0].F, batch[f"source_sem_labels{s}"].long()) for s in (0, 1)]
+        total = self.w[0] * sem_l[0] + self.w[1] * sem_l[1]
+        if epoch >= self.aux_epoch:
+            aux_l = [iw_loss([m.F for m in outs[s][1]])[0] for s in (0, 1)]
+            total = total + 0.5 * (aux_l[0] + aux_l[1])
+        else:
+            aux_l = [torch.zeros((), device=outs[s][0].F.device) for s in (0, 1)]
+        self.last_paths = tuple(type(o[0].F.grad_fn).__name__ for o in outs)
+        return {"loss": total, "sem_loss0": sem_l[0], "sem_loss1": sem_l[1], "aux_loss0": aux_l[0],
+                "aux_loss1": aux_l[1], "outputs": [o[0] for o in outs]}

@@ -23,6 +23,9 @@ from . import _lib, me as ME
 from ._lib import call, call_on
 
 ENABLED = os.environ.get("LIDOG_TRUNK_EXEC", "1") != "0"
+# the second backward pass over a model called twice before one backward adds its parameter gradients into the flat
+# buffer on the device (accumulate mode, lidog_grad_accumulate); 0 = hand them back to autograd as fresh tensors
+ACCUMULATE = os.environ.get("LIDOG_TRUNK_ACCUMULATE", "1") != "0"
 if "LIDOG_TRUNK_FUSIONS" in os.environ:     # A/B runs: bit mask of the executor's fusions (see set_fusions)
     _lib.load().lidog_trunk_fusions(int(os.environ["LIDOG_TRUNK_FUSIONS"]))
 
@@ -30,7 +33,7 @@ KIND_K3, KIND_DOWN, KIND_UP, KIND_1X1, KIND_STEM = range(5)
 OP_CONVBN, OP_CAT, OP_CONV = range(3)
 TC_COLS, TM_COLS, TO_COLS, TB_COLS, REC_COLS = 20, 20, 8, 4, 4
 (TC_KIND, TC_MAP, TC_CIN, TC_COUT, TC_K, TC_W, TC_WT, TC_GW, TC_BIAS, TC_GBIAS, TC_BNW, TC_BNB, TC_BNRM, TC_BNRV,
- TC_GBNW, TC_GBNB, TC_ITEMS, TC_NITEMS, TC_ITEMOFF) = range(19)
+ TC_GBNW, TC_GBNB, TC_ITEMS, TC_NITEMS, TC_ITEMOFF, TC_ACC) = range(20)
 # external buffers: the input features and the tensors the model hands back
 EXT_X, EXT_OUT, EXT_LOGITS, EXT_BOTTLE, EXT_LV_BOTTLE, EXT_LV_BLOCK6, EXT_LV_BLOCK7 = range(7)
 N_EXT = 7
@@ -41,6 +44,14 @@ def set_enabled(on):
     """trunk executor on / off (off: every step goes through the operator path)"""
     global ENABLED
     ENABLED = bool(on)
+
+
+def set_accumulate(on):
+    """accumulate mode of the second backward pass over one model in one step on (True) / off (autograd accumulates);
+    returns the previous setting"""
+    global ACCUMULATE
+    prev, ACCUMULATE = ACCUMULATE, bool(on)
+    return prev
 
 
 def set_fusions(mask):
@@ -401,8 +412,10 @@ class _Collectives:
         cached = prog.__dict__.get("_param_bucket")
         if cached is None or cached[0] is not buckets:
             by_slot = [[prog.params[s] if s >= 0 else None for s in slot] for slot in prog.slots]
-            cached = prog._param_bucket = (buckets, buckets.executor_tables(by_slot))
-        self.param_bucket = cached[1]
+            flat_idx = np.array([[buckets.index_of[id(p)] if p is not None else -1 for p in slot] for slot in by_slot],
+                                dtype=np.int64)
+            cached = prog._param_bucket = (buckets, buckets.executor_tables(by_slot), flat_idx)
+        self.param_bucket, self.flat_idx = cached[1], cached[2]
         d[DP_N_BUCKETS] = len(buckets.slices)
         d[DP_BUCKETS] = buckets.slice_table.ctypes.data
         d[DP_PENDING] = buckets.pending.ctypes.data
@@ -519,18 +532,26 @@ class _TrunkFn(torch.autograd.Function):
         # model is called twice before one backward pass (trainer_lighting_2d_multi.py:166-167) the pass that runs
         # second computes into fresh tensors and autograd accumulates; this call has joined the lane by then.
         flat = _flat_targets(prog)
-        direct = False
+        direct = accumulate = False
         if flat is not None:
             gen = flat[0].generation
             direct = all(p.grad is None and p._flat_taken != gen for p in prog.params)
             if direct:
                 for p in prog.params:
                     p._flat_taken = gen
-        if direct:
+                prog._direct_gen = (flat[0], gen)
+            elif ACCUMULATE:
+                # every slice was handed out earlier in this generation (the first backward pass over the model's other
+                # call: this executor directly, or the operator path through me._grad_out) and holds that pass's gradient
+                # or zeros: this pass adds its own on the device (csrc/trunk.hip, TC_ACC)
+                accumulate = all(p._flat_taken == gen and (p.grad is None or p.grad.data_ptr() == v.data_ptr())
+                                 for p, v in zip(prog.params, flat[2]))
+        if direct or accumulate:
             # the common case: every gradient goes straight into the flat buffer through views made once; they are
             # bound to .grad below, by hand (188 AccumulateGrad nodes would only do the same assignment)
             views = flat[2]
             convs[:, [TC_GW, TC_GBIAS, TC_GBNW, TC_GBNB]] = flat[1]
+            convs[:, TC_ACC] = 1 if accumulate else 0
         else:
             views, fresh = [None] * len(prog.params), []
             for i, p in enumerate(prog.params):
@@ -560,7 +581,8 @@ class _TrunkFn(torch.autograd.Function):
         # Data-parallel gradient buckets (lidog_amd.optim.GradientBuckets): with every gradient going straight into the
         # flat buffer the countdown of the trunk's parameters runs in C and a bucket is reduced as soon as its last
         # gradient is queued; otherwise the gradients go back through autograd and the parameters' hooks count.
-        buckets = flat[0].buckets if (direct and flat[0].buckets is not None and flat[0].buckets.active) else None
+        buckets = flat[0].buckets if ((direct or accumulate) and flat[0].buckets is not None and
+                                      flat[0].buckets.active) else None
         coll = run.coll
         if buckets is not None and coll is None:
             coll = run.coll = _Collectives(run, None)
@@ -594,6 +616,20 @@ class _TrunkFn(torch.autograd.Function):
         run.done = True
         grads = [None] * len(prog.params)
         params = prog.params
+        if buckets is not None:    # what C counted down (GradientBuckets._hook counts the rest)
+            idx = coll.flat_idx[done.astype(bool)]
+            buckets.c_uses[idx[idx >= 0]] += 1
+        if accumulate:
+            # the gradients are in the flat buffer.  A slice the operator path handed out is bound to .grad by autograd
+            # (its node returned the view); one the direct pass did not reach (no gradient there) is bound here
+            first_direct = getattr(prog, "_direct_gen", None)
+            first_direct = first_direct is not None and first_direct[0] is flat[0] and first_direct[1] == gen
+            for ci, slot in enumerate(prog.slots):
+                if done[ci] and first_direct:
+                    for s in slot:
+                        if s >= 0 and params[s].grad is None:
+                            params[s].grad = views[s]
+            return (None, None, *grads)
         # without bucket tables in C the gradients of a hooked optimiser go back through autograd so that the hooks fire
         bind = direct and (buckets is not None or not flat[0].hooked)
         for ci, slot in enumerate(prog.slots):

@@ -11,6 +11,9 @@ RULES = [
     (r"ibn_kernel_stats\.txt$", "per-kernel totals of the IBN step, `rocprofv3 --kernel-trace --stats`", "§3i"),
     (r"robust_bench\.jsonl$", "instance-whitening loss fused against the literal bmm path (device time), MinkUNet34 against MinkUNet34Robust steps at epoch 5, alternating (`scripts/bench_robust.py`)", "§3j"),
     (r"(ibn|robust)_bench_ab\.txt$", "`python bench.py` of the parent commit and this tree, same box, alternating", "§3i / §3j"),
+    (r"multi_bench\.jsonl$", "one-source kitti120k / nusc35k steps against the two-source LiDOG step, accumulate mode on and off, alternating (`scripts/bench_multi.py`)", "§3k"),
+    (r"multi_bench_ab\.txt$", "`python bench.py` of the parent commit and this tree, same box, alternating", "§3k"),
+    (r"multi_kernel_stats\.txt$", "accumulate-kernel totals of the two-source step, `rocprofv3 --kernel-trace --stats`", "§3k"),
     (r"kernel_stats_(train|bench)_bs\d(_one_stream|_dp1)?\.csv$", "per-kernel totals of 8 training steps, `rocprofv3 --kernel-trace --stats` over `scripts/prof_train.py` (`_one_stream`: weight gradients in line, `LIDOG_BACKWARD_OVERLAP=0`)", "§5, §8"),
     (r"kernel_breakdown_train_bs\d(_one_stream|_dp1)?\.txt$", "the same trace summed per kernel family (`scripts/kernel_breakdown.py`)", "§8"),
     (r"step_timeline(_one_stream|_dp1)?\.txt$", "dispatch timeline of the last profiled step, per stream (`scripts/step_timeline.py`)", "§8"),

@@ -29,8 +29,7 @@ from . import synth
 from .checkpoint import load_training_checkpoint, save_lightning_checkpoint
 from .evaluate import per_class_iou
 from .optim import make_optimizer, make_scheduler, shard_indices
-from .trainer import (LiDOGMultiStep, LiDOGStep, RobustMultiStep, RobustStep, SourceMultiStep, SourceStep,
-                      setup_data_parallel)
+from .trainer import LiDOGStep, RobustStep, SourceStep, setup_data_parallel
 
 
 class SynthScans:
@@ -119,29 +118,21 @@ def build_model(kind="MinkUNet34BEV", bound_2d=50.0, in_channels=1, out_channels
 def build_step(model, kind="MinkUNet34BEV", optimizer="Adam", lr=1e-3, scheduler=None, weight_decay=1e-4,
                momentum=0.98, warmup_epochs=0, source_weights=(0.5, 0.5), num_classes=7, ignore_label=-1, num_sources=1):
     """SyncBN conversion when data-parallel (train_lidog.py:227-231), optimiser + scheduler
-    (trainer_lighting_2d.py:349-394), step object (PLTTrainer2D / PLTRobustNet / PLTTrainer, or their two-source
-    versions for num_sources=2).  Returns (model, step, scheduler)."""
+    (trainer_lighting_2d.py:349-394), step object (PLTTrainer2D / PLTRobustNet / PLTTrainer, on one or two sources).
+    Returns (model, step, scheduler)."""
     if num_sources not in (1, 2):
         raise NotImplementedError(f"{num_sources} sources (the reference takes one or two)")
     model = setup_data_parallel(model)
     model.train()
     opt = make_optimizer(optimizer, model, lr, weight_decay=weight_decay, momentum=momentum)
     sched = make_scheduler(scheduler, opt)
-    if num_sources == 2:
-        if kind == "MinkUNet34BEV":
-            step = LiDOGMultiStep(model, opt, source_weights=source_weights, warmup_epochs=warmup_epochs,
-                                  num_classes=num_classes, ignore_label=ignore_label)
-        elif kind == "MinkUNet34Robust":
-            step = RobustMultiStep(model, opt, source_weights=source_weights, ignore_label=ignore_label)
-        else:
-            step = SourceMultiStep(model, opt, source_weights=source_weights, ignore_label=ignore_label)
-    elif kind == "MinkUNet34BEV":
-        step = LiDOGStep(model, opt, source_weights=source_weights, warmup_epochs=warmup_epochs,
-                         num_classes=num_classes, ignore_label=ignore_label)
+    kw = dict(source_weights=source_weights, ignore_label=ignore_label, num_sources=num_sources)
+    if kind == "MinkUNet34BEV":
+        step = LiDOGStep(model, opt, warmup_epochs=warmup_epochs, num_classes=num_classes, **kw)
     elif kind == "MinkUNet34Robust":
-        step = RobustStep(model, opt, source_weights=source_weights, ignore_label=ignore_label)
+        step = RobustStep(model, opt, **kw)
     else:
-        step = SourceStep(model, opt, ignore_label=ignore_label)
+        step = SourceStep(model, opt, **kw)
     return model, step, sched
 
 
@@ -215,8 +206,7 @@ class Fit:
         out = self.model(st)
         logits = (out[0] if isinstance(out, tuple) else out).F
         labels = batch["source_sem_labels0"].long()
-        crit = self.step.sem_criterion if hasattr(self.step, "sem_criterion") else self.step.criterion
-        loss = crit(logits, labels)
+        loss = self.step.sem_criterion(logits, labels)
         iou = per_class_iou(logits.max(dim=1)[1], labels)      # sklearn jaccard_score(labels=0..C-1), -1 = absent
         self.model.train(was)
         present = iou >= 0

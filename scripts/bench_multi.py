@@ -64,7 +64,7 @@ def main():
         b = batches[name]
         rows = int(b["coords_int"].shape[0]) + (int(b["coords_int1"].shape[0]) if "coords_int1" in b else 0)
         print(json.dumps({"variant": name, "batch": a.batch, "rows": rows, "steps": a.steps, "rounds": a.rounds,
-                          "paths": list(getattr(steps[name], "last_paths", [steps[name].last_path])),
+                          "paths": list(steps[name].last_paths),
                           "step_ms_median": round(statistics.median(times[name]), 3),
                           "step_ms_min": round(min(times[name]), 3), "step_ms_rounds": [round(t, 3) for t in times[name]],
                           "loss": losses[name]}), flush=True)

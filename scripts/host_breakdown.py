@@ -13,18 +13,14 @@ READY = torch.cuda.Event(); READY.record(); torch.cuda.synchronize()
 def one(i, timed):
     b, nxt = batches[i % 2], batches[(i + 1) % 2]
     t = [time.perf_counter()]
-    if kind == "MinkUNet34BEV":
-        total, *_ = step.forward_loss(b)
-    else:
-        st = step._sparse_input(b)
-        total = step.criterion(step.model(st, is_seg=True).F, b["source_sem_labels0"].long())
+    total, *_ = step.forward_loss(b)
     t.append(time.perf_counter())
     step.opt.zero_grad()
     total.backward()
     t.append(time.perf_counter())
     step.opt.step()
     t.append(time.perf_counter())
-    step._after_step(nxt, READY)
+    step.prefetch_maps(nxt, READY)
     t.append(time.perf_counter())
     if timed:
         torch.cuda.synchronize()

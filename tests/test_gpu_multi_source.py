@@ -242,11 +242,12 @@ def test_full_size_two_source_lidog_step():
 def test_cli_two_sources_fit_validate_resume_predict(tmp_path):
     from lidog_amd.evaluate import predict
     from lidog_amd.train import SynthScans, _fit_from_args, build_model, parse_args
+    from lidog_amd.trainer import LiDOGStep
     argv = ["--sources", "source8k", "nusc35k", "--source-weights", "0.4", "0.6", "--epochs", "2", "--scans", "4",
             "--batch", "2", "--val-scans", "2", "--check-val-every-n-epoch", "1", "--save-dir", str(tmp_path)]
     fit = _fit_from_args(parse_args(argv))
     fit.log = lambda *_: None
-    assert type(fit.step).__name__ == "LiDOGMultiStep" and fit.step.w == (0.4, 0.6)
+    assert type(fit.step) is LiDOGStep and fit.step.num_sources == 2 and fit.step.w == (0.4, 0.6)
     hist = fit.run()
     assert len(hist) == 2 and all(np.isfinite(h["losses"]).all() for h in hist)
     for h in hist:
@@ -286,7 +287,7 @@ def _dp_body(rank, world, port, q, executor):
     from lidog_amd import trunk
     from lidog_amd.losses import DICELoss, SoftDICELoss
     from lidog_amd.optim import FlatAdam
-    from lidog_amd.trainer import LiDOGMultiStep, setup_data_parallel
+    from lidog_amd.trainer import LiDOGStep, setup_data_parallel
     trunk.set_enabled(executor)
     kw = dict(in_channels=1, out_channels=7, D=3, decoder_2d_level=["block8"], mapping_bound_2d=5.0)
     torch.manual_seed(200 + rank)
@@ -297,12 +298,11 @@ def _dp_body(rank, world, port, q, executor):
     model = setup_data_parallel(model.cuda())
     model.train()
     opt = FlatAdam(model, lr=1e-3, weight_decay=1e-4, bucket_bytes=8 << 20)
-    step = LiDOGMultiStep(model, opt)
+    step = LiDOGStep(model, opt, num_sources=2)
     mine = two_source_batch((20 + rank,), (30 + rank,))
     grads = []
     for deferred in (False, True):
         opt.buckets.deferred = deferred
-        step._two_uses()
         out = step.forward_loss(mine)
         took = step.last_paths
         opt.zero_grad()
@@ -319,6 +319,8 @@ def _dp_body(rank, world, port, q, executor):
         ok, msg = False, f"paths {took}"
     if executor and strays:
         ok, msg = False, msg + f" {strays} strays"
+    if opt.buckets.uses != 2:       # set once by the two-source step's constructor
+        ok, msg = False, msg + f" buckets expect {opt.buckets.uses} uses"
     if not torch.equal(grads[0], grads[1]):
         ok, msg = False, msg + " deferred reduction differs"
     g = grads[0].cpu()

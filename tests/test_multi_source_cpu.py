@@ -102,16 +102,18 @@ def test_more_than_two_sources_is_not_implemented():
 @pytest.mark.parametrize("kind", KINDS)
 def test_cli_sources_pick_the_two_source_step(kind):
     from lidog_amd.train import build_model, build_step, parse_args
+    from lidog_amd.trainer import LiDOGStep, RobustStep, SourceStep
     a = parse_args(["--model", kind, "--sources", "kitti120k", "nusc35k", "--source-weights", "0.3", "0.7"])
     assert a.sources == ["kitti120k", "nusc35k"] and a.source_weights == [0.3, 0.7]
     _, step, _ = build_step(build_model(kind, device="cpu"), kind, source_weights=tuple(a.source_weights),
                             num_sources=len(a.sources))
-    want = {"MinkUNet34BEV": "LiDOGMultiStep", "MinkUNet34Robust": "RobustMultiStep"}.get(kind, "SourceMultiStep")
-    assert type(step).__name__ == want and tuple(step.w) == (0.3, 0.7)
+    want = {"MinkUNet34BEV": LiDOGStep, "MinkUNet34Robust": RobustStep}.get(kind, SourceStep)
+    assert type(step) is want and step.num_sources == 2 and tuple(step.w) == (0.3, 0.7)
+    assert step.opt.buckets.uses == 2
     plain = parse_args(["--model", kind])
     assert plain.sources is None and list(plain.source_weights) == [0.5, 0.5]
     _, one, _ = build_step(build_model(kind, device="cpu"), kind)
-    assert "Multi" not in type(one).__name__
+    assert type(one) is want and one.num_sources == 1 and one.opt.buckets.uses == 1
 
 
 def test_validation_keys_are_unique_source_names():

@@ -21,29 +21,25 @@
 // and 16 im2col columns; its (ci,ky,kx) columns are fixed for the whole kernel (packed offset + tap), its pixel
 // advances by 32 per stage with adds only.  Loads are unconditional (invalid taps read element 0) and zeroed
 // when the stage is written to LDS; LDS row pitch 129 makes the transposing stores conflict-free.
-#define WG_KB 32
 #define WG_LD 129
 __global__ __launch_bounds__(256) void k_conv_wgrad(IgParams p) {
-    __shared__ float As[WG_KB * WG_LD];
-    __shared__ float Bs[WG_KB * WG_LD];
+    __shared__ float As[C2_KB * WG_LD];
+    __shared__ float Bs[C2_KB * WG_LD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i0 = blockIdx.y * IG_T, j0 = blockIdx.x * IG_T;
-    const int HoWo = p.Ho * p.Wo, HW = p.H * p.W;
+    const int HoWo = p.Ho * p.Wo;
     const int k_begin = blockIdx.z * p.k_chunk;
     const int k_end = k_begin + p.k_chunk < p.Kd ? k_begin + p.k_chunk : p.Kd;
     const int kk = tid & 31, rg = tid >> 5;
 
-    int cpk[16];  // ((element offset of the tap relative to the window corner) << 4) | tap, -1 past Nj
+    int cpk[16];  // -1 past Nj
     unsigned a_mask = 0;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         int j = j0 + rg + 8 * r;
         cpk[r] = -1;
-        if (j < p.Nj) {
-            int ci = j / 9, t = j - ci * 9;
-            int ty = t / 3, tx = t - ty * 3;
-            cpk[r] = ((ci * HW + ty * p.W + tx) << 4) | t;
-        }
+        int ci = j / 9;
+        if (j < p.Nj) cpk[r] = wgrad_col(p, ci, j - ci * 9);
         a_mask |= (unsigned)(i0 + rg + 8 * r < p.Mi) << r;
     }
     // pixel of this thread in the current stage (clamped to the last pixel once past the end)
@@ -57,91 +53,33 @@ __global__ __launch_bounds__(256) void k_conv_wgrad(IgParams p) {
         xo = r_ - yo * p.Wo;
     }
 
-    float ra[16], rb[16];
-    unsigned okb = 0;
-    bool mv = false;
-    auto load_stage = [&]() {
-        mv = m < k_end;
-        const int a_base = (pb * p.Cout + i0 + rg) * HoWo + yo * p.Wo + xo;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) ra[r] = p.A[a_base + (((a_mask >> r) & 1u) ? r * 8 * HoWo : 0)];
-        const int b_base = pb * p.Cin * HW + (2 * yo - 1) * p.W + 2 * xo - 1;  // window corner (may lie outside)
-        const unsigned ym = (unsigned)(yo > 0) | 2u | ((unsigned)(2 * yo + 1 < p.H) << 2);
-        const unsigned xm = (unsigned)(xo > 0) | 2u | ((unsigned)(2 * xo + 1 < p.W) << 2);
-        const unsigned tapmask = mv ? (((ym & 1u) ? xm : 0u) | ((ym & 2u) ? xm << 3 : 0u) | ((ym & 4u) ? xm << 6 : 0u)) : 0u;
-        okb = 0;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int c = cpk[r];
-            const unsigned ok = (c >= 0) ? ((tapmask >> (c & 15)) & 1u) : 0u;
-            okb |= ok << r;
-            rb[r] = p.Bm[ok ? b_base + (c >> 4) : 0];
-        }
-    };
-    auto advance = [&]() {
-        m += WG_KB;
-        if (m < p.Kd) {
-            xo += WG_KB;
-            while (xo >= p.Wo) {
-                xo -= p.Wo;
-                ++yo;
-            }
-            while (yo >= p.Ho) {
-                yo -= p.Ho;
-                ++pb;
+    WgradStage<16> st;
+    // stage s > 0: step the pixel 32 on first (past the end: the last prefetch stages pixels with mv false)
+    auto load = [&](int s) {
+        if (s > 0) {
+            m += C2_KB;
+            if (m < p.Kd) {
+                xo += C2_KB;
+                while (xo >= p.Wo) {
+                    xo -= p.Wo;
+                    ++yo;
+                }
+                while (yo >= p.Ho) {
+                    yo -= p.Ho;
+                    ++pb;
+                }
             }
         }
+        st.load(p, i0, a_mask, cpk, m < k_end, pb, yo, xo, rg);
     };
-    auto store_stage = [&]() {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            As[kk * WG_LD + rg + 8 * r] = (mv && ((a_mask >> r) & 1u)) ? ra[r] : 0.f;
-            Bs[kk * WG_LD + rg + 8 * r] = ((okb >> r) & 1u) ? rb[r] : 0.f;
-        }
-    };
+    auto store = [&]() { st.store(&As[kk * WG_LD + rg], &Bs[kk * WG_LD + rg], a_mask); };
 
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
     const int wi = (wave >> 1) * 64, wj = (wave & 1) * 64;
     const int li = lane & 31, kh = lane >> 5;
-    const float *a_rd = &As[kh * WG_LD + wi + li];
-    const float *b_rd = &Bs[kh * WG_LD + wj + li];
+    f32x16 acc[2][2];
+    mfma_stages<2, 2, WG_LD, WG_LD>(acc, &As[kh * WG_LD + wi + li], &Bs[kh * WG_LD + wj + li],
+                                    (k_end - k_begin + C2_KB - 1) / C2_KB, load, store);
 
-    load_stage();
-    for (int k0 = k_begin; k0 < k_end; k0 += WG_KB) {
-        __syncthreads();
-        store_stage();
-        __syncthreads();
-        advance();
-        load_stage();  // unconditional prefetch: past the end it re-reads the last pixel and is zeroed (mv false)
-        float af[2], bf[2], an[2], bn[2];
-        af[0] = a_rd[0]; af[1] = a_rd[32];
-        bf[0] = b_rd[0]; bf[1] = b_rd[32];
-#pragma unroll
-        for (int k2 = 0; k2 < WG_KB / 2; ++k2) {
-            if (k2 + 1 < WG_KB / 2) {
-                an[0] = a_rd[(2 * k2 + 2) * WG_LD]; an[1] = a_rd[(2 * k2 + 2) * WG_LD + 32];
-                bn[0] = b_rd[(2 * k2 + 2) * WG_LD]; bn[1] = b_rd[(2 * k2 + 2) * WG_LD + 32];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[0], bf[0], acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[0], bf[1], acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[1], bf[0], acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[1], bf[1], acc[1][1], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (k2 + 1 < WG_KB / 2) {
-                af[0] = an[0]; af[1] = an[1];
-                bf[0] = bn[0]; bf[1] = bn[1];
-            }
-        }
-    }
-
-    // D layout of 32x32 MFMA: column = lane & 31, row = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5)
 #pragma unroll
     for (int tj = 0; tj < 2; ++tj) {
         int j = j0 + wj + 32 * tj + li;
@@ -151,7 +89,7 @@ __global__ __launch_bounds__(256) void k_conv_wgrad(IgParams p) {
         for (int ti = 0; ti < 2; ++ti) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                int i = i0 + wi + 32 * ti + (e & 3) + 8 * (e >> 2) + 4 * kh;
+                int i = i0 + wi + 32 * ti + mfma_row(e, kh);
                 if (i < p.Mi) d[(size_t)i * p.Nj] = acc[ti][tj][e];
             }
         }
@@ -165,8 +103,8 @@ __global__ __launch_bounds__(256) void k_conv_wgrad(IgParams p) {
 //    per staged element only a table read, a tap-validity bit test (per-lane 9-bit / 4-bit mask), one add
 //    and one select remain; all offsets are 32-bit;
 //  - invalid taps load a known-good address; they (and rows past Mi) are zeroed when the stage is written to
-//    LDS, not after the load: a select right behind a load makes the wave wait for it before its MFMA phase;
-//  - the LDS operand reads of MFMA step k2+1 are issued before the MFMAs of step k2 (sched_barrier).
+//    LDS, not after the load;
+//  - the LDS operand reads of MFMA step k2+1 are issued before the MFMAs of step k2 (mfma_stages).
 // WM x (4/WM) waves, each TI x TJ MFMA tiles: 128 x 128 (WM=2,TI=2,TJ=2) or 96 x 128 (WM=1,TI=3,TJ=1; the
 // data gradient of a 96-channel input would waste a quarter of a 128-row tile).
 template <int MODE, int WM, int TI, int TJ>
@@ -181,146 +119,49 @@ __device__ __forceinline__ void conv_s2_tile(const IgParams &p, const int bx, co
     const int i0 = by * TMR, j0 = bx * IG_T;
     const int HoWo = p.Ho * p.Wo, HW = p.H * p.W;
     const int kw = __builtin_amdgcn_readfirstlane(tid >> 7);
-    const int nt = p.nky * p.nkx;
 
     for (int kk = tid; kk < p.Kd; kk += 256) {
-        int koff, t;
         if (MODE == IG_FWD) {
-            int ci = kk / 9;
-            t = kk - ci * 9;
+            int ci = kk / 9, t = kk - ci * 9;
             int ty = t / 3, tx = t - ty * 3;
-            koff = ci * HW + (ty - 1) * p.W + (tx - 1);
+            s_tab[kk] = make_int2(ci * HW + (ty - 1) * p.W + (tx - 1), t);
         } else {
-            int co = kk / nt, tap = kk - co * nt;
-            int ty = tap / p.nkx, tx = tap - ty * p.nkx;
-            koff = co * HoWo - ty * p.Wo - tx;
-            t = ty * 2 + tx;
+            s_tab[kk] = dgrad_tab(p, kk);
         }
-        s_tab[kk] = make_int2(koff, t);
     }
 
-    // ---- the pixel of this lane (fixed for the whole kernel): 32-bit element offsets, tap validity mask
     const int j = j0 + (tid & 127);
-    const bool jvalid = j < p.Nj;
-    const int jj = jvalid ? j : 0;
-    int base, safe;
-    unsigned tapmask = 0;
-    if (MODE == IG_FWD) {
-        int pb = jj / HoWo, r = jj - pb * HoWo;
-        int yo = r / p.Wo, xo = r - yo * p.Wo;
-        base = pb * p.Cin * HW + (2 * yo) * p.W + 2 * xo;  // centre tap, always inside the image
-        safe = base;
-#pragma unroll
-        for (int ty = 0; ty < 3; ++ty)
-#pragma unroll
-            for (int tx = 0; tx < 3; ++tx) {
-                int y = 2 * yo - 1 + ty, x = 2 * xo - 1 + tx;
-                tapmask |= (unsigned)(y >= 0 && y < p.H && x >= 0 && x < p.W) << (ty * 3 + tx);
-            }
-    } else {
-        int hw = p.Hc * p.Wc;
-        int pb = jj / hw, r = jj - pb * hw;
-        int pyy = (r / p.Wc) * 2 + p.py, pxx = (r % p.Wc) * 2 + p.px;
-        int y0 = (pyy + 1 - p.ky0) >> 1, x0 = (pxx + 1 - p.kx0) >> 1;  // output pixel of the class's first tap
-        safe = pb * p.Cout * HoWo;
-        base = safe + y0 * p.Wo + x0;  // y0 - ty / x0 - tx for the later taps
-#pragma unroll
-        for (int ty = 0; ty < 2; ++ty)
-#pragma unroll
-            for (int tx = 0; tx < 2; ++tx)
-                tapmask |= (unsigned)(y0 - ty >= 0 && y0 - ty < p.Ho && x0 - tx >= 0 && x0 - tx < p.Wo)
-                           << (ty * 2 + tx);
-    }
-    if (!jvalid) tapmask = 0;
+    const PixelTaps px = MODE == IG_FWD ? fwd_pixel(p, j) : dgrad_pixel(p, j);
 
     // ---- the A rows this thread stages
     const float *a_ptr[AV];
     bool a_ok[AV];
 #pragma unroll
     for (int v = 0; v < AV; ++v) {
-        int f = tid + 256 * v;
-        int i = i0 + (f >> 3);
+        int i = i0 + 32 * v + (tid >> 3);
         a_ok[v] = i < p.Mi;
-        a_ptr[v] = p.A + (size_t)(a_ok[v] ? i : p.Mi - 1) * p.Kd + (f & 7) * 4;
+        a_ptr[v] = p.A + (size_t)(a_ok[v] ? i : p.Mi - 1) * p.Kd + (tid & 7) * 4;
     }
     __syncthreads();  // table complete
 
     float4 ra[AV];
-    float rb[16];
-    unsigned okbits = 0;
-    auto load_stage = [&](int k0) {
+    GatherB gb;
+    auto load = [&](int s) {
+        const int k0 = s * C2_KB;
 #pragma unroll
         for (int v = 0; v < AV; ++v) ra[v] = *reinterpret_cast<const float4 *>(a_ptr[v] + k0);
-        okbits = 0;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int2 e = s_tab[k0 + kw + 2 * r];  // wave-uniform address: a broadcast read
-            const unsigned ok = (tapmask >> e.y) & 1u;
-            okbits |= ok << r;
-            rb[r] = p.Bm[ok ? base + e.x : safe];
-        }
+        gb.load(p.Bm, &s_tab[k0 + kw], px);
     };
-    auto store_stage = [&]() {
-#pragma unroll
-        for (int v = 0; v < AV; ++v) {
-            int f = tid + 256 * v;
-            int il = f >> 3, q = f & 7;
-            const bool ok = a_ok[v];
-            As[(q * 4 + 0) * IG_LD + il] = ok ? ra[v].x : 0.f;
-            As[(q * 4 + 1) * IG_LD + il] = ok ? ra[v].y : 0.f;
-            As[(q * 4 + 2) * IG_LD + il] = ok ? ra[v].z : 0.f;
-            As[(q * 4 + 3) * IG_LD + il] = ok ? ra[v].w : 0.f;
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) Bs[(kw + 2 * r) * IG_LD + (tid & 127)] = ((okbits >> r) & 1u) ? rb[r] : 0.f;
+    auto store = [&]() {
+        store_a_rows(As, ra, a_ok, tid);
+        gb.store(&Bs[kw * IG_LD + (tid & 127)]);
     };
 
-    f32x16 acc[TI][TJ];
-#pragma unroll
-    for (int a = 0; a < TI; ++a)
-#pragma unroll
-        for (int b = 0; b < TJ; ++b)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
     const int wi = (WM == 1 ? 0 : (wave >> 1)) * (TI * 32), wj = (WM == 1 ? wave : (wave & 1)) * (TJ * 32);
     const int li = lane & 31, kh = lane >> 5;
-    const float *a_rd = &As[kh * IG_LD + wi + li];
-    const float *b_rd = &Bs[kh * IG_LD + wj + li];
-
-    load_stage(0);
-    for (int k0 = 0; k0 < p.Kd; k0 += C2_KB) {
-        __syncthreads();
-        store_stage();
-        __syncthreads();
-        load_stage(k0 + C2_KB < p.Kd ? k0 + C2_KB : k0);  // unconditional prefetch (last stage re-reads itself)
-        float af[TI], bf[TJ], an[TI], bn[TJ];
-#pragma unroll
-        for (int a = 0; a < TI; ++a) af[a] = a_rd[32 * a];
-#pragma unroll
-        for (int b = 0; b < TJ; ++b) bf[b] = b_rd[32 * b];
-#pragma unroll
-        for (int k2 = 0; k2 < C2_KB / 2; ++k2) {
-            if (k2 + 1 < C2_KB / 2) {
-#pragma unroll
-                for (int a = 0; a < TI; ++a) an[a] = a_rd[(2 * k2 + 2) * IG_LD + 32 * a];
-#pragma unroll
-                for (int b = 0; b < TJ; ++b) bn[b] = b_rd[(2 * k2 + 2) * IG_LD + 32 * b];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int a = 0; a < TI; ++a)
-#pragma unroll
-                for (int b = 0; b < TJ; ++b)
-                    acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[a], bf[b], acc[a][b], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (k2 + 1 < C2_KB / 2) {
-#pragma unroll
-                for (int a = 0; a < TI; ++a) af[a] = an[a];
-#pragma unroll
-                for (int b = 0; b < TJ; ++b) bf[b] = bn[b];
-            }
-        }
-    }
+    f32x16 acc[TI][TJ];
+    mfma_stages<TI, TJ, IG_LD, IG_LD>(acc, &As[kh * IG_LD + wi + li], &Bs[kh * IG_LD + wj + li], p.Kd / C2_KB, load,
+                                      store);
 
 #pragma unroll
     for (int tj = 0; tj < TJ; ++tj) {
@@ -332,17 +173,14 @@ __device__ __forceinline__ void conv_s2_tile(const IgParams &p, const int bx, co
             col_off = (size_t)b * p.Cout * HoWo + (jo - b * HoWo);
             i_stride = HoWo;
         } else {
-            int hw = p.Hc * p.Wc;
-            int b = jo / hw, r = jo - b * hw;
-            int y = (r / p.Wc) * 2 + p.py, x = (r % p.Wc) * 2 + p.px;
-            col_off = (size_t)b * p.Cin * HW + (size_t)y * p.W + x;
+            col_off = dgrad_pixel_offset(p, jo);
             i_stride = HW;
         }
 #pragma unroll
         for (int ti = 0; ti < TI; ++ti) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                int i = i0 + wi + 32 * ti + (e & 3) + 8 * (e >> 2) + 4 * kh;
+                int i = i0 + wi + 32 * ti + mfma_row(e, kh);
                 if (i < p.Mi) p.D[col_off + (size_t)i * i_stride] = acc[ti][tj][e];
             }
         }
@@ -492,7 +330,25 @@ __global__ __launch_bounds__(256) void k_pw_wgrad(const float *__restrict__ X, c
 }
 
 // ------------------------------------------------------------------ C ABI
-static int out_dim(int H, int k, int s, int p) { return (H + 2 * p - k) / s + 1; }
+void lidog_dgrad_classes(const float *gy, const float *Wd, int B, int Cin, int H, int W, int Cout, float *gx,
+                         IgParams cls[4]) {
+    const float *slab = Wd;
+    for (int c = 0; c < 4; ++c) {
+        IgParams &p = cls[c];
+        p = IgParams{};
+        p.Bm = gy; p.D = gx;
+        p.Cin = Cin; p.H = H; p.W = W; p.Cout = Cout; p.Ho = c2_out_dim(H); p.Wo = c2_out_dim(W);
+        p.py = c >> 1; p.px = c & 1;
+        // y + 1 - ky even: y even -> ky = 1; y odd -> ky in {0, 2}
+        p.nky = p.py ? 2 : 1; p.ky0 = p.py ? 0 : 1;
+        p.nkx = p.px ? 2 : 1; p.kx0 = p.px ? 0 : 1;
+        p.Hc = (H - p.py + 1) / 2; p.Wc = (W - p.px + 1) / 2;
+        const int nt = p.nky * p.nkx;
+        p.Mi = Cin; p.Nj = B * p.Hc * p.Wc; p.Kd = Cout * nt;
+        p.A = slab;
+        slab += (int64_t)Cin * Cout * nt;
+    }
+}
 
 extern "C" int lidog_conv2d_fwd(const float *x, const float *w, const float *bias, int32_t B, int32_t Cin, int32_t H,
                                 int32_t W, int32_t Cout, int32_t ksize, int32_t stride, int32_t pad, float *y,
@@ -510,8 +366,8 @@ extern "C" int lidog_conv2d_fwd(const float *x, const float *w, const float *bia
     LIDOG_REQUIRE((Cin * 9) % C2_KB == 0, "conv2d_fwd: Cin*9 must be a multiple of 32");
     IgParams p = {};
     p.A = w; p.Bm = x; p.D = y;
-    p.Bn = B; p.Cin = Cin; p.H = H; p.W = W; p.Cout = Cout;
-    p.Ho = out_dim(H, 3, 2, 1); p.Wo = out_dim(W, 3, 2, 1);
+    p.Cin = Cin; p.H = H; p.W = W; p.Cout = Cout;
+    p.Ho = c2_out_dim(H); p.Wo = c2_out_dim(W);
     p.Mi = Cout; p.Nj = B * p.Ho * p.Wo; p.Kd = Cin * 9;
     if (p.Nj == 0) return 0;
     LIDOG_REQUIRE((int64_t)B * Cin * H * W < ((int64_t)1 << 31) && (int64_t)p.Kd * 8 <= 24576,
@@ -540,33 +396,14 @@ extern "C" int lidog_conv2d_dgrad(const float *gy, const float *w, int32_t B, in
     LIDOG_REQUIRE(ksize == 3 && stride == 2 && pad == 1, "conv2d_dgrad: MFMA path implements k3 s2 p1");
     LIDOG_REQUIRE(ws != nullptr, "conv2d_dgrad: needs a 9*Cin*Cout float workspace for the repacked weights");
     LIDOG_REQUIRE(Cout % C2_KB == 0, "conv2d_dgrad: Cout must be a multiple of 32");
-    LIDOG_REQUIRE((int64_t)B * Cout * out_dim(H, 3, 2, 1) * out_dim(W, 3, 2, 1) < ((int64_t)1 << 31) &&
+    LIDOG_REQUIRE((int64_t)B * Cout * c2_out_dim(H) * c2_out_dim(W) < ((int64_t)1 << 31) &&
                       (int64_t)Cout * 4 * 8 <= 24576,
                   "conv2d_dgrad: tensor too large for 32-bit offsets / reduction table");
-    int Ho = out_dim(H, 3, 2, 1), Wo = out_dim(W, 3, 2, 1);
-    float *slab = ws;
     lidog_launch_repack_dgrad_all(w, Cin, Cout, ws, st);
     const bool rows96 = Cin % 128 != 0 && Cin % 96 == 0;   // 96-row tiles: no idle quarter of a 128-row tile
     IgClasses pc = {};
     IgParams cls_p[4];
-    for (int py = 0; py < 2; ++py) {
-        for (int px = 0; px < 2; ++px) {
-            IgParams &p = cls_p[2 * py + px];
-            p = IgParams{};
-            p.Bm = gy; p.D = gx;
-            p.Bn = B; p.Cin = Cin; p.H = H; p.W = W; p.Cout = Cout; p.Ho = Ho; p.Wo = Wo;
-            p.py = py; p.px = px;
-            // y + 1 - ky even: y even -> ky = 1; y odd -> ky in {0, 2}
-            p.nky = py ? 2 : 1; p.ky0 = py ? 0 : 1; p.kystep = 2;
-            p.nkx = px ? 2 : 1; p.kx0 = px ? 0 : 1; p.kxstep = 2;
-            p.Hc = (H - py + 1) / 2; p.Wc = (W - px + 1) / 2;
-            int nt = p.nky * p.nkx;
-            p.Mi = Cin; p.Nj = B * p.Hc * p.Wc; p.Kd = Cout * nt;
-            int64_t total = (int64_t)Cin * Cout * nt;
-            p.A = slab;
-            slab += total;
-        }
-    }
+    lidog_dgrad_classes(gy, ws, B, Cin, H, W, Cout, gx, cls_p);
     // longest reduction first: (py, px) = (1, 1) has four taps, (0, 1) and (1, 0) two, (0, 0) one
     const int rt = rows96 ? Cin / 96 : (int)cdiv64(Cin, IG_T);
     size_t tab = 0;
@@ -608,8 +445,8 @@ extern "C" int lidog_conv2d_wgrad(const float *x, const float *gy, int32_t B, in
     LIDOG_REQUIRE(ksize == 3 && stride == 2 && pad == 1 && gbias == nullptr, "conv2d_wgrad: MFMA path implements k3 s2 p1");
     IgParams p = {};
     p.A = gy; p.Bm = x;
-    p.Bn = B; p.Cin = Cin; p.H = H; p.W = W; p.Cout = Cout;
-    p.Ho = out_dim(H, 3, 2, 1); p.Wo = out_dim(W, 3, 2, 1);
+    p.Cin = Cin; p.H = H; p.W = W; p.Cout = Cout;
+    p.Ho = c2_out_dim(H); p.Wo = c2_out_dim(W);
     p.Mi = Cout; p.Nj = Cin * 9; p.Kd = B * p.Ho * p.Wo;
     int64_t slab = (int64_t)p.Mi * p.Nj;
     int tiles = (int)(cdiv64(p.Nj, IG_T) * cdiv64(p.Mi, IG_T));
@@ -621,49 +458,16 @@ extern "C" int lidog_conv2d_wgrad(const float *x, const float *gy, int32_t B, in
     LIDOG_REQUIRE((int64_t)Cin * H * W < ((int64_t)1 << 27) && (int64_t)B * Cin * H * W < ((int64_t)1 << 31) &&
                       (int64_t)B * Cout * p.Ho * p.Wo < ((int64_t)1 << 31),
                   "conv2d_wgrad: tensor too large for the packed 32-bit offsets");
-    int64_t max_by_k = cdiv64(p.Kd, 4 * WG_KB);
+    int64_t max_by_k = cdiv64(p.Kd, 4 * C2_KB);
     if (splits > max_by_k) splits = (int)(max_by_k < 1 ? 1 : max_by_k);
     if ((int64_t)splits * slab > ws_floats) splits = (int)(ws_floats / slab);
     LIDOG_REQUIRE(splits >= 1, "conv2d_wgrad: workspace too small (%lld floats needed per split)", (long long)slab);
-    p.k_chunk = (int)(cdiv64(cdiv64(p.Kd, splits), WG_KB) * WG_KB);
+    p.k_chunk = (int)(cdiv64(cdiv64(p.Kd, splits), C2_KB) * C2_KB);
     splits = (int)cdiv64(p.Kd, p.k_chunk);
     p.D = (splits == 1) ? gw : ws;
     dim3 grid((unsigned)cdiv64(p.Nj, IG_T), (unsigned)cdiv64(p.Mi, IG_T), (unsigned)splits);
     k_conv_wgrad<<<grid, 256, 0, st>>>(p);
     if (splits > 1) k_sum_splits<<<(unsigned)cdiv64(slab, 256), 256, 0, st>>>(ws, slab, splits, slab, gw);
-    LIDOG_LAUNCH_CHECK();
-    return 0;
-}
-
-// ------------------------------------------------------------------ Adam on a flat buffer
-// torch.optim.Adam semantics (L2 weight decay folded into the gradient; bias-corrected step)
-__global__ __launch_bounds__(256) void k_adam(float *__restrict__ p, const float *__restrict__ g,
-                                              float *__restrict__ m, float *__restrict__ v, int64_t n, float lr_bc1,
-                                              float beta1, float beta2, float eps, float wd, float bc2_sqrt,
-                                              float grad_scale) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        float pi = p[i];
-        float gi = g[i] * grad_scale + wd * pi;
-        float mi = m[i];
-        mi = mi + (gi - mi) * (1.f - beta1);
-        float vi = v[i] * beta2 + (1.f - beta2) * gi * gi;
-        float denom = sqrtf(vi) / bc2_sqrt + eps;
-        p[i] = pi - lr_bc1 * (mi / denom);
-        m[i] = mi;
-        v[i] = vi;
-    }
-}
-
-extern "C" int lidog_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
-                               float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step,
-                               float grad_scale, void *stream) {
-    if (n == 0) return 0;
-    double bc1 = 1.0 - pow((double)beta1, (double)step);
-    double bc2 = 1.0 - pow((double)beta2, (double)step);
-    int64_t g = cdiv64(n, 256);
-    if (g > 8192) g = 8192;
-    k_adam<<<(unsigned)g, 256, 0, (hipStream_t)stream>>>(param, grad, exp_avg, exp_avg_sq, n, (float)((double)lr / bc1),
-                                                         beta1, beta2, eps, weight_decay, (float)sqrt(bc2), grad_scale);
     LIDOG_LAUNCH_CHECK();
     return 0;
 }

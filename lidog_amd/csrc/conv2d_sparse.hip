@@ -142,14 +142,12 @@ struct ActLayout {
     int fwd_tiles, dgrad_tiles[4], groups;
 };
 
-static int out_dim2(int H) { return (H + 2 - 3) / 2 + 1; }
-
 static ActLayout act_layout(int B, int C, int H, int W) {
     ActLayout L;
     L.words = (W + 63) / 64;
     L.bits_off = 0;
     int64_t off = 2 * (int64_t)B * C * H * L.words;  // uint64 words as int32 pairs (offset stays even)
-    L.fwd_tiles = (int)cdiv64((int64_t)B * out_dim2(H) * out_dim2(W), IG_T);
+    L.fwd_tiles = (int)cdiv64((int64_t)B * c2_out_dim(H) * c2_out_dim(W), IG_T);
     L.fwd_off = off;
     off += (int64_t)L.fwd_tiles * (C + 1);
     off += off & 1;
@@ -186,7 +184,7 @@ extern "C" int lidog_conv2d_support(const int32_t *support, int32_t B, int32_t C
         k_support_rowbits<<<(unsigned)cdiv64(rows, 4), 256, 0, st>>>(support, rows, W, L.words, bits);
     ListGeom g;
     g.C = Cin; g.H = H; g.W = W;
-    g.Hc = out_dim2(H); g.Wc = out_dim2(W); g.Nj = B * g.Hc * g.Wc;
+    g.Hc = c2_out_dim(H); g.Wc = c2_out_dim(W); g.Nj = B * g.Hc * g.Wc;
     g.ya = -1; g.ny = 3; g.xlo = -1; g.xhi = 1; g.mask = ~0ull;
     uint64_t *tbits = reinterpret_cast<uint64_t *>(act + L.tbits_off);
     k_tile_lists<<<(unsigned)L.fwd_tiles, 128, 0, st>>>(bits, L.words, g, act + L.fwd_off, tbits);
@@ -216,16 +214,18 @@ __global__ __launch_bounds__(256) void k_conv_fwd_act(IgParams p, const int32_t 
                                                       const float *__restrict__ Wt) {
     __shared__ __attribute__((aligned(16))) float As[C2_KB * IG_LD];
     __shared__ float Bs[C2_KB * IG_LD];
-    extern __shared__ int2 s_tab[];  // [Kp] (x offset, tap | weight row << 4)
+    extern __shared__ int2 s_tab[];  // [max(Kp, C2_KB)] (x offset, tap | weight row << 5)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i0 = blockIdx.y * IG_T, j0 = blockIdx.x * IG_T;
-    const int HoWo = p.Ho * p.Wo, HW = p.H * p.W;
+    const int HW = p.H * p.W, HoWo = p.Ho * p.Wo;
     const int kw = __builtin_amdgcn_readfirstlane(tid >> 7);
     const int32_t *lst = lists + (size_t)blockIdx.x * (p.Cin + 1);
     const int n_act = lst[0];
     const int Kd = n_act * 9, Kp = (Kd + C2_KB - 1) / C2_KB * C2_KB;
 
-    for (int kk = tid; kk < Kp; kk += 256) {
+    // padded to a whole stage with entries whose tap never validates, and to one stage at least: load(0) of a tile
+    // without active channels reads weight row 0 and the lane's own pixel
+    for (int kk = tid; kk < (Kp > 0 ? Kp : C2_KB); kk += 256) {
         int koff = 0, t = 15, row = 0;
         if (kk < Kd) {
             int a = kk / 9;
@@ -235,95 +235,33 @@ __global__ __launch_bounds__(256) void k_conv_fwd_act(IgParams p, const int32_t 
             koff = ci * HW + (ty - 1) * p.W + (tx - 1);
             row = ci * 9 + t;
         }
-        s_tab[kk] = make_int2(koff, t | (row << 4));
+        s_tab[kk] = make_int2(koff, t | (row << 5));
     }
-
-    const int j = j0 + (tid & 127);
-    const bool jvalid = j < p.Nj;
-    const int jj = jvalid ? j : 0;
-    int base;
-    unsigned tapmask = 0;
-    {
-        int pb = jj / HoWo, r = jj - pb * HoWo;
-        int yo = r / p.Wo, xo = r - yo * p.Wo;
-        base = pb * p.Cin * HW + (2 * yo) * p.W + 2 * xo;  // centre tap, always inside the image
-#pragma unroll
-        for (int ty = 0; ty < 3; ++ty)
-#pragma unroll
-            for (int tx = 0; tx < 3; ++tx) {
-                int y = 2 * yo - 1 + ty, x = 2 * xo - 1 + tx;
-                tapmask |= (unsigned)(y >= 0 && y < p.H && x >= 0 && x < p.W) << (ty * 3 + tx);
-            }
-    }
-    if (!jvalid) tapmask = 0;
-    const int safe = base;
+    const PixelTaps px = fwd_pixel(p, j0 + (tid & 127));
     __syncthreads();  // table complete
 
     float4 ra[4];
-    float rb[16];
-    unsigned okbits = 0;
+    GatherB gb;
     const int a_kr = tid >> 5, a_c4 = (tid & 31) * 4;  // stage row / column quad of float4 v: row a_kr + 8 v
-    auto load_stage = [&](int k0) {
+    auto load = [&](int s) {
+        const int k0 = s * C2_KB;
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
-            const int row = s_tab[k0 + a_kr + 8 * v].y >> 4;
+            const int row = s_tab[k0 + a_kr + 8 * v].y >> 5;
             ra[v] = *reinterpret_cast<const float4 *>(Wt + (size_t)row * p.Cout + i0 + a_c4);
         }
-        okbits = 0;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int2 e = s_tab[k0 + kw + 2 * r];  // wave-uniform address: a broadcast read
-            const unsigned ok = (tapmask >> (e.y & 15)) & 1u;
-            okbits |= ok << r;
-            rb[r] = p.Bm[ok ? base + e.x : safe];
-        }
+        gb.load(p.Bm, &s_tab[k0 + kw], px);
     };
-    auto store_stage = [&]() {
+    auto store = [&]() {
 #pragma unroll
         for (int v = 0; v < 4; ++v) *reinterpret_cast<float4 *>(&As[(a_kr + 8 * v) * IG_LD + a_c4]) = ra[v];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) Bs[(kw + 2 * r) * IG_LD + (tid & 127)] = ((okbits >> r) & 1u) ? rb[r] : 0.f;
+        gb.store(&Bs[kw * IG_LD + (tid & 127)]);
     };
 
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
     const int wi = (wave >> 1) * 64, wj = (wave & 1) * 64;
     const int li = lane & 31, kh = lane >> 5;
-    const float *a_rd = &As[kh * IG_LD + wi + li];
-    const float *b_rd = &Bs[kh * IG_LD + wj + li];
-
-    if (Kp > 0) load_stage(0);
-    for (int k0 = 0; k0 < Kp; k0 += C2_KB) {
-        __syncthreads();
-        store_stage();
-        __syncthreads();
-        load_stage(k0 + C2_KB < Kp ? k0 + C2_KB : k0);  // unconditional prefetch (last stage re-reads itself)
-        float af[2], bf[2], an[2], bn[2];
-        af[0] = a_rd[0]; af[1] = a_rd[32];
-        bf[0] = b_rd[0]; bf[1] = b_rd[32];
-#pragma unroll
-        for (int k2 = 0; k2 < C2_KB / 2; ++k2) {
-            if (k2 + 1 < C2_KB / 2) {
-                an[0] = a_rd[(2 * k2 + 2) * IG_LD]; an[1] = a_rd[(2 * k2 + 2) * IG_LD + 32];
-                bn[0] = b_rd[(2 * k2 + 2) * IG_LD]; bn[1] = b_rd[(2 * k2 + 2) * IG_LD + 32];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[0], bf[0], acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[0], bf[1], acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[1], bf[0], acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[1], bf[1], acc[1][1], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (k2 + 1 < C2_KB / 2) {
-                af[0] = an[0]; af[1] = an[1];
-                bf[0] = bn[0]; bf[1] = bn[1];
-            }
-        }
-    }
+    f32x16 acc[2][2];
+    mfma_stages<2, 2, IG_LD, IG_LD>(acc, &As[kh * IG_LD + wi + li], &Bs[kh * IG_LD + wj + li], Kp / C2_KB, load, store);
 
 #pragma unroll
     for (int tj = 0; tj < 2; ++tj) {
@@ -335,7 +273,7 @@ __global__ __launch_bounds__(256) void k_conv_fwd_act(IgParams p, const int32_t 
         for (int ti = 0; ti < 2; ++ti) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                int i = i0 + wi + 32 * ti + (e & 3) + 8 * (e >> 2) + 4 * kh;
+                int i = i0 + wi + 32 * ti + mfma_row(e, kh);
                 if (i < p.Mi) p.D[col_off + (size_t)i * HoWo] = acc[ti][tj][e];
             }
         }
@@ -349,8 +287,8 @@ extern "C" int lidog_conv2d_fwd_sparse(const float *x, const float *w, const int
     LIDOG_REQUIRE(ws != nullptr, "conv2d_fwd_sparse: needs a Cin*9*Cout float workspace (transposed weights)");
     IgParams p = {};
     p.Bm = x; p.D = y;
-    p.Bn = B; p.Cin = Cin; p.H = H; p.W = W; p.Cout = Cout;
-    p.Ho = out_dim2(H); p.Wo = out_dim2(W);
+    p.Cin = Cin; p.H = H; p.W = W; p.Cout = Cout;
+    p.Ho = c2_out_dim(H); p.Wo = c2_out_dim(W);
     p.Mi = Cout; p.Nj = B * p.Ho * p.Wo; p.Kd = Cin * 9;
     if (p.Nj == 0) return 0;
     LIDOG_REQUIRE((int64_t)B * Cin * H * W < ((int64_t)1 << 31) && (int64_t)(p.Kd + C2_KB) * 8 <= 24576,
@@ -373,29 +311,8 @@ __device__ __forceinline__ void conv_dgrad_act_body(const IgParams &p, const int
                                                     float *As, float *Bs, const int2 *s_tab) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j0 = tile * IG_T;
-    const int HoWo = p.Ho * p.Wo, HW = p.H * p.W;
     const int kw = __builtin_amdgcn_readfirstlane(tid >> 7);
-
-    const int j = j0 + (tid & 127);
-    const bool jvalid = j < p.Nj;
-    const int jj = jvalid ? j : 0;
-    int base, safe;
-    unsigned tapmask = 0;
-    {
-        int hw = p.Hc * p.Wc;
-        int pb = jj / hw, r = jj - pb * hw;
-        int pyy = (r / p.Wc) * 2 + p.py, pxx = (r % p.Wc) * 2 + p.px;
-        int y0 = (pyy + 1 - p.ky0) >> 1, x0 = (pxx + 1 - p.kx0) >> 1;  // output pixel of the class's first tap
-        safe = pb * p.Cout * HoWo;
-        base = safe + y0 * p.Wo + x0;
-#pragma unroll
-        for (int ty = 0; ty < 2; ++ty)
-#pragma unroll
-            for (int tx = 0; tx < 2; ++tx)
-                tapmask |= (unsigned)(y0 - ty >= 0 && y0 - ty < p.Ho && x0 - tx >= 0 && x0 - tx < p.Wo)
-                           << (ty * 2 + tx);
-    }
-    if (!jvalid) tapmask = 0;
+    const PixelTaps px = dgrad_pixel(p, j0 + (tid & 127));
 
     // A rows this thread stages: float4 v covers rows 32 v + (tid >> 3)
     const float *a_ptr[TIA];
@@ -408,85 +325,33 @@ __device__ __forceinline__ void conv_dgrad_act_body(const IgParams &p, const int
     }
 
     float4 ra[TIA];
-    float rb[16];
-    unsigned okbits = 0;
-    auto load_stage = [&](int k0) {
+    GatherB gb;
+    auto load = [&](int s) {
+        const int k0 = s * C2_KB;
 #pragma unroll
         for (int v = 0; v < TIA; ++v) ra[v] = *reinterpret_cast<const float4 *>(a_ptr[v] + k0);
-        okbits = 0;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int2 e = s_tab[k0 + kw + 2 * r];
-            const unsigned ok = (tapmask >> e.y) & 1u;
-            okbits |= ok << r;
-            rb[r] = p.Bm[ok ? base + e.x : safe];
-        }
+        gb.load(p.Bm, &s_tab[k0 + kw], px);
     };
-    auto store_stage = [&]() {
-#pragma unroll
-        for (int v = 0; v < TIA; ++v) {
-            int il = 32 * v + (tid >> 3), q = tid & 7;
-            const bool ok = a_ok[v];
-            As[(q * 4 + 0) * IG_LD + il] = ok ? ra[v].x : 0.f;
-            As[(q * 4 + 1) * IG_LD + il] = ok ? ra[v].y : 0.f;
-            As[(q * 4 + 2) * IG_LD + il] = ok ? ra[v].z : 0.f;
-            As[(q * 4 + 3) * IG_LD + il] = ok ? ra[v].w : 0.f;
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) Bs[(kw + 2 * r) * IG_LD + (tid & 127)] = ((okbits >> r) & 1u) ? rb[r] : 0.f;
+    auto store = [&]() {
+        store_a_rows(As, ra, a_ok, tid);
+        gb.store(&Bs[kw * IG_LD + (tid & 127)]);
     };
 
-    f32x16 acc[TIA];
-#pragma unroll
-    for (int a = 0; a < TIA; ++a)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[a][e] = 0.f;
     const int wj = wave * 32;
     const int li = lane & 31, kh = lane >> 5;
-    const float *a_rd = &As[kh * IG_LD + li];
-    const float *b_rd = &Bs[kh * IG_LD + wj + li];
-
-    load_stage(0);
-    for (int k0 = 0; k0 < p.Kd; k0 += C2_KB) {
-        __syncthreads();
-        store_stage();
-        __syncthreads();
-        load_stage(k0 + C2_KB < p.Kd ? k0 + C2_KB : k0);
-        float af[TIA], an[TIA], bf, bn = 0.f;
-#pragma unroll
-        for (int a = 0; a < TIA; ++a) af[a] = a_rd[32 * a];
-        bf = b_rd[0];
-#pragma unroll
-        for (int k2 = 0; k2 < C2_KB / 2; ++k2) {
-            if (k2 + 1 < C2_KB / 2) {
-#pragma unroll
-                for (int a = 0; a < TIA; ++a) an[a] = a_rd[(2 * k2 + 2) * IG_LD + 32 * a];
-                bn = b_rd[(2 * k2 + 2) * IG_LD];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int a = 0; a < TIA; ++a) acc[a] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[a], bf, acc[a], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (k2 + 1 < C2_KB / 2) {
-#pragma unroll
-                for (int a = 0; a < TIA; ++a) af[a] = an[a];
-                bf = bn;
-            }
-        }
-    }
+    f32x16 acc[TIA][1];
+    mfma_stages<TIA, 1, IG_LD, IG_LD>(acc, &As[kh * IG_LD + li], &Bs[kh * IG_LD + wj + li], p.Kd / C2_KB, load, store);
 
     const int jo = j0 + wj + li;
     if (jo < p.Nj) {
-        int hw = p.Hc * p.Wc;
-        int b = jo / hw, r = jo - b * hw;
-        int y = (r / p.Wc) * 2 + p.py, x = (r % p.Wc) * 2 + p.px;
-        size_t col_off = (size_t)b * p.Cin * HW + (size_t)y * p.W + x;
+        const size_t col_off = dgrad_pixel_offset(p, jo);
+        const int HW = p.H * p.W;
 #pragma unroll
         for (int ti = 0; ti < TIA; ++ti) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                int il = 32 * ti + (e & 3) + 8 * (e >> 2) + 4 * kh;
-                if (il < n_act) p.D[col_off + (size_t)s_ch[il] * HW] = acc[ti][e];
+                int il = 32 * ti + mfma_row(e, kh);
+                if (il < n_act) p.D[col_off + (size_t)s_ch[il] * HW] = acc[ti][0][e];
             }
         }
     }
@@ -507,12 +372,7 @@ __global__ __launch_bounds__(256) void k_conv_dgrad_act(IgClasses pc, const int3
     const int n_act = lst[0];
     if (n_act == 0) return;  // workgroup-uniform: nothing of this tile is needed
     if (tid < n_act) s_ch[tid] = lst[1 + tid];
-    const int nt = p.nky * p.nkx, HoWo = p.Ho * p.Wo;
-    for (int kk = tid; kk < p.Kd; kk += 256) {
-        int co = kk / nt, tap = kk - co * nt;
-        int ty = tap / p.nkx, tx = tap - ty * p.nkx;
-        s_tab[kk] = make_int2(co * HoWo - ty * p.Wo - tx, ty * 2 + tx);
-    }
+    for (int kk = tid; kk < p.Kd; kk += 256) s_tab[kk] = dgrad_tab(p, kk);
     __syncthreads();
     if (n_act <= 32) conv_dgrad_act_body<1>(p, tile, s_ch, n_act, As, Bs, s_tab);
     else if (n_act <= 64) conv_dgrad_act_body<2>(p, tile, s_ch, n_act, As, Bs, s_tab);
@@ -525,30 +385,13 @@ extern "C" int lidog_conv2d_dgrad_sparse(const float *gy, const float *w, const 
     hipStream_t st = (hipStream_t)stream;
     LIDOG_REQUIRE(Cin >= 1 && Cin <= 128 && Cout % C2_KB == 0, "conv2d_dgrad_sparse: Cin <= 128, Cout % 32 == 0");
     LIDOG_REQUIRE(ws != nullptr, "conv2d_dgrad_sparse: needs a 9*Cin*Cout float workspace for the repacked weights");
-    int Ho = out_dim2(H), Wo = out_dim2(W);
-    LIDOG_REQUIRE((int64_t)B * Cout * Ho * Wo < ((int64_t)1 << 31) && (int64_t)Cout * 4 * 8 <= 24576 &&
-                      (int64_t)B * Cin * H * W < ((int64_t)1 << 31),
+    LIDOG_REQUIRE((int64_t)B * Cout * c2_out_dim(H) * c2_out_dim(W) < ((int64_t)1 << 31) &&
+                      (int64_t)Cout * 4 * 8 <= 24576 && (int64_t)B * Cin * H * W < ((int64_t)1 << 31),
                   "conv2d_dgrad_sparse: tensor too large for 32-bit offsets / reduction table");
     ActLayout L = act_layout(B, Cin, H, W);
-    float *slab = ws;
     lidog_launch_repack_dgrad_all(w, Cin, Cout, ws, st);   // conv2d.hip: the four classes' weight slabs, one launch
     IgParams cls_p[4];
-    for (int cls = 0; cls < 4; ++cls) {
-        int py = cls >> 1, px = cls & 1;
-        IgParams &p = cls_p[cls];
-        p = IgParams{};
-        p.Bm = gy; p.D = gx;
-        p.Bn = B; p.Cin = Cin; p.H = H; p.W = W; p.Cout = Cout; p.Ho = Ho; p.Wo = Wo;
-        p.py = py; p.px = px;
-        p.nky = py ? 2 : 1; p.ky0 = py ? 0 : 1; p.kystep = 2;
-        p.nkx = px ? 2 : 1; p.kx0 = px ? 0 : 1; p.kxstep = 2;
-        p.Hc = (H - py + 1) / 2; p.Wc = (W - px + 1) / 2;
-        int nt = p.nky * p.nkx;
-        p.Mi = Cin; p.Nj = B * p.Hc * p.Wc; p.Kd = Cout * nt;
-        int64_t total = (int64_t)Cin * Cout * nt;
-        p.A = slab;
-        slab += total;
-    }
+    lidog_dgrad_classes(gy, ws, B, Cin, H, W, Cout, gx, cls_p);
     IgClasses pc = {};
     size_t tab = 0;
     for (int cls : {3, 1, 2, 0}) {
@@ -572,17 +415,16 @@ extern "C" int lidog_conv2d_dgrad_sparse(const float *gy, const float *w, const 
 // (no atomics).  A pixel tile in which none of the group's channels is active contributes exact zeros and is
 // never visited.  Narrow groups skip more tiles but re-read gY once per group (WA_GC = 3: 41 % of the tiles, twice
 // the gY traffic of the dense kernel, no faster; 7: 57 %, 1.2 x the traffic; 14: 69 %, 0.7 x).
-#define WA_KB 32
 #define WA_TPI 16  // pixel tiles per work item
 #define WA_LDA 129
 #define WA_LDB (32 * WA_NT + 1)
 __global__ __launch_bounds__(256) void k_conv_wgrad_act(IgParams p, const int32_t *__restrict__ glists, int n_tiles,
                                                         int splits) {
-    __shared__ float As[WA_KB * WA_LDA];
-    __shared__ float Bs[WA_KB * WA_LDB];
+    __shared__ float As[C2_KB * WA_LDA];
+    __shared__ float Bs[C2_KB * WA_LDB];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = blockIdx.x, i0 = blockIdx.y * IG_T, sp = blockIdx.z;
-    const int HoWo = p.Ho * p.Wo, HW = p.H * p.W;
+    const int HoWo = p.Ho * p.Wo;
     const int32_t *gl = glists + (size_t)g * (n_tiles + 1);
     const int n_g = gl[0];
     // work item = WA_TPI consecutive entries of the group's tile list: equal work per workgroup whatever the
@@ -593,98 +435,43 @@ __global__ __launch_bounds__(256) void k_conv_wgrad_act(IgParams p, const int32_
     const int nq = t_end > t_begin ? 4 * (t_end - t_begin) : 0;  // stages of 32 pixels
     const int kk = tid & 31, rg = tid >> 5;
 
-    int cpk[4 * WA_NT];  // ((element offset of the tap relative to the window corner) << 4) | tap, -1 = idle column
+    int cpk[4 * WA_NT];  // -1 = idle column
 #pragma unroll
     for (int r = 0; r < 4 * WA_NT; ++r) {
         int j = rg + 8 * r;
-        int ci = g * WA_GC + j / 9, t = j % 9;
+        int ci = g * WA_GC + j / 9;
         cpk[r] = -1;
-        if (j < 9 * WA_GC && ci < p.Cin) {
-            int ty = t / 3, tx = t - ty * 3;
-            cpk[r] = ((ci * HW + ty * p.W + tx) << 4) | t;
-        }
+        if (j < 9 * WA_GC && ci < p.Cin) cpk[r] = wgrad_col(p, ci, j % 9);
     }
     unsigned a_mask = 0;
 #pragma unroll
     for (int r = 0; r < 16; ++r) a_mask |= (unsigned)(i0 + rg + 8 * r < p.Mi) << r;
 
-    float ra[16], rb[4 * WA_NT];
-    unsigned okb = 0;
-    bool mv = false;
+    WgradStage<4 * WA_NT> st;
     // tile ids are fetched one tile (four stages) ahead: the address chain list -> gY / X of a stage would
     // otherwise be two dependent memory latencies long, more than the MFMA phase it hides behind
     const int n_my = t_end - t_begin;
     int tile_cur = n_my > 0 ? gl[1 + t_begin] : 0;
     int tile_nxt = n_my > 1 ? gl[2 + t_begin] : tile_cur;
-    auto load_stage = [&](int q) {
+    auto load = [&](int q) {
         if ((q & 3) == 0 && q > 0) {
             tile_cur = tile_nxt;
             const int ahead = (q >> 2) + 1;
             tile_nxt = gl[1 + t_begin + (ahead < n_my ? ahead : n_my - 1)];
         }
-        const int tile = tile_cur;
-        const int m = tile * IG_T + (q & 3) * WA_KB + kk;
-        mv = m < p.Kd;
+        const int m = tile_cur * IG_T + (q & 3) * C2_KB + kk;
+        const bool mv = m < p.Kd;
         const int mc = mv ? m : p.Kd - 1;
         const int pb = mc / HoWo, r_ = mc - pb * HoWo;
         const int yo = r_ / p.Wo, xo = r_ - yo * p.Wo;
-        const int a_base = (pb * p.Cout + i0 + rg) * HoWo + yo * p.Wo + xo;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) ra[r] = p.A[a_base + (((a_mask >> r) & 1u) ? r * 8 * HoWo : 0)];
-        const int b_base = pb * p.Cin * HW + (2 * yo - 1) * p.W + 2 * xo - 1;  // window corner (may lie outside)
-        const unsigned ym = (unsigned)(yo > 0) | 2u | ((unsigned)(2 * yo + 1 < p.H) << 2);
-        const unsigned xm = (unsigned)(xo > 0) | 2u | ((unsigned)(2 * xo + 1 < p.W) << 2);
-        const unsigned tapmask = mv ? (((ym & 1u) ? xm : 0u) | ((ym & 2u) ? xm << 3 : 0u) | ((ym & 4u) ? xm << 6 : 0u)) : 0u;
-        okb = 0;
-#pragma unroll
-        for (int r = 0; r < 4 * WA_NT; ++r) {
-            const int c = cpk[r];
-            const unsigned ok = (c >= 0) ? ((tapmask >> (c & 15)) & 1u) : 0u;
-            okb |= ok << r;
-            rb[r] = p.Bm[ok ? b_base + (c >> 4) : 0];
-        }
+        st.load(p, i0, a_mask, cpk, mv, pb, yo, xo, rg);
     };
-    auto store_stage = [&]() {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) As[kk * WA_LDA + rg + 8 * r] = (mv && ((a_mask >> r) & 1u)) ? ra[r] : 0.f;
-#pragma unroll
-        for (int r = 0; r < 4 * WA_NT; ++r) Bs[kk * WA_LDB + rg + 8 * r] = ((okb >> r) & 1u) ? rb[r] : 0.f;
-    };
+    auto store = [&]() { st.store(&As[kk * WA_LDA + rg], &Bs[kk * WA_LDB + rg], a_mask); };
 
-    f32x16 acc[WA_NT];
-#pragma unroll
-    for (int t = 0; t < WA_NT; ++t)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
     const int li = lane & 31, kh = lane >> 5;
-    const float *a_rd = &As[kh * WA_LDA + 32 * wave + li];
-    const float *b_rd = &Bs[kh * WA_LDB + li];
-
-    if (nq > 0) load_stage(0);
-    for (int q = 0; q < nq; ++q) {
-        __syncthreads();
-        store_stage();
-        __syncthreads();
-        load_stage(q + 1 < nq ? q + 1 : q);  // unconditional prefetch (the last stage re-reads itself)
-        float af = a_rd[0], an = 0.f, bf[WA_NT], bn[WA_NT];
-#pragma unroll
-        for (int t = 0; t < WA_NT; ++t) { bf[t] = b_rd[32 * t]; bn[t] = 0.f; }
-#pragma unroll
-        for (int k2 = 0; k2 < WA_KB / 2; ++k2) {
-            if (k2 + 1 < WA_KB / 2) {
-                an = a_rd[(2 * k2 + 2) * WA_LDA];
-#pragma unroll
-                for (int t = 0; t < WA_NT; ++t) bn[t] = b_rd[(2 * k2 + 2) * WA_LDB + 32 * t];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int t = 0; t < WA_NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(af, bf[t], acc[t], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            af = an;
-#pragma unroll
-            for (int t = 0; t < WA_NT; ++t) bf[t] = bn[t];
-        }
-    }
+    f32x16 acc[1][WA_NT];
+    mfma_stages<1, WA_NT, WA_LDA, WA_LDB>(acc, &As[kh * WA_LDA + 32 * wave + li], &Bs[kh * WA_LDB + li], nq, load,
+                                          store);
 
 #pragma unroll
     for (int t = 0; t < WA_NT; ++t) {
@@ -694,8 +481,8 @@ __global__ __launch_bounds__(256) void k_conv_wgrad_act(IgParams p, const int32_
             float *d = p.D + (size_t)sp * p.Mi * p.Nj + (size_t)ci * 9 + j % 9;
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                int i = i0 + 32 * wave + (e & 3) + 8 * (e >> 2) + 4 * kh;
-                if (i < p.Mi) d[(size_t)i * p.Nj] = acc[t][e];
+                int i = i0 + 32 * wave + mfma_row(e, kh);
+                if (i < p.Mi) d[(size_t)i * p.Nj] = acc[0][t][e];
             }
         }
     }
@@ -729,8 +516,8 @@ extern "C" int lidog_conv2d_wgrad_sparse(const float *x, const float *gy, const 
     LIDOG_REQUIRE(Cin >= 1 && Cin <= 128 && Cout % 8 == 0, "conv2d_wgrad_sparse: Cin <= 128, Cout % 8 == 0");
     IgParams p = {};
     p.A = gy; p.Bm = x;
-    p.Bn = B; p.Cin = Cin; p.H = H; p.W = W; p.Cout = Cout;
-    p.Ho = out_dim2(H); p.Wo = out_dim2(W);
+    p.Cin = Cin; p.H = H; p.W = W; p.Cout = Cout;
+    p.Ho = c2_out_dim(H); p.Wo = c2_out_dim(W);
     p.Mi = Cout; p.Nj = Cin * 9; p.Kd = B * p.Ho * p.Wo;
     LIDOG_REQUIRE((int64_t)Cin * H * W < ((int64_t)1 << 27) && (int64_t)B * Cin * H * W < ((int64_t)1 << 31) &&
                       (int64_t)B * Cout * p.Ho * p.Wo < ((int64_t)1 << 31),

@@ -1,6 +1,6 @@
 // Fused optimiser steps on slices of the flat parameter / gradient buffers (lidog_amd/optim.py).
 // SGD: torch.optim.SGD(lr, momentum, weight_decay, nesterov=True, dampening=0) as configured at
-// utils/pipelines/trainer_lighting_2d.py:351-355 (momentum 0.98, :26).  Adam lives in conv2d.hip (k_adam).
+// utils/pipelines/trainer_lighting_2d.py:351-355 (momentum 0.98, :26).  Adam: torch.optim.Adam (k_adam).
 #include "common.h"
 
 // g' = g * grad_scale + wd * p;  buf = mu * buf + g'  (buf starts at 0: the first step gives buf = g' like
@@ -27,6 +27,38 @@ extern "C" int lidog_sgd_step(float *param, const float *grad, float *momentum_b
     if (g > 8192) g = 8192;
     k_sgd<<<(unsigned)g, 256, 0, (hipStream_t)stream>>>(param, grad, momentum_buf, n, lr, momentum, weight_decay,
                                                         nesterov, grad_scale);
+    LIDOG_LAUNCH_CHECK();
+    return 0;
+}
+
+// Adam on a flat buffer: torch.optim.Adam semantics (L2 weight decay folded into the gradient; bias-corrected step)
+__global__ __launch_bounds__(256) void k_adam(float *__restrict__ p, const float *__restrict__ g,
+                                              float *__restrict__ m, float *__restrict__ v, int64_t n, float lr_bc1,
+                                              float beta1, float beta2, float eps, float wd, float bc2_sqrt,
+                                              float grad_scale) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        float pi = p[i];
+        float gi = g[i] * grad_scale + wd * pi;
+        float mi = m[i];
+        mi = mi + (gi - mi) * (1.f - beta1);
+        float vi = v[i] * beta2 + (1.f - beta2) * gi * gi;
+        float denom = sqrtf(vi) / bc2_sqrt + eps;
+        p[i] = pi - lr_bc1 * (mi / denom);
+        m[i] = mi;
+        v[i] = vi;
+    }
+}
+
+extern "C" int lidog_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
+                               float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step,
+                               float grad_scale, void *stream) {
+    if (n == 0) return 0;
+    double bc1 = 1.0 - pow((double)beta1, (double)step);
+    double bc2 = 1.0 - pow((double)beta2, (double)step);
+    int64_t g = cdiv64(n, 256);
+    if (g > 8192) g = 8192;
+    k_adam<<<(unsigned)g, 256, 0, (hipStream_t)stream>>>(param, grad, exp_avg, exp_avg_sq, n, (float)((double)lr / bc1),
+                                                         beta1, beta2, eps, weight_decay, (float)sqrt(bc2), grad_scale);
     LIDOG_LAUNCH_CHECK();
     return 0;
 }

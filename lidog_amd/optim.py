@@ -9,7 +9,7 @@ Restates what the reference configures through pytorch-lightning (python the GPU
   DDP gradient averaging  train_lidog.py:227-231 (strategy='ddp')
 
 Parameters, gradients and optimiser state live in contiguous fp32 buffers: one fused HIP kernel per step
-(csrc/conv2d.hip:k_adam, csrc/optim.hip:k_sgd), one RCCL all-reduce per 32 MiB bucket.
+(csrc/optim.hip:k_adam, csrc/optim.hip:k_sgd), one RCCL all-reduce per 32 MiB bucket.
 """
 import math
 
@@ -389,7 +389,7 @@ class _FlatOptimizer:
 
 class FlatAdam(_FlatOptimizer):
     """torch.optim.Adam(lr, betas=(0.9, 0.999), eps=1e-8, weight_decay) semantics, one fused HIP kernel
-    over the flat buffer (csrc/conv2d.hip:k_adam); `grad_scale` folds the 1/world_size of DDP averaging."""
+    over the flat buffer (csrc/optim.hip:k_adam); `grad_scale` folds the 1/world_size of DDP averaging."""
     _state = ("exp_avg", "exp_avg_sq")
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, group=None,

@@ -2,10 +2,15 @@
 120k-point / 0.05 m scans (BASELINE.json configs[1], batch 4 per GPU), one process per GPU over RCCL.
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step = forward (is_train=True, BEV head included) + both DICE losses + backward + gradient
 all-reduce + Adam update; inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
+A plain run does only what that line's headline needs: set-up, warm-up, the timed steps, --dump-outputs and the
+roofline of the kernels timed inside those steps.  --full adds what the headline does not need: the check of scan
+seed 0's voxel counts, the forward-only rate and the CPU oracle baseline (--no-cpu-baseline leaves the last one out).
+An N > 1 run checks its replicas and probes its data-parallel paths either way.
 """
 import argparse
 import json
@@ -52,7 +57,9 @@ def parse():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=4, help="scans per GPU (configs[1]: bs=4)")
     ap.add_argument("--config", default="kitti120k")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also check scan seed 0's voxel counts and measure the forward-only rate and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--no-prefetch", action="store_true", help="build coordinate maps inside the forward pass")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--dump-outputs", metavar="DIR",
@@ -703,9 +710,10 @@ def main():
                for i in range(2)]
     n_vox = sum(b["coords_int"].shape[0] for b in batches) / (2 * args.batch)
     beat("model, optimiser and batches ready")
-    # the workload is BASELINE.md's: scan seed 0 must have SURVEY.md 8(d)'s per-stride voxel counts
+    # the workload is BASELINE.md's: scan seed 0 must have SURVEY.md 8(d)'s per-stride voxel counts (--full: the scan is
+    # voxelised once more on the host for it; tests/test_oracle_cpu.py checks the same counts)
     seed0_counts = None
-    if args.config in synth.BASELINE_COUNTS:
+    if args.full and args.config in synth.BASELINE_COUNTS:
         seed0_counts = list(synth.stride_counts(synth.scan_voxels(0, args.config)[0]))
         assert tuple(seed0_counts) == synth.BASELINE_COUNTS[args.config], (seed0_counts, synth.BASELINE_COUNTS[args.config])
 
@@ -833,7 +841,7 @@ def main():
             collective_us[name] = round(1e3 * e0.elapsed_time(e1) / reps, 2)
         sync()
     eval_rate = None
-    if world == 1:
+    if world == 1 and args.full:
         # secondary figure: forward-only validation path, is_train=False, same batches
         from lidog_amd.evaluate import Predictor
         run_eval = Predictor(model)
@@ -964,7 +972,7 @@ def main():
             if ratios:
                 res["roofline"]["traffic_ratio"] = ratios     # PMC HBM bytes / algorithmic bytes per launch
                 res["roofline"]["traffic_ratio_source"] = f"profiles/{PMC_TRAFFIC_TAG}_pmc_traffic_*.json"
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(args.config)
             res["gpu_over_cpu"] = value / res["cpu_baseline"]["value"]
             wh = res["cpu_baseline"].get("whole_host") or {}

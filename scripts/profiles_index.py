@@ -26,7 +26,7 @@ RULES = [
     (r"gemm_units.*\.txt$|c1_source8k_gemm_units_ab\.txt$", "gathered GEMM alone, one unit per workgroup against several (`scripts/bench_gemm_units.py`) / C1 line with and without", "§8 Round 6"),
     (r"os_offset_group_split\.txt$", "output-stationary kernel with a tile's offsets cut into 3 groups, measured against the exact kernel and the two-pass path (experiment of commit d6c0076)", "§8 Round 6"),
     (r"gpu_test_durations.*\.txt$", "`pytest -m gpu --durations` of the round's suite", "§4"),
-    (r"bench_default.*\.json$|bench\.json$|bench_line\.json$|bench\.log$|bench_dp1\.json$", "`python bench.py` (the headline line, with `roofline` and `cpu_baseline`)", "§5"),
+    (r"bench_default.*\.json$|bench\.json$|bench_line\.json$|bench\.log$|bench_dp1\.json$", "`python bench.py --full` (the headline line, with `roofline` and `cpu_baseline`)", "§5"),
     (r"bench_bs2\.json$", "`python bench.py --batch 2` (configs[2]'s per-GPU load)", "§5"),
     (r"bench_one_stream\.json$", "`LIDOG_BACKWARD_OVERLAP=0 python bench.py`", "§5"),
     (r"bench_single_rank_dp\.json$", "`LIDOG_BENCH_SINGLE_RANK_DP=1 python bench.py`: one-rank RCCL group with every data-parallel path on", "§6"),

@@ -671,6 +671,37 @@ int lidog_iw_fwd(const float *const *x, const int64_t *n, const int32_t *C, cons
 int lidog_iw_bwd(const float *const *x, const int64_t *n, const int32_t *C, const double *w, int32_t M, double scale,
                  const float *gout, float *const *gx, void *stream);
 
+/* ------------------------------------------------------------------ scan mixing (PointCutMix, CoSMix)
+ * The per-point work of PointCutMixSourceDataset.merge_data (utils/datasets/pointcutmix.py:43-135) and
+ * CoSMixSourceDataset.merge_data (utils/datasets/cosmix.py:50-171), which the reference runs with numpy in DataLoader
+ * workers.  The random draws stay on the host; both quantisations are lidog_voxel_floor + lidog_coords_insert +
+ * lidog_coords_compact.  Every position is computed from counts and scans, never taken by an atomic: the same result on
+ * every run. */
+/* counts[b] = number of keys equal to b for b in [0, nbins); keys outside are skipped; counts is zeroed here.
+ * np.unique(inverse_map, return_counts=True) of the 10 m cells (pointcutmix.py:91-92) and the classes present in the
+ * source, np.unique(source_sem_labels) (cosmix.py:108-112) */
+int lidog_mix_histogram(const int32_t *keys, int64_t n, int32_t nbins, int32_t *counts, void *stream);
+/* int32 workspace of lidog_mix_split */
+int64_t lidog_mix_split_ws(int64_t n, int32_t n_slots);
+/* Stable multi-way split: row i goes to slot slot_of_key[keys[i]] (a key outside [0, n_keys) or a slot outside
+ * [0, n_slots): not taken).  rows_out (room for n) = the taken rows grouped by slot in ascending slot order, ascending
+ * row order inside a slot; slot_start [n_slots + 1] (device) = start of each slot in rows_out, then the total.
+ * n_slots <= 256.  The reference's concatenation of `source[inverse_map == sv]` over the drawn cells
+ * (pointcutmix.py:100-106) and of `source[source_sem_labels == sv]` over the drawn classes (cosmix.py:120-126). */
+int lidog_mix_split(const int32_t *keys, int64_t n, const int32_t *slot_of_key, int32_t n_keys, int32_t n_slots,
+                    int32_t *rows_out, int32_t *slot_start, int32_t *ws, void *stream);
+/* The merged point set before its re-quantisation (pointcutmix.py:94-112, cosmix.py:114-148): merged row r < n_target
+ * is target row r; row n_target + j is source row rows[j] when perm is NULL (every row of every slot), else
+ * rows[slot_start[s] + perm[j]] for the slot s with take_start[s] <= j < take_start[s + 1] (device, n_slots + 1
+ * entries): the random sub-sample of cosmix.py:56-63,128-133, perm[j] < size of slot s.  coords_out [n_target + n_take, 3]
+ * = float(coordinate) * voxel_size in float32 (`coordinates * self.voxel_size`, pointcutmix.py:45-46, cosmix.py:68-69).  Columns: cols_host
+ * holds 3 * n_cols HOST-side entries (target, source, merged device pointers of column k) and col_words_host the 32-bit
+ * words per row of each column (features, labels, xyz, sampled_idx); n_cols <= 6. */
+int lidog_mix_gather(const int32_t *coords_t, int64_t n_target, const int32_t *coords_s, const int32_t *rows,
+                     const int32_t *slot_start, const int32_t *perm, const int32_t *take_start, int32_t n_slots,
+                     int64_t n_take, float voxel_size, float *coords_out, int32_t n_cols, void *const *cols_host,
+                     const int32_t *col_words_host, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

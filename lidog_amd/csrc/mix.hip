@@ -1,0 +1,285 @@
+// Scan-mixing kernels of the augmentation-based baselines: PointCutMixSourceDataset.merge_data
+// (utils/datasets/pointcutmix.py:43-135) and CoSMixSourceDataset.merge_data (utils/datasets/cosmix.py:50-171).
+// The host makes the reference's random draws; the device counts (cells of the 10 m quantisation, classes), splits the
+// source rows into the drawn cells / classes in the reference's concatenation order and writes the merged point set in
+// one gather.  The two quantisations reuse lidog_voxel_floor / lidog_coords_insert / lidog_coords_compact (data.py).
+// No position comes from an atomic: the result is the same on every run.
+#include "common.h"
+
+#define MIX_THREADS 256
+#define MIX_WAVES (MIX_THREADS / 64)
+#define MIX_HIST_BINS 4096      // LDS bins per pass of the histogram; more bins take more passes over the keys
+#define MIX_MAX_SLOTS 256
+#define MIX_SPLIT_ITERS 4       // rows per split block: MIX_THREADS * MIX_SPLIT_ITERS
+#define MIX_SPLIT_TILE (MIX_THREADS * MIX_SPLIT_ITERS)
+#define MIX_MAX_COLS 6
+
+// ------------------------------------------------------------------ histogram
+// per-block LDS counts (one pass per MIX_HIST_BINS bins), then one global atomic per block per non-empty bin
+__global__ __launch_bounds__(MIX_THREADS) void k_mix_hist(const int32_t *__restrict__ keys, int64_t n, int32_t nbins,
+                                                          int32_t *counts) {
+    __shared__ int32_t h[MIX_HIST_BINS];
+    const int64_t stride = (int64_t)gridDim.x * MIX_THREADS;
+    for (int32_t b0 = 0; b0 < nbins; b0 += MIX_HIST_BINS) {
+        const int32_t nb = min(MIX_HIST_BINS, nbins - b0);
+        for (int j = threadIdx.x; j < nb; j += MIX_THREADS) h[j] = 0;
+        __syncthreads();
+        for (int64_t i = (int64_t)blockIdx.x * MIX_THREADS + threadIdx.x; i < n; i += stride) {
+            const int64_t k = (int64_t)keys[i] - b0;
+            if (k >= 0 && k < nb) atomicAdd(&h[k], 1);
+        }
+        __syncthreads();
+        for (int j = threadIdx.x; j < nb; j += MIX_THREADS)
+            if (h[j]) atomicAdd(&counts[b0 + j], h[j]);
+        __syncthreads();
+    }
+}
+
+extern "C" int lidog_mix_histogram(const int32_t *keys, int64_t n, int32_t nbins, int32_t *counts, void *stream) {
+    hipStream_t st = (hipStream_t)stream;
+    LIDOG_REQUIRE(n >= 0 && nbins >= 0, "lidog_mix_histogram: n = %lld, nbins = %d", (long long)n, nbins);
+    if (nbins == 0) return 0;
+    LIDOG_CHECK_HIP(hipMemsetAsync(counts, 0, sizeof(int32_t) * (size_t)nbins, st));
+    if (n == 0) return 0;
+    const int64_t blocks = cdiv64(n, MIX_THREADS);
+    const unsigned grid = (unsigned)(blocks < 1024 ? blocks : 1024);
+    k_mix_hist<<<grid, MIX_THREADS, 0, st>>>(keys, n, nbins, counts);
+    LIDOG_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------ stable multi-way split
+__device__ __forceinline__ int mix_slot(const int32_t *__restrict__ keys, int64_t i, int64_t n,
+                                        const int32_t *__restrict__ slot_of_key, int32_t n_keys, int32_t S) {
+    if (i >= n) return -1;
+    const int32_t k = keys[i];
+    if (k < 0 || k >= n_keys) return -1;
+    const int32_t s = slot_of_key[k];
+    return (s >= 0 && s < S) ? s : -1;
+}
+
+// taken rows per (slot, block): cnt[s * nblocks + b]
+__global__ __launch_bounds__(MIX_THREADS) void k_mix_split_count(const int32_t *__restrict__ keys, int64_t n,
+                                                                 const int32_t *__restrict__ slot_of_key,
+                                                                 int32_t n_keys, int32_t S, int64_t nblocks,
+                                                                 int32_t *__restrict__ cnt) {
+    __shared__ int32_t c[MIX_MAX_SLOTS];
+    for (int s = threadIdx.x; s < S; s += MIX_THREADS) c[s] = 0;
+    __syncthreads();
+    const int64_t base = (int64_t)blockIdx.x * MIX_SPLIT_TILE;
+#pragma unroll
+    for (int it = 0; it < MIX_SPLIT_ITERS; ++it) {
+        const int s = mix_slot(keys, base + it * MIX_THREADS + threadIdx.x, n, slot_of_key, n_keys, S);
+        if (s >= 0) atomicAdd(&c[s], 1);   // a count: the order of the adds does not matter
+    }
+    __syncthreads();
+    for (int s = threadIdx.x; s < S; s += MIX_THREADS) cnt[(int64_t)s * nblocks + blockIdx.x] = c[s];
+}
+
+// exclusive scan of cnt[len] in place (one block, chunks of 1024 with a carry); slot_start[s] = cnt[s * nblocks] after
+// the scan, slot_start[S] = the total
+__global__ __launch_bounds__(MIX_THREADS) void k_mix_split_scan(int32_t *cnt, int64_t len, int64_t nblocks, int32_t S,
+                                                                int32_t *__restrict__ slot_start) {
+    __shared__ int32_t wsum[MIX_WAVES];
+    __shared__ int32_t carry_s;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (threadIdx.x == 0) carry_s = 0;
+    __syncthreads();
+    for (int64_t c0 = 0; c0 < len; c0 += 4 * MIX_THREADS) {
+        const int64_t b = c0 + 4 * threadIdx.x;
+        int v[4], t = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            v[j] = (b + j < len) ? cnt[b + j] : 0;
+            t += v[j];
+        }
+        int x = t;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int y = __shfl_up(x, d);
+            if (lane >= d) x += y;
+        }
+        if (lane == 63) wsum[w] = x;
+        __syncthreads();
+        int off = carry_s, tot = 0;
+#pragma unroll
+        for (int i = 0; i < MIX_WAVES; ++i) {
+            if (i < w) off += wsum[i];
+            tot += wsum[i];
+        }
+        int e = off + x - t;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (b + j < len) cnt[b + j] = e;
+            e += v[j];
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) carry_s += tot;
+        __syncthreads();
+    }
+    for (int s = threadIdx.x; s < S; s += MIX_THREADS) slot_start[s] = cnt[(int64_t)s * nblocks];
+    if (threadIdx.x == 0) slot_start[S] = carry_s;
+}
+
+// position of a taken row = start of its (slot, block) + taken rows of its slot in earlier chunks of the block + in
+// earlier waves of the chunk + its rank among the lanes of its wave holding the same slot (ballot, popcount of the lower
+// lanes).  Each pass of the loop below resolves the lanes of one slot, so a wave runs (distinct slots in it) passes.
+__global__ __launch_bounds__(MIX_THREADS) void k_mix_split_scatter(const int32_t *__restrict__ keys, int64_t n,
+                                                                   const int32_t *__restrict__ slot_of_key,
+                                                                   int32_t n_keys, int32_t S, int64_t nblocks,
+                                                                   const int32_t *__restrict__ start,
+                                                                   int32_t *__restrict__ rows_out) {
+    __shared__ int32_t run[MIX_MAX_SLOTS];
+    __shared__ int32_t wcnt[MIX_WAVES][MIX_MAX_SLOTS];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const uint64_t lower = (1ull << lane) - 1ull;
+    for (int s = threadIdx.x; s < S; s += MIX_THREADS) {
+        run[s] = start[(int64_t)s * nblocks + blockIdx.x];
+#pragma unroll
+        for (int i = 0; i < MIX_WAVES; ++i) wcnt[i][s] = 0;
+    }
+    __syncthreads();
+    const int64_t base = (int64_t)blockIdx.x * MIX_SPLIT_TILE;
+    for (int it = 0; it < MIX_SPLIT_ITERS; ++it) {
+        const int64_t row = base + it * MIX_THREADS + threadIdx.x;
+        const int slot = mix_slot(keys, row, n, slot_of_key, n_keys, S);
+        int rank = 0;
+        uint64_t pending = __ballot(slot >= 0);
+        while (pending) {   // wave-uniform
+            const int leader = __builtin_ctzll(pending);
+            const int s = __shfl(slot, leader);
+            const uint64_t same = __ballot(slot == s);
+            if (slot == s) rank = __popcll(same & lower);
+            if (lane == leader) wcnt[w][s] = __popcll(same);
+            pending &= ~same;
+        }
+        __syncthreads();
+        if (slot >= 0) {
+            int pos = run[slot] + rank;
+            for (int i = 0; i < w; ++i) pos += wcnt[i][slot];
+            rows_out[pos] = (int32_t)row;
+        }
+        __syncthreads();
+        for (int s = threadIdx.x; s < S; s += MIX_THREADS) {
+            int add = 0;
+#pragma unroll
+            for (int i = 0; i < MIX_WAVES; ++i) {
+                add += wcnt[i][s];
+                wcnt[i][s] = 0;
+            }
+            run[s] += add;
+        }
+        __syncthreads();
+    }
+}
+
+extern "C" int64_t lidog_mix_split_ws(int64_t n, int32_t n_slots) {
+    return (int64_t)(n_slots > 0 ? n_slots : 0) * cdiv64(n > 0 ? n : 0, MIX_SPLIT_TILE) + 1;
+}
+
+extern "C" int lidog_mix_split(const int32_t *keys, int64_t n, const int32_t *slot_of_key, int32_t n_keys,
+                               int32_t n_slots, int32_t *rows_out, int32_t *slot_start, int32_t *ws, void *stream) {
+    hipStream_t st = (hipStream_t)stream;
+    LIDOG_REQUIRE(n >= 0 && n < (int64_t)INT32_MAX, "lidog_mix_split: n = %lld out of range", (long long)n);
+    LIDOG_REQUIRE(n_slots >= 0 && n_slots <= MIX_MAX_SLOTS, "lidog_mix_split: %d slots (at most %d)", n_slots,
+                  MIX_MAX_SLOTS);
+    LIDOG_REQUIRE(n_keys >= 0, "lidog_mix_split: n_keys = %d", n_keys);
+    const int64_t nblocks = cdiv64(n, MIX_SPLIT_TILE);
+    if (nblocks == 0 || n_slots == 0) {
+        LIDOG_CHECK_HIP(hipMemsetAsync(slot_start, 0, sizeof(int32_t) * (size_t)(n_slots + 1), st));
+        return 0;
+    }
+    LIDOG_REQUIRE(nblocks < (int64_t)UINT32_MAX, "lidog_mix_split: grid too large");
+    k_mix_split_count<<<(unsigned)nblocks, MIX_THREADS, 0, st>>>(keys, n, slot_of_key, n_keys, n_slots, nblocks, ws);
+    k_mix_split_scan<<<1, MIX_THREADS, 0, st>>>(ws, (int64_t)n_slots * nblocks, nblocks, n_slots, slot_start);
+    k_mix_split_scatter<<<(unsigned)nblocks, MIX_THREADS, 0, st>>>(keys, n, slot_of_key, n_keys, n_slots, nblocks,
+                                                                   ws, rows_out);
+    LIDOG_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------ fused concatenating gather
+struct MixCols {
+    const uint32_t *t[MIX_MAX_COLS];   // target rows
+    const uint32_t *s[MIX_MAX_COLS];   // source rows
+    uint32_t *o[MIX_MAX_COLS];         // merged rows
+    int32_t words[MIX_MAX_COLS];       // 32-bit words per row
+    int32_t n;
+};
+
+// merged row r < n_target: target row r; r = n_target + j: source row rows[j] (perm == NULL), or
+// rows[slot_start[s] + perm[j]] with take_start[s] <= j < take_start[s + 1].  Coordinates: float(c) * voxel, the float32
+// product torch computes for `int_tensor * voxel_size`.
+__global__ __launch_bounds__(MIX_THREADS) void k_mix_gather(const int32_t *__restrict__ coords_t, int64_t n_target,
+                                                            const int32_t *__restrict__ coords_s,
+                                                            const int32_t *__restrict__ rows,
+                                                            const int32_t *__restrict__ slot_start,
+                                                            const int32_t *__restrict__ perm,
+                                                            const int32_t *__restrict__ take_start, int32_t S,
+                                                            int64_t n_take, float voxel, float *__restrict__ coords_out,
+                                                            MixCols cols) {
+    __shared__ int32_t ts[MIX_MAX_SLOTS + 1];
+    if (perm) {
+        for (int s = threadIdx.x; s <= S; s += MIX_THREADS) ts[s] = take_start[s];
+        __syncthreads();
+    }
+    const int64_t r = (int64_t)blockIdx.x * MIX_THREADS + threadIdx.x;
+    if (r >= n_target + n_take) return;
+    const bool tgt = r < n_target;
+    int64_t src;
+    if (tgt) {
+        src = r;
+    } else {
+        const int64_t j = r - n_target;
+        if (perm) {
+            int lo = 0, hi = S;   // the last slot whose take_start <= j (empty slots share their start)
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if (ts[mid] <= j) lo = mid;
+                else hi = mid;
+            }
+            src = rows[slot_start[lo] + perm[j]];
+        } else {
+            src = rows[j];
+        }
+    }
+    const int32_t *c = (tgt ? coords_t : coords_s) + 3 * src;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) coords_out[3 * r + d] = (float)c[d] * voxel;
+    for (int k = 0; k < cols.n; ++k) {
+        const int wd = cols.words[k];
+        const uint32_t *in = (tgt ? cols.t[k] : cols.s[k]) + src * wd;
+        uint32_t *out = cols.o[k] + r * wd;
+        for (int q = 0; q < wd; ++q) out[q] = in[q];
+    }
+}
+
+extern "C" int lidog_mix_gather(const int32_t *coords_t, int64_t n_target, const int32_t *coords_s,
+                                const int32_t *rows, const int32_t *slot_start, const int32_t *perm,
+                                const int32_t *take_start, int32_t n_slots, int64_t n_take, float voxel_size,
+                                float *coords_out, int32_t n_cols, void *const *cols_host,
+                                const int32_t *col_words_host, void *stream) {
+    hipStream_t st = (hipStream_t)stream;
+    LIDOG_REQUIRE(n_target >= 0 && n_take >= 0, "lidog_mix_gather: negative row count");
+    LIDOG_REQUIRE(n_cols >= 0 && n_cols <= MIX_MAX_COLS, "lidog_mix_gather: %d columns (at most %d)", n_cols,
+                  MIX_MAX_COLS);
+    LIDOG_REQUIRE(n_take == 0 || rows, "lidog_mix_gather: source rows missing");
+    LIDOG_REQUIRE(!perm || (n_slots >= 1 && n_slots <= MIX_MAX_SLOTS && slot_start && take_start),
+                  "lidog_mix_gather: a permutation needs 1..%d slots, slot_start and take_start", MIX_MAX_SLOTS);
+    MixCols cols = {};
+    cols.n = n_cols;
+    for (int k = 0; k < n_cols; ++k) {
+        cols.t[k] = (const uint32_t *)cols_host[3 * k];
+        cols.s[k] = (const uint32_t *)cols_host[3 * k + 1];
+        cols.o[k] = (uint32_t *)cols_host[3 * k + 2];
+        cols.words[k] = col_words_host[k];
+        LIDOG_REQUIRE(cols.words[k] >= 0, "lidog_mix_gather: column %d has %d words", k, cols.words[k]);
+    }
+    const int64_t total = n_target + n_take;
+    if (total == 0) return 0;
+    k_mix_gather<<<(unsigned)cdiv64(total, MIX_THREADS), MIX_THREADS, 0, st>>>(
+        coords_t, n_target, coords_s, rows, slot_start, perm, take_start, n_slots, n_take, voxel_size, coords_out,
+        cols);
+    LIDOG_LAUNCH_CHECK();
+    return 0;
+}

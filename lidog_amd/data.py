@@ -7,7 +7,12 @@
                    coordinates (bev_points = quantized_coords * voxel_size, :244)
 
 The reference runs these in DataLoader worker processes with numpy; at >50 scans/s per GPU that becomes the
-bottleneck, and both are the same hash / winner-map kernels as the hot path."""
+bottleneck, and both are the same hash / winner-map kernels as the hot path.
+
+  pointcutmix_merge, cosmix_merge   PointCutMix / CoSMix scan mixing (utils/datasets/pointcutmix.py, cosmix.py), below
+"""
+import ctypes
+
 import numpy as np
 import torch
 
@@ -131,3 +136,230 @@ def mix3d_merge(scan0, scan1, voxel_size=0.05, ignore_label=-1):
     q, _, _, idx = sparse_quantize(coords, feats, labels=labels, ignore_label=ignore_label,
                                    quantization_size=voxel_size, return_index=True)
     return {"coordinates": q, "features": feats[idx], "sem_labels": labels[idx], "index": idx}
+
+
+# ------------------------------------------------------------------ scan mixing: PointCutMix and CoSMix
+# PointCutMixSourceDataset.merge_data (utils/datasets/pointcutmix.py:43-135) and CoSMixSourceDataset.merge_data
+# (utils/datasets/cosmix.py:50-171), which pair their sources as MultiBEVSourceDataset (lidog_amd.train.MultiSynthScans).
+# The random draws are made on the host in the reference's exact sequence (rng: numpy's legacy RandomState, or the
+# np.random module itself), so that `np.random.seed(s)` then a merge here selects the same source, cells or classes and
+# sub-samples as the reference's merge_data after the same seed.  The device does the per-point work (mix.hip): the
+# counts the draws need, the stable split of the source rows into the drawn cells / classes, the merged point set, and
+# the re-quantisation.  Device -> host reads: the counts of the draws and the sizes sparse_quantize reads back.
+
+_MERGE_STREAMS = {}
+
+
+def merge_stream(device=None):
+    """the stream the merges of `device` run on.  A caller that makes a merge's input tensors on this stream and calls
+    the merge with it current (lidog_amd.train.MixedSynthScans) keeps the merge's read-backs off any work queued on its
+    other streams, a training step among them."""
+    dev = torch.device("cuda") if device is None else torch.device(device)
+    idx = dev.index if dev.index is not None else torch.cuda.current_device()
+    if idx not in _MERGE_STREAMS:
+        _MERGE_STREAMS[idx] = torch.cuda.Stream(device=idx)
+    return _MERGE_STREAMS[idx]
+
+
+def on_merge_stream(work, device, inputs=(), wait=True):
+    """run `work()` on merge_stream(device) and hand its result (a dict or list of tensors) to the caller's current stream
+    with an event; the caching allocator is told about the tensors that cross streams.  wait=True: the merge stream first
+    waits for the work queued on the caller's stream, where `inputs` may have been made; wait=False: work() makes its own
+    inputs on the merge stream, and nothing queued on the caller's stream delays it."""
+    cur = torch.cuda.current_stream(device)
+    side = merge_stream(device)
+    if side == cur:
+        return work()
+    if wait:
+        side.wait_stream(cur)
+    for t in inputs:
+        if torch.is_tensor(t) and t.is_cuda:
+            t.record_stream(side)
+    with torch.cuda.stream(side):
+        out = work()
+    cur.wait_stream(side)
+    for t in (out.values() if isinstance(out, dict) else out):
+        if torch.is_tensor(t) and t.is_cuda:
+            t.record_stream(cur)
+    return out
+
+
+def draw_source(rng):
+    """`selected_source = np.random.choice([0, 1])` (pointcutmix.py:66, cosmix.py:90); the other scan is the target"""
+    return int(rng.choice([0, 1]))
+
+
+def draw_cells(rng, counts, min_points=300, n_cells=4):
+    """pointcutmix.py:91-92: `np.random.choice(vox_idx[count > 300], 4, replace=False)` over the cells of the source's
+    cell_size quantisation (counts[c] = source rows in cell c); raises ValueError when fewer than n_cells qualify"""
+    counts = np.asarray(counts)
+    vox_idx = np.arange(counts.shape[0])
+    return rng.choice(vox_idx[counts > min_points], n_cells, replace=False)
+
+
+def draw_classes(rng, counts, weights, sub_p):
+    """cosmix.py:108-133 (random_sample :53-63): the classes present in the source (counts[c] = its rows of class c), `int(len / 2)` of them
+    drawn with p = weights[class_idx] * (1 / weights[class_idx].sum()), then for each drawn class, in order, the
+    sub-sample `np.random.choice(np.arange(n_c), int(sub_p * n_c), replace=False)` (sub_p None: arange(n_c)).
+    Returns (classes, [sub-sample of each class])."""
+    counts = np.asarray(counts)
+    weights = np.asarray(weights, dtype=np.float64)
+    class_idx = np.nonzero(counts)[0]
+    sampling_weights = weights[class_idx] * (1 / weights[class_idx].sum())
+    classes = rng.choice(class_idx, int(len(class_idx) / 2), p=sampling_weights, replace=False)
+    subs = []
+    for c in classes:
+        n_c = int(counts[c])
+        subs.append(rng.choice(np.arange(n_c), int(sub_p * n_c), replace=False) if sub_p is not None
+                    else np.arange(n_c))
+    return classes, subs
+
+
+_MERGE_COLUMNS = ("features", "sem_labels", "xyz", "sampled_idx")
+
+
+def _check_scans(scan0, scan1):
+    for s, scan in enumerate((scan0, scan1)):
+        for k in ("coordinates", "features", "sem_labels"):
+            if k not in scan:
+                raise KeyError(f"scan {s} has no '{k}'")
+        for k in ("coordinates",) + _MERGE_COLUMNS:
+            if k in scan:
+                _lib.require_gpu(scan[k], f"scan {s} '{k}'")
+    for k in ("xyz", "sampled_idx", "idx"):
+        if (k in scan0) != (k in scan1):
+            raise KeyError(f"'{k}' in one scan only")
+    return (scan0, scan1)
+
+
+def _device_counts(keys, nbins):
+    """counts of keys in [0, nbins) (lidog_mix_histogram), read back: one small device -> host copy"""
+    counts = torch.empty(max(nbins, 1), dtype=torch.int32, device=keys.device)
+    call("lidog_mix_histogram", ptr(keys), keys.shape[0], nbins, ptr(counts))
+    return counts[:nbins].cpu().numpy().astype(np.int64)
+
+
+def _split(keys, slot_of_key, n_slots):
+    """(rows grouped by slot, slot_start) of lidog_mix_split"""
+    dev = keys.device
+    n = keys.shape[0]
+    table = torch.from_numpy(np.ascontiguousarray(slot_of_key, dtype=np.int32)).to(dev)
+    rows = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    start = torch.empty(n_slots + 1, dtype=torch.int32, device=dev)
+    ws = torch.empty(_lib.load().lidog_mix_split_ws(n, n_slots), dtype=torch.int32, device=dev)
+    call("lidog_mix_split", ptr(keys), n, ptr(table), table.shape[0], n_slots, ptr(rows), ptr(start), ptr(ws))
+    return rows, start
+
+
+def _merge(scan0, scan1, sel, voxel_size, rows, start, n_take, subs=None):
+    """target rows, then the selected source rows (lidog_mix_gather), re-quantised at voxel_size; the reference's dict"""
+    src, tgt = (scan0, scan1) if sel == 0 else (scan1, scan0)
+    dev = tgt["coordinates"].device
+    nt = tgt["coordinates"].shape[0]
+    total = nt + n_take
+    coords_t = tgt["coordinates"].to(torch.int32).contiguous()
+    coords_s = src["coordinates"].to(torch.int32).contiguous()
+    merged = torch.empty((total, 3), dtype=torch.float32, device=dev)
+    cols, ptrs, words = {}, [], []
+    for k in _MERGE_COLUMNS:
+        if k not in tgt:
+            continue
+        t = tgt[k].contiguous()
+        s = src[k].to(t.dtype).contiguous()
+        row_bytes = int(np.prod(t.shape[1:], dtype=np.int64)) * t.element_size()
+        if row_bytes % 4 or t.shape[1:] != s.shape[1:]:
+            raise NotImplementedError(f"'{k}': rows of {row_bytes} bytes ({t.dtype}, {tuple(t.shape[1:])}) "
+                                      f"against {tuple(s.shape[1:])} (whole 32-bit words and equal shapes only)")
+        cols[k] = torch.empty((total,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev)
+        ptrs += [t.data_ptr(), s.data_ptr(), cols[k].data_ptr()]
+        words.append(row_bytes // 4)
+    perm = take = None
+    n_slots = 0 if start is None else start.shape[0] - 1
+    if subs is not None and n_slots:
+        take_start = np.concatenate([[0], np.cumsum([len(p) for p in subs])]).astype(np.int32)
+        buf = torch.from_numpy(np.concatenate([take_start] + [np.asarray(p, dtype=np.int32) for p in subs])).to(dev)
+        take, perm = buf[:n_slots + 1], buf[n_slots + 1:]
+    call("lidog_mix_gather", ptr(coords_t), nt, ptr(coords_s), ptr(rows), ptr(start), ptr(perm), ptr(take), n_slots,
+         n_take, float(np.float32(voxel_size)), ptr(merged), len(words), (ctypes.c_void_p * max(len(ptrs), 1))(*ptrs),
+         (ctypes.c_int32 * max(len(words), 1))(*words))
+    q, index = sparse_quantize(merged, quantization_size=voxel_size, return_index=True)
+    out = {"coordinates": q}
+    for k in ("xyz", "features", "sem_labels"):
+        if k in cols:
+            out[k] = cols[k][index]
+    if "idx" in scan0:
+        out["idx"] = torch.cat([scan0["idx"].view(1, -1), scan1["idx"].view(1, -1)], dim=0)
+    if "sampled_idx" in cols:
+        out["sampled_idx"] = cols["sampled_idx"][index]
+    out["index"] = index
+    out["source"] = sel
+    return out
+
+
+def pointcutmix_merge(scan0, scan1, voxel_size=0.05, ignore_label=-1, rng=np.random, cell_size=10.0, min_points=300,
+                      n_cells=4):
+    """PointCutMixSourceDataset.merge_data (utils/datasets/pointcutmix.py:43-135) on the GPU.
+    scan = dict of device tensors: coordinates int [n,3], features [n,C], sem_labels [n], optionally xyz [n,3],
+    sampled_idx [n], idx.  One scan (`source`, drawn first) is quantised at cell_size (float32 coordinates
+    `coordinates * voxel_size`, as the reference); n_cells of its cells holding more than min_points rows are drawn, and
+    the other scan's rows followed by the rows of those cells (cell by cell in the order drawn, ascending rows inside a
+    cell) are re-quantised at voxel_size.  features / xyz / sem_labels / sampled_idx are those of the first point of
+    every voxel (no label vote, as the reference).  Returns the reference's dict plus `index` (the first point of every
+    voxel in the concatenation) and `source`.  Raises ValueError when fewer than n_cells cells qualify, as the
+    reference's np.random.choice.  `ignore_label` is the reference's argument; its label vote is discarded."""
+    scans = _check_scans(scan0, scan1)
+    sel = draw_source(rng)
+    dev = scan0["coordinates"].device
+
+    def work():
+        src = scans[sel]
+        n = src["coordinates"].shape[0]
+        points = src["coordinates"].to(torch.float32) * voxel_size
+        cells, inverse = sparse_quantize(points, quantization_size=cell_size, return_inverse=True)
+        inverse = inverse.to(torch.int32)
+        counts = _device_counts(inverse, cells.shape[0])
+        chosen = draw_cells(rng, counts, min_points, n_cells)
+        slot_of_cell = np.full(cells.shape[0], -1, dtype=np.int32)
+        slot_of_cell[chosen] = np.arange(len(chosen), dtype=np.int32)
+        rows, start = _split(inverse, slot_of_cell, len(chosen))
+        n_take = int(counts[chosen].sum())
+        assert n_take <= n
+        return _merge(scan0, scan1, sel, voxel_size, rows, start, n_take)
+
+    return on_merge_stream(work, dev, [t for s in scans for t in s.values()])
+
+
+def cosmix_merge(scan0, scan1, voxel_size=0.05, class_weights=None, sub_p=0.8, ignore_label=-1, rng=np.random,
+                 augmentations=None):
+    """CoSMixSourceDataset.merge_data (utils/datasets/cosmix.py:50-171) on the GPU; scans as pointcutmix_merge.
+    class_weights = (w0, w1): per-class point counts of each source's training set (Synth4DDataset.get_dataset_stats,
+    synth4d.py:203-220).  Of the classes present in the drawn source (labels in [0, len(w)); -1 is never a class) half
+    are drawn with probability proportional to their weight; each class's rows (ascending) are sub-sampled by a random
+    permutation prefix of int(sub_p * n_c) rows (sub_p None: all of them, in order) and appended, class by class in the
+    order drawn, to the other scan's rows; the union is re-quantised at voxel_size.  Returns the reference's dict plus
+    `index` and `source`."""
+    if augmentations is not None:
+        raise NotImplementedError("cosmix_merge: augmentations (augmentation_list is null in every shipped config)")
+    if class_weights is None or len(class_weights) != 2:
+        raise ValueError("cosmix_merge needs class_weights = (w0, w1), one per-class count array per source")
+    scans = _check_scans(scan0, scan1)
+    sel = draw_source(rng)
+    weights = np.asarray(class_weights[sel], dtype=np.float64)
+    dev = scan0["coordinates"].device
+
+    def work():
+        labels = scans[sel]["sem_labels"].to(torch.int32).contiguous()
+        counts = _device_counts(labels, weights.shape[0])
+        classes, subs = draw_classes(rng, counts, weights, sub_p)
+        for c, p in zip(classes, subs):      # the gather reads rows[slot_start[s] + p]: p must lie inside the class
+            if len(p) and (int(np.min(p)) < 0 or int(np.max(p)) >= int(counts[c])):
+                raise RuntimeError("cosmix_merge: a sub-sample index outside its class")
+        if len(classes) == 0:
+            return _merge(scan0, scan1, sel, voxel_size, None, None, 0)
+        slot_of_class = np.full(weights.shape[0], -1, dtype=np.int32)
+        slot_of_class[classes] = np.arange(len(classes), dtype=np.int32)
+        rows, start = _split(labels, slot_of_class, len(classes))
+        n_take = int(sum(len(p) for p in subs))
+        return _merge(scan0, scan1, sel, voxel_size, rows, start, n_take, subs if sub_p is not None else None)
+
+    return on_merge_stream(work, dev, [t for s in scans for t in s.values()])

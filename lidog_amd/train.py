@@ -11,12 +11,14 @@ What the reference's entry scripts do through pytorch-lightning, as plain argume
     python -m lidog_amd.train --model MinkUNet34BEV --epochs 2 --scans 16 --batch 4 --save-dir /tmp/run
     python -m torch.distributed.run --nproc-per-node N -m lidog_amd.train ...        (one process per GPU, RCCL)
     python -m lidog_amd.train --sources kitti120k nusc35k --source-weights 0.5 0.5 ...   (two sources, */multi/*.yaml)
+    python -m lidog_amd.train --model MinkUNet34 --mix cosmix ...    (PointCutMix / CoSMix, configs/{pointcutmix,cosmix})
 
 Scans are synthetic (lidog_amd.synth; there are no datasets on the box); anything with `__len__` and
 `batch(indices, device) -> dict` (keys of CollateFNSingleSourceBEVMultiLevel, collation.py:318-325) can be passed as
 `train_data` / `val_data` instead.
 """
 import argparse
+import functools
 import os
 import re
 
@@ -27,6 +29,7 @@ import torch.distributed as dist
 from . import me as ME
 from . import synth
 from .checkpoint import load_training_checkpoint, save_lightning_checkpoint
+from .data import cosmix_merge, on_merge_stream, pointcutmix_merge
 from .evaluate import per_class_iou
 from .optim import make_optimizer, make_scheduler, shard_indices
 from .trainer import LiDOGStep, RobustStep, SourceStep, setup_data_parallel
@@ -77,6 +80,84 @@ class MultiSynthScans:
         pairs = [self.pair(i) for i in indices]
         return synth.make_batch([self.first + a for a, _ in pairs], self.configs[0], device, bev_size=self.bev_size,
                                 mix3d=self.mix3d, seeds1=[self.first + b for _, b in pairs], config1=self.configs[1])
+
+
+class MixedSynthScans:
+    """PointCutMixSourceDataset / CoSMixSourceDataset (utils/datasets/pointcutmix.py, cosmix.py; train_aug_based.py:
+    97-102): two sources paired as MultiSynthScans.pair, each item ONE scan merged from its pair on the GPU
+    (lidog_amd.data.pointcutmix_merge / cosmix_merge), so a batch is a one-source batch (num_sources = 1) with the keys
+    SourceStep reads.  The draws of item i in epoch e come from np.random.RandomState([seed, e, i]): a mix does not depend
+    on the world size, the batch split or a resume (Fit calls set_epoch).  The scans are uploaded and merged on
+    data.merge_stream, and the batch is handed to the caller's stream with an event: the merges' read-backs do not wait
+    for a training step queued earlier.  CoSMix's class weights are the per-class label counts over each source's
+    training scans (get_dataset_stats, synth4d.py:203-220); the voxel size is source 0's, as the reference's."""
+
+    num_sources = 1
+    METHODS = ("pointcutmix", "cosmix")
+
+    def __init__(self, n0, n1, configs=("kitti120k", "kitti120k"), method="cosmix", sub_p=0.8, seed=1234, first=0,
+                 num_classes=7):
+        if method not in self.METHODS:
+            raise NotImplementedError(f"mixing method {method!r} (one of {self.METHODS})")
+        self.pairs = MultiSynthScans(n0, n1, configs, seed=seed, first=first)
+        self.configs, self.method, self.sub_p, self.seed, self.first = tuple(configs), method, sub_p, int(seed), first
+        self.voxel = synth.CONFIGS[self.configs[0]]["voxel"]
+        self.epoch = 0
+        if method == "pointcutmix":
+            self.merge = functools.partial(pointcutmix_merge, voxel_size=self.voxel)
+        else:
+            self.class_weights = tuple(
+                source_class_counts(c, [first + j + s * synth.SOURCE1_SEED for j in range(n)], num_classes)
+                for s, (c, n) in enumerate(zip(self.configs, (n0, n1))))
+            self.merge = functools.partial(cosmix_merge, voxel_size=self.voxel, class_weights=self.class_weights,
+                                           sub_p=sub_p)
+
+    def __len__(self):
+        return len(self.pairs)
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def item_rng(self, i):
+        return np.random.RandomState([self.seed, self.epoch, int(i)])
+
+    def _scan(self, s, j, device):
+        vox, labels = synth.scan_voxels(self.first + j + s * synth.SOURCE1_SEED, self.configs[s])
+        return {"coordinates": torch.from_numpy(vox).to(device),
+                "features": torch.ones((vox.shape[0], 1), dtype=torch.float32, device=device),
+                "sem_labels": torch.from_numpy(labels).to(device)}
+
+    def _batch(self, indices, device):
+        coords, feats, labels = [], [], []
+        for b, i in enumerate(indices):
+            j0, j1 = self.pairs.pair(i)
+            m = self.merge(self._scan(0, j0, device), self._scan(1, j1, device), rng=self.item_rng(i))
+            c = m["coordinates"].to(torch.int32)
+            coords.append(torch.cat([torch.full((c.shape[0], 1), b, dtype=torch.int32, device=c.device), c], dim=1))
+            feats.append(m["features"])
+            labels.append(m["sem_labels"].long())
+        coords = torch.cat(coords)
+        return {"coords_int": coords, "source_coordinates0": coords.float(), "source_features0": torch.cat(feats),
+                "source_sem_labels0": torch.cat(labels)}
+
+    def batch(self, indices, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            return self._batch(indices, device)
+        # the scans are made on the merge stream itself: it does not wait for the caller's stream
+        return on_merge_stream(lambda: self._batch(indices, device), device, wait=False)
+
+
+def source_class_counts(config, seeds, num_classes=7):
+    """Synth4DDataset.get_dataset_stats (synth4d.py:203-220) over synthetic scans: per-class label counts, the ignore
+    label (-1) left out"""
+    w = np.zeros(num_classes)
+    for s in seeds:
+        _, labels = synth.scan_voxels(s, config)
+        lbl, count = np.unique(labels, return_counts=True)
+        keep = (lbl >= 0) & (lbl < num_classes)
+        w[lbl[keep]] += count[keep]
+    return w
 
 
 def source_names(configs):
@@ -251,6 +332,8 @@ class Fit:
             s = self.validate(-1, limit=self.sanity)            # num_sanity_val_steps=2 (train_lidog.py:294)
             self.log(f"sanity validation: {s}")
         for epoch in range(self.epoch, self.epochs):
+            if hasattr(self.train_data, "set_epoch"):
+                self.train_data.set_epoch(epoch)
             batches = self._epoch_batches(self.train_data, epoch, self.shuffle)
             cur = self.train_data.batch(batches[0], self.device) if batches else None
             losses = []
@@ -300,12 +383,25 @@ def parse_args(argv=None):
                          "MultiBEVSourceDataset; each source is validated on its own")
     ap.add_argument("--source-weights", nargs=2, type=float, default=(0.5, 0.5))
     ap.add_argument("--mix3d", action="store_true")
+    ap.add_argument("--mix", default=None, choices=MixedSynthScans.METHODS,
+                    help="PointCutMix / CoSMix (train_aug_based.py, pipeline.method): each item one scan mixed from a "
+                         "pair of the two --sources (default: --config twice), trained as one source with SoftDICE")
+    ap.add_argument("--sub-p", type=float, default=0.8, help="CoSMix: share of each drawn class's rows mixed in")
     ap.add_argument("--check-val-every-n-epoch", type=int, default=5)
     ap.add_argument("--save-dir", default=None)
     ap.add_argument("--resume", default=None)
     ap.add_argument("--auto-resume", action="store_true")
     ap.add_argument("--seed", type=int, default=1234)
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.mix is not None:
+        if a.model in ("MinkUNet34BEV", "MinkUNet34Robust"):   # PLTMixed.training_step: SoftDICE only
+            ap.error(f"--mix trains with the SoftDICE-only step of PLTMixed: --model MinkUNet34 or MinkUNet34IBN, "
+                     f"not {a.model}")
+        if a.mix3d:
+            ap.error("--mix and --mix3d are two different methods (pipeline.method): pass one of them")
+        if a.sources is None:
+            a.sources = [a.config, a.config]    # the single configs list one dataset twice
+    return a
 
 
 def main(argv=None):
@@ -324,7 +420,11 @@ def _fit_from_args(a):
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))
     bev = bev_image_size(a.bound)
-    if a.sources:
+    if getattr(a, "mix", None):
+        train = MixedSynthScans(a.scans, a.scans, a.sources, method=a.mix, sub_p=a.sub_p, seed=a.seed)
+        val = {name: SynthScans(a.val_scans, c, first=10 ** 6 + i * synth.SOURCE1_SEED, bev_size=bev)
+               for i, (name, c) in enumerate(zip(source_names(a.sources), a.sources))} if a.val_scans else None
+    elif a.sources:
         train = MultiSynthScans(a.scans, a.scans, a.sources, seed=a.seed, mix3d=a.mix3d, bev_size=bev)
         val = {name: SynthScans(a.val_scans, c, first=10 ** 6 + i * synth.SOURCE1_SEED, mix3d=a.mix3d, bev_size=bev)
                for i, (name, c) in enumerate(zip(source_names(a.sources), a.sources))} if a.val_scans else None

@@ -35,7 +35,8 @@ extern "C" int lidog_bev_winner(const int32_t *coords, int64_t n, const int32_t 
 
 // out[b][c'][yo][xo] = max over the pool window of V[c'][yy][xx], V = the [H,W,C] image of sample b
 // read through view(C,H,W): flat f = c'*H*W + yy*W + xx  ->  pixel f / C, feature channel f % C.
-// Ties keep the first cell in window scan order (torch max_pool2d uses a strict >).  PK >= pool kernel size.
+// Ties keep the first cell in window scan order, and a NaN is taken whenever it is met, so the last NaN of a window
+// wins (torch max_pool2d's rule: `v > best || isnan(v)`).  PK >= pool kernel size.
 struct PoolGeom {
     int C, H, W, pk, ps, pp, Ho, Wo, w_div_c, w_mod_c;
     uint64_t c_magic;  // ceil(2^40 / C): x / C = (x * c_magic) >> 40, exact while x * C < 2^40
@@ -98,7 +99,7 @@ __device__ __forceinline__ void pool_one(const float *__restrict__ feats, const 
                 for (int i = 0; i < PK; ++i) v[i] = feats[base + (i < seg ? i : 0)];
 #pragma unroll
                 for (int i = 0; i < PK; ++i)
-                    if (i < seg && v[i] > best) {
+                    if (i < seg && (v[i] > best || isnan(v[i]))) {
                         best = v[i];
                         src = base + i;
                     }
@@ -114,7 +115,7 @@ __device__ __forceinline__ void pool_one(const float *__restrict__ feats, const 
                 s = row * C + ch;
                 v = feats[(int64_t)s];
             }
-            if (v > best) {
+            if (v > best || isnan(v)) {
                 best = v;
                 src = s;
             }
@@ -205,6 +206,7 @@ extern "C" int lidog_bev_pool_fwd(const float *feats, int32_t C, const int32_t *
     LIDOG_REQUIRE(pk >= 1 && pk <= 8 && ps >= 1, "bev_pool_fwd: pool kernel size must be 1..8");
     LIDOG_REQUIRE(2 * pp <= pk, "bev_pool_fwd: padding must be at most half the kernel size (as torch requires)");
     LIDOG_REQUIRE((int64_t)H * W < ((int64_t)1 << 24), "bev_pool_fwd: H*W must stay below 2^24");
+    LIDOG_REQUIRE(n * C < ((int64_t)1 << 31), "bev_pool_fwd: n*C must stay below 2^31 (int32 cell indices)");
     hipStream_t st = (hipStream_t)stream;
     // windows without an occupied pixel: max over zeros = 0, no source cell
     if (hipMemsetAsync(out, 0, sizeof(float) * (size_t)total, st) != hipSuccess) return 1;
@@ -282,6 +284,7 @@ extern "C" int lidog_bev_pool_bwd(const float *gout, const int32_t *argsrc, cons
     if (n == 0) return 0;
     LIDOG_REQUIRE((int64_t)H * W * C < ((int64_t)1 << 31), "bev_pool_bwd: C*H*W must stay below 2^31");
     LIDOG_REQUIRE(pk >= 1 && pk <= 8 && ps >= 1 && 2 * pp <= pk, "bev_pool_bwd: bad pooling geometry");
+    LIDOG_REQUIRE(n * C < ((int64_t)1 << 31), "bev_pool_bwd: n*C must stay below 2^31 (int32 cell indices)");
     PoolGeom g;
     g.C = C; g.H = H; g.W = W; g.pk = pk; g.ps = ps; g.pp = pp; g.Ho = Ho; g.Wo = Wo;
     g.w_div_c = W / C; g.w_mod_c = W % C;

@@ -702,6 +702,31 @@ int lidog_mix_gather(const int32_t *coords_t, int64_t n_target, const int32_t *c
                      int64_t n_take, float voxel_size, float *coords_out, int32_t n_cols, void *const *cols_host,
                      const int32_t *col_words_host, void *stream);
 
+/* ------------------------------------------------------------------ SN car-size scaling: DBSCAN, cluster boxes, scaling
+ * The start-up statistics of train_scaling_based.py:35-129 (get_average_dims clusters the car voxels of every drawn
+ * scan with sklearn.cluster.DBSCAN) and the per-item scaling of utils/datasets/sn_scaling.py.  Integer atomics whose
+ * result does not depend on their order only: the same bytes on every run. */
+/* bytes of workspace lidog_dbscan needs for n points */
+int64_t lidog_dbscan_ws(int64_t n);
+/* labels [n] (device, int32) = sklearn.cluster.DBSCAN(eps, min_samples).fit_predict(x), x = float32(coords) *
+ * float32(voxel_size) (`coordinates * voxel_size`, train_scaling_based.py:46), label for label: -1 noise, clusters
+ * numbered in the order of their smallest core row, a border point in the smallest-numbered cluster it touches.  Two
+ * points are neighbours when sum_k (double(x_i[k]) - double(x_j[k]))^2 <= eps^2 in float64 (a point is its own
+ * neighbour).  coords [n, 3] int32, distinct rows, |c| <= 65535.  info [2] (device, int32): info[0] = 0, or 1 (a
+ * coordinate out of range) or 2 (the grid of eps-sized cells over the bounding box has more than 2^32 cells) and then
+ * labels are not written; info[1] = the number of clusters.  n = 0: info zeroed, nothing else touched. */
+int lidog_dbscan(const int32_t *coords, int64_t n, float voxel_size, double eps, int32_t min_samples, int32_t *labels,
+                 int32_t *info, void *ws, int64_t ws_bytes, void *stream);
+/* counts [k] (int64), lo / hi [k, 3] (int32): rows and per-axis minimum / maximum coordinate of every label in [0, k)
+ * (other labels are skipped; a label without rows keeps count 0, lo INT32_MAX, hi INT32_MIN).  The integer form of
+ * np.sum(cluster_idx == c) and np.min / np.max of the cluster's columns (train_scaling_based.py:58-79). */
+int lidog_cluster_boxes(const int32_t *coords, const int32_t *labels, int64_t n, int32_t k, int64_t *counts,
+                        int32_t *lo, int32_t *hi, void *stream);
+/* out [n, 3] float32 = (float(coords) * voxel_size) * (sx, sy, sz), each product rounded to float32
+ * (sn_scaling.py:39,53-55 / :109-110,133-139): the input of the item's re-quantisation */
+int lidog_sn_scale_coords(const int32_t *coords, int64_t n, float voxel_size, float sx, float sy, float sz, float *out,
+                          void *stream);
+
 #ifdef __cplusplus
 }
 #endif

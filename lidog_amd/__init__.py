@@ -7,6 +7,7 @@ Public surface:
   lidog_amd.losses        SoftDICELoss / DICELoss on the device
   lidog_amd.trainer       training step, Adam, RCCL data parallelism
   lidog_amd.trunk         the whole encoder-decoder as one launch sequence per pass (csrc/trunk.hip)
+  lidog_amd.cluster       DBSCAN and per-cluster boxes on the device (csrc/cluster.hip; the SN baseline's statistics)
 """
 import os as _os
 

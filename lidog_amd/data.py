@@ -10,8 +10,11 @@ The reference runs these in DataLoader worker processes with numpy; at >50 scans
 bottleneck, and both are the same hash / winner-map kernels as the hot path.
 
   pointcutmix_merge, cosmix_merge   PointCutMix / CoSMix scan mixing (utils/datasets/pointcutmix.py, cosmix.py), below
+  average_dims, scaling_params, sn_scale   the SN car-size scaling baseline (train_scaling_based.py:35-129,
+                   utils/datasets/sn_scaling.py), at the end
 """
 import ctypes
+import os
 
 import numpy as np
 import torch
@@ -363,3 +366,166 @@ def cosmix_merge(scan0, scan1, voxel_size=0.05, class_weights=None, sub_p=0.8, i
         return _merge(scan0, scan1, sel, voxel_size, rows, start, n_take, subs if sub_p is not None else None)
 
     return on_merge_stream(work, dev, [t for s in scans for t in s.values()])
+
+
+# ------------------------------------------------------------------ SN (statistical normalisation): car-size scaling
+# train_scaling_based.py:35-129 and utils/datasets/sn_scaling.py.  At start-up the car voxels (class 0) of 20 % of every
+# dataset's scans are clustered (lidog_amd.cluster.dbscan in place of sklearn's DBSCAN) and the mean (width, height,
+# length) of the car-shaped clusters gives one per-axis scale per (source, target) pair; every training item is then
+# scaled and re-quantised.  `c -> float32(c) * float32(voxel)` is monotone, so the device returns integer boxes and
+# counts and the host finishes the handful of floats with the reference's own numpy expressions: bit-equal by
+# construction.  The reference's names are kept: "height" is the y extent, "l" the z extent of a cluster.
+
+NUSCENES_NAME = "NuScenesDataset"      # the dataset name that switches get_average_dims to min_pts 2000, min_car_pts 300
+
+
+def draw_scans(rng, n):
+    """train_scaling_based.py:37-38: 20 % of the scans, drawn with replacement"""
+    selected_idx = np.arange(n)
+    return rng.choice(selected_idx, int(0.2 * selected_idx.shape[0]))
+
+
+def sn_thresholds(name, min_pts=5000, min_car_pts=1000):
+    """train_scaling_based.py:40-42"""
+    return (2000, 300) if name == NUSCENES_NAME else (min_pts, min_car_pts)
+
+
+def box_dims(counts, lo, hi, voxel_size, min_car_pts):
+    """train_scaling_based.py:61-85 from the integer boxes of one scan's clusters (counts [k], lo / hi [k, 3]): the
+    float32 rows [[width, height, length]] of the clusters of more than min_car_pts voxels that look like a car"""
+    rows = []
+    lo_f = torch.from_numpy(np.ascontiguousarray(lo, dtype=np.int32)) * voxel_size     # `coordinates * voxel_size`:
+    hi_f = torch.from_numpy(np.ascontiguousarray(hi, dtype=np.int32)) * voxel_size     # an int tensor times a float
+    lo_f, hi_f = lo_f.numpy(), hi_f.numpy()
+    for c in range(len(counts)):
+        if counts[c] > min_car_pts:
+            w = hi_f[c, 0] - lo_f[c, 0]
+            height = hi_f[c, 1] - lo_f[c, 1]
+            l = hi_f[c, 2] - lo_f[c, 2]
+            length = np.max([w, l])
+            width = np.min([w, l])
+            if 1 < width < 4 and 1 < height < 4 and 3 < length < 7:
+                rows.append(np.array([width, height, length])[np.newaxis, ...])
+    return rows
+
+
+def mean_dims(rows):
+    """train_scaling_based.py:87; no kept box: the ValueError np.concatenate raises on an empty list"""
+    return np.mean(np.concatenate(rows, axis=0), axis=0)
+
+
+def average_dims(dataset, rng=np.random, min_pts=5000, min_cluster_pts=50, min_car_pts=1000, car_class=0,
+                 device="cuda", record=None):
+    """get_average_dims (train_scaling_based.py:35-87) with the clustering on the GPU.  `dataset`: `len`, `name`,
+    `voxel_size` and items with `coordinates` (int [n, 3]) and `sem_labels` ([n]), tensors or arrays anywhere (they are
+    moved to `device`).  The scans are drawn on the host in the reference's sequence, so `np.random.seed(s)` selects
+    the same scans; a scan is clustered only with MORE than min_pts car voxels, a cluster counts only with MORE than
+    min_car_pts voxels (2000 / 300 for a dataset named 'NuScenesDataset'); min_cluster_pts is accepted and unused, as
+    in the reference.  Returns the float32 mean [width, height, length] of the kept boxes; none kept: ValueError.
+    `record`: a list that receives (scan, counts, lo, hi) of every clustered scan."""
+    from . import cluster
+    selected = draw_scans(rng, len(dataset))
+    min_pts, min_car_pts = sn_thresholds(dataset.name, min_pts, min_car_pts)
+    voxel = dataset.voxel_size
+    dev = torch.device(device)
+    rows = []
+
+    def work(item):
+        coords = torch.as_tensor(item["coordinates"]).to(dev)
+        labels = torch.as_tensor(item["sem_labels"]).to(dev)
+        car = torch.nonzero(labels == car_class).view(-1)
+        if car.shape[0] <= min_pts:           # the shape is known to the host: torch.nonzero has read it
+            return None
+        car_pts = coords[car].to(torch.int32).contiguous()
+        labels, k = cluster.dbscan_count(car_pts, voxel, eps=0.5, min_samples=10)
+        counts, lo, hi = cluster.cluster_boxes(car_pts, labels, k)
+        return [counts.cpu().numpy(), lo.cpu().numpy(), hi.cpu().numpy()]
+
+    for s in selected:
+        item = dataset[int(s)]
+        if dev.type == "cuda":                # what comes back is host arrays: nothing to hand to the caller's stream
+            side = merge_stream(dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):
+                boxes = work(item)
+        else:
+            boxes = work(item)
+        if boxes is None:
+            continue
+        if record is not None:
+            record.append((int(s), *boxes))
+        rows += box_dims(*boxes, voxel, min_car_pts)
+    return mean_dims(rows)
+
+
+def scaling_params(sources, targets, cache_dir=None, **kw):
+    """get_scaling_params (train_scaling_based.py:90-129): one float32 [n_targets, 3] array per source, target / source
+    per component.  An entry of `sources` / `targets` is either the average dimensions of a dataset (an array of 3) or
+    a dataset, whose average_dims(dataset, **kw) is then computed, sources first, and with `cache_dir` kept in
+    `<cache_dir>/<dataset.name.lower()>.npy` as the reference keeps it in utils/datasets/_avg_sizes."""
+    def dims(d):
+        if isinstance(d, np.ndarray):
+            return d
+        if cache_dir is None:
+            return average_dims(d, **kw)
+        os.makedirs(cache_dir, exist_ok=True)
+        path = os.path.join(cache_dir, d.name.lower() + ".npy")
+        if not os.path.exists(path):
+            np.save(path, average_dims(d, **kw))
+        return np.load(path)
+
+    source_avg_shape = [dims(d) for d in sources]
+    target_avg_shape = [dims(d) for d in targets]
+    scaling_set = []
+    for s_avg_tmp in source_avg_shape:
+        scaling_tmp = []
+        for t_avg_tmp in target_avg_shape:
+            scaling_tmp.append(np.array([t_avg_tmp[0] / s_avg_tmp[0], t_avg_tmp[1] / s_avg_tmp[1],
+                                         t_avg_tmp[2] / s_avg_tmp[2]])[np.newaxis, ...])
+        scaling_set.append(np.concatenate(scaling_tmp, axis=0))
+    return scaling_set
+
+
+def draw_scaling(rng, scaling_list, num_sources):
+    """the scale rows of one item.  One source (SingleSNSourceDataset.__getitem__, sn_scaling.py:46-51):
+    `len(self.scaling_list) > 1` tests the number of SOURCES, which is one, so the first target's row is always taken
+    and nothing is drawn.  Two sources (MultiSNSourceDataset.merge_data, :124-131): one target row per source, drawn with
+    np.random.choice, source 0 first."""
+    if num_sources == 1:
+        if len(scaling_list) > 1:
+            return [scaling_list[rng.choice(np.arange(len(scaling_list)))][0]]
+        return [scaling_list[0][0]]
+    i0 = rng.choice(np.arange(scaling_list[0].shape[0]))
+    i1 = rng.choice(np.arange(scaling_list[1].shape[0]))
+    return [scaling_list[0][i0], scaling_list[1][i1]]
+
+
+def sn_scale(scan, scaling, voxel_size=0.05, ignore_label=-1):
+    """The item of SingleSNSourceDataset.__getitem__ (sn_scaling.py:36-71), one half of MultiSNSourceDataset.merge_data
+    (:107-175): x = coordinates * voxel_size in float32, x[:, k] *= float32(scaling[k]) in float32, re-quantised at
+    voxel_size; features and labels are those of the FIRST point of every voxel (the voted labels are discarded, as in
+    mix3d_merge); xyz / sampled_idx / idx pass through untouched, as in the reference.  `scan`: dict of device tensors
+    (coordinates int [n, 3], features [n, C], sem_labels [n]).  Returns the reference's dict plus `index`, the first
+    point of every voxel.  `ignore_label` is the reference's argument; its label vote is discarded."""
+    for k in ("coordinates", "features", "sem_labels"):
+        if k not in scan:
+            raise KeyError(f"scan has no '{k}'")
+        _lib.require_gpu(scan[k], f"scan '{k}'")
+    sc = np.asarray(scaling, dtype=np.float32).reshape(3)
+    dev = scan["coordinates"].device
+
+    def work():
+        coords = scan["coordinates"].to(torch.int32).contiguous()
+        n = coords.shape[0]
+        x = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        call("lidog_sn_scale_coords", ptr(coords), n, float(np.float32(voxel_size)), float(sc[0]), float(sc[1]),
+             float(sc[2]), ptr(x))
+        q, index = sparse_quantize(x, quantization_size=voxel_size, return_index=True)
+        out = {"coordinates": q, "features": scan["features"][index], "sem_labels": scan["sem_labels"][index]}
+        for k in ("xyz", "idx", "sampled_idx"):
+            if k in scan:
+                out[k] = scan[k]
+        out["index"] = index
+        return out
+
+    return on_merge_stream(work, dev, [t for t in scan.values()])

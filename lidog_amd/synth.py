@@ -17,10 +17,51 @@ CONFIGS = {
     "source8k": dict(n_beams=16, n_az=500, elev=(-24.8, 2.0), h=1.73, voxel=0.1, lidog_bounds=False),
     "nusc35k": dict(n_beams=32, n_az=1090, elev=(-30.0, 10.0), h=1.84, voxel=0.05, lidog_bounds=False),
     "highres524k": dict(n_beams=128, n_az=4096, elev=(-24.8, 2.0), h=1.73, voxel=0.02, lidog_bounds=True),
+    # the same sensors over a scene with parked cars (`cars`: size factor of the boxes): the scans of the SN car-size
+    # scaling baseline (train_scaling_based.py), whose statistics need voxels labelled car (class 0)
+    "kitti120k_cars": dict(n_beams=64, n_az=1875, elev=(-24.8, 2.0), h=1.73, voxel=0.05, lidog_bounds=True, cars=1.0,
+                           dataset="SemanticKITTIDataset"),
+    "nusc35k_cars": dict(n_beams=32, n_az=1090, elev=(-30.0, 10.0), h=1.84, voxel=0.05, lidog_bounds=False, cars=1.1,
+                         dataset="NuScenesDataset"),
 }
+CAR_CLASS = 0
+
+
+def car_boxes(seed, scale=1.0):
+    """axis-aligned car-sized boxes resting on the ground, drawn from the scan's seed (a stream of its own: the scan's
+    other draws do not move): 1 to 7 boxes, centre 5-14 m from the sensor, 3.8-5.0 x 1.6-2.0 x 1.4-1.8 m times `scale`,
+    the long side along x or y.  Rows (cx, cy, half x, half y, height)."""
+    rng = np.random.default_rng([int(seed), 0xCA5])
+    n = int(rng.integers(1, 8))
+    dist, ang = rng.uniform(5.0, 14.0, n), rng.uniform(0.0, 2 * np.pi, n)
+    size = np.stack([rng.uniform(3.8, 5.0, n), rng.uniform(1.6, 2.0, n), rng.uniform(1.4, 1.8, n)], axis=1) * scale
+    along_y = rng.random(n) < 0.35
+    hx = np.where(along_y, size[:, 1], size[:, 0]) / 2
+    hy = np.where(along_y, size[:, 0], size[:, 1]) / 2
+    return np.stack([dist * np.cos(ang), dist * np.sin(ang), hx, hy, size[:, 2]], axis=1)
+
+
+def _box_range(boxes, h, dirs):
+    """range at which each ray (unit directions [..., 3] from the sensor at the origin, ground at z = -h) enters the
+    nearest box (slab test), inf where it enters none"""
+    best = np.full(dirs.shape[:-1], np.inf)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        inv = 1.0 / dirs
+        for cx, cy, hx, hy, height in boxes:
+            lo = np.array([cx - hx, cy - hy, -h]) * inv
+            hi = np.array([cx + hx, cy + hy, -h + height]) * inv
+            t0 = np.nanmax(np.minimum(lo, hi), axis=-1)
+            t1 = np.nanmin(np.maximum(lo, hi), axis=-1)
+            best = np.where((t0 > 0) & (t0 <= t1), np.minimum(best, t0), best)
+    return best
 
 
 def scan_points(seed, n_beams, n_az, elev, h, **_):
+    return _scan(seed, n_beams, n_az, elev, h)[:2]
+
+
+def _scan(seed, n_beams, n_az, elev, h, boxes=None):
+    """(points, the scan's generator after its draws, per point: hit a box)"""
     rng = np.random.default_rng(seed)
     el = np.deg2rad(np.linspace(elev[0], elev[1], n_beams))
     # evenly spaced azimuths (a spinning sensor fires at a fixed angular step): this is the generator behind the
@@ -33,20 +74,31 @@ def scan_points(seed, n_beams, n_az, elev, h, **_):
     r_wall = wall[sector] / np.cos(EL)
     with np.errstate(divide="ignore"):
         r_ground = np.where(EL < 0, h / np.sin(-EL), np.inf)
-    r = np.minimum(r_ground, r_wall) + rng.normal(0.0, 0.02, EL.shape)
+    r = np.minimum(r_ground, r_wall)
+    car = np.zeros(EL.shape, dtype=bool)
+    if boxes is not None:     # a box is hit before ground or wall
+        dirs = np.stack([np.cos(EL) * np.cos(AZ), np.cos(EL) * np.sin(AZ), np.sin(EL)], axis=-1)
+        r_box = _box_range(boxes, h, dirs)
+        car = r_box < r
+        r = np.minimum(r, r_box)
+    r = r + rng.normal(0.0, 0.02, EL.shape)
     pts = np.stack([r * np.cos(EL) * np.cos(AZ), r * np.cos(EL) * np.sin(AZ), r * np.sin(EL)], axis=-1)
     pts = pts.reshape(-1, 3).astype(np.float32)
-    return pts[(pts ** 2).sum(axis=1) < 50.0 ** 2], rng
+    keep = (pts ** 2).sum(axis=1) < 50.0 ** 2
+    return pts[keep], rng, car.reshape(-1)[keep]
 
 
-def voxelize(pts, voxel, lidog_bounds):
+def voxelize(pts, voxel, lidog_bounds, return_index=False):
+    """`return_index`: also the row (of `pts`) of the first point of every voxel"""
+    rows = np.arange(pts.shape[0])
     if lidog_bounds:
         x, y, z = pts[:, 0], pts[:, 1], pts[:, 2]
         keep = (np.abs(x) < 60) & (np.abs(y) < 60) & (z > -10) & (z < 8) & ~((np.abs(x) < 3) & (np.abs(y) < 2))
-        pts = pts[keep]
+        pts, rows = pts[keep], rows[keep]
     vox = np.floor(pts / np.float32(voxel)).astype(np.int32)
     _, first = np.unique(vox, axis=0, return_index=True)
-    return vox[np.sort(first)]
+    first = np.sort(first)
+    return (vox[first], rows[first]) if return_index else vox[first]
 
 
 # voxels per tensor stride 1/2/4/8/16 of scan seed 0 (SURVEY.md 8(d), BASELINE.md section 2)
@@ -66,9 +118,22 @@ def stride_counts(vox):
 def scan_voxels(seed, config="kitti120k"):
     """(coords int32 [n,3], labels int64 [n]) of synthetic scan `seed`"""
     cfg = CONFIGS[config]
+    if cfg.get("cars") is not None:
+        return _car_scan_voxels(seed, cfg)
     pts, rng = scan_points(seed, **cfg)
     vox = voxelize(pts, cfg["voxel"], cfg["lidog_bounds"])
     labels = rng.integers(-1, 7, vox.shape[0])
+    return vox, labels
+
+
+def _car_scan_voxels(seed, cfg):
+    """a `_cars` configuration: a voxel whose first point hit a box is a car (class 0); every other voxel draws its
+    label from -1, 1..6, so no other voxel is"""
+    pts, rng, car = _scan(seed, cfg["n_beams"], cfg["n_az"], cfg["elev"], cfg["h"], boxes=car_boxes(seed, cfg["cars"]))
+    vox, first = voxelize(pts, cfg["voxel"], cfg["lidog_bounds"], return_index=True)
+    labels = rng.integers(-1, 6, vox.shape[0])
+    labels[labels >= 0] += 1
+    labels[car[first]] = CAR_CLASS
     return vox, labels
 
 

@@ -12,6 +12,7 @@ What the reference's entry scripts do through pytorch-lightning, as plain argume
     python -m torch.distributed.run --nproc-per-node N -m lidog_amd.train ...        (one process per GPU, RCCL)
     python -m lidog_amd.train --sources kitti120k nusc35k --source-weights 0.5 0.5 ...   (two sources, */multi/*.yaml)
     python -m lidog_amd.train --model MinkUNet34 --mix cosmix ...    (PointCutMix / CoSMix, configs/{pointcutmix,cosmix})
+    python -m lidog_amd.train --model MinkUNet34 --config kitti120k_cars --sn-targets nusc35k_cars ...   (SN, configs/SN)
 
 Scans are synthetic (lidog_amd.synth; there are no datasets on the box); anything with `__len__` and
 `batch(indices, device) -> dict` (keys of CollateFNSingleSourceBEVMultiLevel, collation.py:318-325) can be passed as
@@ -29,7 +30,7 @@ import torch.distributed as dist
 from . import me as ME
 from . import synth
 from .checkpoint import load_training_checkpoint, save_lightning_checkpoint
-from .data import cosmix_merge, on_merge_stream, pointcutmix_merge
+from .data import cosmix_merge, draw_scaling, on_merge_stream, pointcutmix_merge, scaling_params, sn_scale
 from .evaluate import per_class_iou
 from .optim import make_optimizer, make_scheduler, shard_indices
 from .trainer import LiDOGStep, RobustStep, SourceStep, setup_data_parallel
@@ -139,6 +140,109 @@ class MixedSynthScans:
         coords = torch.cat(coords)
         return {"coords_int": coords, "source_coordinates0": coords.float(), "source_features0": torch.cat(feats),
                 "source_sem_labels0": torch.cat(labels)}
+
+    def batch(self, indices, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            return self._batch(indices, device)
+        # the scans are made on the merge stream itself: it does not wait for the caller's stream
+        return on_merge_stream(lambda: self._batch(indices, device), device, wait=False)
+
+
+class SynthDataset:
+    """the face of a reference dataset that the SN statistics read (train_scaling_based.py:35-87): `name`, `voxel_size`,
+    `len` and items with `coordinates` and `sem_labels`, over `n` synthetic scans (scan i = seed `first + i`).  The name
+    is the configuration's `dataset` when it has one ('NuScenesDataset' switches get_average_dims' thresholds)."""
+
+    def __init__(self, n, config, first=0):
+        self.n, self.config, self.first = int(n), config, int(first)
+        self.name = synth.CONFIGS[config].get("dataset", config)
+        self.voxel_size = synth.CONFIGS[config]["voxel"]
+        self.ignore_label = -1
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, i):
+        vox, labels = synth.scan_voxels(self.first + int(i), self.config)
+        return {"coordinates": torch.from_numpy(vox), "sem_labels": torch.from_numpy(labels)}
+
+
+class ScaledSynthScans:
+    """SingleSNSourceDataset / MultiSNSourceDataset (utils/datasets/sn_scaling.py; train_scaling_based.py:253-264) over
+    synthetic scans: every item is a source scan whose coordinates are scaled per axis by (target car size / source car
+    size) and re-quantised on the GPU (lidog_amd.data.sn_scale).  One source: a one-source batch with the keys
+    SourceStep reads; two sources: paired as MultiSynthScans.pair, a two-source batch.
+    The car sizes are computed once, here, on the device (lidog_amd.data.average_dims over the `n` training scans of
+    every source, then over `n_target` scans of every target, which start at scan 10^6 as the validation scans do: the
+    reference takes its targets' validation split), with the draws of np.random.RandomState(seed); `scaling` (the list
+    scaling_params returns) skips that.  Quirks kept: with ONE source the first target's row is always applied
+    (sn_scaling.py:46-51 tests the number of sources); with two, each item draws one target row per source.  Item i of
+    epoch e draws from np.random.RandomState([seed, e, i]), as MixedSynthScans: a batch does not depend on the world
+    size, the batch split or a resume."""
+
+    def __init__(self, n, configs, targets, seed=1234, first=0, n_target=None, scaling=None, device="cuda",
+                 cache_dir=None):
+        configs = (configs,) if isinstance(configs, str) else tuple(configs)
+        if len(configs) not in (1, 2):
+            raise NotImplementedError(f"{len(configs)} sources (the reference takes one or two)")
+        if not targets:
+            raise ValueError("ScaledSynthScans needs at least one target configuration")
+        self.configs, self.targets = configs, tuple(targets)
+        self.num_sources = len(configs)
+        self.n, self.seed, self.first, self.epoch = int(n), int(seed), int(first), 0
+        self.pairs = MultiSynthScans(n, n, configs, seed=seed, first=first) if self.num_sources == 2 else None
+        self.voxel = synth.CONFIGS[configs[0]]["voxel"]      # the reference's self.voxel_size = source_dataset0.voxel_size
+        if scaling is None:
+            rng = np.random.RandomState(self.seed)
+            sources = [SynthDataset(n, c, first + s * synth.SOURCE1_SEED) for s, c in enumerate(configs)]
+            tgts = [SynthDataset(n if n_target is None else n_target, c, 10 ** 6 + t * synth.SOURCE1_SEED)
+                    for t, c in enumerate(self.targets)]
+            scaling = scaling_params(sources, tgts, cache_dir=cache_dir, rng=rng, device=device)
+        self.scaling = [np.asarray(a, dtype=np.float32) for a in scaling]
+        if len(self.scaling) != self.num_sources or any(a.ndim != 2 or a.shape[1] != 3 for a in self.scaling):
+            raise ValueError("scaling: one [n_targets, 3] array per source")
+
+    def __len__(self):
+        return self.n
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def item_rng(self, i):
+        return np.random.RandomState([self.seed, self.epoch, int(i)])
+
+    def item(self, i):
+        """[(source, scan index, scale row)] of item i in the current epoch"""
+        rows = draw_scaling(self.item_rng(i), self.scaling, self.num_sources)
+        js = (int(i),) if self.pairs is None else self.pairs.pair(i)
+        return [(s, j, rows[s]) for s, j in enumerate(js)]
+
+    def scan(self, s, j, device):
+        vox, labels = synth.scan_voxels(self.first + j + s * synth.SOURCE1_SEED, self.configs[s])
+        return {"coordinates": torch.from_numpy(vox).to(device),
+                "features": torch.ones((vox.shape[0], 1), dtype=torch.float32, device=device),
+                "sem_labels": torch.from_numpy(labels).to(device)}
+
+    scale = staticmethod(sn_scale)
+
+    def _batch(self, indices, device):
+        cols = [([], [], []) for _ in range(self.num_sources)]
+        for b, i in enumerate(indices):
+            for s, j, row in self.item(i):
+                m = self.scale(self.scan(s, j, device), row, voxel_size=self.voxel)
+                c = m["coordinates"].to(torch.int32)
+                cols[s][0].append(torch.cat([torch.full((c.shape[0], 1), b, dtype=torch.int32, device=c.device), c],
+                                            dim=1))
+                cols[s][1].append(m["features"])
+                cols[s][2].append(m["sem_labels"].long())
+        batch = {}
+        for s, (coords, feats, labels) in enumerate(cols):
+            coords = torch.cat(coords)
+            batch["coords_int1" if s else "coords_int"] = coords
+            batch.update({f"source_coordinates{s}": coords.float(), f"source_features{s}": torch.cat(feats),
+                          f"source_sem_labels{s}": torch.cat(labels)})
+        return batch
 
     def batch(self, indices, device):
         device = torch.device(device)
@@ -387,6 +491,10 @@ def parse_args(argv=None):
                     help="PointCutMix / CoSMix (train_aug_based.py, pipeline.method): each item one scan mixed from a "
                          "pair of the two --sources (default: --config twice), trained as one source with SoftDICE")
     ap.add_argument("--sub-p", type=float, default=0.8, help="CoSMix: share of each drawn class's rows mixed in")
+    ap.add_argument("--sn-targets", nargs="+", default=None, choices=sorted(synth.CONFIGS), metavar="CONFIG",
+                    help="SN car-size scaling (train_scaling_based.py): every scan of --config (or of the two --sources) "
+                         "is scaled to the car size of these target configurations and re-quantised; the car sizes "
+                         "are clustered on the GPU at start-up; trained with SoftDICE (use the *_cars configurations)")
     ap.add_argument("--check-val-every-n-epoch", type=int, default=5)
     ap.add_argument("--save-dir", default=None)
     ap.add_argument("--resume", default=None)
@@ -401,6 +509,12 @@ def parse_args(argv=None):
             ap.error("--mix and --mix3d are two different methods (pipeline.method): pass one of them")
         if a.sources is None:
             a.sources = [a.config, a.config]    # the single configs list one dataset twice
+    if a.sn_targets is not None:
+        if a.model in ("MinkUNet34BEV", "MinkUNet34Robust"):   # train_scaling_based.py:142-155, PLTTrainer: SoftDICE only
+            ap.error(f"--sn-targets trains with the SoftDICE-only step of PLTTrainer: --model MinkUNet34 or "
+                     f"MinkUNet34IBN, not {a.model}")
+        if a.mix is not None or a.mix3d:
+            ap.error("--sn-targets, --mix and --mix3d are different methods: pass one of them")
     return a
 
 
@@ -420,7 +534,15 @@ def _fit_from_args(a):
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))
     bev = bev_image_size(a.bound)
-    if getattr(a, "mix", None):
+    if getattr(a, "sn_targets", None):
+        configs = a.sources or [a.config]
+        train = ScaledSynthScans(a.scans, configs, a.sn_targets, seed=a.seed)
+        if a.sources:
+            val = {name: SynthScans(a.val_scans, c, first=10 ** 6 + i * synth.SOURCE1_SEED, bev_size=bev)
+                   for i, (name, c) in enumerate(zip(source_names(a.sources), a.sources))} if a.val_scans else None
+        else:
+            val = SynthScans(a.val_scans, a.config, first=10 ** 6, bev_size=bev) if a.val_scans else None
+    elif getattr(a, "mix", None):
         train = MixedSynthScans(a.scans, a.scans, a.sources, method=a.mix, sub_p=a.sub_p, seed=a.seed)
         val = {name: SynthScans(a.val_scans, c, first=10 ** 6 + i * synth.SOURCE1_SEED, bev_size=bev)
                for i, (name, c) in enumerate(zip(source_names(a.sources), a.sources))} if a.val_scans else None

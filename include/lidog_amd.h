@@ -727,6 +727,31 @@ int lidog_cluster_boxes(const int32_t *coords, const int32_t *labels, int64_t n,
 int lidog_sn_scale_coords(const int32_t *coords, int64_t n, float voxel_size, float sx, float sy, float sz, float *out,
                           void *stream);
 
+/* ------------------------------------------------------------------ training augmentation (sub_p, augmentation_list)
+ * The per-point part of a training item of the reference's datasets when `augmentation_list` is not null
+ * (utils/datasets/semantickitti_bev.py:209-238, synth4d.py:141-162): the sub-sample gather (dataset.py:58-72),
+ * RandomRotation / RandomScale (utils/common/augmentation.py:7-44) under numpy's dtype rules, the bounds filter
+ * (semantickitti_bev.py:155-172) and the voxel floor of ME.utils.sparse_quantize in the point's own dtype.  The host
+ * makes the draws.  Positions of the kept rows come from lidog_mix_split: the same bytes on every run. */
+/* 1 when the list holds a rotation: the points leave as float64 (`coords @ R`, R float64), else 0 (float32) */
+int32_t lidog_augment_is_f64(const int32_t *op_kinds_host, int32_t n_ops);
+/* int32 workspace of lidog_augment_points for k sampled rows (read only with use_bounds) */
+int64_t lidog_augment_ws(int64_t k);
+/* points [n, 3] float32; sampled_idx [k] int32 (device; NULL: every row in order, k = n; an entry outside [0, n) is
+ * clamped and info[1] set).  Operations, applied in order (HOST arrays, n_ops <= 4): op_kinds_host[o] = 0 rotation
+ * (op_params_host[9 o ..] = R row-major, p <- p @ R, each output (p0 R0j + p1 R1j) + p2 R2j in float64, the point is
+ * float64 from here on) or 1 scale (three float64 factors; a float64 point takes one float64 product per axis, a point
+ * that is still float32 takes float32(float64(p_k) * s_k)).  use_bounds: only rows with -60 < x, y < 60, -10 < z < 8
+ * outside the ego box (-3 < x < 3 and -2 < y < 2) are kept, in order.  Per kept row r (all device, room for k rows):
+ * rows [k, 4] int32 = (batch, floor(p / q)) with float64 division for a float64 point and float32 division by
+ * float32(q) otherwise; xyz [k, 3] float64 or float32 (lidog_augment_is_f64); src [k] = its row in `points`;
+ * labels_out [k] = labels[src] when labels (int32 [n]) is given.  info [2] int32 (device): info[0] = kept rows, info[1]
+ * = 1 when a sampled index was out of range.  ws: lidog_augment_ws(k) int32. */
+int lidog_augment_points(const float *points, int64_t n, const int32_t *sampled_idx, int64_t k,
+                         const int32_t *op_kinds_host, const double *op_params_host, int32_t n_ops, int32_t use_bounds,
+                         double qx, double qy, double qz, int32_t batch, const int32_t *labels, int32_t *rows, void *xyz,
+                         int32_t *src, int32_t *labels_out, int32_t *info, int32_t *ws, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,178 @@
+// The per-point part of one augmented training item (sub_p / augmentation_list of the reference's training datasets):
+// the sub-sample gather (random_sample, utils/datasets/dataset.py:58-72), RandomRotation / RandomScale
+// (utils/common/augmentation.py:7-44) with numpy's dtype rules, the bounds filter with the ego box
+// (utils/datasets/semantickitti_bev.py:155-172), the voxel floor of ME.utils.sparse_quantize in the point's own dtype,
+// and the stable compaction of the kept rows.  The host makes the draws; the rotation matrix and the scales travel by
+// value in the launch arguments.  The kept rows take their positions from lidog_mix_split (mix.hip: per-block counts,
+// one scan, in-wave ballot ranks), never from an atomic: the same rows in the same order on every run.
+#include "common.h"
+
+#define AUG_THREADS 256
+#define AUG_MAX_OPS 4
+#define AUG_ROTATION 0
+#define AUG_SCALE 1
+
+struct AugOps {
+    int32_t n;
+    int32_t kind[AUG_MAX_OPS];
+    double p[AUG_MAX_OPS][9];   // rotation: R row-major (out_j = sum_k p_k R[k][j]); scale: s_x, s_y, s_z
+};
+
+struct AugPoint {
+    double d[3];   // the point once it is float64
+    float f[3];    // the point while it is float32
+    bool is64;
+};
+
+// numpy's arithmetic on one row.  `coords @ R` with a float64 R: the float32 row is widened (exactly) and every output
+// is (p0 R0j + p1 R1j) + p2 R2j in float64.  `coords[:, k] = coords[:, k] * s_k` with a float64 s_k: one float64
+// product, which the in-place assignment rounds back to float32 while the array still is float32.
+__device__ __forceinline__ AugPoint aug_transform(const float *__restrict__ pts, int64_t i, const AugOps &ops) {
+    AugPoint a;
+    a.is64 = false;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        a.f[k] = pts[3 * i + k];
+        a.d[k] = 0.0;
+    }
+    for (int o = 0; o < ops.n; ++o) {
+        const double *p = ops.p[o];
+        if (ops.kind[o] == AUG_ROTATION) {
+            double x[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) x[k] = a.is64 ? a.d[k] : (double)a.f[k];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) a.d[j] = (x[0] * p[j] + x[1] * p[3 + j]) + x[2] * p[6 + j];
+            a.is64 = true;
+        } else if (a.is64) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) a.d[k] = a.d[k] * p[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) a.f[k] = (float)((double)a.f[k] * p[k]);
+        }
+    }
+    return a;
+}
+
+// filter_bounds: strict comparisons on the value in its own dtype (a float32 widens exactly)
+__device__ __forceinline__ bool aug_in_bounds(const AugPoint &a) {
+    const double x = a.is64 ? a.d[0] : (double)a.f[0];
+    const double y = a.is64 ? a.d[1] : (double)a.f[1];
+    const double z = a.is64 ? a.d[2] : (double)a.f[2];
+    const bool in = (-60.0 < x) & (x < 60.0) & (-60.0 < y) & (y < 60.0) & (-10.0 < z) & (z < 8.0);
+    const bool ego = (-3.0 < x) & (x < 3.0) & (-2.0 < y) & (y < 2.0);
+    return in & !ego;
+}
+
+__device__ __forceinline__ int64_t aug_source_row(const int32_t *__restrict__ sampled_idx, int64_t j, int64_t n,
+                                                  int32_t *info) {
+    int64_t i = sampled_idx ? (int64_t)sampled_idx[j] : j;
+    if (i < 0 || i >= n) {   // never read outside the scan: the row is clamped and the caller told
+        info[1] = 1;
+        i = i < 0 ? 0 : n - 1;
+    }
+    return i;
+}
+
+// keys[j] = 0 for a sampled row inside the bounds, -1 otherwise; table[0] = 0: the one-slot table of lidog_mix_split
+__global__ __launch_bounds__(AUG_THREADS) void k_aug_flag(const float *__restrict__ pts, int64_t n,
+                                                          const int32_t *__restrict__ sampled_idx, int64_t k, AugOps ops,
+                                                          int32_t *__restrict__ keys, int32_t *__restrict__ table,
+                                                          int32_t *info) {
+    const int64_t j = (int64_t)blockIdx.x * AUG_THREADS + threadIdx.x;
+    if (j == 0) table[0] = 0;
+    if (j >= k) return;
+    const int64_t i = aug_source_row(sampled_idx, j, n, info);
+    keys[j] = aug_in_bounds(aug_transform(pts, i, ops)) ? 0 : -1;
+}
+
+// output row r: sampled row kept[r] (kept == NULL: r itself), r < count (count_dev == NULL: k).  The transform is
+// computed again rather than stored: 30 flops against 24 bytes of traffic each way.
+__global__ __launch_bounds__(AUG_THREADS) void k_aug_emit(const float *__restrict__ pts, int64_t n,
+                                                          const int32_t *__restrict__ sampled_idx, int64_t k, AugOps ops,
+                                                          const int32_t *__restrict__ kept,
+                                                          const int32_t *__restrict__ count_dev, double qx, double qy,
+                                                          double qz, int32_t batch, const int32_t *__restrict__ labels,
+                                                          int4 *__restrict__ rows, void *__restrict__ xyz,
+                                                          int32_t *__restrict__ src, int32_t *__restrict__ labels_out,
+                                                          int32_t *info) {
+    const int64_t r = (int64_t)blockIdx.x * AUG_THREADS + threadIdx.x;
+    const int64_t count = count_dev ? (int64_t)*count_dev : k;
+    if (r == 0) info[0] = (int32_t)count;
+    if (r >= count || r >= k) return;
+    const int64_t j = kept ? (int64_t)kept[r] : r;
+    if (j < 0 || j >= k) {
+        info[1] = 1;
+        return;
+    }
+    const int64_t i = aug_source_row(sampled_idx, j, n, info);
+    const AugPoint a = aug_transform(pts, i, ops);
+    if (a.is64) {   // np.floor(c / q) on a float64 array, q = float64(quantization_size)
+        rows[r] = make_int4(batch, (int)floor(a.d[0] / qx), (int)floor(a.d[1] / qy), (int)floor(a.d[2] / qz));
+        double *o = (double *)xyz + 3 * r;
+        o[0] = a.d[0]; o[1] = a.d[1]; o[2] = a.d[2];
+    } else {        // on a float32 array, q = float32(quantization_size): k_voxel_floor
+        rows[r] = make_int4(batch, (int)floorf(a.f[0] / (float)qx), (int)floorf(a.f[1] / (float)qy),
+                            (int)floorf(a.f[2] / (float)qz));
+        float *o = (float *)xyz + 3 * r;
+        o[0] = a.f[0]; o[1] = a.f[1]; o[2] = a.f[2];
+    }
+    src[r] = (int32_t)i;
+    if (labels) labels_out[r] = labels[i];
+}
+
+extern "C" int32_t lidog_augment_is_f64(const int32_t *op_kinds_host, int32_t n_ops) {
+    for (int o = 0; o < n_ops; ++o)
+        if (op_kinds_host[o] == AUG_ROTATION) return 1;
+    return 0;
+}
+
+extern "C" int64_t lidog_augment_ws(int64_t k) {
+    const int64_t kk = k > 0 ? k : 0;   // keys [k], kept [k], table [1], slot_start [2], the split's own workspace
+    return 2 * kk + 3 + lidog_mix_split_ws(kk, 1);
+}
+
+extern "C" int lidog_augment_points(const float *points, int64_t n, const int32_t *sampled_idx, int64_t k,
+                                    const int32_t *op_kinds_host, const double *op_params_host, int32_t n_ops,
+                                    int32_t use_bounds, double qx, double qy, double qz, int32_t batch,
+                                    const int32_t *labels, int32_t *rows, void *xyz, int32_t *src, int32_t *labels_out,
+                                    int32_t *info, int32_t *ws, void *stream) {
+    hipStream_t st = (hipStream_t)stream;
+    LIDOG_REQUIRE(n >= 0 && k >= 0 && k < (int64_t)INT32_MAX && n < (int64_t)INT32_MAX,
+                  "lidog_augment_points: n = %lld, k = %lld out of range", (long long)n, (long long)k);
+    LIDOG_REQUIRE(sampled_idx || k == n || k == 0,
+                  "lidog_augment_points: without sampled_idx every row is taken (k = n)");
+    LIDOG_REQUIRE(n_ops >= 0 && n_ops <= AUG_MAX_OPS, "lidog_augment_points: %d operations (at most %d)", n_ops,
+                  AUG_MAX_OPS);
+    LIDOG_REQUIRE(n_ops == 0 || (op_kinds_host && op_params_host), "lidog_augment_points: operations missing");
+    LIDOG_REQUIRE(qx > 0 && qy > 0 && qz > 0, "lidog_augment_points: voxel size must be positive");
+    LIDOG_REQUIRE(info, "lidog_augment_points: info is required");
+    LIDOG_REQUIRE(k == 0 || (n > 0 && points && rows && xyz && src && (!labels || labels_out)),
+                  "lidog_augment_points: an input or output array is missing");
+    LIDOG_REQUIRE(!use_bounds || k == 0 || ws, "lidog_augment_points: the bounds filter needs the workspace");
+    AugOps ops = {};
+    ops.n = n_ops;
+    for (int o = 0; o < n_ops; ++o) {
+        LIDOG_REQUIRE(op_kinds_host[o] == AUG_ROTATION || op_kinds_host[o] == AUG_SCALE,
+                      "lidog_augment_points: operation %d of kind %d (0 rotation, 1 scale)", o, op_kinds_host[o]);
+        ops.kind[o] = op_kinds_host[o];
+        for (int q = 0; q < 9; ++q) ops.p[o][q] = op_params_host[9 * o + q];
+    }
+    LIDOG_CHECK_HIP(hipMemsetAsync(info, 0, 2 * sizeof(int32_t), st));
+    if (k == 0) return 0;
+    const unsigned grid = (unsigned)cdiv64(k, AUG_THREADS);
+    const int32_t *kept = nullptr, *count = nullptr;
+    if (use_bounds) {
+        int32_t *keys = ws, *kept_w = ws + k, *table = ws + 2 * k, *slot_start = table + 1, *split_ws = table + 3;
+        k_aug_flag<<<grid, AUG_THREADS, 0, st>>>(points, n, sampled_idx, k, ops, keys, table, info);
+        LIDOG_LAUNCH_CHECK();
+        if (lidog_mix_split(keys, k, table, 1, 1, kept_w, slot_start, split_ws, stream)) return 1;
+        kept = kept_w;
+        count = slot_start + 1;
+    }
+    k_aug_emit<<<grid, AUG_THREADS, 0, st>>>(points, n, sampled_idx, k, ops, kept, count, qx, qy, qz, batch, labels,
+                                             (int4 *)rows, xyz, src, labels_out, info);
+    LIDOG_LAUNCH_CHECK();
+    return 0;
+}

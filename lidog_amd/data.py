@@ -11,7 +11,9 @@ bottleneck, and both are the same hash / winner-map kernels as the hot path.
 
   pointcutmix_merge, cosmix_merge   PointCutMix / CoSMix scan mixing (utils/datasets/pointcutmix.py, cosmix.py), below
   average_dims, scaling_params, sn_scale   the SN car-size scaling baseline (train_scaling_based.py:35-129,
-                   utils/datasets/sn_scaling.py), at the end
+                   utils/datasets/sn_scaling.py)
+  draw_augmentation, augment_item   sub_p / augmentation_list of the training datasets (dataset.py:58-72,
+                   utils/common/augmentation.py, semantickitti_bev.py:209-252, synth4d.py:141-162), at the end
 """
 import ctypes
 import os
@@ -30,22 +32,29 @@ def sparse_quantize(points, features=None, labels=None, ignore_label=-100, quant
     _lib.require_gpu(points, "points")
     points = points.contiguous().float()
     n = points.shape[0]
-    dev = points.device
     q = np.broadcast_to(np.asarray(quantization_size, dtype=np.float32), (3,))
-    rows = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    rows = torch.empty((n, 4), dtype=torch.int32, device=points.device)
     call("lidog_voxel_floor", ptr(points), n, float(q[0]), float(q[1]), float(q[2]), 0, ptr(rows))
+    return quantize_rows(rows, features, labels, ignore_label, return_index, return_inverse)
+
+
+def quantize_rows(rows, features=None, labels=None, ignore_label=-100, return_index=False, return_inverse=False):
+    """sparse_quantize from ready-made voxel rows (int32 [n,4]: batch, x, y, z; contiguous, on the GPU), as
+    lidog_voxel_floor or lidog_augment_points write them: first point of every voxel, label vote, index and inverse maps.
+    One device -> host read after the last launch: the number of voxels together with the range flag."""
+    n = rows.shape[0]
+    dev = rows.device
     cap = _lib.load().lidog_hash_capacity(n)
     keys = torch.empty(cap, dtype=torch.int64, device=dev)
     vals = torch.empty(cap, dtype=torch.int32, device=dev)
     first = torch.empty(n, dtype=torch.int32, device=dev)
-    n_unique = torch.zeros(1, dtype=torch.int64, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    call("lidog_coords_insert", ptr(rows), n, ptr(keys), ptr(vals), cap, ptr(first), ptr(n_unique), ptr(err))
+    sizes = torch.zeros(2, dtype=torch.int64, device=dev)      # (voxels, range flag in the low word): read together
+    call("lidog_coords_insert", ptr(rows), n, ptr(keys), ptr(vals), cap, ptr(first), ptr(sizes[:1]), ptr(sizes[1:]))
     uniq = torch.empty(n, dtype=torch.int32, device=dev)
     inv = torch.empty(n, dtype=torch.int32, device=dev)
     ws = torch.empty(n + 2048, dtype=torch.int32, device=dev)
     call("lidog_coords_compact", ptr(first), n, ptr(keys), ptr(vals), cap, ptr(rows), ptr(uniq), ptr(inv), ptr(ws))
-    m, bad = int(n_unique.item()), int(err.item())
+    m, bad = sizes.cpu().tolist()
     if bad:
         raise ValueError("voxel coordinates out of the supported range |c| <= 65535")
     uniq = uniq[:m]
@@ -166,25 +175,35 @@ def merge_stream(device=None):
 
 def on_merge_stream(work, device, inputs=(), wait=True):
     """run `work()` on merge_stream(device) and hand its result (a dict or list of tensors) to the caller's current stream
-    with an event; the caching allocator is told about the tensors that cross streams.  wait=True: the merge stream first
-    waits for the work queued on the caller's stream, where `inputs` may have been made; wait=False: work() makes its own
-    inputs on the merge stream, and nothing queued on the caller's stream delays it."""
+    with an event; the caching allocator is told about every tensor that crosses streams, nested ones included (a batch
+    holds its BEV label images in a dict of their own).  wait=True: the merge stream first waits for the work queued on
+    the caller's stream, where `inputs` may have been made; wait=False: work() makes its own inputs on the merge stream,
+    and nothing queued on the caller's stream delays it."""
     cur = torch.cuda.current_stream(device)
     side = merge_stream(device)
     if side == cur:
         return work()
     if wait:
         side.wait_stream(cur)
-    for t in inputs:
-        if torch.is_tensor(t) and t.is_cuda:
-            t.record_stream(side)
+    for t in _device_tensors(list(inputs)):
+        t.record_stream(side)
     with torch.cuda.stream(side):
         out = work()
     cur.wait_stream(side)
-    for t in (out.values() if isinstance(out, dict) else out):
-        if torch.is_tensor(t) and t.is_cuda:
-            t.record_stream(cur)
+    for t in _device_tensors(out):
+        t.record_stream(cur)
     return out
+
+
+def _device_tensors(obj):
+    """every CUDA tensor reachable from obj through dicts, lists and tuples (a batch nests its BEV label images)"""
+    if torch.is_tensor(obj):
+        return [obj] if obj.is_cuda else []
+    if isinstance(obj, dict):
+        obj = list(obj.values())
+    if isinstance(obj, (list, tuple)):
+        return [t for v in obj for t in _device_tensors(v)]
+    return []
 
 
 def draw_source(rng):
@@ -529,3 +548,143 @@ def sn_scale(scan, scaling, voxel_size=0.05, ignore_label=-1):
         return out
 
     return on_merge_stream(work, dev, [t for t in scan.values()])
+
+
+# ------------------------------------------------------------------ training augmentation: sub_p and augmentation_list
+# With a non-null `augmentation_list` a training dataset's __getitem__ (semantickitti_bev.py:209-252, synth4d.py:141-162)
+# draws int(sub_p * n) of the scan's points in random order, rotates and scales them (float64 from the rotation on),
+# filters them by the bounds and the ego box (BEV datasets), and voxelises what is left: the first point of a voxel
+# wins, so the random order matters.  The host makes the draws in the reference's sequence; lidog_augment_points does
+# the per-point work and the existing hash / vote / BEV-label kernels the rest.  Device -> host reads per item: the
+# number of rows the bounds filter kept (BEV form only: it sizes the hash table), then the number of voxels.
+
+AUGMENTATIONS = ("RandomRotation", "RandomScale")
+SCALE_RANGE = (0.9, 1.1)               # get_augmentations: RandomScale(0.9, 1.1)
+
+
+def check_augmentations(augmentation_list):
+    """get_augmentations (utils/common/augmentation.py:61-69): any list over RandomRotation / RandomScale, the empty
+    one included; another name raises NotImplementedError"""
+    names = list(augmentation_list)
+    for a in names:
+        if a not in AUGMENTATIONS:
+            raise NotImplementedError(f"augmentation {a!r} (one of {AUGMENTATIONS})")
+    return names
+
+
+def rotation_matrix(axis, theta):
+    """RandomRotation._M: expm(cross(eye(3), axis / norm(axis) * theta)), scipy's expm when scipy imports; otherwise the
+    closed form of the same exponential (Rodrigues), which agrees with it to a few 1e-17"""
+    axis = np.asarray(axis, dtype=np.float64)
+    theta = np.asarray(theta, dtype=np.float64)
+    try:
+        from scipy.linalg import expm, norm
+    except ImportError:
+        v = axis / np.sqrt(np.sum(axis * axis)) * theta
+        K = np.cross(np.eye(3), v)
+        a = float(np.sqrt(np.sum(v * v)))
+        if a == 0.0:
+            return np.eye(3)
+        return np.eye(3) + (np.sin(a) / a) * K + ((1.0 - np.cos(a)) / (a * a)) * (K @ K)
+    return expm(np.cross(np.eye(3), axis / norm(axis) * theta))
+
+
+def draw_augmentation(rng, n, sub_p, augmentation_list):
+    """The draws of one training item in the reference's sequence (rng: a legacy RandomState or the np.random module):
+    random_sample's `choice(arange(n), int(sub_p * n), replace=False)` (sub_p None: nothing drawn, every row in order),
+    then per list entry RandomRotation's `rand(3)`, `rand(1)` or RandomScale's three `rand(1)`.  Returns
+    {'sampled_idx': int64 [k], 'ops': [(name, float64 parameters)]}: R [3, 3] for a rotation, [s_x, s_y, s_z] for a
+    scale."""
+    names = check_augmentations(augmentation_list)
+    n = int(n)
+    sampled_idx = rng.choice(np.arange(n), int(sub_p * n), replace=False) if sub_p is not None else np.arange(n)
+    ops = []
+    for a in names:
+        if a == "RandomRotation":
+            axis = rng.rand(3) - 0.5
+            theta = np.pi / 4 * (rng.rand(1) - 0.5)
+            ops.append((a, np.ascontiguousarray(rotation_matrix(axis, theta), dtype=np.float64)))
+        else:
+            scale, bias = SCALE_RANGE[1] - SCALE_RANGE[0], SCALE_RANGE[0]
+            ops.append((a, np.concatenate([scale * rng.rand(1) + bias for _ in range(3)]).astype(np.float64)))
+    return {"sampled_idx": np.asarray(sampled_idx, dtype=np.int64), "ops": ops}
+
+
+def augment_points(points, sampled_idx, ops, voxel_size=0.05, bounds=False, labels=None, batch=0):
+    """lidog_augment_points: points float32 [n,3] and labels (int32 [n], optional) on the GPU, sampled_idx int32 [k] on
+    the GPU or None (every row in order), ops as draw_augmentation returns them.  Returns (rows int32 [k,4], xyz [k,3]
+    float64 with a rotation in the list, else float32, src int32 [k], labels int32 [k] or None, info int32 [2]) on the
+    device; with `bounds` only the first info[0] rows are meaningful."""
+    _lib.require_gpu(points, "points")
+    dev = points.device
+    if points.dtype != torch.float32 or not points.is_contiguous():
+        raise ValueError("augment_points: points must be contiguous float32 [n, 3]")
+    n = points.shape[0]
+    k = n if sampled_idx is None else sampled_idx.shape[0]
+    kinds = (ctypes.c_int32 * max(len(ops), 1))(*[AUGMENTATIONS.index(a) for a, _ in ops])
+    params = np.zeros((max(len(ops), 1), 9), dtype=np.float64)
+    for o, (a, p) in enumerate(ops):
+        p = np.asarray(p, dtype=np.float64).reshape(-1)
+        if p.shape[0] != (9 if a == "RandomRotation" else 3) or not np.all(np.isfinite(p)):
+            raise ValueError(f"augment_points: parameters of {a}: {p}")
+        params[o, :p.shape[0]] = p
+    f64 = bool(_lib.load().lidog_augment_is_f64(kinds, len(ops)))
+    q = np.broadcast_to(np.asarray(voxel_size, dtype=np.float64), (3,))
+    rows = torch.empty((k, 4), dtype=torch.int32, device=dev)
+    xyz = torch.empty((k, 3), dtype=torch.float64 if f64 else torch.float32, device=dev)
+    src = torch.empty(k, dtype=torch.int32, device=dev)
+    lab_out = torch.empty(k, dtype=torch.int32, device=dev) if labels is not None else None
+    info = torch.empty(2, dtype=torch.int32, device=dev)
+    ws = torch.empty(_lib.load().lidog_augment_ws(k), dtype=torch.int32, device=dev) if bounds else None
+    call("lidog_augment_points", ptr(points), n, ptr(sampled_idx), k, kinds, params.ctypes.data, len(ops),
+         1 if bounds else 0, float(q[0]), float(q[1]), float(q[2]), int(batch), ptr(labels), ptr(rows), ptr(xyz),
+         ptr(src), ptr(lab_out), ptr(info), ptr(ws))
+    return rows, xyz, src, lab_out, info
+
+
+def augment_item(scan, draws, voxel_size=0.05, bounds=False, ignore_label=-1, bev=None, bev_from="voted"):
+    """One augmented training item (semantickitti_bev.py:209-277 with `bounds`, synth4d.py:141-190 without) on the GPU.
+    scan: dict of device tensors `points` float32 [n,3], `features` [n,C], `sem_labels` [n]; draws: what
+    draw_augmentation returned.  Returns the reference's item: `coordinates` int32 [m,3], `xyz` [m,3] (the transformed
+    first point of every voxel, float64 with a rotation in the list), `features`, `sem_labels` (the label of the voxel's
+    FIRST point), `sampled_idx` (its row in the scan), `inverse_map`, plus `index` (its row among the kept rows) and
+    `voted_labels` (the label vote of sparse_quantize).  bev=(bound, img_size): also `bev_labels` / `bev_selected_idx`
+    [S, S] from the voted labels (semantickitti_bev.py:244-252, the default) or with bev_from='first' from the
+    first-point labels (nuscenes_bev.py:252-261)."""
+    for k in ("points", "features", "sem_labels"):
+        if k not in scan:
+            raise KeyError(f"scan has no '{k}'")
+        _lib.require_gpu(scan[k], f"scan '{k}'")
+    if bev_from not in ("voted", "first"):
+        raise ValueError(f"bev_from = {bev_from!r} ('voted' or 'first')")
+    points = scan["points"]
+    n = points.shape[0]
+    dev = points.device
+    idx = np.asarray(draws["sampled_idx"])
+    if idx.ndim != 1 or (idx.shape[0] and (int(idx.min()) < 0 or int(idx.max()) >= n)):
+        raise ValueError("augment_item: sampled_idx outside the scan")
+    ops = list(draws["ops"])
+
+    def work():
+        sampled = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int32)).to(dev)
+        labels = scan["sem_labels"].to(torch.int32).contiguous()
+        rows, xyz, src, lab, info = augment_points(points, sampled, ops, voxel_size, bounds, labels)
+        if bounds:      # the hash table and every later launch are sized by the number of kept rows
+            kept, bad = info.cpu().tolist()
+            if bad:
+                raise RuntimeError("augment_item: a sampled index outside the scan reached the device")
+            rows, xyz, src, lab = rows[:kept], xyz[:kept], src[:kept], lab[:kept]
+        _, voted, index, inverse = quantize_rows(rows, labels=lab, ignore_label=ignore_label, return_index=True,
+                                                 return_inverse=True)
+        first = src[index].long()
+        out = {"coordinates": rows[index][:, 1:].contiguous(), "xyz": xyz[index], "features": scan["features"][first],
+               "sem_labels": scan["sem_labels"][first], "sampled_idx": first, "inverse_map": inverse, "index": index,
+               "voted_labels": voted.to(scan["sem_labels"].dtype)}
+        if bev is not None:
+            bound, img_size = bev
+            img, pidx = bev_labels(rows[index].contiguous(), voted if bev_from == "voted" else lab[index], bound=bound,
+                                   img_size=img_size, voxel=voxel_size, batch_size=1)
+            out["bev_labels"], out["bev_selected_idx"] = img[0], pidx[0].long()
+        return out
+
+    return on_merge_stream(work, dev, [points, scan["features"], scan["sem_labels"]])

@@ -60,8 +60,9 @@ def scan_points(seed, n_beams, n_az, elev, h, **_):
     return _scan(seed, n_beams, n_az, elev, h)[:2]
 
 
-def _scan(seed, n_beams, n_az, elev, h, boxes=None):
-    """(points, the scan's generator after its draws, per point: hit a box)"""
+def _scan(seed, n_beams, n_az, elev, h, boxes=None, details=False):
+    """(points, the scan's generator after its draws, per point: hit a box); `details`: also per point (hit the ground,
+    azimuth sector, beam)"""
     rng = np.random.default_rng(seed)
     el = np.deg2rad(np.linspace(elev[0], elev[1], n_beams))
     # evenly spaced azimuths (a spinning sensor fires at a fixed angular step): this is the generator behind the
@@ -85,7 +86,38 @@ def _scan(seed, n_beams, n_az, elev, h, boxes=None):
     pts = np.stack([r * np.cos(EL) * np.cos(AZ), r * np.cos(EL) * np.sin(AZ), r * np.sin(EL)], axis=-1)
     pts = pts.reshape(-1, 3).astype(np.float32)
     keep = (pts ** 2).sum(axis=1) < 50.0 ** 2
+    if details:
+        ground = (r_ground < r_wall) & ~car
+        beam = np.broadcast_to(np.arange(n_beams)[:, None], EL.shape)
+        return pts[keep], rng, car.reshape(-1)[keep], (ground.reshape(-1)[keep], sector.reshape(-1)[keep],
+                                                      beam.reshape(-1)[keep])
     return pts[keep], rng, car.reshape(-1)[keep]
+
+
+GROUND_CLASS = 1
+UNLABELLED_SHARE = 0.08     # of the (sector, band of 8 beams) patches of a scan
+
+
+def scan_points_labels(seed, config="kitti120k"):
+    """(points float32 [n,3], labels int64 [n]): the points of scan_points / scan_voxels of the same seed with one label
+    per POINT, what the training augmentation starts from (it re-voxelises the points of every item).  Spatially
+    coherent, so that the label vote of sparse_quantize leaves most voxels labelled: the ground is GROUND_CLASS, the
+    wall of every azimuth sector has one class of its own (2..6, and 0 where the configuration has no cars), a box is
+    CAR_CLASS, and UNLABELLED_SHARE of the (sector, band of 8 beams) patches are -1.  The labels are drawn from a
+    generator stream of their own (as car_boxes): no other function's output moves."""
+    cfg = CONFIGS[config]
+    boxes = car_boxes(seed, cfg["cars"]) if cfg.get("cars") is not None else None
+    pts, _, car, (ground, sector, beam) = _scan(seed, cfg["n_beams"], cfg["n_az"], cfg["elev"], cfg["h"], boxes=boxes,
+                                                details=True)
+    rng = np.random.default_rng([int(seed), 0x1AB])
+    classes = np.array([2, 3, 4, 5, 6] if boxes is not None else [0, 2, 3, 4, 5, 6])
+    wall_class = classes[rng.integers(0, len(classes), 64)]
+    bands = (cfg["n_beams"] + 7) // 8
+    unlabelled = rng.random((64, bands)) < UNLABELLED_SHARE
+    labels = np.where(ground, GROUND_CLASS, wall_class[sector]).astype(np.int64)
+    labels[car] = CAR_CLASS
+    labels[unlabelled[sector, beam // 8]] = -1
+    return pts, labels
 
 
 def voxelize(pts, voxel, lidog_bounds, return_index=False):

@@ -13,6 +13,7 @@ What the reference's entry scripts do through pytorch-lightning, as plain argume
     python -m lidog_amd.train --sources kitti120k nusc35k --source-weights 0.5 0.5 ...   (two sources, */multi/*.yaml)
     python -m lidog_amd.train --model MinkUNet34 --mix cosmix ...    (PointCutMix / CoSMix, configs/{pointcutmix,cosmix})
     python -m lidog_amd.train --model MinkUNet34 --config kitti120k_cars --sn-targets nusc35k_cars ...   (SN, configs/SN)
+    python -m lidog_amd.train --augment RandomRotation RandomScale --sub-p 0.8 ...   (sub_p / augmentation_list of the configs)
 
 Scans are synthetic (lidog_amd.synth; there are no datasets on the box); anything with `__len__` and
 `batch(indices, device) -> dict` (keys of CollateFNSingleSourceBEVMultiLevel, collation.py:318-325) can be passed as
@@ -30,7 +31,8 @@ import torch.distributed as dist
 from . import me as ME
 from . import synth
 from .checkpoint import load_training_checkpoint, save_lightning_checkpoint
-from .data import cosmix_merge, draw_scaling, on_merge_stream, pointcutmix_merge, scaling_params, sn_scale
+from .data import (augment_item, check_augmentations, cosmix_merge, draw_augmentation, draw_scaling, on_merge_stream,
+                   pointcutmix_merge, scaling_params, sn_scale)
 from .evaluate import per_class_iou
 from .optim import make_optimizer, make_scheduler, shard_indices
 from .trainer import LiDOGStep, RobustStep, SourceStep, setup_data_parallel
@@ -249,6 +251,86 @@ class ScaledSynthScans:
         if device.type != "cuda":
             return self._batch(indices, device)
         # the scans are made on the merge stream itself: it does not wait for the caller's stream
+        return on_merge_stream(lambda: self._batch(indices, device), device, wait=False)
+
+
+class AugmentedSynthScans:
+    """A training dataset with `sub_p` and a non-null `augmentation_list` (25 of the reference's 48 configurations:
+    semantickitti_bev.py:209-252, synth4d.py:141-162) over synthetic scans: every item is made from the scan's POINTS
+    (synth.scan_points_labels) each time it is asked for: a random int(sub_p * n) of them in random order, rotated and
+    scaled, voxelised on the GPU (lidog_amd.data.augment_item).  `bev=(bound, image size)` is the BEV datasets' form:
+    the bounds filter with the ego box, and BEV label images rasterised from the voted labels; without it neither
+    (Synth4DDataset).  One configuration: a one-source batch; two: paired as MultiSynthScans.pair, each source's item
+    augmented on its own, source 0 first (MultiBEVSourceDataset.__getitem__).  The draws of item i in epoch e come from
+    np.random.RandomState([seed, e, i]) in the reference's sequence: a batch does not depend on the world size, the
+    batch split or a resume (Fit calls set_epoch).  Items are made on data.merge_stream."""
+
+    CACHE_SCANS = 256
+
+    def __init__(self, n, configs, augmentations, sub_p=0.8, seed=1234, first=0, bev=None, ignore_label=-1):
+        configs = (configs,) if isinstance(configs, str) else tuple(configs)
+        if len(configs) not in (1, 2):
+            raise NotImplementedError(f"{len(configs)} sources (the reference takes one or two)")
+        self.configs, self.num_sources = configs, len(configs)
+        self.augmentations = check_augmentations(augmentations)
+        self.sub_p, self.bev, self.ignore_label = sub_p, bev, ignore_label
+        self.n, self.seed, self.first, self.epoch = int(n), int(seed), int(first), 0
+        self.pairs = MultiSynthScans(n, n, configs, seed=seed, first=first) if self.num_sources == 2 else None
+        self._cache = {}
+
+    def __len__(self):
+        return self.n
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def item_rng(self, i):
+        return np.random.RandomState([self.seed, self.epoch, int(i)])
+
+    def points(self, s, j):
+        """(points, labels) of scan j of source s, on the host (kept, as the reference's use_cache)"""
+        if (s, j) not in self._cache:
+            if len(self._cache) >= self.CACHE_SCANS:
+                self._cache.clear()
+            self._cache[(s, j)] = synth.scan_points_labels(self.first + j + s * synth.SOURCE1_SEED, self.configs[s])
+        return self._cache[(s, j)]
+
+    def item(self, i):
+        """[(source, scan index, draws)] of item i in the current epoch"""
+        rng = self.item_rng(i)
+        js = (int(i),) if self.pairs is None else self.pairs.pair(i)
+        return [(s, j, draw_augmentation(rng, self.points(s, j)[0].shape[0], self.sub_p, self.augmentations))
+                for s, j in enumerate(js)]
+
+    def _batch(self, indices, device):
+        cols = [([], [], [], []) for _ in range(self.num_sources)]
+        for b, i in enumerate(indices):
+            for s, j, draws in self.item(i):
+                pts, labels = self.points(s, j)
+                scan = {"points": torch.from_numpy(pts).to(device), "sem_labels": torch.from_numpy(labels).to(device),
+                        "features": torch.ones((pts.shape[0], 1), dtype=torch.float32, device=device)}
+                m = augment_item(scan, draws, voxel_size=synth.CONFIGS[self.configs[s]]["voxel"],
+                                 bounds=self.bev is not None, ignore_label=self.ignore_label, bev=self.bev)
+                c = m["coordinates"]
+                cols[s][0].append(torch.cat([torch.full((c.shape[0], 1), b, dtype=torch.int32, device=c.device), c],
+                                            dim=1))
+                cols[s][1].append(m["features"])
+                cols[s][2].append(m["sem_labels"].long())
+                if self.bev is not None:
+                    cols[s][3].append(m["bev_labels"])
+        batch = {}
+        for s, (coords, feats, labels, bev) in enumerate(cols):
+            coords = torch.cat(coords)
+            batch["coords_int1" if s else "coords_int"] = coords
+            batch.update({f"source_coordinates{s}": coords.float(), f"source_features{s}": torch.cat(feats),
+                          f"source_sem_labels{s}": torch.cat(labels)})
+            if self.bev is not None:
+                batch[f"source_bev_labels{s}"] = {"block8": torch.stack(bev)}
+        return batch
+
+    def batch(self, indices, device):
+        device = torch.device(device)
+        # the scans are uploaded on the merge stream itself: it does not wait for the caller's stream
         return on_merge_stream(lambda: self._batch(indices, device), device, wait=False)
 
 
@@ -490,7 +572,14 @@ def parse_args(argv=None):
     ap.add_argument("--mix", default=None, choices=MixedSynthScans.METHODS,
                     help="PointCutMix / CoSMix (train_aug_based.py, pipeline.method): each item one scan mixed from a "
                          "pair of the two --sources (default: --config twice), trained as one source with SoftDICE")
-    ap.add_argument("--sub-p", type=float, default=0.8, help="CoSMix: share of each drawn class's rows mixed in")
+    ap.add_argument("--sub-p", type=float, default=0.8, help="CoSMix: share of each drawn class's rows mixed in; "
+                                                             "--augment: the datasets' sub_p, the share of a scan's "
+                                                             "points every item draws")
+    ap.add_argument("--augment", nargs="*", default=None, metavar="NAME",
+                    help="the training datasets' augmentation_list: any ordered list of RandomRotation and RandomScale "
+                         "(the empty list: sub-sampling only).  Every item is then made from the scan's points on the "
+                         "GPU: --sub-p of them in random order, transformed, voxelised; MinkUNet34BEV also gets the "
+                         "bounds filter and BEV labels rasterised from the item")
     ap.add_argument("--sn-targets", nargs="+", default=None, choices=sorted(synth.CONFIGS), metavar="CONFIG",
                     help="SN car-size scaling (train_scaling_based.py): every scan of --config (or of the two --sources) "
                          "is scaled to the car size of these target configurations and re-quantised; the car sizes "
@@ -515,6 +604,11 @@ def parse_args(argv=None):
                      f"MinkUNet34IBN, not {a.model}")
         if a.mix is not None or a.mix3d:
             ap.error("--sn-targets, --mix and --mix3d are different methods: pass one of them")
+    if a.augment is not None:
+        check_augmentations(a.augment)       # NotImplementedError for another name, as get_augmentations
+        if a.mix is not None or a.mix3d or a.sn_targets is not None:
+            ap.error("--augment with --mix, --mix3d or --sn-targets: those datasets interleave the augmentation's draws "
+                     "with their own in the reference, which is not implemented")
     return a
 
 
@@ -534,7 +628,15 @@ def _fit_from_args(a):
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))
     bev = bev_image_size(a.bound)
-    if getattr(a, "sn_targets", None):
+    if getattr(a, "augment", None) is not None:
+        train = AugmentedSynthScans(a.scans, a.sources or a.config, a.augment, sub_p=a.sub_p, seed=a.seed,
+                                    bev=(a.bound, bev) if a.model == "MinkUNet34BEV" else None)
+        if a.sources:                       # validation data is never augmented (phase == 'train' only)
+            val = {name: SynthScans(a.val_scans, c, first=10 ** 6 + i * synth.SOURCE1_SEED, bev_size=bev)
+                   for i, (name, c) in enumerate(zip(source_names(a.sources), a.sources))} if a.val_scans else None
+        else:
+            val = SynthScans(a.val_scans, a.config, first=10 ** 6, bev_size=bev) if a.val_scans else None
+    elif getattr(a, "sn_targets", None):
         configs = a.sources or [a.config]
         train = ScaledSynthScans(a.scans, configs, a.sn_targets, seed=a.seed)
         if a.sources:

@@ -752,6 +752,29 @@ int lidog_augment_points(const float *points, int64_t n, const int32_t *sampled_
                          double qx, double qy, double qz, int32_t batch, const int32_t *labels, int32_t *rows, void *xyz,
                          int32_t *src, int32_t *labels_out, int32_t *info, int32_t *ws, void *stream);
 
+/* ------------------------------------------------------------------ evaluation statistics (eval_target)
+ * What test_step computes per loader batch (utils/pipelines/trainer_lighting.py:186-253, trainer_lighting_bev.py:
+ * 265-323) up to integer counts: the arg-max and the confusion counts that sklearn's jaccard_score and the
+ * present-label mask are made of, and the packed records of the prediction dump.  Integer LDS bins, one global integer
+ * atomic per non-empty bin and block, positions from lidog_mix_split: the same bytes on every run. */
+/* logits [n, n_classes] float32 (n_classes <= 32), labels [n] int64, coords [n, 4] int32 (column 0 = scan of the row).
+ * preds [n] int64 = torch's CPU `logits.max(dim=1)[1]`: the first maximal index, the first NaN in a row holding one.
+ * counts [n_scans, n_classes + 1, n_classes] int64 is ADDED to: counts[scan, label + 1, pred] for labels in
+ * [0, n_classes) other than ignore_label, counts[scan, 0, pred] for every other label.  A row whose scan is outside
+ * [0, n_scans) is not counted and sets err[0] = 1 (device int32, never cleared here).  Rows of one scan need not be
+ * contiguous. */
+int lidog_eval_confusion(const float *logits, const int64_t *labels, const int32_t *coords, int64_t n,
+                         int32_t n_classes, int32_t n_scans, int64_t ignore_label, int64_t *preds, int64_t *counts,
+                         int32_t *err, void *stream);
+/* int32 workspace of lidog_eval_pack */
+int64_t lidog_eval_pack_ws(int64_t n, int32_t n_scans);
+/* The prediction dump of test_step: per scan the rows with label != ignore_label in ascending row order.  out (int32,
+ * room for n_scans + 1 + 5 n): out[s] = first record of scan s, out[n_scans] = number of records, then the records
+ * (x, y, z, prediction, label) grouped by scan: the voxel coordinates, as the reference writes them.  n_scans <= 256.
+ * A row whose scan is outside [0, n_scans) is left out and sets err[0] = 1. */
+int lidog_eval_pack(const int32_t *coords, const int64_t *preds, const int64_t *labels, int64_t n, int32_t n_scans,
+                    int64_t ignore_label, int32_t *out, int32_t *err, int32_t *ws, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,118 @@
+"""Checkpoint evaluation on target domains: the reference's sixth entry script, eval_target.py.
+
+    python -m lidog_amd.eval_target --checkpoint RUN/checkpoints/epoch=0-step=4.ckpt --targets kitti120k nusc35k
+    python -m lidog_amd.eval_target --checkpoint ... --model MinkUNet34 --targets nusc35k --save-predictions
+
+What the reference does through pytorch-lightning's trainer.test, as plain arguments:
+  get_model / get_target_domains / loaders with batch_size * 2, shuffle=False        eval_target.py:46-89,119-167
+  the checkpoint is required; save_dir = two directories above it                    eval_target.py:169-181
+  test_step: one IoU row per loader BATCH, optional point clouds per scan            trainer_lighting.py:186-253,
+                                                                                     trainer_lighting_bev.py:265-323
+  test_epoch_end: `<save_dir>/results/<sources>-TO-<targets>.csv`                    trainer_lighting.py:255-313
+
+The metric runs on the device up to integer confusion counts (lidog_amd.evaluate.TargetEvaluator); the counts cross to
+the host once per target.  Target scans are synthetic (lidog_amd.synth), drawn as train.py draws validation scans: scan
+i of target t has seed 10**6 + t * synth.SOURCE1_SEED + i.  `main(argv)` returns the per-target results.
+"""
+import argparse
+import json
+import os
+import time
+
+import torch
+
+from . import synth
+from .checkpoint import load_lightning_checkpoint
+from .evaluate import (CLASS_NAMES, TargetEvaluator, dataset_batches, palette, write_ply, write_results_csv)
+from .train import SynthScans, bev_image_size, build_model, source_names
+
+MODELS = ("MinkUNet34BEV", "MinkUNet34", "MinkUNet34IBN", "MinkUNet34Robust")
+NO_CHECKPOINT = "You must provide a checkpoint for evaluation!"          # eval_target.py:174
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--checkpoint", default=None, help="checkpoint to evaluate (required); results and predictions go "
+                                                       "to the directory two levels above it")
+    ap.add_argument("--model", default="MinkUNet34BEV", choices=MODELS)
+    ap.add_argument("--bound", type=float, default=50.0)
+    ap.add_argument("--sources", nargs="+", default=["kitti120k"], metavar="NAME",
+                    help="names of the training sources: the CSV's source column and file name")
+    ap.add_argument("--targets", nargs="+", default=["nusc35k"], choices=sorted(synth.CONFIGS), metavar="CONFIG",
+                    help="one or two target configurations")
+    ap.add_argument("--scans", type=int, default=16, help="scans per target")
+    ap.add_argument("--batch", type=int, default=8, help="loader batch: twice train's, as eval_target.py doubles it")
+    ap.add_argument("--rows", default="batch", choices=["batch", "scan"],
+                    help="one IoU row per loader batch (the reference) or per scan")
+    ap.add_argument("--save-predictions", action="store_true")
+    ap.add_argument("--seed", type=int, default=1234)
+    a = ap.parse_args(argv)
+    if a.checkpoint is None:
+        ap.error(NO_CHECKPOINT)
+    if len(a.targets) > 2:
+        raise NotImplementedError(f"{len(a.targets)} targets (the reference takes one or two)")
+    if a.scans < 1 or a.batch < 1:
+        ap.error("--scans and --batch must be positive")
+    return a
+
+
+def save_dir_of(checkpoint):
+    """eval_target.py:176-177: the checkpoint's directory is `<save_dir>/checkpoints`"""
+    return os.path.split(os.path.split(checkpoint)[0])[0]
+
+
+class PredictionWriter:
+    """the point clouds of test_step: `<folder>/<target>/preds/<idx>.ply` coloured by prediction, and, except for the
+    BEV model (trainer_lighting_bev.py:293-320 writes only preds), `<folder>/<target>/labels/<idx>.ply` coloured by
+    label.  The points are the integer voxel coordinates, as the reference writes them."""
+
+    def __init__(self, folder, target, with_labels, num_classes=7):
+        self.dirs = {"preds": os.path.join(folder, target, "preds")}
+        if with_labels:
+            self.dirs["labels"] = os.path.join(folder, target, "labels")
+        for d in self.dirs.values():
+            os.makedirs(d, exist_ok=True)
+        self.colors = palette(num_classes)
+
+    def __call__(self, idx, rec):
+        write_ply(os.path.join(self.dirs["preds"], f"{idx}.ply"), rec[:, :3], self.colors[rec[:, 3] + 1])
+        if "labels" in self.dirs:
+            write_ply(os.path.join(self.dirs["labels"], f"{idx}.ply"), rec[:, :3], self.colors[rec[:, 4] + 1])
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    torch.manual_seed(a.seed)
+    device = "cuda"
+    model = build_model(a.model, a.bound, device=device)
+    epoch, _ = load_lightning_checkpoint(model, a.checkpoint)
+    model.eval()
+    save_dir = save_dir_of(a.checkpoint)
+    sources = "".join(source_names(a.sources))                       # test_epoch_end concatenates the names
+    targets = source_names(a.targets)
+    file_targets = "".join(targets)
+    bev = bev_image_size(a.bound)
+    ev = TargetEvaluator(model, num_classes=len(CLASS_NAMES))
+    results = []
+    for t, (name, config) in enumerate(zip(targets, a.targets)):
+        data = SynthScans(a.scans, config, first=10 ** 6 + t * synth.SOURCE1_SEED, bev_size=bev)
+        writer = None
+        if a.save_predictions:
+            writer = PredictionWriter(os.path.join(save_dir, "predictions"), name, a.model != "MinkUNet34BEV",
+                                      len(CLASS_NAMES))
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = ev.run(dataset_batches(data, a.batch, device), len(data), rows=a.rows, on_predictions=writer)
+        dt = time.perf_counter() - t0                                # run() ends with the host copy of the counts
+        path = write_results_csv(save_dir, sources, name, res["rows"], CLASS_NAMES, first_target=t == 0,
+                                 file_targets=file_targets)
+        out = {"target": name, "checkpoint_epoch": epoch, "per_class_iou": [float(x) for x in res["per_class"]],
+               "mean_iou": res["mean"], "rows": int(res["rows"].shape[0]), "rows_per": a.rows,
+               "scans": int(res["scans"]), "scans_per_s": res["scans"] / dt, "csv": path}
+        print(json.dumps(out), flush=True)
+        results.append(dict(out, iou_rows=res["rows"], counts=res["counts"]))
+    return results
+
+
+if __name__ == "__main__":
+    main()

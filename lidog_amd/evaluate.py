@@ -5,7 +5,11 @@
                  of the class they are predicted as), -1 for classes absent from the scan's labels
   test_epoch_end utils/pipelines/trainer_lighting_bev.py:325-383  -- -1 -> NaN, nan-mean over scans per class,
                  x100, nan-mean over classes
-Everything stays on the device (the reference moves predictions to the CPU for sklearn)."""
+Everything stays on the device (the reference moves predictions to the CPU for sklearn).
+
+eval_target (second half of this file): confusion / TargetEvaluator take the metric from logits to integer counts in
+one HIP kernel (csrc/evalstats.hip) and read the counts once per target; iou_rows turns them into test_step's rows on
+the host, per loader batch as the reference or per scan as evaluate() above."""
 import torch
 
 from . import me as ME
@@ -80,8 +84,9 @@ class Predictor:
 
 @torch.no_grad()
 def evaluate(model, batches, num_classes=7, ignore_label=-1):
-    """batches: iterable of dicts with coords_int [N,4], source_features0, source_sem_labels0 (one IoU row per
-    scan, as test_step is called with batch size 1 in eval_target.py)"""
+    """batches: iterable of dicts with coords_int [N,4], source_features0, source_sem_labels0; one IoU row per SCAN.
+    (The reference's eval_target.py builds its loaders with batch_size * 2 and test_step computes one row per loader
+    batch: that table is TargetEvaluator's rows="batch"; rows="scan" gives this function's.)"""
     rows = []
     run = Predictor(model)
     batches = list(batches)
@@ -96,17 +101,23 @@ def evaluate(model, batches, num_classes=7, ignore_label=-1):
     return mean_iou(torch.stack(rows))
 
 
-def write_results_csv(save_dir, source_names, target_name, per_scan_iou, class_names, first_target=True):
+def write_results_csv(save_dir, source_names, target_name, per_scan_iou, class_names, first_target=True,
+                      file_targets=None):
     """The result file of test_epoch_end (utils/pipelines/trainer_lighting_bev.py:325-383):
     `<save_dir>/results/<source>-TO-<target>.csv`, appended; header `source,target,<class names>,mean` before the first
     target's row; per-class IoU = nan-mean over scans (-1 = class absent from the scan) x 100, rounded to 2 decimals with a
     decimal COMMA, last column the nan-mean over classes.  `per_scan_iou`: [n_scans, C] as returned by per_class_iou;
-    `class_names`: the C names (the reference takes `training_dataset.class2names[1:]`).  Returns the path."""
+    `class_names`: the C names (the reference takes `training_dataset.class2names[1:]`).  `file_targets`: the target
+    part of the file name when it is not this row's target: with two targets the reference names the file after both,
+    concatenated, and each row after its own (trainer_lighting.py:264-313).  Returns the path."""
     import csv
     import os
     import numpy as np
     os.makedirs(os.path.join(save_dir, "results"), exist_ok=True)
-    path = os.path.join(save_dir, "results", f"{source_names}-TO-{target_name}.csv")
+    path = os.path.join(save_dir, "results",
+                        f"{source_names}-TO-{target_name if file_targets is None else file_targets}.csv")
+    if not torch.is_tensor(per_scan_iou):
+        per_scan_iou = torch.from_numpy(np.asarray(per_scan_iou, dtype=np.float64))
     x = per_scan_iou.detach().double().cpu().numpy().copy()
     x[x == -1] = np.nan
     per_class = np.nanmean(x, axis=0) * 100
@@ -118,3 +129,249 @@ def write_results_csv(save_dir, source_names, target_name, per_scan_iou, class_n
         w.writerow([source_names, target_name] + [str(round(p, 2)).replace(".", ",") for p in per_class] +
                    [str(round(float(average), 2)).replace(".", ",")])
     return path
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# eval_target: the metric from logits to integer counts on the device (csrc/evalstats.hip), the IoU rows on the host
+# ---------------------------------------------------------------------------------------------------------------------
+MAX_CLASSES = 32
+
+# class2names[1:] of the reference's common label space, and the colours of the prediction dump: PALETTE[0] is the
+# ignore label's, a class takes PALETTE[class + 1] (as the reference indexes its color_map).  The colours are this
+# project's own.
+CLASS_NAMES = ("vehicle", "person", "road", "sidewalk", "terrain", "manmade", "vegetation")
+PALETTE = ((0, 0, 0), (30, 120, 255), (255, 40, 40), (200, 60, 200), (90, 30, 150), (150, 240, 80), (255, 200, 0),
+           (0, 160, 60))
+
+
+def palette(num_classes=7):
+    """[num_classes + 1, 3] uint8: PALETTE, extended deterministically past 7 classes"""
+    import numpy as np
+    p = [PALETTE[i] if i < len(PALETTE) else ((53 * i) % 256, (97 * i + 80) % 256, (193 * i + 160) % 256)
+         for i in range(num_classes + 1)]
+    return np.asarray(p, dtype=np.uint8)
+
+
+def check_scan_error(err, what="confusion"):
+    """raises when a kernel met a batch index outside [0, n_scans) (one read of a device word)"""
+    if int(err.item()) != 0:
+        raise ValueError(f"{what}: a row's batch index lies outside [0, n_scans); such rows were not counted")
+
+
+def confusion(logits, labels, coords, n_scans, out=None, ignore_label=-1, err=None):
+    """(preds [N] int64, counts [n_scans, C + 1, C] int64) of lidog_eval_confusion, on the device: preds = torch's CPU
+    `logits.max(dim=1)[1]`; counts[scan, label + 1, pred], row 0 for every label outside 0..C-1 and the ignore label.
+    `out`: counts to ADD to (a contiguous [n_scans, C + 1, C] int64 tensor or slice of one).  `err`: an int32 [1] device
+    word the caller checks later with check_scan_error (nothing is read back here); without it this call checks, which
+    costs one synchronisation."""
+    from ._lib import call, ptr, require_gpu
+    require_gpu(logits, "logits")
+    if logits.dim() != 2 or logits.dtype != torch.float32:
+        raise ValueError(f"confusion: logits must be float32 [N, C], got {logits.dtype} {tuple(logits.shape)}")
+    n, c = logits.shape
+    if not 1 <= c <= MAX_CLASSES:
+        raise ValueError(f"confusion: {c} classes (at most {MAX_CLASSES})")
+    if labels.shape != (n,) or labels.dtype != torch.int64:
+        raise ValueError(f"confusion: labels must be int64 [{n}], got {labels.dtype} {tuple(labels.shape)}")
+    if coords.shape != (n, 4) or coords.dtype != torch.int32:
+        raise ValueError(f"confusion: coords must be int32 [{n}, 4], got {coords.dtype} {tuple(coords.shape)}")
+    n_scans = int(n_scans)
+    if out is None:
+        out = torch.zeros((n_scans, c + 1, c), dtype=torch.int64, device=logits.device)
+    elif out.shape != (n_scans, c + 1, c) or out.dtype != torch.int64 or not out.is_contiguous() or \
+            out.device != logits.device:
+        raise ValueError(f"confusion: out must be a contiguous int64 [{n_scans}, {c + 1}, {c}] tensor on {logits.device}")
+    own_err = err is None
+    if own_err:
+        err = torch.zeros(1, dtype=torch.int32, device=logits.device)
+    preds = torch.empty(n, dtype=torch.int64, device=logits.device)
+    call("lidog_eval_confusion", ptr(logits.contiguous()), ptr(labels.contiguous()), ptr(coords.contiguous()), n, c,
+         n_scans, int(ignore_label), ptr(preds), ptr(out), ptr(err))
+    if own_err:
+        check_scan_error(err)
+    return preds, out
+
+
+def pack_predictions(coords, preds, labels, n_scans, ignore_label=-1, err=None):
+    """The prediction dump of test_step as ONE int32 device buffer (lidog_eval_pack): buf[s] = first record of scan s,
+    buf[n_scans] = number of records, then [records, 5] = (x, y, z, prediction, label) of the rows with label !=
+    ignore_label, grouped by scan in ascending row order.  unpack_predictions splits the host copy."""
+    from . import _lib
+    from ._lib import call, ptr, require_gpu
+    require_gpu(coords, "coords")
+    n, n_scans = coords.shape[0], int(n_scans)
+    dev = coords.device
+    own_err = err is None
+    if own_err:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    buf = torch.empty(n_scans + 1 + 5 * n, dtype=torch.int32, device=dev)
+    ws = torch.empty(_lib.load().lidog_eval_pack_ws(n, n_scans), dtype=torch.int32, device=dev)
+    call("lidog_eval_pack", ptr(coords.contiguous()), ptr(preds.contiguous()), ptr(labels.contiguous()), n, n_scans,
+         int(ignore_label), ptr(buf), ptr(err), ptr(ws))
+    if own_err:
+        check_scan_error(err, "pack_predictions")
+    return buf
+
+
+def unpack_predictions(buf, n_scans):
+    """host copy of pack_predictions' buffer (the one copy of a batch) -> list of [k_s, 5] int32 arrays, one per scan"""
+    host = buf.cpu().numpy()
+    start = host[:n_scans + 1]
+    rec = host[n_scans + 1:n_scans + 1 + 5 * int(start[n_scans])].reshape(-1, 5)
+    return [rec[start[s]:start[s + 1]] for s in range(n_scans)]
+
+
+def iou_rows(counts, rows="batch", batch_of_scan=None):
+    """IoU rows of test_step from confusion counts [n_scans, C + 1, C], on the host in float64.  Per row and class:
+    tp / (true + pred - tp) as one division, 0 where the denominator is 0, -1 where the class is absent from the row's
+    labels: sklearn's jaccard_score(preds, labels, average=None, labels=arange(C), zero_division=0.) followed by
+    test_step's masking; a point labelled -1 still enlarges the union of the class it is predicted as.
+    rows="batch": the counts of a loader batch's scans are summed first, one row per batch, as the reference, whose
+    test_step sees a whole batch (eval_target.py:162-167 builds the loaders with batch_size * 2); `batch_of_scan`
+    [n_scans] gives every scan's batch (non-decreasing; None: all scans are one batch).  rows="scan": one row per scan,
+    what evaluate() computes."""
+    import numpy as np
+    m = counts.detach().cpu().numpy() if torch.is_tensor(counts) else np.asarray(counts)
+    m = m.astype(np.int64)
+    if m.ndim != 3 or m.shape[1] != m.shape[2] + 1:
+        raise ValueError(f"iou_rows: counts must be [n_scans, C + 1, C], got {m.shape}")
+    if rows == "batch":
+        b = np.zeros(m.shape[0], np.int64) if batch_of_scan is None else np.asarray(batch_of_scan, dtype=np.int64)
+        if b.shape != (m.shape[0],):
+            raise ValueError(f"iou_rows: batch_of_scan must hold {m.shape[0]} entries")
+        ids = np.unique(b)
+        m = np.stack([m[b == i].sum(axis=0) for i in ids]) if m.shape[0] else m
+    elif rows != "scan":
+        raise ValueError(f"iou_rows: rows={rows!r} (one of 'batch', 'scan')")
+    c = m.shape[2]
+    tp = m[:, 1:, :][:, np.arange(c), np.arange(c)]
+    true = m[:, 1:, :].sum(axis=2)
+    pred = m.sum(axis=1)
+    den = true + pred - tp
+    iou = np.where(den > 0, tp.astype(np.float64) / np.where(den > 0, den, 1).astype(np.float64), 0.0)
+    return np.where(true > 0, iou, -1.0)
+
+
+def mean_iou_rows(rows):
+    """test_epoch_end's arithmetic on the host: -1 -> NaN, nan-mean over rows x 100, nan-mean over classes"""
+    import warnings
+    import numpy as np
+    x = np.array(rows, dtype=np.float64)
+    x[x == -1] = np.nan
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)        # a class absent from every row: NaN, as the reference
+        per_class = np.nanmean(x, axis=0) * 100
+        return per_class, float(np.nanmean(per_class, axis=0))
+
+
+def dataset_batches(data, batch_size, device="cuda"):
+    """(batch, scan indices) over a dataset in order, as an unshuffled DataLoader: the last batch may be short"""
+    for i in range(0, len(data), batch_size):
+        ids = list(range(i, min(i + batch_size, len(data))))
+        yield data.batch(ids, device), ids
+
+
+class TargetEvaluator:
+    """The loop of trainer.test over one target: Predictor with the next batch's coordinate maps in flight, the metric
+    of every batch added by lidog_eval_confusion into ONE preallocated [n_scans_total, C + 1, C] tensor.  Nothing is read
+    from the device per batch unless predictions are saved; the counts (and the error word) cross to the host once, at
+    the end.  A batch's scan count is the number of its dataset indices.
+
+        ev = TargetEvaluator(model)
+        res = ev.run(dataset_batches(data, 8), n_scans=len(data))          # rows="batch": the reference's table
+    `on_predictions(index, records)`: called per scan with its [k, 5] int32 records (x, y, z, prediction, label) of the
+    labelled voxels; asking for it costs one device -> host copy per batch."""
+
+    def __init__(self, model, num_classes=7, ignore_label=-1):
+        self.model, self.num_classes, self.ignore_label = model, int(num_classes), int(ignore_label)
+
+    @torch.no_grad()
+    def run(self, batches, n_scans, rows="batch", on_predictions=None):
+        """`batches`: iterable of (batch dict, scan indices); `n_scans`: scans of all batches together.  Returns a dict:
+        counts [n_scans, C + 1, C] (numpy), batch_of_scan, rows (IoU rows), per_class (percent), mean, scans."""
+        import numpy as np
+        if rows not in ("batch", "scan"):
+            raise ValueError(f"rows={rows!r} (one of 'batch', 'scan')")
+        c = self.num_classes
+        run = Predictor(self.model)
+        it = iter(batches)
+        cur = next(it, None)
+        counts = err = None
+        batch_of_scan = []
+        done = 0
+        nb = 0
+        while cur is not None:
+            nxt = next(it, None)
+            b, ids = cur
+            coords = b["coords_int"]
+            if counts is None:
+                counts = torch.zeros((int(n_scans), c + 1, c), dtype=torch.int64, device=coords.device)
+                err = torch.zeros(1, dtype=torch.int32, device=coords.device)
+            k = len(ids)
+            if done + k > counts.shape[0]:
+                raise ValueError(f"TargetEvaluator: more than n_scans = {n_scans} scans in the batches")
+            _, logits = run(coords, b["source_features0"], nxt[0]["coords_int"] if nxt is not None else None)
+            labels = b["source_sem_labels0"]
+            preds, _ = confusion(logits, labels, coords, k, out=counts[done:done + k], ignore_label=self.ignore_label,
+                                 err=err)
+            if on_predictions is not None:
+                buf = pack_predictions(coords, preds, labels, k, self.ignore_label, err=err)
+                for idx, rec in zip(ids, unpack_predictions(buf, k)):
+                    on_predictions(idx, rec)
+            batch_of_scan += [nb] * k
+            done += k
+            nb += 1
+            cur = nxt
+        if counts is None:
+            raise ValueError("TargetEvaluator: no batches")
+        check_scan_error(err, "TargetEvaluator")
+        counts = counts[:done].cpu().numpy()                     # the one read of a target
+        batch_of_scan = np.asarray(batch_of_scan, dtype=np.int64)
+        r = iou_rows(counts, rows, batch_of_scan)
+        per_class, mean = mean_iou_rows(r)
+        return {"counts": counts, "batch_of_scan": batch_of_scan, "rows": r, "per_class": per_class, "mean": mean,
+                "scans": done}
+
+
+# ------------------------------------------------------------------ point clouds of the prediction dump
+_PLY_FIELDS = (("x", "<f8", "double"), ("y", "<f8", "double"), ("z", "<f8", "double"),
+               ("red", "u1", "uchar"), ("green", "u1", "uchar"), ("blue", "u1", "uchar"))
+
+
+def write_ply(path, points, colors):
+    """binary little-endian PLY: `double x y z`, `uchar red green blue` (the properties of the point clouds test_step
+    writes; open3d's exact bytes are not pinned).  points [n, 3], colors [n, 3] uint8; n = 0 writes an empty cloud."""
+    import numpy as np
+    points = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    colors = np.asarray(colors, dtype=np.uint8).reshape(-1, 3)
+    if points.shape[0] != colors.shape[0]:
+        raise ValueError(f"write_ply: {points.shape[0]} points, {colors.shape[0]} colours")
+    v = np.empty(points.shape[0], dtype=np.dtype([(n, t) for n, t, _ in _PLY_FIELDS]))
+    for i, n in enumerate("xyz"):
+        v[n] = points[:, i]
+    for i, n in enumerate(("red", "green", "blue")):
+        v[n] = colors[:, i]
+    header = ["ply", "format binary_little_endian 1.0", "comment lidog_amd prediction dump",
+              f"element vertex {points.shape[0]}"] + [f"property {p} {n}" for n, _, p in _PLY_FIELDS] + ["end_header"]
+    with open(path, "wb") as f:
+        f.write(("\n".join(header) + "\n").encode("ascii"))
+        f.write(v.tobytes())
+    return path
+
+
+def read_ply(path):
+    """(points [n, 3] float64, colors [n, 3] uint8) of a file written by write_ply"""
+    import numpy as np
+    with open(path, "rb") as f:
+        raw = f.read()
+    end = raw.index(b"end_header\n") + len(b"end_header\n")
+    lines = raw[:end].decode("ascii").split("\n")
+    if lines[0] != "ply" or lines[1] != "format binary_little_endian 1.0":
+        raise ValueError(f"{path}: not a binary little-endian PLY")
+    n = [int(l.split()[2]) for l in lines if l.startswith("element vertex ")][0]
+    props = [tuple(l.split()[1:]) for l in lines if l.startswith("property ")]
+    if props != [(p, name) for name, _, p in _PLY_FIELDS]:
+        raise ValueError(f"{path}: properties {props} (this reader takes double x y z, uchar red green blue)")
+    v = np.frombuffer(raw, dtype=np.dtype([(name, t) for name, t, _ in _PLY_FIELDS]), count=n, offset=end)
+    return (np.stack([v["x"], v["y"], v["z"]], axis=1).reshape(-1, 3),
+            np.stack([v["red"], v["green"], v["blue"]], axis=1).reshape(-1, 3))

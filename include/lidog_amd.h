@@ -775,6 +775,33 @@ int64_t lidog_eval_pack_ws(int64_t n, int32_t n_scans);
 int lidog_eval_pack(const int32_t *coords, const int64_t *preds, const int64_t *labels, int64_t n, int32_t n_scans,
                     int64_t ignore_label, int32_t *out, int32_t *err, int32_t *ws, void *stream);
 
+/* ------------------------------------------------------------------ scans read from files (SemanticKITTI, nuScenes, Synth4D)
+ * What the reference's datasets do with numpy between the file and the cached `data` dict of __getitem__
+ * (utils/datasets/semantickitti.py:100-131,190-197, nuscenes.py:144-178,238-248, synth4d.py:106-137) and in
+ * get_dataset_stats (semantickitti.py:199-213): unpack the records, map the labels, apply the radius mask, compact the
+ * kept rows in order, count the labels per class.  The host uploads the files' bytes unmodified.  Positions come from
+ * lidog_mix_split and the statistics are integer counts: the same bytes on every run.  No allocation, synchronisation or
+ * blocking copy inside. */
+/* int32 workspace of lidog_scan_load for a file of n rows */
+int64_t lidog_scan_load_ws(int64_t n);
+/* points_raw: n records of point_stride >= 3 float32, the first three x y z (4: SemanticKITTI .bin, 5: nuScenes .bin);
+ * NULL: the labels alone (the statistics of a label file), nothing but counts and info[1] is written.
+ * labels_raw [n]: label_kind 1 = int32, 2 = uint8, 0 = none (label 0 for every row, unmapped; labels_raw is not read).
+ * Mapped label = lut[idx] under numpy's indexing, idx = raw & label_mask for int32 labels (-1: no mask; 0xFFFF for
+ * SemanticKITTI) or the byte itself: 0 <= idx < lut_len as is, -lut_len <= idx < 0 wraps, anything else adds one to
+ * info[1] (numpy's IndexError).  use_radius: only rows with ((x x + y y) + z z) < radius_sq are kept, every product and
+ * sum rounded to float32 on its own (no fused multiply-add), the comparison strict, a NaN dropped:
+ * `np.sum(np.square(points), axis=1) < in_R ** 2` with radius_sq = float32(in_R ** 2).
+ * points_out [n, 3] float32 and labels_out [n] int32 (room for n rows): the kept rows in ascending order, the
+ * coordinates copied bit for bit.  counts [num_classes] int64 (optional, num_classes <= 256) is ADDED to: the mapped
+ * labels of ALL n rows, before the radius mask, labels outside [0, num_classes) skipped.  info [4] int32 (device,
+ * cleared here): kept rows, label errors, kept rows with a non-finite coordinate (only possible without the radius
+ * mask), 0.  ws: lidog_scan_load_ws(n) int32. */
+int lidog_scan_load(const float *points_raw, int32_t point_stride, const void *labels_raw, int32_t label_kind,
+                    int32_t label_mask, int64_t n, const int32_t *lut, int32_t lut_len, int32_t use_radius,
+                    float radius_sq, float *points_out, int32_t *labels_out, int64_t *counts, int32_t num_classes,
+                    int32_t *info, int32_t *ws, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -688,3 +688,27 @@ def augment_item(scan, draws, voxel_size=0.05, bounds=False, ignore_label=-1, be
         return out
 
     return on_merge_stream(work, dev, [points, scan["features"], scan["sem_labels"]])
+
+
+def collate_items(items, with_bev):
+    """the batch of `items[b][s]`, the item (augment_item) of source s at batch position b: the keys of
+    synth.make_batch; `source_bev_labels{s}` only with_bev.  Shared by lidog_amd.train.AugmentedSynthScans and
+    lidog_amd.scans.FileScans."""
+    batch = {}
+    for s in range(len(items[0])):
+        coords, feats, labels, bev = [], [], [], []
+        for b, row in enumerate(items):
+            m = row[s]
+            c = m["coordinates"]
+            coords.append(torch.cat([torch.full((c.shape[0], 1), b, dtype=torch.int32, device=c.device), c], dim=1))
+            feats.append(m["features"])
+            labels.append(m["sem_labels"].long())
+            if with_bev:
+                bev.append(m["bev_labels"])
+        coords = torch.cat(coords)
+        batch["coords_int1" if s else "coords_int"] = coords
+        batch.update({f"source_coordinates{s}": coords.float(), f"source_features{s}": torch.cat(feats),
+                      f"source_sem_labels{s}": torch.cat(labels)})
+        if with_bev:
+            batch[f"source_bev_labels{s}"] = {"block8": torch.stack(bev)}
+    return batch

@@ -2,6 +2,7 @@
 
     python -m lidog_amd.eval_target --checkpoint RUN/checkpoints/epoch=0-step=4.ckpt --targets kitti120k nusc35k
     python -m lidog_amd.eval_target --checkpoint ... --model MinkUNet34 --targets nusc35k --save-predictions
+    python -m lidog_amd.eval_target --checkpoint ... --target-files SemanticKITTI=/data/SemanticKITTI --label-maps semantickitti2common.yaml
 
 What the reference does through pytorch-lightning's trainer.test, as plain arguments:
   get_model / get_target_domains / loaders with batch_size * 2, shuffle=False        eval_target.py:46-89,119-167
@@ -24,6 +25,7 @@ import torch
 from . import synth
 from .checkpoint import load_lightning_checkpoint
 from .evaluate import (CLASS_NAMES, TargetEvaluator, dataset_batches, palette, write_ply, write_results_csv)
+from . import scans
 from .train import SynthScans, bev_image_size, build_model, source_names
 
 MODELS = ("MinkUNet34BEV", "MinkUNet34", "MinkUNet34IBN", "MinkUNet34Robust")
@@ -46,9 +48,15 @@ def parse_args(argv=None):
                     help="one IoU row per loader batch (the reference) or per scan")
     ap.add_argument("--save-predictions", action="store_true")
     ap.add_argument("--seed", type=int, default=1234)
+    scans.add_file_arguments(ap, "--target-files", "evaluate on the validation")
     a = ap.parse_args(argv)
     if a.checkpoint is None:
         ap.error(NO_CHECKPOINT)
+    if a.target_files is not None:
+        a.target_files = scans.check_file_arguments(ap, a.target_files, a, "--target-files")
+        a.targets = [n for n, _ in a.target_files]               # the CSV's target names
+    elif a.label_maps is not None or a.synth4d_splits is not None or a.limit_files is not None:
+        ap.error("--label-maps, --synth4d-splits and --limit-files go with --target-files")
     if len(a.targets) > 2:
         raise NotImplementedError(f"{len(a.targets)} targets (the reference takes one or two)")
     if a.scans < 1 or a.batch < 1:
@@ -94,8 +102,15 @@ def main(argv=None):
     bev = bev_image_size(a.bound)
     ev = TargetEvaluator(model, num_classes=len(CLASS_NAMES))
     results = []
+    luts = None
+    if a.target_files is not None:
+        luts = scans.luts_from_files(a.label_maps)
     for t, (name, config) in enumerate(zip(targets, a.targets)):
-        data = SynthScans(a.scans, config, first=10 ** 6 + t * synth.SOURCE1_SEED, bev_size=bev)
+        if luts is not None:      # the validation listing of the target, every kept point, voxelised
+            data = scans.FileScans(scans.listing(config, a.target_files[t][1], "validation", version=a.version,
+                                                 synth4d_splits=a.synth4d_splits, limit=a.limit_files), luts[t])
+        else:
+            data = SynthScans(a.scans, config, first=10 ** 6 + t * synth.SOURCE1_SEED, bev_size=bev)
         writer = None
         if a.save_predictions:
             writer = PredictionWriter(os.path.join(save_dir, "predictions"), name, a.model != "MinkUNet34BEV",

@@ -14,8 +14,11 @@ What the reference's entry scripts do through pytorch-lightning, as plain argume
     python -m lidog_amd.train --model MinkUNet34 --mix cosmix ...    (PointCutMix / CoSMix, configs/{pointcutmix,cosmix})
     python -m lidog_amd.train --model MinkUNet34 --config kitti120k_cars --sn-targets nusc35k_cars ...   (SN, configs/SN)
     python -m lidog_amd.train --augment RandomRotation RandomScale --sub-p 0.8 ...   (sub_p / augmentation_list of the configs)
+    python -m lidog_amd.train --files SemanticKITTI=/data/SemanticKITTI --label-maps semantickitti2common.yaml ...
+                                                                       (scans from files: lidog_amd.scans)
 
-Scans are synthetic (lidog_amd.synth; there are no datasets on the box); anything with `__len__` and
+Scans are synthetic (lidog_amd.synth; there are no datasets on the box) unless --files names a dataset on disk
+(lidog_amd.scans: SemanticKITTI, Synth4D, a nuScenes pair list); anything with `__len__` and
 `batch(indices, device) -> dict` (keys of CollateFNSingleSourceBEVMultiLevel, collation.py:318-325) can be passed as
 `train_data` / `val_data` instead.
 """
@@ -29,10 +32,11 @@ import torch
 import torch.distributed as dist
 
 from . import me as ME
+from . import scans
 from . import synth
 from .checkpoint import load_training_checkpoint, save_lightning_checkpoint
-from .data import (augment_item, check_augmentations, cosmix_merge, draw_augmentation, draw_scaling, on_merge_stream,
-                   pointcutmix_merge, scaling_params, sn_scale)
+from .data import (augment_item, check_augmentations, collate_items, cosmix_merge, draw_augmentation, draw_scaling,
+                   on_merge_stream, pointcutmix_merge, scaling_params, sn_scale)
 from .evaluate import per_class_iou
 from .optim import make_optimizer, make_scheduler, shard_indices
 from .trainer import LiDOGStep, RobustStep, SourceStep, setup_data_parallel
@@ -303,30 +307,17 @@ class AugmentedSynthScans:
                 for s, j in enumerate(js)]
 
     def _batch(self, indices, device):
-        cols = [([], [], [], []) for _ in range(self.num_sources)]
-        for b, i in enumerate(indices):
+        items = []
+        for i in indices:
+            row = []
             for s, j, draws in self.item(i):
                 pts, labels = self.points(s, j)
                 scan = {"points": torch.from_numpy(pts).to(device), "sem_labels": torch.from_numpy(labels).to(device),
                         "features": torch.ones((pts.shape[0], 1), dtype=torch.float32, device=device)}
-                m = augment_item(scan, draws, voxel_size=synth.CONFIGS[self.configs[s]]["voxel"],
-                                 bounds=self.bev is not None, ignore_label=self.ignore_label, bev=self.bev)
-                c = m["coordinates"]
-                cols[s][0].append(torch.cat([torch.full((c.shape[0], 1), b, dtype=torch.int32, device=c.device), c],
-                                            dim=1))
-                cols[s][1].append(m["features"])
-                cols[s][2].append(m["sem_labels"].long())
-                if self.bev is not None:
-                    cols[s][3].append(m["bev_labels"])
-        batch = {}
-        for s, (coords, feats, labels, bev) in enumerate(cols):
-            coords = torch.cat(coords)
-            batch["coords_int1" if s else "coords_int"] = coords
-            batch.update({f"source_coordinates{s}": coords.float(), f"source_features{s}": torch.cat(feats),
-                          f"source_sem_labels{s}": torch.cat(labels)})
-            if self.bev is not None:
-                batch[f"source_bev_labels{s}"] = {"block8": torch.stack(bev)}
-        return batch
+                row.append(augment_item(scan, draws, voxel_size=synth.CONFIGS[self.configs[s]]["voxel"],
+                                        bounds=self.bev is not None, ignore_label=self.ignore_label, bev=self.bev))
+            items.append(row)
+        return collate_items(items, self.bev is not None)
 
     def batch(self, indices, device):
         device = torch.device(device)
@@ -563,7 +554,7 @@ def parse_args(argv=None):
     ap.add_argument("--warmup-epochs", type=int, default=0)
     ap.add_argument("--scans", type=int, default=16, help="synthetic training scans per epoch (all ranks together)")
     ap.add_argument("--val-scans", type=int, default=0)
-    ap.add_argument("--config", default="kitti120k", choices=sorted(synth.CONFIGS))
+    ap.add_argument("--config", default=None, choices=sorted(synth.CONFIGS), help="default: kitti120k")
     ap.add_argument("--sources", nargs=2, default=None, choices=sorted(synth.CONFIGS), metavar="CONFIG",
                     help="train on two sources (configs/*/multi/*.yaml): --scans scans of each, paired as "
                          "MultiBEVSourceDataset; each source is validated on its own")
@@ -589,7 +580,19 @@ def parse_args(argv=None):
     ap.add_argument("--resume", default=None)
     ap.add_argument("--auto-resume", action="store_true")
     ap.add_argument("--seed", type=int, default=1234)
+    scans.add_file_arguments(ap, "--files", "train on")
     a = ap.parse_args(argv)
+    if a.files is not None:
+        for flag, given in (("--config", a.config is not None), ("--sources", a.sources is not None),
+                            ("--mix", a.mix is not None), ("--mix3d", a.mix3d), ("--sn-targets", a.sn_targets is not None)):
+            if given:
+                ap.error(f"--files with {flag}: scans come either from files or from the synthetic generator; mixing "
+                         f"and SN over files are not implemented")
+        a.files = scans.check_file_arguments(ap, a.files, a, "--files")
+    elif a.label_maps is not None or a.synth4d_splits is not None or a.limit_files is not None:
+        ap.error("--label-maps, --synth4d-splits and --limit-files go with --files")
+    if a.config is None:
+        a.config = "kitti120k"
     if a.mix is not None:
         if a.model in ("MinkUNet34BEV", "MinkUNet34Robust"):   # PLTMixed.training_step: SoftDICE only
             ap.error(f"--mix trains with the SoftDICE-only step of PLTMixed: --model MinkUNet34 or MinkUNet34IBN, "
@@ -628,7 +631,9 @@ def _fit_from_args(a):
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))
     bev = bev_image_size(a.bound)
-    if getattr(a, "augment", None) is not None:
+    if getattr(a, "files", None):
+        train, val = _file_data(a, bev)
+    elif getattr(a, "augment", None) is not None:
         train = AugmentedSynthScans(a.scans, a.sources or a.config, a.augment, sub_p=a.sub_p, seed=a.seed,
                                     bev=(a.bound, bev) if a.model == "MinkUNet34BEV" else None)
         if a.sources:                       # validation data is never augmented (phase == 'train' only)
@@ -659,6 +664,17 @@ def _fit_from_args(a):
                source_weights=tuple(a.source_weights), check_val_every_n_epoch=a.check_val_every_n_epoch,
                save_dir=a.save_dir, seed=a.seed, train_data=train, val_data=val, resume=a.resume,
                auto_resume=a.auto_resume)
+
+
+def _file_data(a, bev):
+    """--files: (training dataset, {name: validation dataset}) over the listings of phase train / validation"""
+    luts = scans.luts_from_files(a.label_maps)
+    kw = dict(version=a.version, synth4d_splits=a.synth4d_splits, limit=a.limit_files)
+    train = scans.FileScans([scans.listing(n, p, "train", **kw) for n, p in a.files], luts, augmentations=a.augment,
+                            sub_p=a.sub_p, seed=a.seed, bev=(a.bound, bev) if a.model == "MinkUNet34BEV" else None)
+    val = {name: scans.FileScans(scans.listing(n, p, "validation", **kw), lut, seed=a.seed)
+           for name, (n, p), lut in zip(source_names([n for n, _ in a.files]), a.files, luts)}
+    return train, val
 
 
 def _finish_distributed():

@@ -16,12 +16,10 @@ from ibn_ref import ADAM_LR, ADAM_STEPS, ADAM_WD, G9, instance_norm64
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.timeout(90)
-@pytest.mark.parametrize("C", [32, 64, 128])
-def test_fused_ibn_relu_is_bit_identical_to_the_literal_composition(C):
+def _fused_equals_literal(coords, C, expect_fused=True):
+    """ME.ibn_relu against relu(cat(bn(x), in(x))) through the module's operators on `coords`: torch.equal on the output,
+    every gradient and the running statistics"""
     import lidog_amd.me as ME
-    coords = small_batch((0, 1), n_points=1500)
-    coords = coords[torch.randperm(coords.shape[0], generator=torch.Generator().manual_seed(1))].contiguous().cuda()
     g = torch.Generator().manual_seed(C)
     n = coords.shape[0]
     f0 = (torch.randn((n, C), generator=g) * 1.5 + 0.3).cuda()
@@ -37,7 +35,7 @@ def test_fused_ibn_relu_is_bit_identical_to_the_literal_composition(C):
         x = ME.SparseTensor(f, coordinates=coords)
         if fused:
             out = ME.ibn_relu(b, i, x)
-            assert type(out.F.grad_fn).__name__ == "_IBNReluFnBackward"
+            assert (type(out.F.grad_fn).__name__ == "_IBNReluFnBackward") == expect_fused
         else:
             out = ME.MinkowskiReLU(inplace=True)(ME.cat(b(x), i(x)))
         out.F.backward(dy)
@@ -46,6 +44,27 @@ def test_fused_ibn_relu_is_bit_identical_to_the_literal_composition(C):
     names = ["y", "dx", "bn dweight", "bn dbias", "in dweight", "in dbias", "running_mean", "running_var"]
     for a, r, what in zip(results[0], results[1], names):
         assert torch.equal(a, r), f"{what} differs (C={C}): max {((a - r).abs().max().item())}"
+
+
+@pytest.mark.timeout(90)
+@pytest.mark.parametrize("C", [32, 64, 128])
+def test_fused_ibn_relu_is_bit_identical_to_the_literal_composition(C):
+    coords = small_batch((0, 1), n_points=1500)
+    coords = coords[torch.randperm(coords.shape[0], generator=torch.Generator().manual_seed(1))].contiguous().cuda()
+    _fused_equals_literal(coords, C)
+
+
+@pytest.mark.timeout(60)
+@pytest.mark.parametrize("name,C,fused", [("tiny16", 32, True), ("b17_literal", 128, False), ("empty_middle", 64, True)])
+def test_fused_ibn_relu_is_bit_identical_on_scan_layouts(name, C, fused):
+    """the layouts of test_gpu_inorm64.MODULE_LAYOUTS: 16 scans shorter than a row block and one long one, 17 scans at
+    C = 128 (2 B C > 4096: ibn_relu itself takes the literal composition), a scan without rows in the middle"""
+    import inorm_ref as IR
+    sizes = {"tiny16": IR.TINY, "b17_literal": IR._uneven(4000, 17), "empty_middle": [3000, 0, 2003]}[name]
+    d = IR.make_case(dict(C=C, sizes=sizes, order="shuffled"))
+    i = torch.arange(d["n"], dtype=torch.int32)
+    coords = torch.stack([d["batch"], i % 64, (i // 64) % 64, i // 4096], dim=1).contiguous().cuda()
+    _fused_equals_literal(coords, C, expect_fused=fused)
 
 
 def _g9_model():

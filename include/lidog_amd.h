@@ -701,6 +701,23 @@ int lidog_mix_gather(const int32_t *coords_t, int64_t n_target, const int32_t *c
                      const int32_t *slot_start, const int32_t *perm, const int32_t *take_start, int32_t n_slots,
                      int64_t n_take, float voxel_size, float *coords_out, int32_t n_cols, void *const *cols_host,
                      const int32_t *col_words_host, void *stream);
+/* The same merged set with CoSMix's in-merge augmentation (cosmix.py:135-136: `self.augmentations(coords_tmp)` on every
+ * pasted class), written as voxel rows in ONE launch, without atomics: merged row r < n_target is target row r, row
+ * n_target + j is source row rows[slot_start[s] + perm[j]] (perm NULL: rows[j]) of the slot s with take_start[s] <= j <
+ * take_start[s + 1]; take_start (device, n_slots + 1) is always read.  coords_s has n_source rows, and rows room for
+ * n_source entries: an index outside is clamped, nothing outside is read.  A class row float(c) * voxel_size (float32) is
+ * transformed by the n_ops <= 4 operations op_kinds_host (HOST, shared by the slots; 0 rotation, 1 scale, the
+ * arithmetic of lidog_augment_points) with the slot's own parameters slot_params[(s * n_ops + o) * 9 ..] (device,
+ * float64, n_slots <= 256); a target row is left as it is.  f64 != 0: the concatenation is float64 (torch.cat of the
+ * float32 target rows with rotated class rows), so EVERY row is floored as float64, floor(double(x) / q); f64 == 0:
+ * every row is float32 and floored as lidog_voxel_floor does.  rows_out [n_target + n_take, 4] int32 = (0, voxel), ready
+ * for lidog_coords_insert.  Columns as lidog_mix_gather. */
+int lidog_mix_gather_aug(const int32_t *coords_t, int64_t n_target, const int32_t *coords_s, int64_t n_source,
+                         const int32_t *rows, const int32_t *slot_start, const int32_t *perm,
+                         const int32_t *take_start, int32_t n_slots, int64_t n_take, float voxel_size,
+                         const int32_t *op_kinds_host, int32_t n_ops, const double *slot_params, int32_t f64, double qx,
+                         double qy, double qz, int32_t *rows_out, int32_t n_cols, void *const *cols_host,
+                         const int32_t *col_words_host, void *stream);
 
 /* ------------------------------------------------------------------ SN car-size scaling: DBSCAN, cluster boxes, scaling
  * The start-up statistics of train_scaling_based.py:35-129 (get_average_dims clusters the car voxels of every drawn

@@ -147,6 +147,8 @@ SIGNATURES = {
     "lidog_mix_split_ws": [_i64, _i32],
     "lidog_mix_split": [_p, _i64, _p, _i32, _i32, _p, _p, _p, _p],
     "lidog_mix_gather": [_p, _i64, _p, _p, _p, _p, _p, _i32, _i64, _f, _p, _i32, _p, _p, _p],
+    "lidog_mix_gather_aug": [_p, _i64, _p, _i64, _p, _p, _p, _p, _i32, _i64, _f, _p, _i32, _p, _i32, _d, _d, _d, _p, _i32,
+                             _p, _p, _p],
     "lidog_dbscan_ws": [_i64],
     "lidog_dbscan": [_p, _i64, _f, _d, _i32, _p, _p, _p, _i64, _p],
     "lidog_cluster_boxes": [_p, _p, _i64, _i32, _p, _p, _p, _p],

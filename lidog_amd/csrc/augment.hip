@@ -5,55 +5,9 @@
 // and the stable compaction of the kept rows.  The host makes the draws; the rotation matrix and the scales travel by
 // value in the launch arguments.  The kept rows take their positions from lidog_mix_split (mix.hip: per-block counts,
 // one scan, in-wave ballot ranks), never from an atomic: the same rows in the same order on every run.
-#include "common.h"
+#include "aug_ops.h"
 
 #define AUG_THREADS 256
-#define AUG_MAX_OPS 4
-#define AUG_ROTATION 0
-#define AUG_SCALE 1
-
-struct AugOps {
-    int32_t n;
-    int32_t kind[AUG_MAX_OPS];
-    double p[AUG_MAX_OPS][9];   // rotation: R row-major (out_j = sum_k p_k R[k][j]); scale: s_x, s_y, s_z
-};
-
-struct AugPoint {
-    double d[3];   // the point once it is float64
-    float f[3];    // the point while it is float32
-    bool is64;
-};
-
-// numpy's arithmetic on one row.  `coords @ R` with a float64 R: the float32 row is widened (exactly) and every output
-// is (p0 R0j + p1 R1j) + p2 R2j in float64.  `coords[:, k] = coords[:, k] * s_k` with a float64 s_k: one float64
-// product, which the in-place assignment rounds back to float32 while the array still is float32.
-__device__ __forceinline__ AugPoint aug_transform(const float *__restrict__ pts, int64_t i, const AugOps &ops) {
-    AugPoint a;
-    a.is64 = false;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        a.f[k] = pts[3 * i + k];
-        a.d[k] = 0.0;
-    }
-    for (int o = 0; o < ops.n; ++o) {
-        const double *p = ops.p[o];
-        if (ops.kind[o] == AUG_ROTATION) {
-            double x[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) x[k] = a.is64 ? a.d[k] : (double)a.f[k];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) a.d[j] = (x[0] * p[j] + x[1] * p[3 + j]) + x[2] * p[6 + j];
-            a.is64 = true;
-        } else if (a.is64) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) a.d[k] = a.d[k] * p[k];
-        } else {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) a.f[k] = (float)((double)a.f[k] * p[k]);
-        }
-    }
-    return a;
-}
 
 // filter_bounds: strict comparisons on the value in its own dtype (a float32 widens exactly)
 __device__ __forceinline__ bool aug_in_bounds(const AugPoint &a) {
@@ -108,13 +62,11 @@ __global__ __launch_bounds__(AUG_THREADS) void k_aug_emit(const float *__restric
     }
     const int64_t i = aug_source_row(sampled_idx, j, n, info);
     const AugPoint a = aug_transform(pts, i, ops);
-    if (a.is64) {   // np.floor(c / q) on a float64 array, q = float64(quantization_size)
-        rows[r] = make_int4(batch, (int)floor(a.d[0] / qx), (int)floor(a.d[1] / qy), (int)floor(a.d[2] / qz));
+    rows[r] = aug_voxel_row(a, batch, qx, qy, qz);   // the floor in the point's own dtype
+    if (a.is64) {
         double *o = (double *)xyz + 3 * r;
         o[0] = a.d[0]; o[1] = a.d[1]; o[2] = a.d[2];
-    } else {        // on a float32 array, q = float32(quantization_size): k_voxel_floor
-        rows[r] = make_int4(batch, (int)floorf(a.f[0] / (float)qx), (int)floorf(a.f[1] / (float)qy),
-                            (int)floorf(a.f[2] / (float)qz));
+    } else {
         float *o = (float *)xyz + 3 * r;
         o[0] = a.f[0]; o[1] = a.f[1]; o[2] = a.f[2];
     }

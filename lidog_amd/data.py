@@ -141,13 +141,26 @@ def mix3d_merge(scan0, scan1, voxel_size=0.05, ignore_label=-1):
     """Mix3DSourceDataset.merge_data (utils/datasets/mix3D.py:44-87): union of two voxelised scans, re-quantised.
     scan = dict(coordinates int [n,3], features [n,C], sem_labels [n]) on the GPU.  As in the reference the
     coordinates go through float32 (`coordinates * voxel_size`, then floor(x / voxel_size)), and the label of a
-    merged voxel is the label of its FIRST point (the voted labels returned by sparse_quantize are discarded)."""
+    merged voxel is the label of its FIRST point (the voted labels returned by sparse_quantize are discarded).  Scans
+    that carry `xyz` / `sampled_idx` / `idx` also give the reference's `xyz` (the unfiltered concatenation),
+    `sampled_idx` (of the voxels' first points) and `idx` [2, 1]."""
     coords = torch.cat([scan0["coordinates"], scan1["coordinates"]], dim=0).float() * voxel_size
     feats = torch.cat([scan0["features"], scan1["features"]], dim=0)
     labels = torch.cat([scan0["sem_labels"], scan1["sem_labels"]], dim=0)
     q, _, _, idx = sparse_quantize(coords, feats, labels=labels, ignore_label=ignore_label,
                                    quantization_size=voxel_size, return_index=True)
-    return {"coordinates": q, "features": feats[idx], "sem_labels": labels[idx], "index": idx}
+    out = {"coordinates": q, "features": feats[idx], "sem_labels": labels[idx], "index": idx}
+    # the reference's remaining keys (mix3D.py:61-86), when the scans carry them: xyz is NOT filtered by the voxels
+    for k in ("xyz", "sampled_idx", "idx"):
+        if (k in scan0) != (k in scan1):
+            raise KeyError(f"'{k}' in one scan only")
+    if "xyz" in scan0:
+        out["xyz"] = torch.cat([scan0["xyz"], scan1["xyz"]], dim=0)
+    if "sampled_idx" in scan0:
+        out["sampled_idx"] = torch.cat([scan0["sampled_idx"], scan1["sampled_idx"]], dim=0)[idx]
+    if "idx" in scan0:
+        out["idx"] = torch.cat([scan0["idx"].view(1, -1), scan1["idx"].view(1, -1)], dim=0)
+    return out
 
 
 # ------------------------------------------------------------------ scan mixing: PointCutMix and CoSMix
@@ -219,22 +232,25 @@ def draw_cells(rng, counts, min_points=300, n_cells=4):
     return rng.choice(vox_idx[counts > min_points], n_cells, replace=False)
 
 
-def draw_classes(rng, counts, weights, sub_p):
-    """cosmix.py:108-133 (random_sample :53-63): the classes present in the source (counts[c] = its rows of class c), `int(len / 2)` of them
+def draw_classes(rng, counts, weights, sub_p, augmentations=None):
+    """cosmix.py:108-136 (random_sample :53-63): the classes present in the source (counts[c] = its rows of class c), `int(len / 2)` of them
     drawn with p = weights[class_idx] * (1 / weights[class_idx].sum()), then for each drawn class, in order, the
-    sub-sample `np.random.choice(np.arange(n_c), int(sub_p * n_c), replace=False)` (sub_p None: arange(n_c)).
-    Returns (classes, [sub-sample of each class])."""
+    sub-sample `np.random.choice(np.arange(n_c), int(sub_p * n_c), replace=False)` (sub_p None: arange(n_c)) and, with
+    `augmentations` (a list of names, the empty one included), the list's own draws (draw_ops) right after it.
+    Returns (classes, [sub-sample of each class]), with a list also [ops of each class]."""
     counts = np.asarray(counts)
     weights = np.asarray(weights, dtype=np.float64)
     class_idx = np.nonzero(counts)[0]
     sampling_weights = weights[class_idx] * (1 / weights[class_idx].sum())
     classes = rng.choice(class_idx, int(len(class_idx) / 2), p=sampling_weights, replace=False)
-    subs = []
+    subs, ops = [], []
     for c in classes:
         n_c = int(counts[c])
         subs.append(rng.choice(np.arange(n_c), int(sub_p * n_c), replace=False) if sub_p is not None
                     else np.arange(n_c))
-    return classes, subs
+        if augmentations is not None:
+            ops.append(draw_ops(rng, augmentations))
+    return (classes, subs) if augmentations is None else (classes, subs, ops)
 
 
 _MERGE_COLUMNS = ("features", "sem_labels", "xyz", "sampled_idx")
@@ -273,15 +289,16 @@ def _split(keys, slot_of_key, n_slots):
     return rows, start
 
 
-def _merge(scan0, scan1, sel, voxel_size, rows, start, n_take, subs=None):
-    """target rows, then the selected source rows (lidog_mix_gather), re-quantised at voxel_size; the reference's dict"""
+def _merge(scan0, scan1, sel, voxel_size, rows, start, n_take, subs=None, class_ops=None):
+    """target rows, then the selected source rows (lidog_mix_gather), re-quantised at voxel_size; the reference's dict.
+    class_ops (one op list per slot, as draw_ops returns them; [] when no class was drawn): CoSMix's in-merge
+    augmentation, lidog_mix_gather_aug writes the voxel rows itself."""
     src, tgt = (scan0, scan1) if sel == 0 else (scan1, scan0)
     dev = tgt["coordinates"].device
     nt = tgt["coordinates"].shape[0]
     total = nt + n_take
     coords_t = tgt["coordinates"].to(torch.int32).contiguous()
     coords_s = src["coordinates"].to(torch.int32).contiguous()
-    merged = torch.empty((total, 3), dtype=torch.float32, device=dev)
     cols, ptrs, words = {}, [], []
     for k in _MERGE_COLUMNS:
         if k not in tgt:
@@ -301,10 +318,16 @@ def _merge(scan0, scan1, sel, voxel_size, rows, start, n_take, subs=None):
         take_start = np.concatenate([[0], np.cumsum([len(p) for p in subs])]).astype(np.int32)
         buf = torch.from_numpy(np.concatenate([take_start] + [np.asarray(p, dtype=np.int32) for p in subs])).to(dev)
         take, perm = buf[:n_slots + 1], buf[n_slots + 1:]
-    call("lidog_mix_gather", ptr(coords_t), nt, ptr(coords_s), ptr(rows), ptr(start), ptr(perm), ptr(take), n_slots,
-         n_take, float(np.float32(voxel_size)), ptr(merged), len(words), (ctypes.c_void_p * max(len(ptrs), 1))(*ptrs),
-         (ctypes.c_int32 * max(len(words), 1))(*words))
-    q, index = sparse_quantize(merged, quantization_size=voxel_size, return_index=True)
+    col_ptrs = (ctypes.c_void_p * max(len(ptrs), 1))(*ptrs)
+    col_words = (ctypes.c_int32 * max(len(words), 1))(*words)
+    if class_ops is None:
+        merged = torch.empty((total, 3), dtype=torch.float32, device=dev)
+        call("lidog_mix_gather", ptr(coords_t), nt, ptr(coords_s), ptr(rows), ptr(start), ptr(perm), ptr(take), n_slots,
+             n_take, float(np.float32(voxel_size)), ptr(merged), len(words), col_ptrs, col_words)
+        q, index = sparse_quantize(merged, quantization_size=voxel_size, return_index=True)
+    else:
+        q, index = _gather_aug(coords_t, coords_s, rows, start, perm, take, n_slots, n_take, subs, class_ops, voxel_size,
+                               len(words), col_ptrs, col_words)
     out = {"coordinates": q}
     for k in ("xyz", "features", "sem_labels"):
         if k in cols:
@@ -316,6 +339,39 @@ def _merge(scan0, scan1, sel, voxel_size, rows, start, n_take, subs=None):
     out["index"] = index
     out["source"] = sel
     return out
+
+
+def _gather_aug(coords_t, coords_s, rows, start, perm, take, n_slots, n_take, subs, class_ops, voxel_size, n_cols,
+                col_ptrs, col_words):
+    """lidog_mix_gather_aug, then quantize_rows: (voxel coordinates, first point of every voxel).  The dtype the
+    reference floors in: a class's rows leave a rotation as float64 (`float32_tensor @ float64_ndarray`), and torch.cat
+    promotes the whole concatenation, the float32 target rows included, once one class tensor is float64, an EMPTY one
+    too ([0, 3] tensors take part in cat's type promotion).  No class drawn, or no rotation in the list: float32."""
+    dev = coords_t.device
+    nt, total = coords_t.shape[0], coords_t.shape[0] + n_take
+    names = [a for a, _ in class_ops[0]] if class_ops else []
+    if any([a for a, _ in ops] != names for ops in class_ops) or len(class_ops) != n_slots:
+        raise ValueError("cosmix_merge: one op list per drawn class, over the same names")
+    if len(names) > 4:
+        raise NotImplementedError(f"cosmix_merge: {len(names)} augmentations (at most 4)")
+    kinds = (ctypes.c_int32 * max(len(names), 1))(*[AUGMENTATIONS.index(a) for a in names])
+    params = np.zeros((max(n_slots, 1), max(len(names), 1), 9), dtype=np.float64)
+    for s_, ops in enumerate(class_ops):
+        for o, (a, p) in enumerate(ops):
+            p = np.asarray(p, dtype=np.float64).reshape(-1)
+            if p.shape[0] != (9 if a == "RandomRotation" else 3) or not np.all(np.isfinite(p)):
+                raise ValueError(f"cosmix_merge: parameters of {a}: {p}")
+            params[s_, o, :p.shape[0]] = p
+    f64 = 1 if (n_slots and "RandomRotation" in names) else 0
+    if n_slots and (take is None or perm is None):
+        raise ValueError("cosmix_merge: the augmented gather needs every class's sub-sample")
+    slot_params = torch.from_numpy(params).to(dev) if n_slots and names else None
+    q3 = np.broadcast_to(np.asarray(voxel_size, dtype=np.float64), (3,))
+    vrows = torch.empty((total, 4), dtype=torch.int32, device=dev)
+    call("lidog_mix_gather_aug", ptr(coords_t), nt, ptr(coords_s), coords_s.shape[0], ptr(rows), ptr(start), ptr(perm),
+         ptr(take), n_slots, n_take, float(np.float32(voxel_size)), kinds, len(names), ptr(slot_params), f64,
+         float(q3[0]), float(q3[1]), float(q3[2]), ptr(vrows), n_cols, col_ptrs, col_words)
+    return quantize_rows(vrows, return_index=True)
 
 
 def pointcutmix_merge(scan0, scan1, voxel_size=0.05, ignore_label=-1, rng=np.random, cell_size=10.0, min_points=300,
@@ -359,9 +415,18 @@ def cosmix_merge(scan0, scan1, voxel_size=0.05, class_weights=None, sub_p=0.8, i
     are drawn with probability proportional to their weight; each class's rows (ascending) are sub-sampled by a random
     permutation prefix of int(sub_p * n_c) rows (sub_p None: all of them, in order) and appended, class by class in the
     order drawn, to the other scan's rows; the union is re-quantised at voxel_size.  Returns the reference's dict plus
-    `index` and `source`."""
+    `index` and `source`.
+    augmentations: the source datasets' `augmentation_list` (20 of the reference's configurations set it under the
+    mixing datasets: mix3D/, pointcutmix/, cosmix/, SN/), a list over RandomRotation / RandomScale, the empty one
+    included: every pasted class is transformed by draws of its own made right after its sub-sample (cosmix.py:128-136);
+    `xyz` is sub-sampled but not transformed.  With a rotation in the list and a class drawn the reference floors the
+    whole concatenation, the target's rows too, in float64, which moves about 40 % of the target's voxels by one: kept.
+    None: no transform and nothing drawn for it.  Anything but a list of names raises NotImplementedError."""
     if augmentations is not None:
-        raise NotImplementedError("cosmix_merge: augmentations (augmentation_list is null in every shipped config)")
+        if not isinstance(augmentations, (list, tuple)) or not all(isinstance(a, str) for a in augmentations):
+            raise NotImplementedError("cosmix_merge: augmentations must be None or a list of names over "
+                                      f"{AUGMENTATIONS}, not {type(augmentations).__name__}")
+        augmentations = check_augmentations(augmentations)
     if class_weights is None or len(class_weights) != 2:
         raise ValueError("cosmix_merge needs class_weights = (w0, w1), one per-class count array per source")
     scans = _check_scans(scan0, scan1)
@@ -372,17 +437,21 @@ def cosmix_merge(scan0, scan1, voxel_size=0.05, class_weights=None, sub_p=0.8, i
     def work():
         labels = scans[sel]["sem_labels"].to(torch.int32).contiguous()
         counts = _device_counts(labels, weights.shape[0])
-        classes, subs = draw_classes(rng, counts, weights, sub_p)
+        drawn = draw_classes(rng, counts, weights, sub_p, augmentations)
+        classes, subs = drawn[0], drawn[1]
+        class_ops = drawn[2] if augmentations is not None else None
         for c, p in zip(classes, subs):      # the gather reads rows[slot_start[s] + p]: p must lie inside the class
             if len(p) and (int(np.min(p)) < 0 or int(np.max(p)) >= int(counts[c])):
                 raise RuntimeError("cosmix_merge: a sub-sample index outside its class")
         if len(classes) == 0:
-            return _merge(scan0, scan1, sel, voxel_size, None, None, 0)
+            return _merge(scan0, scan1, sel, voxel_size, None, None, 0, class_ops=class_ops)
         slot_of_class = np.full(weights.shape[0], -1, dtype=np.int32)
         slot_of_class[classes] = np.arange(len(classes), dtype=np.int32)
         rows, start = _split(labels, slot_of_class, len(classes))
         n_take = int(sum(len(p) for p in subs))
-        return _merge(scan0, scan1, sel, voxel_size, rows, start, n_take, subs if sub_p is not None else None)
+        # with the transforms the gather needs every class's extent: sub_p None passes its identity sub-samples
+        return _merge(scan0, scan1, sel, voxel_size, rows, start, n_take,
+                      subs if sub_p is not None or class_ops is not None else None, class_ops=class_ops)
 
     return on_merge_stream(work, dev, [t for s in scans for t in s.values()])
 
@@ -589,6 +658,22 @@ def rotation_matrix(axis, theta):
     return expm(np.cross(np.eye(3), axis / norm(axis) * theta))
 
 
+def draw_ops(rng, augmentation_list):
+    """the draws of one pass through the list, in order: RandomRotation's `rand(3)`, `rand(1)`, RandomScale's three
+    `rand(1)` (utils/common/augmentation.py:12-34).  Returns [(name, float64 parameters)]: R [3, 3] for a rotation,
+    [s_x, s_y, s_z] for a scale.  Shared by the items (draw_augmentation) and CoSMix's pasted classes (draw_classes)."""
+    ops = []
+    for a in check_augmentations(augmentation_list):
+        if a == "RandomRotation":
+            axis = rng.rand(3) - 0.5
+            theta = np.pi / 4 * (rng.rand(1) - 0.5)
+            ops.append((a, np.ascontiguousarray(rotation_matrix(axis, theta), dtype=np.float64)))
+        else:
+            scale, bias = SCALE_RANGE[1] - SCALE_RANGE[0], SCALE_RANGE[0]
+            ops.append((a, np.concatenate([scale * rng.rand(1) + bias for _ in range(3)]).astype(np.float64)))
+    return ops
+
+
 def draw_augmentation(rng, n, sub_p, augmentation_list):
     """The draws of one training item in the reference's sequence (rng: a legacy RandomState or the np.random module):
     random_sample's `choice(arange(n), int(sub_p * n), replace=False)` (sub_p None: nothing drawn, every row in order),
@@ -598,16 +683,7 @@ def draw_augmentation(rng, n, sub_p, augmentation_list):
     names = check_augmentations(augmentation_list)
     n = int(n)
     sampled_idx = rng.choice(np.arange(n), int(sub_p * n), replace=False) if sub_p is not None else np.arange(n)
-    ops = []
-    for a in names:
-        if a == "RandomRotation":
-            axis = rng.rand(3) - 0.5
-            theta = np.pi / 4 * (rng.rand(1) - 0.5)
-            ops.append((a, np.ascontiguousarray(rotation_matrix(axis, theta), dtype=np.float64)))
-        else:
-            scale, bias = SCALE_RANGE[1] - SCALE_RANGE[0], SCALE_RANGE[0]
-            ops.append((a, np.concatenate([scale * rng.rand(1) + bias for _ in range(3)]).astype(np.float64)))
-    return {"sampled_idx": np.asarray(sampled_idx, dtype=np.int64), "ops": ops}
+    return {"sampled_idx": np.asarray(sampled_idx, dtype=np.int64), "ops": draw_ops(rng, names)}
 
 
 def augment_points(points, sampled_idx, ops, voxel_size=0.05, bounds=False, labels=None, batch=0):

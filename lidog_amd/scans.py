@@ -25,7 +25,8 @@ import torch
 
 from . import _lib
 from ._lib import call, ptr
-from .data import augment_item, check_augmentations, collate_items, draw_augmentation, merge_stream, on_merge_stream
+from .data import (NUSCENES_NAME, augment_item, check_augmentations, collate_items, draw_augmentation, merge_stream,
+                   on_merge_stream)
 
 NAMES = ("SemanticKITTI", "Synth4D-kitti", "Synth4D-nuscenes", "nuScenes")
 # per dataset: how a file is laid out and what the reference's dataset does with it.  `stride`: floats per point record
@@ -381,6 +382,37 @@ class FileScans:
                                     bounds=self.bev is not None, ignore_label=self.ignore_label, bev=self.bev,
                                     bev_from=self.listings[s].format["bev_from"]))
         return row
+
+    # ---- the item provider of lidog_amd.train.MixedSynthScans / ScaledSynthScans (see train.PlainSynthItems)
+    @property
+    def voxel(self):
+        return self.voxel_size
+
+    def draw_item(self, s, j, rng, device="cuda"):
+        """the draws of file j of source s: the number of kept points is known once the file is loaded, so this needs the
+        device; the loaded scan is kept for make_item"""
+        device = torch.device("cuda" if device is None else device)
+        scan = on_merge_stream(lambda: self.scan(s, j, device), device, wait=False)
+        self._last = ((s, int(j), str(device)), scan)
+        return self.draws(rng, scan["points"].shape[0])
+
+    def make_item(self, s, j, draws, device):
+        from .train import merge_scan
+        device = torch.device(device)
+        key, scan = getattr(self, "_last", (None, None))
+        if key != (s, int(j), str(device)):
+            scan = self.scan(s, j, device)
+        self._last = (None, None)
+        return merge_scan(augment_item(scan, draws, voxel_size=self.voxel_size, bounds=self.bev is not None,
+                                       ignore_label=self.ignore_label), j)
+
+    def class_weights(self, n=None, num_classes=None):
+        w = self.class_counts()
+        return (w,) if isinstance(w, np.ndarray) else tuple(w)
+
+    def face_name(self, s):
+        name = self.listings[s].name
+        return NUSCENES_NAME if name == "nuScenes" else name
 
     def item(self, i, device="cuda"):
         """the items (one per source, lidog_amd.data.augment_item's dict) of index i in the current epoch"""

@@ -12,6 +12,8 @@ What the reference's entry scripts do through pytorch-lightning, as plain argume
     python -m torch.distributed.run --nproc-per-node N -m lidog_amd.train ...        (one process per GPU, RCCL)
     python -m lidog_amd.train --sources kitti120k nusc35k --source-weights 0.5 0.5 ...   (two sources, */multi/*.yaml)
     python -m lidog_amd.train --model MinkUNet34 --mix cosmix ...    (PointCutMix / CoSMix, configs/{pointcutmix,cosmix})
+    python -m lidog_amd.train --model MinkUNet34 --mix cosmix --source-augment RandomRotation RandomScale ...
+                                              (the source datasets' augmentation_list under --mix / --mix3d / --sn-targets)
     python -m lidog_amd.train --model MinkUNet34 --config kitti120k_cars --sn-targets nusc35k_cars ...   (SN, configs/SN)
     python -m lidog_amd.train --augment RandomRotation RandomScale --sub-p 0.8 ...   (sub_p / augmentation_list of the configs)
     python -m lidog_amd.train --files SemanticKITTI=/data/SemanticKITTI --label-maps semantickitti2common.yaml ...
@@ -35,8 +37,8 @@ from . import me as ME
 from . import scans
 from . import synth
 from .checkpoint import load_training_checkpoint, save_lightning_checkpoint
-from .data import (augment_item, check_augmentations, collate_items, cosmix_merge, draw_augmentation, draw_scaling,
-                   on_merge_stream, pointcutmix_merge, scaling_params, sn_scale)
+from .data import (augment_item, check_augmentations, collate_items, cosmix_merge, draw_augmentation,
+                   draw_scaling, draw_source, mix3d_merge, on_merge_stream, pointcutmix_merge, scaling_params, sn_scale)
 from .evaluate import per_class_iou
 from .optim import make_optimizer, make_scheduler, shard_indices
 from .trainer import LiDOGStep, RobustStep, SourceStep, setup_data_parallel
@@ -89,35 +91,84 @@ class MultiSynthScans:
                                 mix3d=self.mix3d, seeds1=[self.first + b for _, b in pairs], config1=self.configs[1])
 
 
+class PlainSynthItems:
+    """The item provider of MixedSynthScans / ScaledSynthScans over plain synthetic voxel scans (the default): an item is
+    the scan as it is and draws nothing, the reference's `if self.phase == 'train' and self.augmentations is not None`
+    with a null augmentation_list.  A provider has `augmentations` (the source datasets' list or None), `sub_p`,
+    `voxel`, `draw_item(s, j, rng, device)` (host draws of scan j of source s, in the reference's __getitem__ sequence),
+    `make_item(s, j, draws, device)` (the item as the merges read it, on the device), `class_weights(n, num_classes)` and
+    `face_name(s)`.  AugmentedSynthScans and scans.FileScans are the other two."""
+
+    augmentations = None
+    sub_p = None
+
+    def __init__(self, configs, first=0):
+        self.configs, self.first = tuple(configs), int(first)
+        self.voxel = synth.CONFIGS[self.configs[0]]["voxel"]
+
+    def draw_item(self, s, j, rng, device=None):
+        return None
+
+    def make_item(self, s, j, draws, device):
+        vox, labels = synth.scan_voxels(self.first + j + s * synth.SOURCE1_SEED, self.configs[s])
+        return {"coordinates": torch.from_numpy(vox).to(device),
+                "features": torch.ones((vox.shape[0], 1), dtype=torch.float32, device=device),
+                "sem_labels": torch.from_numpy(labels).to(device)}
+
+    def class_weights(self, n, num_classes=7):
+        return tuple(source_class_counts(c, [self.first + j + s * synth.SOURCE1_SEED for j in range(k)], num_classes)
+                     for s, (c, k) in enumerate(zip(self.configs, n)))
+
+    def face_name(self, s):
+        return synth.CONFIGS[self.configs[s]].get("dataset", self.configs[s])
+
+
+def merge_scan(item, j):
+    """an item of augment_item as the merges and sn_scale read it: the reference's keys, `idx` the scan's index"""
+    scan = {k: item[k] for k in ("coordinates", "features", "sem_labels", "xyz", "sampled_idx")}
+    scan["idx"] = torch.tensor(int(j))
+    return scan
+
+
 class MixedSynthScans:
-    """PointCutMixSourceDataset / CoSMixSourceDataset (utils/datasets/pointcutmix.py, cosmix.py; train_aug_based.py:
-    97-102): two sources paired as MultiSynthScans.pair, each item ONE scan merged from its pair on the GPU
-    (lidog_amd.data.pointcutmix_merge / cosmix_merge), so a batch is a one-source batch (num_sources = 1) with the keys
-    SourceStep reads.  The draws of item i in epoch e come from np.random.RandomState([seed, e, i]): a mix does not depend
-    on the world size, the batch split or a resume (Fit calls set_epoch).  The scans are uploaded and merged on
-    data.merge_stream, and the batch is handed to the caller's stream with an event: the merges' read-backs do not wait
-    for a training step queued earlier.  CoSMix's class weights are the per-class label counts over each source's
-    training scans (get_dataset_stats, synth4d.py:203-220); the voxel size is source 0's, as the reference's."""
+    """Mix3DSourceDataset / PointCutMixSourceDataset / CoSMixSourceDataset (utils/datasets/mix3D.py, pointcutmix.py,
+    cosmix.py; train_aug_based.py:86-102): two sources paired as MultiSynthScans.pair, each item ONE scan merged from its
+    pair on the GPU (lidog_amd.data.mix3d_merge / pointcutmix_merge / cosmix_merge), so a batch is a one-source batch
+    (num_sources = 1) with the keys SourceStep reads.  The two scans come from an item provider (`items`): plain synthetic
+    voxel scans (PlainSynthItems, the default), the augmented items of an AugmentedSynthScans, or the items of a
+    scans.FileScans.  Item i of epoch e draws from ONE np.random.RandomState([seed, e, i]) in the order of the
+    reference's __getitem__: source 0's item, source 1's item, then the merge's own draws, CoSMix applying the
+    provider's augmentation list once more to every pasted class: a mix does not depend on the world size, the batch
+    split or a resume (Fit calls set_epoch).  `plan(i)` gives the host side of that.  The scans are uploaded and merged
+    on data.merge_stream, and the batch is handed to the caller's stream with an event: the merges' read-backs do not
+    wait for a training step queued earlier.  CoSMix's class weights are the per-class label counts over each source's
+    training scans (get_dataset_stats, synth4d.py:203-220; FileScans.class_counts over files); the voxel size is source
+    0's, as the reference's."""
 
     num_sources = 1
     METHODS = ("pointcutmix", "cosmix")
+    ALL_METHODS = ("mix3d",) + METHODS
 
     def __init__(self, n0, n1, configs=("kitti120k", "kitti120k"), method="cosmix", sub_p=0.8, seed=1234, first=0,
-                 num_classes=7):
-        if method not in self.METHODS:
-            raise NotImplementedError(f"mixing method {method!r} (one of {self.METHODS})")
+                 num_classes=7, items=None):
+        if method not in self.ALL_METHODS:
+            raise NotImplementedError(f"mixing method {method!r} (one of {self.ALL_METHODS})")
+        self.items = PlainSynthItems(configs, first) if items is None else items
         self.pairs = MultiSynthScans(n0, n1, configs, seed=seed, first=first)
-        self.configs, self.method, self.sub_p, self.seed, self.first = tuple(configs), method, sub_p, int(seed), first
-        self.voxel = synth.CONFIGS[self.configs[0]]["voxel"]
+        self.configs, self.method, self.seed, self.first = tuple(configs), method, int(seed), first
+        # the reference's self.sub_p / self.augmentations = source_dataset0's; plain scans keep the constructor's sub_p
+        self.sub_p = sub_p if items is None else self.items.sub_p
+        self.augmentations = self.items.augmentations
+        self.voxel = self.items.voxel
         self.epoch = 0
-        if method == "pointcutmix":
+        if method == "mix3d":
+            self.merge = lambda s0, s1, rng: mix3d_merge(s0, s1, voxel_size=self.voxel)
+        elif method == "pointcutmix":
             self.merge = functools.partial(pointcutmix_merge, voxel_size=self.voxel)
         else:
-            self.class_weights = tuple(
-                source_class_counts(c, [first + j + s * synth.SOURCE1_SEED for j in range(n)], num_classes)
-                for s, (c, n) in enumerate(zip(self.configs, (n0, n1))))
+            self.class_weights = tuple(self.items.class_weights((int(n0), int(n1)), num_classes))
             self.merge = functools.partial(cosmix_merge, voxel_size=self.voxel, class_weights=self.class_weights,
-                                           sub_p=sub_p)
+                                           sub_p=self.sub_p, augmentations=self.augmentations)
 
     def __len__(self):
         return len(self.pairs)
@@ -128,17 +179,39 @@ class MixedSynthScans:
     def item_rng(self, i):
         return np.random.RandomState([self.seed, self.epoch, int(i)])
 
+    def _draws(self, i, device=None):
+        """(scan indices, the two items' draws, the generator standing at the merge's first draw)"""
+        rng = self.item_rng(i)
+        js = self.pairs.pair(i)
+        return js, [self.items.draw_item(s, j, rng, device) for s, j in enumerate(js)], rng
+
+    def plan(self, i, device=None):
+        """the host side of item i in the current epoch: {'scans': (j0, j1), 'items': [draws of source 0's item, of
+        source 1's] (None: an item that draws nothing), 'merge': {'source': the merge's first draw} (mix3d: {})}.  The
+        merge's later draws (cells, classes, sub-samples, per-class transforms) follow from the same generator but
+        depend on counts the device makes from the two items.  Synthetic providers need no device; a FileScans
+        provider reads the scan's point count from the loaded file."""
+        js, draws, rng = self._draws(i, device)
+        return {"scans": tuple(js), "items": draws, "merge": {} if self.method == "mix3d" else
+                {"source": draw_source(rng)}}
+
     def _scan(self, s, j, device):
-        vox, labels = synth.scan_voxels(self.first + j + s * synth.SOURCE1_SEED, self.configs[s])
-        return {"coordinates": torch.from_numpy(vox).to(device),
-                "features": torch.ones((vox.shape[0], 1), dtype=torch.float32, device=device),
-                "sem_labels": torch.from_numpy(labels).to(device)}
+        return self.items.make_item(s, j, None, device)
+
+    def _item(self, i, device):
+        js, draws, rng = self._draws(i, device)
+        scans_ = [self.items.make_item(s, j, d, device) for s, (j, d) in enumerate(zip(js, draws))]
+        return self.merge(scans_[0], scans_[1], rng=rng)
+
+    def item(self, i, device="cuda"):
+        """the merged dict of item i in the current epoch (the merge's keys)"""
+        device = torch.device(device)
+        return on_merge_stream(lambda: self._item(i, device), device, wait=False)
 
     def _batch(self, indices, device):
         coords, feats, labels = [], [], []
         for b, i in enumerate(indices):
-            j0, j1 = self.pairs.pair(i)
-            m = self.merge(self._scan(0, j0, device), self._scan(1, j1, device), rng=self.item_rng(i))
+            m = self._item(i, device)
             c = m["coordinates"].to(torch.int32)
             coords.append(torch.cat([torch.full((c.shape[0], 1), b, dtype=torch.int32, device=c.device), c], dim=1))
             feats.append(m["features"])
@@ -174,6 +247,24 @@ class SynthDataset:
         return {"coordinates": torch.from_numpy(vox), "sem_labels": torch.from_numpy(labels)}
 
 
+class ItemFace:
+    """the same face over the items of an item provider (source s): item i is made with draws taken from `rng`, the
+    generator average_dims is given, so the sequence is draw_scans first, then every selected item's own draws
+    (get_average_dims reads `dataset.__getitem__(i)` of the augmented training dataset, train_scaling_based.py:44-46)"""
+
+    def __init__(self, items, s, n, rng, device="cuda"):
+        self.items, self.s, self.n, self.rng, self.device = items, int(s), int(n), rng, torch.device(device)
+        self.name, self.voxel_size, self.ignore_label = items.face_name(s), items.voxel, -1
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, i):
+        draws = self.items.draw_item(self.s, int(i), self.rng, self.device)
+        item = on_merge_stream(lambda: self.items.make_item(self.s, int(i), draws, self.device), self.device, wait=False)
+        return {"coordinates": item["coordinates"], "sem_labels": item["sem_labels"]}
+
+
 class ScaledSynthScans:
     """SingleSNSourceDataset / MultiSNSourceDataset (utils/datasets/sn_scaling.py; train_scaling_based.py:253-264) over
     synthetic scans: every item is a source scan whose coordinates are scaled per axis by (target car size / source car
@@ -185,25 +276,38 @@ class ScaledSynthScans:
     scaling_params returns) skips that.  Quirks kept: with ONE source the first target's row is always applied
     (sn_scaling.py:46-51 tests the number of sources); with two, each item draws one target row per source.  Item i of
     epoch e draws from np.random.RandomState([seed, e, i]), as MixedSynthScans: a batch does not depend on the world
-    size, the batch split or a resume."""
+    size, the batch split or a resume.
+    `items`: an item provider as MixedSynthScans takes (default: the plain voxel scans).  An item then draws, from that
+    one generator, source 0's item, source 1's item, then the scale rows (sn_scaling.py:36-51,107-131), and the source
+    statistics are taken on the provider's (augmented) training items, the targets' on their plain validation items
+    (`target_faces`: ready-made dataset faces, for targets read from files).  `plan(i)` is the host side of an item."""
 
     def __init__(self, n, configs, targets, seed=1234, first=0, n_target=None, scaling=None, device="cuda",
-                 cache_dir=None):
+                 cache_dir=None, items=None, target_faces=None):
         configs = (configs,) if isinstance(configs, str) else tuple(configs)
         if len(configs) not in (1, 2):
             raise NotImplementedError(f"{len(configs)} sources (the reference takes one or two)")
-        if not targets:
+        if not targets and not target_faces:
             raise ValueError("ScaledSynthScans needs at least one target configuration")
         self.configs, self.targets = configs, tuple(targets)
         self.num_sources = len(configs)
-        self.n, self.seed, self.first, self.epoch = int(n), int(seed), int(first), 0
-        self.pairs = MultiSynthScans(n, n, configs, seed=seed, first=first) if self.num_sources == 2 else None
-        self.voxel = synth.CONFIGS[configs[0]]["voxel"]      # the reference's self.voxel_size = source_dataset0.voxel_size
+        ns = tuple(int(k) for k in n) if isinstance(n, (tuple, list)) else (int(n),) * self.num_sources
+        if len(ns) != self.num_sources:
+            raise ValueError("n: one number of scans, or one per source")
+        n = max(ns)
+        self.n, self.seed, self.first, self.epoch = n, int(seed), int(first), 0
+        self.pairs = MultiSynthScans(ns[0], ns[1], configs, seed=seed, first=first) if self.num_sources == 2 else None
+        self.items = PlainSynthItems(configs, first) if items is None else items
+        self.voxel = self.items.voxel                        # the reference's self.voxel_size = source_dataset0.voxel_size
         if scaling is None:
             rng = np.random.RandomState(self.seed)
-            sources = [SynthDataset(n, c, first + s * synth.SOURCE1_SEED) for s, c in enumerate(configs)]
-            tgts = [SynthDataset(n if n_target is None else n_target, c, 10 ** 6 + t * synth.SOURCE1_SEED)
-                    for t, c in enumerate(self.targets)]
+            if items is None:
+                sources = [SynthDataset(ns[s], c, first + s * synth.SOURCE1_SEED) for s, c in enumerate(configs)]
+            else:
+                sources = [ItemFace(items, s, ns[s], rng, device) for s in range(self.num_sources)]
+            tgts = list(target_faces) if target_faces else [
+                SynthDataset(n if n_target is None else n_target, c, 10 ** 6 + t * synth.SOURCE1_SEED)
+                for t, c in enumerate(self.targets)]
             scaling = scaling_params(sources, tgts, cache_dir=cache_dir, rng=rng, device=device)
         self.scaling = [np.asarray(a, dtype=np.float32) for a in scaling]
         if len(self.scaling) != self.num_sources or any(a.ndim != 2 or a.shape[1] != 3 for a in self.scaling):
@@ -218,25 +322,30 @@ class ScaledSynthScans:
     def item_rng(self, i):
         return np.random.RandomState([self.seed, self.epoch, int(i)])
 
+    def plan(self, i, device=None):
+        """the host side of item i in the current epoch: {'scans': scan indices, 'items': [draws of each source's item]
+        (None: an item that draws nothing), 'merge': {'rows': the scale row of each source}}, drawn in that order"""
+        rng = self.item_rng(i)
+        js = (int(i),) if self.pairs is None else self.pairs.pair(i)
+        draws = [self.items.draw_item(s, j, rng, device) for s, j in enumerate(js)]
+        return {"scans": tuple(js), "items": draws, "merge": {"rows": draw_scaling(rng, self.scaling, self.num_sources)}}
+
     def item(self, i):
         """[(source, scan index, scale row)] of item i in the current epoch"""
-        rows = draw_scaling(self.item_rng(i), self.scaling, self.num_sources)
-        js = (int(i),) if self.pairs is None else self.pairs.pair(i)
-        return [(s, j, rows[s]) for s, j in enumerate(js)]
+        p = self.plan(i)
+        return [(s, j, p["merge"]["rows"][s]) for s, j in enumerate(p["scans"])]
 
-    def scan(self, s, j, device):
-        vox, labels = synth.scan_voxels(self.first + j + s * synth.SOURCE1_SEED, self.configs[s])
-        return {"coordinates": torch.from_numpy(vox).to(device),
-                "features": torch.ones((vox.shape[0], 1), dtype=torch.float32, device=device),
-                "sem_labels": torch.from_numpy(labels).to(device)}
+    def scan(self, s, j, device, draws=None):
+        return self.items.make_item(s, j, draws, device)
 
     scale = staticmethod(sn_scale)
 
     def _batch(self, indices, device):
         cols = [([], [], []) for _ in range(self.num_sources)]
         for b, i in enumerate(indices):
-            for s, j, row in self.item(i):
-                m = self.scale(self.scan(s, j, device), row, voxel_size=self.voxel)
+            p = self.plan(i, device)
+            for s, (j, draws, row) in enumerate(zip(p["scans"], p["items"], p["merge"]["rows"])):
+                m = self.scale(self.scan(s, j, device, draws), row, voxel_size=self.voxel)
                 c = m["coordinates"].to(torch.int32)
                 cols[s][0].append(torch.cat([torch.full((c.shape[0], 1), b, dtype=torch.int32, device=c.device), c],
                                             dim=1))
@@ -305,6 +414,35 @@ class AugmentedSynthScans:
         js = (int(i),) if self.pairs is None else self.pairs.pair(i)
         return [(s, j, draw_augmentation(rng, self.points(s, j)[0].shape[0], self.sub_p, self.augmentations))
                 for s, j in enumerate(js)]
+
+    # ---- the item provider of MixedSynthScans / ScaledSynthScans (see PlainSynthItems)
+    @property
+    def voxel(self):
+        return synth.CONFIGS[self.configs[0]]["voxel"]
+
+    def draw_item(self, s, j, rng, device=None):
+        return draw_augmentation(rng, self.points(s, j)[0].shape[0], self.sub_p, self.augmentations)
+
+    def make_item(self, s, j, draws, device):
+        pts, labels = self.points(s, j)
+        scan = {"points": torch.from_numpy(pts).to(device), "sem_labels": torch.from_numpy(labels).to(device),
+                "features": torch.ones((pts.shape[0], 1), dtype=torch.float32, device=device)}
+        return merge_scan(augment_item(scan, draws, voxel_size=synth.CONFIGS[self.configs[s]]["voxel"],
+                                       bounds=self.bev is not None, ignore_label=self.ignore_label), j)
+
+    def class_weights(self, n, num_classes=7):
+        """get_dataset_stats: per-class counts of the labels of ALL points of each source's training scans"""
+        out = []
+        for s, k in enumerate(n):
+            w = np.zeros(num_classes)
+            for j in range(k):
+                lab = self.points(s, j)[1]
+                w += np.bincount(lab[(lab >= 0) & (lab < num_classes)], minlength=num_classes)
+            out.append(w)
+        return tuple(out)
+
+    def face_name(self, s):
+        return synth.CONFIGS[self.configs[s]].get("dataset", self.configs[s])
 
     def _batch(self, indices, device):
         items = []
@@ -580,39 +718,95 @@ def parse_args(argv=None):
     ap.add_argument("--resume", default=None)
     ap.add_argument("--auto-resume", action="store_true")
     ap.add_argument("--seed", type=int, default=1234)
+    # the flags below have no attribute unless they are given (argparse.SUPPRESS): read them with getattr
+    ap.add_argument("--source-augment", nargs="*", default=argparse.SUPPRESS, metavar="NAME",
+                    help="with --mix, --mix3d, --sn-targets or --sn-target-files: the SOURCE datasets' augmentation_list "
+                         "(and --sub-p their sub_p), as the reference's configs/{mix3D,pointcutmix,cosmix,SN} set it: "
+                         "every item is sub-sampled, transformed and voxelised before it is mixed or scaled, CoSMix "
+                         "transforms every pasted class once more, and the SN car sizes are measured on the augmented "
+                         "items.  With --mix3d every item becomes one scan merged on the GPU")
+    ap.add_argument("--sn-target-files", nargs="+", default=argparse.SUPPRESS, metavar="NAME=PATH",
+                    help="SN over --files: the target datasets (their validation listings give the target car sizes)")
+    ap.add_argument("--sn-target-label-maps", nargs="+", default=argparse.SUPPRESS, metavar="FILE",
+                    help="one label map per --sn-target-files entry")
     scans.add_file_arguments(ap, "--files", "train on")
     a = ap.parse_args(argv)
+    source_augment = getattr(a, "source_augment", None)
+    sn_target_files = getattr(a, "sn_target_files", None)
+    sn_target_label_maps = getattr(a, "sn_target_label_maps", None)
     if a.files is not None:
-        for flag, given in (("--config", a.config is not None), ("--sources", a.sources is not None),
-                            ("--mix", a.mix is not None), ("--mix3d", a.mix3d), ("--sn-targets", a.sn_targets is not None)):
+        for flag, given in (("--config", a.config is not None), ("--sources", a.sources is not None)):
             if given:
-                ap.error(f"--files with {flag}: scans come either from files or from the synthetic generator; mixing "
-                         f"and SN over files are not implemented")
+                ap.error(f"--files with {flag}: scans come either from files or from the synthetic generator")
+        if a.sn_targets is not None:
+            ap.error("--files with --sn-targets: the targets of SN over files are files too, pass --sn-target-files "
+                     "NAME=PATH ... with --sn-target-label-maps")
+        if (a.mix is not None or a.mix3d) and len(a.files) != 2:
+            ap.error(f"--files with {'--mix' if a.mix is not None else '--mix3d'}: a mix pairs two datasets, pass exactly "
+                     f"two entries A=PATH B=PATH")
         a.files = scans.check_file_arguments(ap, a.files, a, "--files")
     elif a.label_maps is not None or a.synth4d_splits is not None or a.limit_files is not None:
         ap.error("--label-maps, --synth4d-splits and --limit-files go with --files")
+    if sn_target_files is not None:
+        if a.files is None:
+            ap.error("--sn-target-files goes with --files (synthetic scans take --sn-targets)")
+        try:
+            a.sn_target_files = sn_target_files = scans.parse_files(sn_target_files)
+        except ValueError as e:
+            ap.error(f"--sn-target-files: {e}")
+        if sn_target_label_maps is None or len(sn_target_label_maps) != len(sn_target_files):
+            ap.error("--sn-target-files needs --sn-target-label-maps with one file per entry")
+        if any(n.startswith("Synth4D") for n, _ in sn_target_files) and a.synth4d_splits is None:
+            ap.error("--sn-target-files: a Synth4D entry needs --synth4d-splits")
+    elif sn_target_label_maps is not None:
+        ap.error("--sn-target-label-maps goes with --sn-target-files")
+    sn = a.sn_targets is not None or sn_target_files is not None
+    if source_augment is not None:
+        check_augmentations(source_augment)       # NotImplementedError for another name, as get_augmentations
+        if a.augment is not None:
+            ap.error("--source-augment with --augment: --augment is a plain training dataset's list, --source-augment "
+                     "the list of the source datasets under a mixing or SN dataset; pass one of them")
+        if not (a.mix is not None or a.mix3d or sn):
+            ap.error("--source-augment goes with --mix, --mix3d, --sn-targets or --sn-target-files (a plain training "
+                     "dataset takes --augment)")
     if a.config is None:
         a.config = "kitti120k"
+    if mix_method_of(a) == "mix3d":
+        if a.model in ("MinkUNet34BEV", "MinkUNet34Robust"):   # one merged scan per item, PLTMixed: SoftDICE only
+            ap.error(f"--mix3d with --source-augment or --files trains on merged items with the SoftDICE-only step of "
+                     f"PLTMixed: --model MinkUNet34 or MinkUNet34IBN, not {a.model}")
+        if a.files is None and a.sources is None:
+            a.sources = [a.config, a.config]
     if a.mix is not None:
         if a.model in ("MinkUNet34BEV", "MinkUNet34Robust"):   # PLTMixed.training_step: SoftDICE only
             ap.error(f"--mix trains with the SoftDICE-only step of PLTMixed: --model MinkUNet34 or MinkUNet34IBN, "
                      f"not {a.model}")
         if a.mix3d:
             ap.error("--mix and --mix3d are two different methods (pipeline.method): pass one of them")
-        if a.sources is None:
+        if a.sources is None and a.files is None:
             a.sources = [a.config, a.config]    # the single configs list one dataset twice
-    if a.sn_targets is not None:
+    if sn:
+        flag = "--sn-targets" if a.sn_targets is not None else "--sn-target-files"
         if a.model in ("MinkUNet34BEV", "MinkUNet34Robust"):   # train_scaling_based.py:142-155, PLTTrainer: SoftDICE only
-            ap.error(f"--sn-targets trains with the SoftDICE-only step of PLTTrainer: --model MinkUNet34 or "
+            ap.error(f"{flag} trains with the SoftDICE-only step of PLTTrainer: --model MinkUNet34 or "
                      f"MinkUNet34IBN, not {a.model}")
         if a.mix is not None or a.mix3d:
-            ap.error("--sn-targets, --mix and --mix3d are different methods: pass one of them")
+            ap.error(f"{flag}, --mix and --mix3d are different methods: pass one of them")
     if a.augment is not None:
         check_augmentations(a.augment)       # NotImplementedError for another name, as get_augmentations
-        if a.mix is not None or a.mix3d or a.sn_targets is not None:
-            ap.error("--augment with --mix, --mix3d or --sn-targets: those datasets interleave the augmentation's draws "
-                     "with their own in the reference, which is not implemented")
+        if a.mix is not None or a.mix3d or sn:
+            ap.error("--augment with --mix, --mix3d or --sn-targets: under those datasets the list belongs to the SOURCE "
+                     "datasets and is applied to the items and again inside CoSMix's merge: pass --source-augment")
     return a
+
+
+def mix_method_of(a):
+    """the method of MixedSynthScans the arguments ask for, or None: --mix M; --mix3d once its items are merged on the
+    GPU (with --source-augment or --files; plain --mix3d keeps the host-made synthetic union)"""
+    if getattr(a, "mix", None) is not None:
+        return a.mix
+    merged = getattr(a, "source_augment", None) is not None or getattr(a, "files", None) is not None
+    return "mix3d" if getattr(a, "mix3d", False) and merged else None
 
 
 def main(argv=None):
@@ -630,9 +824,35 @@ def _fit_from_args(a):
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))
+    train, val = _data_from_args(a)
+    return Fit(a.model, a.bound, a.batch, a.optimizer, a.lr, a.scheduler, a.epochs, a.warmup_epochs,
+               source_weights=tuple(a.source_weights), check_val_every_n_epoch=a.check_val_every_n_epoch,
+               save_dir=a.save_dir, seed=a.seed, train_data=train, val_data=val, resume=a.resume,
+               auto_resume=a.auto_resume)
+
+
+def _data_from_args(a):
+    """(training dataset, validation dataset or {name: dataset} or None) of parsed command-line arguments"""
     bev = bev_image_size(a.bound)
+    src_aug = getattr(a, "source_augment", None)
+    mix_method = mix_method_of(a)
+
+    def per_source_val():                   # validation data is never augmented or mixed
+        return {name: SynthScans(a.val_scans, c, first=10 ** 6 + i * synth.SOURCE1_SEED, bev_size=bev)
+                for i, (name, c) in enumerate(zip(source_names(a.sources), a.sources))} if a.val_scans else None
+
     if getattr(a, "files", None):
         train, val = _file_data(a, bev)
+    elif src_aug is not None and mix_method is not None:
+        items = AugmentedSynthScans(a.scans, a.sources, src_aug, sub_p=a.sub_p, seed=a.seed)
+        train = MixedSynthScans(a.scans, a.scans, a.sources, method=mix_method, seed=a.seed, items=items)
+        val = per_source_val()
+    elif src_aug is not None:               # --sn-targets
+        configs = a.sources or [a.config]
+        items = AugmentedSynthScans(a.scans, configs, src_aug, sub_p=a.sub_p, seed=a.seed)
+        train = ScaledSynthScans(a.scans, configs, a.sn_targets, seed=a.seed, items=items)
+        val = per_source_val() if a.sources else (
+            SynthScans(a.val_scans, a.config, first=10 ** 6, bev_size=bev) if a.val_scans else None)
     elif getattr(a, "augment", None) is not None:
         train = AugmentedSynthScans(a.scans, a.sources or a.config, a.augment, sub_p=a.sub_p, seed=a.seed,
                                     bev=(a.bound, bev) if a.model == "MinkUNet34BEV" else None)
@@ -660,18 +880,33 @@ def _fit_from_args(a):
     else:
         train = SynthScans(a.scans, a.config, mix3d=a.mix3d, bev_size=bev)
         val = SynthScans(a.val_scans, a.config, first=10 ** 6, mix3d=a.mix3d, bev_size=bev) if a.val_scans else None
-    return Fit(a.model, a.bound, a.batch, a.optimizer, a.lr, a.scheduler, a.epochs, a.warmup_epochs,
-               source_weights=tuple(a.source_weights), check_val_every_n_epoch=a.check_val_every_n_epoch,
-               save_dir=a.save_dir, seed=a.seed, train_data=train, val_data=val, resume=a.resume,
-               auto_resume=a.auto_resume)
+    return train, val
 
 
 def _file_data(a, bev):
     """--files: (training dataset, {name: validation dataset}) over the listings of phase train / validation"""
     luts = scans.luts_from_files(a.label_maps)
     kw = dict(version=a.version, synth4d_splits=a.synth4d_splits, limit=a.limit_files)
-    train = scans.FileScans([scans.listing(n, p, "train", **kw) for n, p in a.files], luts, augmentations=a.augment,
-                            sub_p=a.sub_p, seed=a.seed, bev=(a.bound, bev) if a.model == "MinkUNet34BEV" else None)
+    listings = [scans.listing(n, p, "train", **kw) for n, p in a.files]
+    mix_method, sn_files = mix_method_of(a), getattr(a, "sn_target_files", None)
+    src_aug = getattr(a, "source_augment", None)
+    if mix_method is not None or sn_files:
+        # the source datasets under a mixing / SN dataset: their items are what FileScans makes, with --source-augment
+        items = scans.FileScans(listings, luts, augmentations=src_aug, sub_p=a.sub_p, seed=a.seed)
+        names = [n for n, _ in a.files]
+        if mix_method is not None:
+            train = MixedSynthScans(len(listings[0]), len(listings[1]), names, method=mix_method, seed=a.seed,
+                                    items=items)
+        else:
+            faces = []
+            for (n, p), lut in zip(sn_files, scans.luts_from_files(a.sn_target_label_maps)):
+                tgt = scans.FileScans(scans.listing(n, p, "validation", **kw), lut, seed=a.seed)
+                faces.append(ItemFace(tgt, 0, len(tgt), None))
+            train = ScaledSynthScans([len(l) for l in listings], names, [n for n, _ in sn_files], seed=a.seed,
+                                     items=items, target_faces=faces)
+    else:
+        train = scans.FileScans(listings, luts, augmentations=a.augment, sub_p=a.sub_p, seed=a.seed,
+                                bev=(a.bound, bev) if a.model == "MinkUNet34BEV" else None)
     val = {name: scans.FileScans(scans.listing(n, p, "validation", **kw), lut, seed=a.seed)
            for name, (n, p), lut in zip(source_names([n for n, _ in a.files]), a.files, luts)}
     return train, val

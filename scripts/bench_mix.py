@@ -2,8 +2,11 @@
 
   (a) one merge (lidog_amd.data.pointcutmix_merge / cosmix_merge, sub_p 0.8) of each pair of a batch of --batch
       kitti120k pairs: device time between HIP events recorded on the merge stream around the merge (its host draws
-      and read-backs included, since the stream waits for them), and the host wall time of the call, median over --reps
+      and read-backs included, since the stream waits for them), and the host wall time of the call, median over --reps;
+      the CoSMix merge also with its in-merge augmentation (augmentations = RandomRotation, RandomScale: every pasted
+      class transformed, voxel rows written by the gather itself) on the same scans, next to the plain merge
   (b) MinkUNet34 training steps (SoftDICE, Adam, batch --batch) on --mix cosmix batches (lidog_amd.train.MixedSynthScans)
+      and on --mix cosmix --source-augment RandomRotation RandomScale batches (augmented items, then the augmented merge)
       against plain one-source batches, alternating round by round as Fit.run drives them (the next batch is built
       before this step is queued); each round times --steps steps with the host clock after one synchronisation,
       behind --warmup untimed steps.  Both datasets read scans from an in-process cache, so neither pays for the
@@ -24,12 +27,16 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def bench_merge(method, batch, reps):
+AUGS = ["RandomRotation", "RandomScale"]
+
+
+def bench_merge(method, batch, reps, augmentations=None):
     import numpy as np
     import torch
     from lidog_amd import data
     from lidog_amd.train import MixedSynthScans
     ds = MixedSynthScans(batch, batch, ("kitti120k", "kitti120k"), method=method, seed=1)
+    merge = ds.merge if augmentations is None else functools.partial(ds.merge, augmentations=augmentations)
     dev = torch.device("cuda")
     side = data.merge_stream(dev)
     with torch.cuda.stream(side):
@@ -41,7 +48,7 @@ def bench_merge(method, batch, reps):
                 a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 t0 = time.perf_counter()
                 a.record(side)
-                out = ds.merge(s0, s1, rng=np.random.RandomState([r, i]))
+                out = merge(s0, s1, rng=np.random.RandomState([r, i]))
                 b.record(side)
                 t1 = time.perf_counter()
                 b.synchronize()
@@ -49,7 +56,8 @@ def bench_merge(method, batch, reps):
                 dev_ms.append(a.elapsed_time(b))
                 host_ms.append((t1 - t0) * 1e3)
                 rows.append(int(out["coordinates"].shape[0]))
-    return {"bench": "mix_merge", "method": method, "config": "kitti120k", "batch": batch, "merges": len(dev_ms),
+    return {"bench": "mix_merge", "method": method, "augmentations": augmentations, "config": "kitti120k", "batch": batch,
+            "merges": len(dev_ms),
             "device_ms_median": statistics.median(dev_ms), "device_ms_min": min(dev_ms),
             "host_ms_median": statistics.median(host_ms), "merged_rows_median": statistics.median(rows),
             "device_ms_per_batch": statistics.median(dev_ms) * batch}
@@ -66,11 +74,15 @@ def _steps(step, data, batches, epoch=0):
 def bench_steps(batch, steps, warmup, rounds):
     import torch
     from lidog_amd import synth
-    from lidog_amd.train import MixedSynthScans, SynthScans, build_model, build_step
+    from lidog_amd.train import AugmentedSynthScans, MixedSynthScans, SynthScans, build_model, build_step
     synth.scan_voxels = functools.lru_cache(maxsize=None)(synth.scan_voxels)
     n = batch * 2
+    pair = ("kitti120k", "kitti120k")
     sets = {"plain": SynthScans(n, "kitti120k"),
-            "cosmix": MixedSynthScans(n, n, ("kitti120k", "kitti120k"), method="cosmix", seed=1)}
+            "cosmix": MixedSynthScans(n, n, pair, method="cosmix", seed=1),
+            # its items keep their scans' points on the host (AugmentedSynthScans.points), as the others their voxels
+            "cosmix_aug": MixedSynthScans(n, n, pair, method="cosmix", seed=1,
+                                          items=AugmentedSynthScans(n, pair, AUGS, sub_p=0.8, seed=1))}
     torch.manual_seed(0)
     model = build_model("MinkUNet34")
     model, step, _ = build_step(model, "MinkUNet34", lr=1e-3)
@@ -96,6 +108,7 @@ def bench_steps(batch, steps, warmup, rounds):
         res[f"{name}_ms_per_step_median"] = statistics.median(t)
         res[f"{name}_ms_per_step"] = t
     res["cosmix_over_plain"] = res["cosmix_ms_per_step_median"] / res["plain_ms_per_step_median"]
+    res["cosmix_aug_over_cosmix"] = res["cosmix_aug_ms_per_step_median"] / res["cosmix_ms_per_step_median"]
     return res
 
 
@@ -112,6 +125,7 @@ def main():
     torch.cuda.set_device(0)
     for method in ("pointcutmix", "cosmix"):
         print(json.dumps(bench_merge(method, a.batch, a.reps)), flush=True)
+    print(json.dumps(bench_merge("cosmix", a.batch, a.reps, AUGS)), flush=True)
     if not a.skip_steps:
         print(json.dumps(bench_steps(a.batch, a.steps, a.warmup, a.rounds)), flush=True)
 

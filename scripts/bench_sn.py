@@ -9,7 +9,8 @@
   (b) the whole start-up statistic: lidog_amd.data.average_dims over a dataset of --dataset-scans scans (20 % drawn),
       scans read from an in-process cache so that the synthetic generator is not timed; wall time
   (c) MinkUNet34 training steps (SoftDICE, Adam, batch --batch) on kitti120k_cars with --sn-targets nusc35k_cars
-      (lidog_amd.train.ScaledSynthScans: one re-quantisation per item) against plain batches of the same scans,
+      (lidog_amd.train.ScaledSynthScans: one re-quantisation per item), and with --source-augment RandomRotation
+      RandomScale on top (every item augmented before it is scaled), against plain batches of the same scans,
       alternating round by round as scripts/bench_mix.py does
 
 One JSON line per measurement.
@@ -121,10 +122,14 @@ def _steps(step, data, batches, epoch=0):
 
 def bench_steps(batch, steps, warmup, rounds, scaling):
     import torch
-    from lidog_amd.train import ScaledSynthScans, SynthScans, build_model, build_step
+    from lidog_amd.train import AugmentedSynthScans, ScaledSynthScans, SynthScans, build_model, build_step
     n = batch * 2
+    augs = ["RandomRotation", "RandomScale"]
     sets = {"plain": SynthScans(n, "kitti120k_cars"),
-            "sn": ScaledSynthScans(n, ("kitti120k_cars",), ("nusc35k_cars",), seed=1, scaling=scaling)}
+            "sn": ScaledSynthScans(n, ("kitti120k_cars",), ("nusc35k_cars",), seed=1, scaling=scaling),
+            # --sn-targets with --source-augment: every item augmented (sub_p 0.8) before it is scaled
+            "sn_aug": ScaledSynthScans(n, ("kitti120k_cars",), ("nusc35k_cars",), seed=1, scaling=scaling,
+                                       items=AugmentedSynthScans(n, ("kitti120k_cars",), augs, sub_p=0.8, seed=1))}
     torch.manual_seed(0)
     model = build_model("MinkUNet34")
     model, step, _ = build_step(model, "MinkUNet34", lr=1e-3)
@@ -150,6 +155,7 @@ def bench_steps(batch, steps, warmup, rounds, scaling):
         res[f"{name}_ms_per_step_median"] = statistics.median(t)
         res[f"{name}_ms_per_step"] = t
     res["sn_over_plain"] = res["sn_ms_per_step_median"] / res["plain_ms_per_step_median"]
+    res["sn_aug_over_sn"] = res["sn_aug_ms_per_step_median"] / res["sn_ms_per_step_median"]
     return res
 
 

@@ -1,0 +1,318 @@
+"""CoSMix's in-merge augmentation, Mix3D's remaining keys and the composed datasets, host side: the G16 fixture's own
+conditions, the numpy restatement against it, the draws of draw_classes with a list, the draw order of the composed
+datasets' plan(i), the new command lines and the new C entry."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+import augment_ref as A
+import mixaug_ref as M
+from helpers import REPO
+from lidog_amd import data, synth
+from lidog_amd.data import cosmix_merge, draw_augmentation, draw_classes, draw_ops, draw_source
+from lidog_amd.train import (AugmentedSynthScans, MixedSynthScans, PlainSynthItems, ScaledSynthScans, _data_from_args,
+                             mix_method_of, parse_args)
+
+G16 = M.load_g16()
+COSMIX = [x for x in G16 if x[0]["method"] == "cosmix"]
+ROT, SCALE = M.ROT, M.SCALE
+
+
+def _ids(cases):
+    return [c["name"] for c, _ in cases]
+
+
+# ------------------------------------------------------------------ the fixture
+def test_fixture_holds_the_cases_and_stays_small():
+    assert os.path.getsize(M.G16) < 1 << 20
+    assert [c["name"] for c, _ in G16] == [c["name"] for c in M.CASES]
+    assert all(c["outcome"] == "ok" for c, _ in G16)
+    lists = {tuple(c["augs"]) for c, _ in COSMIX}
+    assert {(ROT, SCALE), (SCALE, ROT), (SCALE,), (ROT,), ()} <= lists
+    by = {c["name"]: c for c, _ in G16}
+    assert by["all_rows"]["sub_p"] is None and by["no_class_drawn"]["classes"] == []
+    assert 0 in by["single_row_class"]["taken"] and by["only_empty_class"]["taken"] == [0]
+    assert by["kitti_rot_scale"]["config0"] == "kitti120k" and not by["kitti_rot_scale"]["full"]
+
+
+@pytest.mark.parametrize("case", COSMIX, ids=_ids(COSMIX))
+def test_fixture_dtype_rule_and_moved_target_voxels(case):
+    c, _ = case
+    f64 = M.floors_f64(c["augs"], len(c["classes"]))
+    assert c["coords_dtype"] == ("float64" if f64 else "float32")
+    if ROT in c["augs"] and c["classes"]:
+        assert c["target_moved"] > 0          # an empty pasted class promotes the concatenation too
+    else:
+        assert c["target_moved"] == 0
+    if c["name"] == "no_class_drawn":
+        assert c["coords_dtype"] == "float32"
+
+
+@pytest.mark.parametrize("case", G16, ids=_ids(G16))
+def test_restatement_equals_the_reference(case):
+    c, arr = case
+    s0, s1 = M.case_scans(c)
+    voxel = M.mix_ref.voxel_size(c)
+    if c["method"] == "mix3d":
+        M.check_outputs(M.mix3d_np(s0, s1, voxel), c, arr, c["name"])
+        return
+    sel, classes, subs, ops = M.case_draws(c, arr)
+    out = M.cosmix_aug_np(s0, s1, sel, classes, subs, ops, voxel)
+    margin = M.class_margin(out, c["augs"], voxel)
+    assert margin > A.MARGIN, f"{c['name']}: class rows {margin} voxels from a face"
+    assert out["_target_moved"] == c["target_moved"]
+    M.check_outputs(out, c, arr, c["name"])
+
+
+# ------------------------------------------------------------------ draws
+@pytest.mark.parametrize("case", COSMIX, ids=_ids(COSMIX))
+def test_draw_classes_with_a_list_reproduces_the_reference(case):
+    c, arr = case
+    sel, classes, subs, ops = M.case_draws(c, arr)
+    np.random.seed(c["seed"])
+    assert draw_source(np.random) == sel
+    got = draw_classes(np.random, arr["counts"], arr[f"w{sel}"], c["sub_p"], c["augs"])
+    assert float(np.random.rand()) == c["next_rand"]              # the generator stands where the reference left it
+    assert len(got) == 3 and [int(x) for x in got[0]] == c["classes"]
+    assert [len(p) for p in got[1]] == c["taken"]
+    for a, b in zip(got[1], subs):
+        np.testing.assert_array_equal(a, b)
+    for mine, want in zip(got[2], ops):
+        assert [a for a, _ in mine] == c["augs"]
+        for (_, p), (_, q) in zip(mine, want):
+            assert np.array_equal(np.asarray(p).reshape(-1), np.asarray(q).reshape(-1))
+    rng = np.random.RandomState(c["seed"])                        # a RandomState of its own draws the same
+    draw_source(rng)
+    again = draw_classes(rng, arr["counts"], arr[f"w{sel}"], c["sub_p"], c["augs"])
+    assert float(rng.rand()) == c["next_rand"] and [int(x) for x in again[0]] == c["classes"]
+
+
+def test_draw_classes_without_a_list_draws_as_before():
+    c, arr = COSMIX[0]
+    a = draw_classes(np.random.RandomState(5), arr["counts"], arr["w0"], 0.8)
+    b = draw_classes(np.random.RandomState(5), arr["counts"], arr["w0"], 0.8, [])
+    assert len(a) == 2 and len(b) == 3 and b[2] == [[] for _ in b[0]]
+    assert a[0].tolist() == b[0].tolist() and all(np.array_equal(x, y) for x, y in zip(a[1], b[1]))
+
+
+def test_draw_augmentation_shares_the_list_draws():
+    for augs in ([ROT, SCALE], [SCALE, ROT], [SCALE], []):
+        r1, r2 = np.random.RandomState(3), np.random.RandomState(3)
+        d = draw_augmentation(r1, 1000, 0.8, augs)
+        idx = r2.choice(np.arange(1000), 800, replace=False)
+        ops = draw_ops(r2, augs)
+        assert np.array_equal(d["sampled_idx"], idx) and r1.rand() == r2.rand()
+        assert [a for a, _ in d["ops"]] == augs
+        assert all(np.array_equal(p, q) for (_, p), (_, q) in zip(d["ops"], ops))
+
+
+def test_cosmix_merge_takes_name_lists_only():
+    w = (np.ones(7), np.ones(7))
+    for bad in (lambda x: x, "RandomRotation", [lambda x: x], 3):
+        with pytest.raises(NotImplementedError):
+            cosmix_merge({}, {}, class_weights=w, augmentations=bad)
+    with pytest.raises(NotImplementedError):
+        cosmix_merge({}, {}, class_weights=w, augmentations=["RandomShear"])
+    with pytest.raises(KeyError):                                  # a list of names passes that check: the scans are read
+        cosmix_merge({}, {}, class_weights=w, augmentations=[ROT, SCALE])
+    assert "null in every shipped config" not in (cosmix_merge.__doc__ + open(data.__file__).read())
+
+
+# ------------------------------------------------------------------ plan(i): source 0's item, source 1's item, the merge
+AUGS = [ROT, SCALE]
+
+
+def _mixed(method, seed=7, plain=False):
+    configs = ("source8k", "source8k")
+    items = None if plain else AugmentedSynthScans(4, configs, AUGS, sub_p=0.8, seed=seed)
+    return MixedSynthScans(4, 4, configs, method=method, seed=seed, items=items)
+
+
+def _same_draws(a, b):
+    if a is None or b is None:
+        return a is None and b is None
+    return (np.array_equal(a["sampled_idx"], b["sampled_idx"]) and [n for n, _ in a["ops"]] == [n for n, _ in b["ops"]]
+            and all(np.array_equal(p, q) for (_, p), (_, q) in zip(a["ops"], b["ops"])))
+
+
+def _same_plan(p, q):
+    same = p["scans"] == q["scans"] and all(_same_draws(a, b) for a, b in zip(p["items"], q["items"]))
+    m, n = p["merge"], q["merge"]
+    return same and set(m) == set(n) and all(np.array_equal(np.asarray(m[k]), np.asarray(n[k])) for k in m)
+
+
+@pytest.mark.parametrize("method", MixedSynthScans.ALL_METHODS)
+def test_mixed_plan_follows_the_reference_order(method):
+    ds = _mixed(method)
+    ds.set_epoch(2)
+    for i in range(4):
+        p = ds.plan(i)
+        j0, j1 = ds.pairs.pair(i)
+        assert p["scans"] == (j0, j1)
+        rng = np.random.RandomState([7, 2, i])
+        n0 = synth.scan_points_labels(j0, "source8k")[0].shape[0]
+        n1 = synth.scan_points_labels(j1 + synth.SOURCE1_SEED, "source8k")[0].shape[0]
+        d0 = draw_augmentation(rng, n0, 0.8, AUGS)                  # source 0's item first,
+        d1 = draw_augmentation(rng, n1, 0.8, AUGS)                  # then source 1's,
+        assert _same_draws(p["items"][0], d0) and _same_draws(p["items"][1], d1)
+        assert p["merge"] == ({} if method == "mix3d" else {"source": draw_source(rng)})      # then the merge
+    assert ds.augmentations == AUGS and ds.sub_p == 0.8 and ds.voxel == 0.1 and ds.num_sources == 1
+
+
+@pytest.mark.parametrize("method", MixedSynthScans.ALL_METHODS)
+def test_mixed_plan_is_stable(method):
+    ds, ds2 = _mixed(method), _mixed(method)
+    ds.set_epoch(1)
+    ds2.set_epoch(1)
+    first = [ds.plan(i) for i in range(4)]
+    assert all(_same_plan(ds2.plan(i), first[i]) for i in (2, 0, 3, 1))         # another construction, another order
+    ds.set_epoch(2)
+    assert not any(_same_plan(ds.plan(i), first[i]) for i in range(4))          # a new epoch, new draws
+    ds.set_epoch(1)
+    assert all(_same_plan(ds.plan(i), first[i]) for i in range(4))              # back (a resume): the same
+
+
+def test_plain_items_draw_nothing():
+    ds = _mixed("cosmix", plain=True)
+    assert isinstance(ds.items, PlainSynthItems) and ds.augmentations is None and ds.sub_p == 0.8
+    p = ds.plan(1)
+    assert p["items"] == [None, None] and p["merge"] == {"source": draw_source(np.random.RandomState([7, 0, 1]))}
+    with pytest.raises(NotImplementedError):
+        MixedSynthScans(4, 4, ("source8k", "source8k"), method="raycast")
+
+
+def test_cosmix_weights_over_augmented_items_count_every_point():
+    ds = _mixed("cosmix")
+    for s in range(2):
+        want = np.zeros(7)
+        for j in range(4):
+            lab = synth.scan_points_labels(j + s * synth.SOURCE1_SEED, "source8k")[1]
+            want += np.bincount(lab[lab >= 0], minlength=7)
+        assert ds.class_weights[s].tolist() == want.tolist()
+
+
+SCALING = [np.array([[1.1, 1.2, 1.3], [0.9, 0.8, 0.7]], np.float32), np.array([[2.0, 2.0, 2.0], [0.5, 0.5, 0.5]], np.float32)]
+
+
+@pytest.mark.parametrize("sources", [1, 2])
+def test_scaled_plan_follows_the_reference_order(sources):
+    configs = ("source8k", "source8k")[:sources]
+
+    def make():
+        items = AugmentedSynthScans(4, configs, AUGS, sub_p=0.8, seed=9)
+        return ScaledSynthScans(4, configs, ("nusc35k", "kitti120k"), seed=9, scaling=SCALING[:sources], items=items)
+
+    ds, ds2 = make(), make()
+    ds.set_epoch(1)
+    ds2.set_epoch(1)
+    plans = []
+    for i in range(4):
+        p = ds.plan(i)
+        plans.append(p)
+        js = (i,) if sources == 1 else ds.pairs.pair(i)
+        assert p["scans"] == tuple(js)
+        rng = np.random.RandomState([9, 1, i])
+        for s, j in enumerate(js):
+            n = synth.scan_points_labels(j + s * synth.SOURCE1_SEED, "source8k")[0].shape[0]
+            assert _same_draws(p["items"][s], draw_augmentation(rng, n, 0.8, AUGS))
+        rows = data.draw_scaling(rng, ds.scaling, sources)           # the scale rows come last
+        assert all(np.array_equal(a, b) for a, b in zip(p["merge"]["rows"], rows))
+        assert [(s, j) for s, j, _ in ds.item(i)] == list(enumerate(js))
+    assert all(_same_plan(ds2.plan(i), plans[i]) for i in (3, 1, 0, 2))
+    ds.set_epoch(0)
+    assert not any(_same_draws(ds.plan(i)["items"][0], plans[i]["items"][0]) for i in range(4))
+
+
+# ------------------------------------------------------------------ command line
+MIX = ["--model", "MinkUNet34", "--config", "source8k", "--scans", "2"]
+
+
+@pytest.mark.parametrize("method", MixedSynthScans.ALL_METHODS)
+def test_cli_source_augment_builds_a_mix_over_augmented_items(method):
+    flag = ["--mix3d"] if method == "mix3d" else ["--mix", method]
+    a = parse_args(MIX + flag + ["--source-augment", ROT, SCALE, "--sub-p", "0.7", "--val-scans", "1"])
+    assert a.source_augment == [ROT, SCALE] and mix_method_of(a) == method and a.sources == ["source8k", "source8k"]
+    train, val = _data_from_args(a)
+    assert isinstance(train, MixedSynthScans) and train.method == method and train.num_sources == 1
+    assert isinstance(train.items, AugmentedSynthScans) and train.items.augmentations == [ROT, SCALE]
+    assert train.sub_p == 0.7 and train.augmentations == [ROT, SCALE]
+    assert set(val) == {"source8k:0", "source8k:1"} and not any(v.mix3d for v in val.values())   # never mixed
+    b = parse_args(MIX + flag + ["--source-augment"])                     # the empty list: sub-sampling only
+    assert b.source_augment == [] and _data_from_args(b)[0].augmentations == []
+
+
+def test_cli_plain_forms_are_unchanged():
+    from lidog_amd.train import MultiSynthScans, SynthScans
+    a = parse_args(["--model", "MinkUNet34", "--mix3d", "--config", "source8k", "--scans", "2"])
+    assert not hasattr(a, "source_augment") and mix_method_of(a) is None
+    train, _ = _data_from_args(a)
+    assert isinstance(train, SynthScans) and train.mix3d
+    b = parse_args(["--model", "MinkUNet34", "--mix3d", "--sources", "source8k", "nusc35k", "--scans", "2"])
+    assert isinstance(_data_from_args(b)[0], MultiSynthScans)
+    c = parse_args(MIX + ["--mix", "cosmix"])
+    train, _ = _data_from_args(c)
+    assert isinstance(train.items, PlainSynthItems) and train.augmentations is None and mix_method_of(c) == "cosmix"
+
+
+def test_cli_files_forms_parse(tmp_path):
+    maps = [os.path.join(REPO, "tests", "golden", "semantickitti2common.yaml")] * 2
+    files = ["--files", f"SemanticKITTI={tmp_path}/a", f"SemanticKITTI={tmp_path}/b", "--label-maps"] + maps
+    a = parse_args(["--model", "MinkUNet34", "--mix", "cosmix", "--source-augment", ROT, SCALE] + files)
+    assert mix_method_of(a) == "cosmix" and len(a.files) == 2 and a.sources is None
+    b = parse_args(["--model", "MinkUNet34IBN", "--mix3d"] + files)
+    assert mix_method_of(b) == "mix3d"
+    c = parse_args(["--model", "MinkUNet34", "--source-augment", ROT, "--files", f"SemanticKITTI={tmp_path}/a",
+                    "--label-maps", maps[0], "--sn-target-files", f"nuScenes={tmp_path}/n", "--sn-target-label-maps",
+                    os.path.join(REPO, "tests", "golden", "nuscenes2common.yaml")])
+    assert c.sn_target_files == [("nuScenes", f"{tmp_path}/n")] and c.source_augment == [ROT] and mix_method_of(c) is None
+
+
+FILES1 = ["--files", "SemanticKITTI=/x", "--label-maps", "m.yaml"]
+FILES2 = ["--files", "SemanticKITTI=/x", "SemanticKITTI=/y", "--label-maps", "m.yaml", "n.yaml"]
+
+
+@pytest.mark.parametrize("argv", [
+    ["--source-augment", ROT],                                                         # no mixing or SN dataset
+    ["--model", "MinkUNet34", "--source-augment", ROT, "--augment", ROT],
+    ["--model", "MinkUNet34", "--mix", "cosmix", "--source-augment", ROT, "--augment", SCALE],
+    ["--model", "MinkUNet34BEV", "--mix3d", "--source-augment", ROT],                 # merged items: SoftDICE only
+    ["--model", "MinkUNet34Robust", "--mix", "cosmix", "--source-augment", ROT],
+    ["--model", "MinkUNet34BEV", "--config", "kitti120k_cars", "--sn-targets", "nusc35k_cars", "--source-augment"],
+    ["--model", "MinkUNet34", "--mix", "cosmix"] + FILES1,                             # a mix pairs two datasets
+    ["--model", "MinkUNet34", "--mix3d", "--source-augment", ROT] + FILES1,
+    ["--model", "MinkUNet34", "--sn-targets", "nusc35k_cars"] + FILES1,
+    ["--model", "MinkUNet34", "--sn-target-files", "nuScenes=/n", "--sn-target-label-maps", "m.yaml"],   # no --files
+    ["--model", "MinkUNet34", "--sn-target-files", "nuScenes=/n"] + FILES1,            # no label map for the target
+    ["--model", "MinkUNet34", "--sn-target-files", "KITTI=/n", "--sn-target-label-maps", "m.yaml"] + FILES1,
+    ["--model", "MinkUNet34", "--sn-target-label-maps", "m.yaml"] + FILES1,
+    ["--model", "MinkUNet34BEV", "--sn-target-files", "nuScenes=/n", "--sn-target-label-maps", "m.yaml"] + FILES1,
+    ["--model", "MinkUNet34", "--mix", "cosmix", "--sn-target-files", "nuScenes=/n", "--sn-target-label-maps",
+     "m.yaml"] + FILES2,
+    ["--model", "MinkUNet34", "--mix", "cosmix", "--augment", ROT] + FILES2,
+])
+def test_cli_new_refusals_exit_with_2(argv, capsys):
+    with pytest.raises(SystemExit) as e:
+        parse_args(argv)
+    assert e.value.code == 2
+
+
+def test_cli_unknown_source_augmentation():
+    with pytest.raises(NotImplementedError):
+        parse_args(MIX + ["--mix", "cosmix", "--source-augment", "RandomShear"])
+
+
+# ------------------------------------------------------------------ C ABI
+def test_the_new_entry_is_declared_bound_and_exported():
+    from lidog_amd import _lib, build
+    header = open(os.path.join(REPO, "include", "lidog_amd.h")).read()
+    lib = __import__("ctypes").CDLL(build.build())
+    name = "lidog_mix_gather_aug"
+    assert re.search(rf"\b{name}\(", header) and name in _lib.SIGNATURES and hasattr(lib, name)
+    assert hasattr(lib, "lidog_mix_gather") and len(_lib.SIGNATURES["lidog_mix_gather"]) == 15      # the old entry stays
+    n_args = len(re.search(rf"\b{name}\((.*?)\);", header, re.S).group(1).split(","))
+    assert n_args == len(_lib.SIGNATURES[name]) == 23
+    assert _lib.ABI_VERSION == 8 and lib.lidog_abi_version() == 8          # an additive entry: the version stays
+    for f in ("mix.hip", "augment.hip"):
+        assert '#include "aug_ops.h"' in open(os.path.join(REPO, "lidog_amd", "csrc", f)).read()

@@ -114,8 +114,11 @@ int lidog_kernel_map_rows(const int32_t *pos, int64_t n, int32_t K, int32_t mark
  * written once).  The product of one row is an fmaf chain over ci ascending starting from 0
  * (bit-identical to oracle/me_oracle.c:orc_conv_fwd before its scatter-add).
  * bias (may be NULL) [Cout] is added after the chain.
- * a_rows: rows of A (every gather index, or every p when gather == NULL, is below it); 0 = not known.  Only a hint for
- * the choice of kernel (an A below 4 GiB lets a workgroup walk several tiles with 32-bit row offsets); never read as a bound. */
+ * a_rows: rows of A, or 0 = not known.  When non-zero it is a HARD upper bound and a precondition: every gather index
+ * (every p when gather == NULL) must lie in [0, a_rows).  It chooses the kernel -- an A below 4 GiB (a_rows * Cin * 4
+ * bytes) lets a workgroup walk several tiles with 32-bit byte offsets built from the gather indices -- so an understated
+ * a_rows wraps those offsets and reads outside A without any diagnostic; the kernels never check an index against it.
+ * Pass the exact row count, as every caller of this library does, or 0. */
 int lidog_sconv_gemm(const float *A, const int32_t *gather, const float *B, const float *bias,
                      const int32_t *tile_k, const int32_t *tile_row0, const int32_t *tile_rows, int32_t n_tiles,
                      int32_t Cin, int32_t Cout, float *T, const int32_t *scatter, int64_t a_rows, void *stream);

@@ -795,6 +795,22 @@ int64_t lidog_eval_pack_ws(int64_t n, int32_t n_scans);
 int lidog_eval_pack(const int32_t *coords, const int64_t *preds, const int64_t *labels, int64_t n, int32_t n_scans,
                     int64_t ignore_label, int32_t *out, int32_t *err, int32_t *ws, void *stream);
 
+/* ------------------------------------------------------------------ training-step statistics (log_losses)
+ * The batch-wide confusion counts behind the per-step training metrics (utils/pipelines/trainer_lighting_2d.py:203-291,
+ * trainer_lighting.py:118-153) of up to 8 tensors ("segments": the point logits of each source, every BEV level) in ONE
+ * launch.  logits, labels and n are HOST arrays of n_segments entries (1..8); the table travels as a kernel argument.
+ * Segment s is n[s] contiguous rows of n_classes float32 (1..32 classes) with one int64 label per row; n[s] == 0 is
+ * legal and its pointers are not read.  A BEV level is passed as it is: the rows of n_classes consecutive floats of the
+ * contiguous NCHW buffer are what `bev_preds.view(b, h, w, -1).argmax(-1)` reads, n = b * h * w.
+ * counts [n_segments, n_classes + 1, n_classes] int64 is ADDED to (the caller zeroes it): counts[s, label + 1, pred]
+ * for labels in [0, n_classes) other than ignore_label, counts[s, 0, pred] for every other label; pred = the first
+ * maximal index, the first NaN in a row holding one (lidog_eval_confusion's rule).  A label other than ignore_label
+ * outside [0, n_classes) also sets bit s of err[0] (device int32, never cleared here).  Nothing outside counts and err
+ * is written.  Integer LDS bins, one global integer atomic per non-empty bin and block: the same bytes on every run. */
+int lidog_train_confusion(const float *const *logits, const int64_t *const *labels, const int64_t *n,
+                          int32_t n_segments, int32_t n_classes, int64_t ignore_label, int64_t *counts, int32_t *err,
+                          void *stream);
+
 /* ------------------------------------------------------------------ scans read from files (SemanticKITTI, nuScenes, Synth4D)
  * What the reference's datasets do with numpy between the file and the cached `data` dict of __getitem__
  * (utils/datasets/semantickitti.py:100-131,190-197, nuscenes.py:144-178,238-248, synth4d.py:106-137) and in

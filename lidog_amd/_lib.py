@@ -159,6 +159,7 @@ SIGNATURES = {
     "lidog_eval_confusion": [_p, _p, _p, _i64, _i32, _i32, _i64, _p, _p, _p, _p],
     "lidog_eval_pack_ws": [_i64, _i32],
     "lidog_eval_pack": [_p, _p, _p, _i64, _i32, _i64, _p, _p, _p, _p],
+    "lidog_train_confusion": [_p, _p, _p, _i32, _i32, _i64, _p, _p, _p],
     "lidog_scan_load_ws": [_i64],
     "lidog_scan_load": [_p, _i32, _p, _i32, _i32, _i64, _p, _i32, _i32, _f, _p, _p, _p, _i32, _p, _p, _p],
 }

@@ -5,6 +5,7 @@
 // per-block counts, one scan, in-wave ballot ranks).  No float atomic, no position from an atomic: two runs give the
 // same bytes.
 #include "common.h"
+#include "row_argmax.h"
 
 #define EV_THREADS 256
 #define EV_ITERS 4                          // rows per thread of the confusion kernel, kept in registers
@@ -12,21 +13,6 @@
 #define EV_MAX_CLASSES 32
 #define EV_LDS_BINS 8192                    // int32 bins of a block (32 KiB): (C + 1) * C per scan of a pass
 #define EV_MAX_SCANS 256                    // of the dump: lidog_mix_split's slots
-
-// torch's CPU max(dim=1): the first maximal index; in a row holding a NaN the first NaN
-__device__ __forceinline__ int ev_argmax(const float *__restrict__ x, int C) {
-    float best = x[0];
-    int idx = 0;
-    for (int c = 0; c < C; ++c) {
-        const float v = x[c];
-        if (!(v <= best)) {
-            best = v;
-            idx = c;
-            if (v != v) break;
-        }
-    }
-    return idx;
-}
 
 // A block takes EV_TILE consecutive rows.  Its LDS holds the bins of `slots` consecutive scans; the scans of its rows
 // [smin, smax] are covered in passes of `slots` scans (one pass when the rows of a scan are contiguous and the batch is

@@ -16,6 +16,8 @@ What the reference's entry scripts do through pytorch-lightning, as plain argume
                                               (the source datasets' augmentation_list under --mix / --mix3d / --sn-targets)
     python -m lidog_amd.train --model MinkUNet34 --config kitti120k_cars --sn-targets nusc35k_cars ...   (SN, configs/SN)
     python -m lidog_amd.train --augment RandomRotation RandomScale --sub-p 0.8 ...   (sub_p / augmentation_list of the configs)
+    python -m lidog_amd.train --log-every-n-steps 50 --save-dir /tmp/run ...   (per-step IoU, class counts, losses, lr ->
+                                                                       /tmp/run/metrics.jsonl: lidog_amd.metrics)
     python -m lidog_amd.train --files SemanticKITTI=/data/SemanticKITTI --label-maps semantickitti2common.yaml ...
                                                                        (scans from files: lidog_amd.scans)
 
@@ -39,7 +41,8 @@ from . import synth
 from .checkpoint import load_training_checkpoint, save_lightning_checkpoint
 from .data import (augment_item, check_augmentations, collate_items, cosmix_merge, draw_augmentation,
                    draw_scaling, draw_source, mix3d_merge, on_merge_stream, pointcutmix_merge, scaling_params, sn_scale)
-from .evaluate import per_class_iou
+from .evaluate import CLASS_NAMES, per_class_iou
+from .metrics import MetricLayout, MetricsWriter, StepMetrics
 from .optim import make_optimizer, make_scheduler, shard_indices
 from .trainer import LiDOGStep, RobustStep, SourceStep, setup_data_parallel
 
@@ -480,6 +483,19 @@ def source_names(configs):
     return [c if list(configs).count(c) == 1 else f"{c}:{i}" for i, c in enumerate(configs)]
 
 
+def training_source_names(data, num_sources):
+    """the names the training metrics file a dataset's sources under: its configurations (`configs` / `config`) or its
+    listings' names, made unique by source_names; `source<s>` for a dataset that has neither"""
+    names = getattr(data, "configs", None)
+    if names is None and hasattr(data, "config"):
+        names = [data.config]
+    if names is None and hasattr(data, "listings"):
+        names = [l.name for l in data.listings]
+    names = list(names or [])[:num_sources]
+    names += [f"source{s}" for s in range(len(names), num_sources)]
+    return source_names(names)
+
+
 def bev_image_size(bound_2d, voxel=0.05, pool=(5, 3, 1)):
     """side of the BEV logits: sparse2super's H = int(2B / voxel) (minkunet_bev.py:184-185) through MaxPool2d(5, 3, 1)
     and the two stride-2 convolutions of Encoder2D: 167 for B = 50 (bev_img_sizes, semantickitti.yaml:8), 100 for 30"""
@@ -557,10 +573,15 @@ class Fit:
                  scheduler=None, epochs=25, warmup_epochs=0, source_weights=(0.5, 0.5), weight_decay=1e-4,
                  momentum=0.98, check_val_every_n_epoch=5, num_sanity_val_steps=2, save_dir=None, seed=1234,
                  train_data=None, val_data=None, shuffle=True, resume=None, auto_resume=False, prefetch=True,
-                 device="cuda", log=None, state_dict=None, num_sources=None):
+                 device="cuda", log=None, state_dict=None, num_sources=None, log_every_n_steps=0, metric_sources=None):
         """`train_data` with `num_sources = 2` (MultiSynthScans) trains on two sources; `val_data` may then be a dict
         {source name: dataset}: every source is validated on its own (the list of loaders of train_lidog.py:186-190),
-        the results keyed by name"""
+        the results keyed by name.
+        `log_every_n_steps` N > 0 (the reference's entry scripts: 50): every step whose number is a multiple of N is
+        recorded by a metrics.StepMetrics (per-class IoU and occurrences of the point predictions and of every BEV level,
+        losses, lr; nothing is launched on the other steps), read at the end of every epoch into the history record's
+        `metrics` and, with `save_dir`, appended by rank 0 to <save_dir>/metrics.jsonl together with the validation
+        results.  0: off.  `metric_sources`: the source names of the keys (default: training_source_names)"""
         self.rank, self.world = _rank_world()
         self.kind, self.batch_size, self.epochs = model_kind, batch_size, epochs
         self.check_val, self.sanity = check_val_every_n_epoch, num_sanity_val_steps
@@ -581,6 +602,13 @@ class Fit:
         self.opt = self.step.opt
         self.epoch, self.global_step = 0, 0
         self.history = []
+        self.log_every, self.metrics, self.metrics_writer = int(log_every_n_steps), None, None
+        if self.log_every > 0:
+            if save_dir and self.rank == 0:
+                self.metrics_writer = MetricsWriter(os.path.join(save_dir, "metrics.jsonl"))
+            names = metric_sources or training_source_names(self.train_data, num_sources)
+            layout = MetricLayout.for_step(self.step, names, levels=tuple(getattr(self.model, "encoders2d", {}).keys()))
+            self.metrics = StepMetrics(layout, self.log_every, device=device, writer=self.metrics_writer)
         if auto_resume and save_dir and resume is None:
             resume = last_checkpoint(save_dir)
         if resume:
@@ -613,10 +641,10 @@ class Fit:
         if self.val_data is None:
             return None
         if isinstance(self.val_data, dict):    # one validation set per source (validation_step's dataloader_idx)
-            return {name: self._validate(data, epoch, limit) for name, data in self.val_data.items()}
+            return {name: self._validate(data, epoch, limit, name) for name, data in self.val_data.items()}
         return self._validate(self.val_data, epoch, limit)
 
-    def _validate(self, data, epoch, limit=None):
+    def _validate(self, data, epoch, limit=None, phase=None):
         res = []
         for ids in self._epoch_batches(data, 0, False)[:limit]:
             res.append(self.validation_step(data.batch(ids, self.device)))
@@ -628,7 +656,23 @@ class Fit:
             t = torch.tensor([out["sem_loss"], out["source_iou"]], device=self.device, dtype=torch.float64)
             dist.all_reduce(t)
             out["sem_loss"], out["source_iou"] = (t / self.world).tolist()
+        if self.metrics_writer is not None and epoch >= 0:       # not the sanity steps: Lightning logs none of them
+            self.metrics_writer.write(self._validation_record(out, res, phase))
         return out
+
+    def _validation_record(self, out, res, phase):
+        """validation_step's keys (trainer_lighting_2d.py:316-324); a class's IoU is the mean over the batches whose
+        labels hold it (on this rank), filed under its own name"""
+        if phase is None:
+            phase = training_source_names(self.train_data, 1)[0]
+        rec = {"step": self.global_step, f"validation/{phase}/sem_loss": out["sem_loss"],
+               f"validation/{phase}/source_iou": out["source_iou"]}
+        for c, name in enumerate(CLASS_NAMES):
+            v = [r["per_class_iou"][c] for r in res if r["per_class_iou"][c] >= 0]
+            if v:
+                rec[f"validation/{phase}/{name}_source_iou"] = sum(v) / len(v)
+        rec["validation/epoch"] = out["epoch"]
+        return rec
 
     # ------------------------------------------------------------------ checkpoints (ModelCheckpoint, :222-225)
     def save(self, epoch):
@@ -654,6 +698,10 @@ class Fit:
             losses = []
             for i in range(len(batches)):
                 nxt = self.train_data.batch(batches[i + 1], self.device) if i + 1 < len(batches) else None
+                if self.metrics is not None:                    # only the logged steps are recorded
+                    due = (self.global_step + 1) % self.log_every == 0
+                    self.step.metrics = self.metrics if due else None
+                    self.metrics.next_step, self.metrics.epoch = self.global_step + 1, epoch
                 out = self.step.training_step(cur, epoch=epoch, prefetch=nxt if self.prefetch else None)
                 losses.append(out["loss"])
                 self.global_step += 1
@@ -664,6 +712,8 @@ class Fit:
             rec = {"epoch": epoch, "global_step": self.global_step, "lr": lr_used,
                    "loss": float(torch.stack(losses).mean()) if losses else float("nan"),
                    "losses": [float(l) for l in losses]}
+            if self.metrics is not None:
+                rec["metrics"] = self.metrics.finish()
             if self.val_data is not None and (epoch + 1) % self.check_val == 0:
                 rec["validation"] = self.validate(epoch)
             if dist.is_available() and dist.is_initialized():
@@ -674,9 +724,14 @@ class Fit:
             self.history.append(rec)
             self.log({k: v for k, v in rec.items() if k != "losses"})
             self.epoch = epoch + 1
+        if self.metrics is not None:
+            self.metrics.finish()
         if self.world > 1:
             dist.barrier()
         return self.history
+
+
+Trainer = Fit
 
 
 def parse_args(argv=None):
@@ -729,6 +784,9 @@ def parse_args(argv=None):
                     help="SN over --files: the target datasets (their validation listings give the target car sizes)")
     ap.add_argument("--sn-target-label-maps", nargs="+", default=argparse.SUPPRESS, metavar="FILE",
                     help="one label map per --sn-target-files entry")
+    ap.add_argument("--log-every-n-steps", type=int, default=argparse.SUPPRESS, metavar="N",
+                    help="record per-class IoU, class counts, losses and lr of every N-th training step on the GPU and "
+                         "append them to <save-dir>/metrics.jsonl (the reference's entry scripts: 50; default 0: off)")
     scans.add_file_arguments(ap, "--files", "train on")
     a = ap.parse_args(argv)
     source_augment = getattr(a, "source_augment", None)
@@ -828,7 +886,7 @@ def _fit_from_args(a):
     return Fit(a.model, a.bound, a.batch, a.optimizer, a.lr, a.scheduler, a.epochs, a.warmup_epochs,
                source_weights=tuple(a.source_weights), check_val_every_n_epoch=a.check_val_every_n_epoch,
                save_dir=a.save_dir, seed=a.seed, train_data=train, val_data=val, resume=a.resume,
-               auto_resume=a.auto_resume)
+               auto_resume=a.auto_resume, log_every_n_steps=getattr(a, "log_every_n_steps", 0))
 
 
 def _data_from_args(a):

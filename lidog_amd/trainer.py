@@ -32,7 +32,15 @@ class _Step:
     `training_step(batch, prefetch=next_batch)` builds the next batch's coordinate maps on a side stream while the GPU
     still works on this step, from the trace of map uses recorded by the first forward pass: the data-loader-side half
     of the reference's step (ME builds its maps inside the forward call) moved off the critical path, not skipped.
-    Subclasses define `_losses(batch, epoch) -> (total, {name: loss}, [semantic output of each source])`."""
+    Subclasses define `_losses(batch, epoch) -> (total, {name: loss}, [semantic output of each source])`.
+    `metrics`: a lidog_amd.metrics.StepMetrics, or None (the default).  When set, training_step hands it the logits and
+    labels of every source (LiDOGStep: and of every BEV level) and the step's losses; the step computes and returns
+    what it does without."""
+
+    metrics = None
+    metric_losses = ("sem_loss",)       # the loss names of one source, in the order of the step's loss dict
+    metric_bev = False                  # the BEV levels are logged too
+    metric_count_ignored = True         # jaccard_score over all rows (the LiDOG trainers filter label == -1 first)
 
     def __init__(self, model, optimizer, num_sources=1, ignore_label=-1):
         if num_sources not in (1, 2):
@@ -95,13 +103,27 @@ class _Step:
         """`prefetch`: the batch of the NEXT call (its coordinate maps are built while this step still runs on
         the GPU); `prefetch_ready`: event after which its coordinates are valid (None: everything queued so far).
         Returns the detached total and losses."""
-        total, losses, _ = self._forward(batch, epoch)
+        total, losses, outs = self._forward(batch, epoch)
+        ready = self.metrics.mark() if self.metrics is not None else None
         self.opt.zero_grad()
         total.backward()
         self.opt.step()
+        if ready is not None:       # here the host is ahead of the device: most of the metrics' host time hides (DESIGN 3q)
+            self._record_metrics(batch, total, losses, outs, ready)
         self.prefetch_maps(prefetch, prefetch_ready)
         _check_transport(self)
         return {k: (v.detach() if torch.is_tensor(v) else v) for k, v in {"loss": total, **losses}.items()}
+
+    def _metric_pairs(self, batch, s, out):
+        """the (logits, labels) of source s that the metrics count, in the order of MetricLayout.segments"""
+        return [(out.F, batch[f"source_sem_labels{s}"].long())]
+
+    @torch.no_grad()
+    def _record_metrics(self, batch, total, losses, outs, ready):
+        """`ready`: the metrics' mark behind the forward pass; the logits and losses are read on the metrics' stream"""
+        m = self.metrics
+        pairs = [p for s, o in enumerate(outs) for p in self._metric_pairs(batch, s, o)]
+        m.record(m.next_step, pairs, {"loss": total, **(losses or {"sem_loss": total})}, self.opt.lr, ready)
 
 
 _PEER_CHECK_EVERY = int(_os.environ.get("LIDOG_PEER_CHECK_EVERY", "200"))
@@ -127,6 +149,10 @@ class LiDOGStep(_Step):
     two sources: total = w0 * (sem0 + bev0) + w1 * (sem1 + bev1)  (:191-197), during warm-up w0 * bev0 + w1 * bev1
     (:198-205).  During warm-up the sem losses are zero tensors."""
 
+    metric_losses = ("sem_loss", "bev_loss")
+    metric_bev = True
+    metric_count_ignored = False
+
     def __init__(self, model, optimizer, source_weights=(0.5, 0.5), warmup_epochs=0, num_classes=7, ignore_label=-1,
                  num_sources=1):
         super().__init__(model, optimizer, num_sources, ignore_label)
@@ -143,6 +169,8 @@ class LiDOGStep(_Step):
     def _losses(self, batch, epoch):
         outs = [self.model(self.sparse_input(batch, s), is_train=True) for s in range(self.num_sources)]
         sems = [o[0] for o in outs]
+        if self.metrics is not None:
+            self._bev_outs = [o[1] for o in outs]
         bev = [self._bev_loss(o[1], batch[f"source_bev_labels{s}"]) for s, o in enumerate(outs)]
         w = self.w
         if epoch >= self.warmup:
@@ -155,6 +183,12 @@ class LiDOGStep(_Step):
             sem = [torch.zeros((), device=o.F.device) for o in sems]
             total = bev[0] if self.num_sources == 1 else w[0] * bev[0] + w[1] * bev[1]
         return total, self._named(sem_loss=sem, bev_loss=bev), sems
+
+    def _metric_pairs(self, batch, s, out):
+        # a level's NCHW logits as they are: the kernel reads the flat buffer in rows of C, as .view(b, h, w, -1) does
+        labels = batch[f"source_bev_labels{s}"]
+        return super()._metric_pairs(batch, s, out) + [(self._bev_outs[s][lvl], labels[lvl].long())
+                                                       for lvl in self.metrics.layout.levels]
 
 
 class SourceStep(_Step):
@@ -179,6 +213,8 @@ class RobustStep(_Step):
     source and direction, lidog_amd.losses.iw_loss); total = w0 * sem (+ 0.5 * aux), or with two sources
     w0 * sem0 + w1 * sem1 (+ 0.5 * (aux0 + aux1)).  Before that epoch aux is a zero tensor: nothing is launched and
     nothing waits for the device."""
+
+    metric_losses = ("sem_loss", "aux_loss")
 
     def __init__(self, model, optimizer, source_weights=(0.5, 0.5), aux_epoch=5, ignore_label=-1, num_sources=1):
         super().__init__(model, optimizer, num_sources, ignore_label)

@@ -838,6 +838,29 @@ int lidog_scan_load(const float *points_raw, int32_t point_stride, const void *l
                     float radius_sq, float *points_out, int32_t *labels_out, int64_t *counts, int32_t num_classes,
                     int32_t *info, int32_t *ws, void *stream);
 
+/* ------------------------------------------------------------------ bf16-operand forward kernels (csrc/sconv_bf16.hip)
+ * Opt-in evaluation path (lidog_amd/precision.py): activations stay fp32 in memory, the gathered rows are rounded to bf16
+ * (nearest even) as they are staged, the weights are packed once, accumulation is fp32 (v_mfma_f32_32x32x16_bf16).
+ * Cin and Cout must be multiples of 32.  The results are NOT the bits of the fp32 kernels.
+ *
+ * lidog_pack_kernels_bf16: fp32 [K][Cin][Cout] -> bf16 [K][Cout][Cin] for every kernel of a table in one launch:
+ * desc int64 [n_mats][6] = (src offset in floats from `src` (may be negative), dst offset in bf16 elements from `dst`,
+ * K, Cin, Cout, first 32x32 tile); total_tiles = sum of K ceil(Cin / 32) ceil(Cout / 32). */
+int lidog_pack_kernels_bf16(const float *src, uint16_t *dst, const int64_t *desc, int32_t n_mats, int64_t total_tiles,
+                            void *stream);
+/* lidog_sconv_gemm_bf16: the gathered GEMM (arguments as lidog_sconv_gemm; Wp = the packed weights): gather == NULL
+ * takes the pair-rows themselves, scatter != NULL writes row scatter[pair] instead of the pair-row, a negative gather
+ * index is a row of zeros.  T is fp32, what lidog_sconv_reduce_rows[_bn] consume. */
+int lidog_sconv_gemm_bf16(const float *A, const int32_t *gather, const uint16_t *Wp, const float *bias,
+                          const int32_t *tile_k, const int32_t *tile_row0, const int32_t *tile_rows, int32_t n_tiles,
+                          int32_t Cin, int32_t Cout, float *T, const int32_t *scatter, void *stream);
+/* lidog_sconv_os_bn_bf16: lidog_sconv_os_bn (forward, evaluation-mode BatchNorm + residual + ReLU) with bf16 operands;
+ * the offsets accumulate into one set of registers. */
+int lidog_sconv_os_bn_bf16(const float *A, const int32_t *nbr, int64_t n, int32_t K, const int32_t *perm,
+                           const uint32_t *wave_masks, const int32_t *tile_order, const uint16_t *Wp, const float *bias,
+                           int32_t Cin, int32_t Cout, const float *mean, const float *invstd, const float *w,
+                           const float *b, const float *residual, int32_t relu, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

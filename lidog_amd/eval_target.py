@@ -2,6 +2,7 @@
 
     python -m lidog_amd.eval_target --checkpoint RUN/checkpoints/epoch=0-step=4.ckpt --targets kitti120k nusc35k
     python -m lidog_amd.eval_target --checkpoint ... --model MinkUNet34 --targets nusc35k --save-predictions
+    python -m lidog_amd.eval_target --checkpoint ... --precision bf16
     python -m lidog_amd.eval_target --checkpoint ... --target-files SemanticKITTI=/data/SemanticKITTI --label-maps semantickitti2common.yaml
 
 What the reference does through pytorch-lightning's trainer.test, as plain arguments:
@@ -48,6 +49,9 @@ def parse_args(argv=None):
                     help="one IoU row per loader batch (the reference) or per scan")
     ap.add_argument("--save-predictions", action="store_true")
     ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16"],
+                    help="bf16: convolutions with channel counts that are multiples of 32 multiply bf16 operands "
+                         "(fp32 accumulation, fp32 activations); the weights are packed once per target")
     scans.add_file_arguments(ap, "--target-files", "evaluate on the validation")
     a = ap.parse_args(argv)
     if a.checkpoint is None:
@@ -100,7 +104,7 @@ def main(argv=None):
     targets = source_names(a.targets)
     file_targets = "".join(targets)
     bev = bev_image_size(a.bound)
-    ev = TargetEvaluator(model, num_classes=len(CLASS_NAMES))
+    ev = TargetEvaluator(model, num_classes=len(CLASS_NAMES), precision=a.precision)
     results = []
     luts = None
     if a.target_files is not None:

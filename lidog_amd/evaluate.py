@@ -13,6 +13,7 @@ the host, per loader batch as the reference or per scan as evaluate() above."""
 import torch
 
 from . import me as ME
+from . import precision as _precision
 
 
 def per_class_iou(preds, labels, num_classes=7, ignore_label=-1):
@@ -37,12 +38,16 @@ def mean_iou(per_scan_iou):
 
 
 @torch.no_grad()
-def predict(model, coords, feats, manager=None):
+def predict(model, coords, feats, manager=None, precision=None, kernels=None):
     """validation / test forward: is_train=False (no BEV head, running BN statistics), arg-max class per voxel.
+    `precision`: None (whatever is current: fp32 unless the caller opened lidog_amd.precision.bf16_inference), "fp32" or
+    "bf16" (the eligible convolutions on the bf16 kernels; `kernels`: a precision.Bf16Kernels of the model packed
+    earlier, else the weights are packed in this call); anything else is a ValueError before any launch.
     After the first call the coordinate maps of a batch are built in one go from the recorded trace of map uses
     (ME.CoordinateManager.prepare: one host synchronisation instead of one per kernel map); `manager`: a manager
     prepared ahead of time for these coordinates (Predictor / evaluate() build the next batch's while the current
     forward pass runs)."""
+    scope = _precision.scope(model, precision, kernels)
     was_training = model.training
     model.eval()
     trace = getattr(model, "_lidog_eval_trace", None)
@@ -52,7 +57,8 @@ def predict(model, coords, feats, manager=None):
         st = ME.SparseTensor(features=feats, coordinates=coords, coordinate_manager=manager)
     else:
         st = ME.SparseTensor(coordinates=coords, features=feats)
-    out = model(st)
+    with scope:
+        out = model(st)
     model._lidog_eval_trace = st.coordinate_manager.trace
     logits = (out[0] if isinstance(out, tuple) else out).F
     model.train(was_training)
@@ -61,10 +67,13 @@ def predict(model, coords, feats, manager=None):
 
 class Predictor:
     """predict() over a stream of batches with the NEXT batch's coordinate maps built on the side stream while
-    the current forward pass runs: p = Predictor(model); preds, logits = p(coords, feats, next_coords)"""
+    the current forward pass runs: p = Predictor(model); preds, logits = p(coords, feats, next_coords).
+    `precision="bf16"`: the weights are packed ONCE, here (`kernels`, a precision.Bf16Kernels); call kernels.refresh()
+    after changing the weights."""
 
-    def __init__(self, model):
-        self.model, self._next = model, None
+    def __init__(self, model, precision=None):
+        self.model, self._next, self.precision = model, None, precision
+        self.kernels = _precision.Bf16Kernels(model) if _precision.resolve(precision) else None
 
     def __call__(self, coords, feats, next_coords=None):
         mgr = None
@@ -75,7 +84,7 @@ class Predictor:
         # forward pass that is about to be launched
         ready = torch.cuda.Event()
         ready.record()
-        out = predict(self.model, coords, feats, mgr)
+        out = predict(self.model, coords, feats, mgr, self.precision, self.kernels)
         trace = getattr(self.model, "_lidog_eval_trace", None)
         if next_coords is not None and trace is not None:
             self._next = (next_coords, ME.CoordinateManager.prepare(next_coords, trace, ready))
@@ -83,12 +92,12 @@ class Predictor:
 
 
 @torch.no_grad()
-def evaluate(model, batches, num_classes=7, ignore_label=-1):
+def evaluate(model, batches, num_classes=7, ignore_label=-1, precision=None):
     """batches: iterable of dicts with coords_int [N,4], source_features0, source_sem_labels0; one IoU row per SCAN.
     (The reference's eval_target.py builds its loaders with batch_size * 2 and test_step computes one row per loader
     batch: that table is TargetEvaluator's rows="batch"; rows="scan" gives this function's.)"""
     rows = []
-    run = Predictor(model)
+    run = Predictor(model, precision)
     batches = list(batches)
     for i, b in enumerate(batches):
         coords = b["coords_int"]
@@ -282,8 +291,12 @@ class TargetEvaluator:
     `on_predictions(index, records)`: called per scan with its [k, 5] int32 records (x, y, z, prediction, label) of the
     labelled voxels; asking for it costs one device -> host copy per batch."""
 
-    def __init__(self, model, num_classes=7, ignore_label=-1):
+    def __init__(self, model, num_classes=7, ignore_label=-1, precision=None):
+        """`precision`: None / "fp32" / "bf16" as predict(); with "bf16" every run() packs the weights once (`kernels`
+        holds the last run's table)"""
+        _precision.resolve(precision)
         self.model, self.num_classes, self.ignore_label = model, int(num_classes), int(ignore_label)
+        self.precision, self.kernels = precision, None
 
     @torch.no_grad()
     def run(self, batches, n_scans, rows="batch", on_predictions=None):
@@ -293,7 +306,8 @@ class TargetEvaluator:
         if rows not in ("batch", "scan"):
             raise ValueError(f"rows={rows!r} (one of 'batch', 'scan')")
         c = self.num_classes
-        run = Predictor(self.model)
+        run = Predictor(self.model, self.precision)
+        self.kernels = run.kernels
         it = iter(batches)
         cur = next(it, None)
         counts = err = None

@@ -25,7 +25,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._lib import call, call_on, ptr
+from . import precision as _precision
+from ._lib import call, call_on, ptr, require_gpu
 
 TILE_ROWS = 128  # GM_TM of csrc/sconv.hip
 
@@ -1220,11 +1221,56 @@ class _ConvBase(nn.Module):
             single_out = self.stride == self.kernel_size and self.stride > 1
         return m, s_out, swap, single_out, single_in
 
+    def _bf16(self):
+        """(context, packed bf16 kernel [K, Cout, Cin]) when this call takes the bf16 route -- a table is current
+        (lidog_amd.precision.bf16_inference), autograd is off, the module is eligible and in the table -- else None.
+        With a table current the fp32 calls are counted too."""
+        ctx = _precision.current()
+        if ctx is None or torch.is_grad_enabled():
+            return None
+        wp = ctx.kernels.get(self) if _precision.eligible(self) else None
+        if wp is None:
+            ctx.count(self, _precision.FP32)
+            return None
+        return ctx, wp
+
+    def _gemm_bf16(self, xf, gather, wp, bias, m, out, scatter):
+        call("lidog_sconv_gemm_bf16", ptr(xf), ptr(gather), ptr(wp), ptr(bias), ptr(m.tiles[0]), ptr(m.tiles[1]),
+             ptr(m.tiles[2]), m.n_tiles, self.in_channels, self.out_channels, ptr(out), ptr(scatter))
+
+    def _forward_bf16(self, xf, m, swap, single_out, ctx, wp):
+        """plain forward on the bf16 kernels: straight into the output for 1x1 and single-pair maps, else product rows
+        + the fp32 reduction pass"""
+        require_gpu(xf, "features")
+        Cout = self.out_channels
+        bias = self.bias.detach() if self.bias is not None else None
+        if isinstance(m, _IdentityMap):
+            out = torch.empty((m.n_out, Cout), dtype=torch.float32, device=xf.device)
+            self._gemm_bf16(xf, None, wp, bias, m, out, None)
+            ctx.count(self, _precision.GEMM_DIRECT)
+            return out
+        g_in, g_out, n_out = (m.pair_in, m.pair_out, m.n_out) if not swap else (m.pair_out, m.pair_in, m.n_in)
+        out = torch.empty((n_out, Cout), dtype=torch.float32, device=xf.device)
+        if single_out:
+            self._gemm_bf16(xf, g_in, wp, bias, m, out, g_out)
+            ctx.count(self, _precision.GEMM_DIRECT)
+            return out
+        T = torch.empty((m.P, Cout), dtype=torch.float32, device=xf.device)
+        self._gemm_bf16(xf, g_in, wp, None, m, T, None)
+        row_ptr, row_list = m.rows("in" if swap else "out")
+        call("lidog_sconv_reduce_rows", ptr(T), ptr(row_ptr), ptr(row_list), n_out, Cout, ptr(bias), None, ptr(out))
+        ctx.count(self, _precision.GEMM_REDUCE)
+        return out
+
     def forward(self, x, stats=None, skip=False):
         """`skip=True` returns (conv(x), x'): x' is x again, but routed through this convolution's autograd node
         so that the gradient of a residual branch taken from x' is added inside the data gradient's reduction"""
         cm, s_in = x.coordinate_manager, x.coordinate_map_key
         m, s_out, swap, single_out, single_in = self._resolve(x)
+        bf = self._bf16() if stats is None and not skip else None
+        if bf is not None:
+            out = self._forward_bf16(x.F.contiguous(), m, swap, single_out, *bf)
+            return SparseTensor(out, coordinate_manager=cm, coordinate_map_key=s_out)
         out = _SparseConvFn.apply(x.F, self.kernel, self.bias, m, swap, single_out, single_in, stats, skip)
         if skip:
             return (SparseTensor(out[0], coordinate_manager=cm, coordinate_map_key=s_out),
@@ -1248,6 +1294,24 @@ class _ConvBase(nn.Module):
         out = torch.empty((m.n_out, Cout), dtype=torch.float32, device=dev)
         res = residual.F.contiguous() if residual is not None else None
         srt = _os_rows(m, swap, Cin, Cout)
+        bf = self._bf16()
+        if bf is not None:
+            ctx, wp = bf
+            require_gpu(xf, "features")
+            bias = self.bias.detach() if self.bias is not None else None
+            tail = (ptr(bn.running_mean), ptr(invstd), ptr(bn.weight.detach()), ptr(bn.bias.detach()), ptr(res),
+                    1 if relu else 0, ptr(out))
+            if srt is not None and not single_out:
+                call("lidog_sconv_os_bn_bf16", ptr(xf), ptr(m.nbr), m.n_out, m.K, ptr(srt[0]), ptr(srt[1]), ptr(srt[2]),
+                     ptr(wp), ptr(bias), Cin, Cout, *tail)
+                ctx.count(self, _precision.OS_BN)
+            else:
+                T = torch.empty((m.P, Cout), dtype=torch.float32, device=dev)
+                self._gemm_bf16(xf, m.pair_in, wp, None, m, T, None)
+                row_ptr, row_list = m.rows("out")
+                call("lidog_sconv_reduce_rows_bn", ptr(T), ptr(row_ptr), ptr(row_list), m.n_out, Cout, ptr(bias), *tail)
+                ctx.count(self, _precision.GEMM_REDUCE_BN)
+            return SparseTensor(out, coordinate_manager=cm, coordinate_map_key=s_out)
         if srt is not None and not single_out:      # sorted rows: output-stationary kernel, same epilogue (same bits)
             call("lidog_sconv_os_bn", ptr(xf), ptr(m.nbr), m.n_out, m.K, ptr(srt[0]), ptr(srt[1]), ptr(srt[2]), ptr(W3),
                  ptr(self.bias.detach()) if self.bias is not None else None, Cin, Cout, ptr(bn.running_mean), ptr(invstd),

@@ -41,6 +41,7 @@ from . import synth
 from .checkpoint import load_training_checkpoint, save_lightning_checkpoint
 from .data import (augment_item, check_augmentations, collate_items, cosmix_merge, draw_augmentation,
                    draw_scaling, draw_source, mix3d_merge, on_merge_stream, pointcutmix_merge, scaling_params, sn_scale)
+from . import precision as _precision
 from .evaluate import CLASS_NAMES, per_class_iou
 from .metrics import MetricLayout, MetricsWriter, StepMetrics
 from .optim import make_optimizer, make_scheduler, shard_indices
@@ -573,16 +574,21 @@ class Fit:
                  scheduler=None, epochs=25, warmup_epochs=0, source_weights=(0.5, 0.5), weight_decay=1e-4,
                  momentum=0.98, check_val_every_n_epoch=5, num_sanity_val_steps=2, save_dir=None, seed=1234,
                  train_data=None, val_data=None, shuffle=True, resume=None, auto_resume=False, prefetch=True,
-                 device="cuda", log=None, state_dict=None, num_sources=None, log_every_n_steps=0, metric_sources=None):
+                 device="cuda", log=None, state_dict=None, num_sources=None, log_every_n_steps=0, metric_sources=None,
+                 val_precision=None):
         """`train_data` with `num_sources = 2` (MultiSynthScans) trains on two sources; `val_data` may then be a dict
         {source name: dataset}: every source is validated on its own (the list of loaders of train_lidog.py:186-190),
         the results keyed by name.
+        `val_precision`: None / "fp32" / "bf16" (lidog_amd.precision): the validation passes' convolutions; a bf16 pass
+        packs the weights once, when it starts.  Training steps are fp32 whatever it says.
         `log_every_n_steps` N > 0 (the reference's entry scripts: 50): every step whose number is a multiple of N is
         recorded by a metrics.StepMetrics (per-class IoU and occurrences of the point predictions and of every BEV level,
         losses, lr; nothing is launched on the other steps), read at the end of every epoch into the history record's
         `metrics` and, with `save_dir`, appended by rank 0 to <save_dir>/metrics.jsonl together with the validation
         results.  0: off.  `metric_sources`: the source names of the keys (default: training_source_names)"""
         self.rank, self.world = _rank_world()
+        _precision.resolve(val_precision)
+        self.val_precision = val_precision
         self.kind, self.batch_size, self.epochs = model_kind, batch_size, epochs
         self.check_val, self.sanity = check_val_every_n_epoch, num_sanity_val_steps
         self.save_dir, self.seed, self.shuffle, self.prefetch = save_dir, seed, shuffle, prefetch
@@ -646,8 +652,9 @@ class Fit:
 
     def _validate(self, data, epoch, limit=None, phase=None):
         res = []
-        for ids in self._epoch_batches(data, 0, False)[:limit]:
-            res.append(self.validation_step(data.batch(ids, self.device)))
+        with _precision.scope(self.model, self.val_precision):     # bf16: one pack per validation pass
+            for ids in self._epoch_batches(data, 0, False)[:limit]:
+                res.append(self.validation_step(data.batch(ids, self.device)))
         if not res:
             return None
         out = {"epoch": epoch, "sem_loss": sum(r["sem_loss"] for r in res) / len(res),
@@ -787,6 +794,9 @@ def parse_args(argv=None):
     ap.add_argument("--log-every-n-steps", type=int, default=argparse.SUPPRESS, metavar="N",
                     help="record per-class IoU, class counts, losses and lr of every N-th training step on the GPU and "
                          "append them to <save-dir>/metrics.jsonl (the reference's entry scripts: 50; default 0: off)")
+    ap.add_argument("--val-precision", default=argparse.SUPPRESS, choices=["fp32", "bf16"],
+                    help="precision of the validation passes' convolutions (default fp32; bf16: lidog_amd.precision, the "
+                         "weights are packed once per validation pass); training is always fp32")
     scans.add_file_arguments(ap, "--files", "train on")
     a = ap.parse_args(argv)
     source_augment = getattr(a, "source_augment", None)
@@ -867,6 +877,11 @@ def mix_method_of(a):
     return "mix3d" if getattr(a, "mix3d", False) and merged else None
 
 
+def val_precision_of(a):
+    """--val-precision of parsed arguments ("fp32" when it was not given)"""
+    return getattr(a, "val_precision", "fp32")
+
+
 def main(argv=None):
     a = parse_args(argv)
     fit = _fit_from_args(a)
@@ -886,7 +901,8 @@ def _fit_from_args(a):
     return Fit(a.model, a.bound, a.batch, a.optimizer, a.lr, a.scheduler, a.epochs, a.warmup_epochs,
                source_weights=tuple(a.source_weights), check_val_every_n_epoch=a.check_val_every_n_epoch,
                save_dir=a.save_dir, seed=a.seed, train_data=train, val_data=val, resume=a.resume,
-               auto_resume=a.auto_resume, log_every_n_steps=getattr(a, "log_every_n_steps", 0))
+               auto_resume=a.auto_resume, log_every_n_steps=getattr(a, "log_every_n_steps", 0),
+               val_precision=val_precision_of(a))
 
 
 def _data_from_args(a):

@@ -861,6 +861,20 @@ int lidog_sconv_os_bn_bf16(const float *A, const int32_t *nbr, int64_t n, int32_
                            int32_t Cin, int32_t Cout, const float *mean, const float *invstd, const float *w,
                            const float *b, const float *residual, int32_t relu, float *out, void *stream);
 
+/* ------------------------------------------------------------------ bf16-operand weight gradient (csrc/sconv_bf16.hip)
+ * Opt-in mixed-precision training (lidog_amd/precision.py): the forward pass and the data gradient of an eligible
+ * convolution run lidog_sconv_gemm_bf16 (the data gradient over the exchanged map with the packed transposed kernel);
+ * the weight gradient is lidog_sconv_wgrad_bf16: arguments and semantics of lidog_sconv_wgrad, both gathered operands
+ * rounded to bf16 (nearest even) as they are staged, fp32 accumulation, fp32 partial slots and fp32 gW (summed per
+ * offset in fixed order: bit-reproducible).  Cin and Cout must be multiples of 32.
+ * lidog_sconv_wgrad_bf16_slabs: Cin * Cout-float slots `partial` needs for n_items work items (0: not a bf16 shape).
+ * lidog_sconv_wgrad_bf16_slots: workgroups of the Cin x Cout kernel resident on the chip at a time (0: unknown). */
+int32_t lidog_sconv_wgrad_bf16_slabs(int32_t Cin, int32_t Cout, int32_t n_items);
+int32_t lidog_sconv_wgrad_bf16_slots(int32_t Cin, int32_t Cout);
+int lidog_sconv_wgrad_bf16(const float *A, const int32_t *pair_a, const float *G, const int32_t *pair_g,
+                           const int32_t *items, int32_t n_items, const int32_t *item_off, int32_t K, int32_t Cin,
+                           int32_t Cout, float *partial, float *gW, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,6 +49,9 @@ SIGNATURES = {
     "lidog_pack_kernels_bf16": [_p, _p, _p, _i32, _i64, _p],
     "lidog_sconv_gemm_bf16": [_p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p],
     "lidog_sconv_os_bn_bf16": [_p, _p, _i64, _i32, _p, _p, _p, _p, _p, _i32, _i32, _p, _p, _p, _p, _p, _i32, _p, _p],
+    "lidog_sconv_wgrad_bf16": [_p, _p, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _p, _p, _p],
+    "lidog_sconv_wgrad_bf16_slabs": [_i32, _i32, _i32],
+    "lidog_sconv_wgrad_bf16_slots": [_i32, _i32],
     "lidog_sconv_wgrad": [_p, _p, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _p, _p, _p],
     "lidog_sconv_gemm_in_bn": [_p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _i32, _i64, _p],
     "lidog_sconv_os_stats_in_bn": [_p, _p, _i64, _i32, _p, _p, _p, _p, _p, _i32, _i32, _p, _p, _p, _d, _f, _f, _p, _p, _p, _p,

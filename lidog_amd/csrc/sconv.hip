@@ -1242,6 +1242,16 @@ extern "C" int32_t lidog_sconv_wgrad_slots(int32_t Cin, int32_t Cout, int32_t fo
     return per > 0 ? per * cus : 0;
 }
 
+// the slot sum of a weight gradient: gW[k] = the `per` x items partial slots of offset k, in fixed order (n = Cin Cout)
+void lidog_launch_items_sum(const float *partial, const int32_t *item_off, int per, int K, int64_t n, float *gW,
+                            hipStream_t st) {
+    if (n % 4 == 0)
+        k_items_sum4<<<dim3((unsigned)cdiv64(n / 4, 16), (unsigned)K), 256, 0, st>>>(
+            (const float4 *)partial, item_off, per, n / 4, (float4 *)gW);
+    else
+        k_items_sum<<<dim3((unsigned)cdiv64(n, 64), (unsigned)K), 256, 0, st>>>(partial, item_off, per, n, gW);
+}
+
 static int sconv_wgrad(const float *A, const int32_t *pair_a, const float *G, const int32_t *pair_g,
                        const int32_t *items, int32_t n_items, const int32_t *item_off, int32_t K, int32_t Cin,
                        int32_t Cout, float *partial, float *gW, InBn in_bn, void *stream) {
@@ -1275,12 +1285,7 @@ static int sconv_wgrad(const float *A, const int32_t *pair_a, const float *G, co
                                                                                       n_items, Cin, Cout, partial);
         }
     }
-    int64_t n = (int64_t)Cin * Cout;
-    if (n % 4 == 0)
-        k_items_sum4<<<dim3((unsigned)cdiv64(n / 4, 16), (unsigned)K), 256, 0, st>>>(
-            (const float4 *)partial, item_off, per, n / 4, (float4 *)gW);
-    else
-        k_items_sum<<<dim3((unsigned)cdiv64(n, 64), (unsigned)K), 256, 0, st>>>(partial, item_off, per, n, gW);
+    lidog_launch_items_sum(partial, item_off, per, K, (int64_t)Cin * Cout, gW, st);
     LIDOG_LAUNCH_CHECK();
     return 0;
 }

@@ -1,4 +1,6 @@
-// bf16-operand versions of the two forward sparse-convolution kernels, for evaluation (lidog_amd/precision.py).
+// bf16-operand versions of the sparse-convolution kernels (lidog_amd/precision.py): the two forward kernels (the gathered
+// GEMM also serves the data gradient of a training step, over the exchanged map with the transposed kernel) and the
+// weight gradient.
 // Activations stay fp32 in memory: the gathered feature rows are rounded to bf16 (nearest even, v_cvt_pk_bf16_f32) on
 // their way into LDS, the weights are packed to bf16 once per run (lidog_pack_kernels_bf16), accumulation is fp32 in
 // v_mfma_f32_32x32x16_bf16 (16 x the multiply-adds per instruction of the exact-f32 32x32x2 form of sconv_mfma.hip).
@@ -12,6 +14,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "sconv_mfma.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -437,6 +440,242 @@ extern "C" int lidog_sconv_os_bn_bf16(const float *A, const int32_t *nbr, int64_
         default: BF_OS(1);
     }
 #undef BF_OS
+    LIDOG_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------ weight gradient
+// gW[k] tile (32 MT) x (32 NT) = sum over the pairs of a work item of bf16(A_row)^T (x) bf16(G_row), fp32 accumulation.
+// The outer structure is sconv_mfma.hip:k_sconv_wgrad_mfma's: the same work items, tile selection, wave shapes, two-level
+// software pipeline of pair indices and gathered rows, unconditional clamped loads and zero-select at the LDS store.
+//
+// The reduction dimension is the PAIR index: for the 32x32x16 instruction lane (li, kh) holds A[row = ci][k = 8 kh + j]
+// and B[k = 8 kh + j][col = co], eight consecutive pairs of ONE channel for both operands.  Both images are therefore
+// staged already transposed, [channel][pair], one chunk of 32 pairs = 64 bytes per channel row + 16 of padding (BF_SA),
+// and a fragment is one 16-byte read of a row -- the read pattern of bf_multiply above.
+//
+// Bank conflicts.  Reads (ds_read_b128, 64 banks of 4 bytes, 256-byte cycle): the 32 lanes of a half read rows li at the
+// same column; rows are 80 bytes apart, so 16 consecutive rows start in 16 different 16-byte groups of the cycle
+// (80 li mod 256 = 16 (5 li mod 16), 5 odd) and the second 16 repeat them in the instruction's other lane group: no
+// conflict, as in the two forward kernels.  Writes (ds_write_b32, 32 banks, per 32-lane half): a staging thread holds
+// the SAME four channels of two consecutive pairs (two float4 loads) and writes four words {bf16(pair 2r), bf16(pair
+// 2r+1)}, one per channel row.  Cell f of a chunk = (pair duo r = f & 15, channel quad c4 = f >> 4): a half-wave is 16
+// duos x 2 quads, word address (4 c4 + i) 20 + r, i.e. banks r for the even quad and 16 + r for the odd one (80 mod 32
+// = 16): every one of the four writes is conflict-free.  The price is the global side: a wave's load touches 64
+// contiguous bytes of 16 rows instead of whole rows (the rest of each line is another wave's, served by the cache).
+// Rows past the end of the item are exact zeros in BOTH images (0 x NaN would be NaN).
+template <int MT, int NT, int NW, int NGRP>
+__global__ __launch_bounds__(64 * NW) void k_sconv_wgrad_bf16(const float *__restrict__ A, const int32_t *__restrict__ pa,
+                                                              const float *__restrict__ G, const int32_t *__restrict__ pg,
+                                                              const int32_t *__restrict__ items, int n_items, int Cin,
+                                                              int Cout, float *__restrict__ partial) {
+    constexpr int TM = 32 * MT, TN = 32 * NT, NTH = 64 * NW;
+    constexpr int TILES = MT * NT;
+    constexpr int WPG = NW / NGRP;                  // waves per group
+    constexpr int TPW = (TILES + WPG - 1) / WPG;    // tiles per wave
+    static_assert(NGRP == 1 || NGRP == 2, "a chunk is two k = 16 steps: one group takes both, or two take one each");
+    __shared__ __attribute__((aligned(16))) uint16_t At[TM * BF_SA];
+    __shared__ __attribute__((aligned(16))) uint16_t Gt[TN * BF_SA];
+    // row 3 of the item table = launch order (me.py:_wgrad_items_host)
+    const int item = items[3 * n_items + blockIdx.x];
+    const int tiles_n = Cout / TN;
+    const int ci0 = (blockIdx.y / tiles_n) * TM, co0 = (blockIdx.y % tiles_n) * TN;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int li = lane & 31, kh = lane >> 5;
+    const int grp = wave / WPG, wig = wave % WPG;
+    const int64_t p0 = items[n_items + item], p1 = items[2 * n_items + item];
+
+    int a_off[TPW], g_off[TPW];
+    bool own[TPW];
+#pragma unroll
+    for (int t = 0; t < TPW; ++t) {
+        const int tt = wig * TPW + t;   // tiles enumerated column-major: tt = nj * MT + mi
+        own[t] = tt < TILES;
+        const int mi = own[t] ? tt % MT : 0, nj = own[t] ? tt / MT : 0;
+        a_off[t] = (32 * mi + li) * BF_SA + 8 * kh;
+        g_off[t] = (32 * nj + li) * BF_SA + 8 * kh;
+    }
+    f32x16 acc[TPW];
+#pragma unroll
+    for (int t = 0; t < TPW; ++t)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
+
+    constexpr int AC = TM * 4, GC = TN * 4;         // cells of a chunk: (channels / 4) quads x 16 pair duos
+    constexpr int AV = (AC + NTH - 1) / NTH, GV = (GC + NTH - 1) / NTH;
+    float4 ra[AV][2], rg[GV][2];
+    int ia[AV][2], ig[GV][2];
+    auto load_idx = [&](int64_t p) {
+#pragma unroll
+        for (int j = 0; j < AV; ++j) {
+            int f = tid + NTH * j;
+            f = f < AC ? f : AC - 1;
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int64_t pr = p + 2 * (f & 15) + u;
+                ia[j][u] = pa[pr < p1 ? pr : p1 - 1];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < GV; ++j) {
+            int f = tid + NTH * j;
+            f = f < GC ? f : GC - 1;
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int64_t pr = p + 2 * (f & 15) + u;
+                ig[j][u] = pg[pr < p1 ? pr : p1 - 1];
+            }
+        }
+    };
+    auto load_rows = [&]() {
+#pragma unroll
+        for (int j = 0; j < AV; ++j) {
+            int f = tid + NTH * j;
+            f = f < AC ? f : AC - 1;
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+                ra[j][u] = *reinterpret_cast<const float4 *>(A + (size_t)ia[j][u] * Cin + ci0 + (f >> 4) * 4);
+        }
+#pragma unroll
+        for (int j = 0; j < GV; ++j) {
+            int f = tid + NTH * j;
+            f = f < GC ? f : GC - 1;
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+                rg[j][u] = *reinterpret_cast<const float4 *>(G + (size_t)ig[j][u] * Cout + co0 + (f >> 4) * 4);
+        }
+    };
+    if (p0 < p1) {
+        load_idx(p0);
+        load_rows();
+        load_idx(p0 + BF_BK);
+    }
+    uint32_t *At32 = reinterpret_cast<uint32_t *>(At), *Gt32 = reinterpret_cast<uint32_t *>(Gt);
+    for (int64_t p = p0; p < p1; p += BF_BK) {
+        __syncthreads();
+        // pairs past the end of the item are zeroed here, not at load time (a select right after the load would make the
+        // wave wait for the gather before its MFMA phase instead of after it)
+#pragma unroll
+        for (int j = 0; j < AV; ++j) {
+            const int f = tid + NTH * j;
+            const int r = f & 15, c = (f >> 4) * 4;
+            const bool ok0 = p + 2 * r < p1, ok1 = p + 2 * r + 1 < p1;
+            const float4 v0 = ra[j][0], v1 = ra[j][1];
+            if (f < AC) {
+                uint32_t *d = At32 + c * (BF_SA / 2) + r;
+                d[0] = bf_pack2(ok0 ? v0.x : 0.f, ok1 ? v1.x : 0.f);
+                d[BF_SA / 2] = bf_pack2(ok0 ? v0.y : 0.f, ok1 ? v1.y : 0.f);
+                d[2 * (BF_SA / 2)] = bf_pack2(ok0 ? v0.z : 0.f, ok1 ? v1.z : 0.f);
+                d[3 * (BF_SA / 2)] = bf_pack2(ok0 ? v0.w : 0.f, ok1 ? v1.w : 0.f);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < GV; ++j) {
+            const int f = tid + NTH * j;
+            const int r = f & 15, c = (f >> 4) * 4;
+            const bool ok0 = p + 2 * r < p1, ok1 = p + 2 * r + 1 < p1;
+            const float4 v0 = rg[j][0], v1 = rg[j][1];
+            if (f < GC) {
+                uint32_t *d = Gt32 + c * (BF_SA / 2) + r;
+                d[0] = bf_pack2(ok0 ? v0.x : 0.f, ok1 ? v1.x : 0.f);
+                d[BF_SA / 2] = bf_pack2(ok0 ? v0.y : 0.f, ok1 ? v1.y : 0.f);
+                d[2 * (BF_SA / 2)] = bf_pack2(ok0 ? v0.z : 0.f, ok1 ? v1.z : 0.f);
+                d[3 * (BF_SA / 2)] = bf_pack2(ok0 ? v0.w : 0.f, ok1 ? v1.w : 0.f);
+            }
+        }
+        __syncthreads();
+        if (p + BF_BK < p1) {
+            load_rows();
+            load_idx(p + 2 * BF_BK);
+        }
+        // k = 16 steps of the chunk: pairs [16 s, 16 s + 16); with two groups each takes one step and its own slab
+#pragma unroll
+        for (int q = 0; q < 2 / NGRP; ++q) {
+            const int ks = 16 * (q * NGRP + grp);
+            bf16x8 af[TPW], gf[TPW];
+#pragma unroll
+            for (int t = 0; t < TPW; ++t) {
+                af[t] = *reinterpret_cast<const bf16x8 *>(&At[a_off[t] + ks]);
+                gf[t] = *reinterpret_cast<const bf16x8 *>(&Gt[g_off[t] + ks]);
+            }
+#pragma unroll
+            for (int t = 0; t < TPW; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[t], gf[t], acc[t], 0, 0, 0);
+        }
+    }
+    float *dst = partial + (size_t)(item * NGRP + grp) * Cin * Cout;
+#pragma unroll
+    for (int t = 0; t < TPW; ++t) {
+        if (!own[t]) continue;
+        const int tt = wig * TPW + t;
+        const int mi = tt % MT, nj = tt / MT;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int ci = ci0 + 32 * mi + (e & 3) + 8 * (e >> 2) + 4 * kh;
+            dst[(size_t)ci * Cout + co0 + 32 * nj + li] = acc[t][e];
+        }
+    }
+}
+
+// (MT, NT, NW, NGRP) per tile shape, tiles as sconv_mfma.hip:tile32; every wave gets the same number of MFMA tiles, or
+// the two k = 16 steps of a chunk are split over two groups of waves that each emit their own partial slab
+#define BF_WG_SHAPES(X)                                                                                             \
+    X(1, 1, 2, 2) X(1, 2, 4, 2) X(2, 1, 4, 2) X(1, 3, 3, 1) X(3, 1, 3, 1) X(1, 4, 4, 1) X(4, 1, 4, 1) X(2, 2, 4, 1) \
+    X(2, 3, 3, 1) X(3, 2, 3, 1) X(2, 4, 4, 1) X(4, 2, 4, 1) X(3, 3, 3, 1) X(3, 4, 4, 1) X(4, 3, 4, 1) X(4, 4, 4, 1)
+
+static bool bf_wgrad_shape(int Cin, int Cout) { return Cin > 0 && Cout > 0 && Cin % 32 == 0 && Cout % 32 == 0; }
+
+// partial slots (Cin * Cout floats each) the caller must provide for n_items work items; 0: not a bf16 shape
+extern "C" int32_t lidog_sconv_wgrad_bf16_slabs(int32_t Cin, int32_t Cout, int32_t n_items) {
+    if (!bf_wgrad_shape(Cin, Cout) || n_items < 0) return 0;
+    return n_items * (bf_nt(Cin) * bf_nt(Cout) <= 2 ? 2 : 1);
+}
+
+// workgroups of the Cin x Cout kernel resident on the chip at a time (per-CU occupancy x CUs), what me._wgrad_chunk
+// fits a launch to; 0: not a bf16 shape, or no device
+extern "C" int32_t lidog_sconv_wgrad_bf16_slots(int32_t Cin, int32_t Cout) {
+    if (!bf_wgrad_shape(Cin, Cout)) return 0;
+    int dev = 0, cus = 0, per = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+        return 0;
+    hipError_t e = hipErrorInvalidValue;
+    switch (bf_nt(Cin) * 10 + bf_nt(Cout)) {
+#define X(MT_, NT_, NW_, NG_)                                                                                          \
+    case MT_ * 10 + NT_:                                                                                               \
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_sconv_wgrad_bf16<MT_, NT_, NW_, NG_>, 64 * NW_, 0); \
+        break;
+        BF_WG_SHAPES(X)
+#undef X
+    }
+    return (e == hipSuccess && per > 0) ? per * cus : 0;
+}
+
+// gW [K][Cin][Cout] = sum over the pairs of offset k of bf16(A[pair_a])^T bf16(G[pair_g]): arguments and semantics of
+// lidog_sconv_wgrad (work items of me._wgrad_items_host, never straddling an offset; one partial slab per item, or per
+// item and k-step group: lidog_sconv_wgrad_bf16_slabs; summed per offset in fixed order by sconv.hip:k_items_sum4).
+extern "C" int lidog_sconv_wgrad_bf16(const float *A, const int32_t *pair_a, const float *G, const int32_t *pair_g,
+                                      const int32_t *items, int32_t n_items, const int32_t *item_off, int32_t K,
+                                      int32_t Cin, int32_t Cout, float *partial, float *gW, void *stream) {
+    hipStream_t st = (hipStream_t)stream;
+    LIDOG_REQUIRE(bf_wgrad_shape(Cin, Cout), "sconv_wgrad_bf16: channel counts must be multiples of 32 (got %d -> %d)",
+                  Cin, Cout);
+    LIDOG_REQUIRE(K >= 1 && n_items >= 0 && item_off && gW, "sconv_wgrad_bf16: bad K / n_items / arguments");
+    LIDOG_REQUIRE(n_items == 0 || (partial && A && G && pair_a && pair_g && items),
+                  "sconv_wgrad_bf16: operands or partial workspace missing");
+    const int mt = bf_nt(Cin), nt = bf_nt(Cout);
+    if (n_items > 0) {
+        dim3 grid((unsigned)n_items, (unsigned)((Cin / (32 * mt)) * (Cout / (32 * nt))));
+        switch (mt * 10 + nt) {
+#define X(MT_, NT_, NW_, NG_)                                                                                    \
+    case MT_ * 10 + NT_:                                                                                         \
+        k_sconv_wgrad_bf16<MT_, NT_, NW_, NG_><<<grid, 64 * NW_, 0, st>>>(A, pair_a, G, pair_g, items, n_items, Cin, \
+                                                                          Cout, partial);                       \
+        break;
+            BF_WG_SHAPES(X)
+#undef X
+        }
+    }
+    lidog_launch_items_sum(partial, item_off, lidog_sconv_wgrad_bf16_slabs(Cin, Cout, 1), K, (int64_t)Cin * Cout, gW, st);
     LIDOG_LAUNCH_CHECK();
     return 0;
 }

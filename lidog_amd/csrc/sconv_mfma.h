@@ -31,3 +31,6 @@ int lidog_launch_wgrad_mfma(const float *A, const int32_t *pa, const float *G, c
                             hipStream_t st);
 int lidog_wgrad_mfma_slabs(int Cin, int Cout, int n_items);
 int lidog_wgrad_mfma_wg_per_cu(int Cin, int Cout, int fold);
+// csrc/sconv.hip: the fixed-order sum of a weight gradient's partial slots (`per` per work item) into gW [K][n]
+void lidog_launch_items_sum(const float *partial, const int32_t *item_off, int per, int K, int64_t n, float *gW,
+                            hipStream_t st);

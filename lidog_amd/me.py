@@ -15,6 +15,7 @@ Mirrors the surface of MinkowskiEngine 0.5.4 that LiDOG's models and pipelines u
 is no CPU path (tensors on the CPU raise).
 """
 import ctypes
+import functools
 import math
 import os
 import sys
@@ -363,6 +364,8 @@ class CoordinateManager:
         # weight-gradient work items of every (map, Cin, Cout) seen
         items_todo = []
         k_off_of = {t[1]: t[3] for t in todo}
+        pctx = _precision.current()         # a bf16 training step cuts the eligible shapes for its own kernel
+        bf_train = pctx is not None and pctx.training
         for key in want:
             if key[0] == "identity":
                 ident, koh = self.maps[key[1]].n, None
@@ -373,7 +376,7 @@ class CoordinateManager:
                 koh = self.kmaps[key].k_off_host
             seen = set()
             for cin, cout in shapes[key]:
-                chunk = _wgrad_chunk(koh, cin, cout)
+                chunk = _wgrad_chunk(koh, cin, cout, bf_train and cin % 32 == 0 and cout % 32 == 0 and cin > 0)
                 if chunk in seen:
                     continue
                 seen.add(chunk)
@@ -721,6 +724,12 @@ def _gemm(A, gather, B, bias, m, Cin, Cout, out, scatter, tiles=None):
          n_tiles, Cin, Cout, ptr(out), ptr(scatter), A.shape[0])
 
 
+def _gemm_bf16(A, gather, B, bias, m, Cin, Cout, out, scatter, wp=None):
+    """_gemm's arguments on lidog_sconv_gemm_bf16; `wp`: the packed bf16 operand [K, Cout, Cin] that stands for B"""
+    call("lidog_sconv_gemm_bf16", ptr(A), ptr(gather), ptr(wp), ptr(bias), ptr(m.tiles[0]), ptr(m.tiles[1]),
+         ptr(m.tiles[2]), m.n_tiles, Cin, Cout, ptr(out), ptr(scatter))
+
+
 # row of the 5^3 neighbour table that holds offset k of the 3^3 kernel (both x fastest, centred)
 _SUBSET_3_OF_5 = np.array([(dz + 2) * 25 + (dy + 2) * 5 + (dx + 2) for dz in (-1, 0, 1) for dy in (-1, 0, 1)
                            for dx in (-1, 0, 1)], dtype=np.int32)
@@ -754,8 +763,17 @@ def _wgrad_slots(Cin, Cout):
     return _wgrad_slots_cache[key]
 
 
-def _wgrad_chunk(k_off_host, Cin, Cout):
-    """pairs per weight-gradient work item for a rule book with offsets k_off_host [K + 1]"""
+def _wgrad_slots_bf16(Cin, Cout):
+    """the same for lidog_sconv_wgrad_bf16: another kernel, with its own occupancy"""
+    key = (Cin, Cout, "bf16")
+    if key not in _wgrad_slots_cache:
+        _wgrad_slots_cache[key] = int(_lib.load().lidog_sconv_wgrad_bf16_slots(Cin, Cout))
+    return _wgrad_slots_cache[key]
+
+
+def _wgrad_chunk(k_off_host, Cin, Cout, bf16=False):
+    """pairs per weight-gradient work item for a rule book with offsets k_off_host [K + 1]; `bf16`: for
+    lidog_sconv_wgrad_bf16 (the slot fitting reads that kernel's slots)"""
     P = int(k_off_host[-1]) - int(k_off_host[0])
 
     def tile(c):
@@ -772,7 +790,7 @@ def _wgrad_chunk(k_off_host, Cin, Cout):
     target = max(1, blocks // tiles)
     max_items = max(1, (192 << 20) // (4 * Cin * Cout))             # at most ~192 MB of partial slots
     fit = _WGRAD_FIT if _WGRAD_FIT >= 0 else (0 if _WgradLane.enabled else 1)
-    slots = _wgrad_slots(Cin, Cout) if fit else 0
+    slots = (_wgrad_slots_bf16(Cin, Cout) if bf16 else _wgrad_slots(Cin, Cout)) if fit else 0
     if slots and blocks > slots:
         # Every offset ends in a partial item (P / chunk items are really ~K / 2 more) and the swept optimum is not a
         # multiple of the slots: 2 048 wanted on 768 slots = 2.7 rounds.  Cut so that the launch is `rounds` whole rounds.
@@ -814,13 +832,13 @@ def _wgrad_items_host(k_off_host, chunk):
     return items[:4 * n].reshape(4, n), int(n), item_off
 
 
-def _wgrad_items(m, Cin, Cout):
+def _wgrad_items(m, Cin, Cout, bf16=False):
     """Work items of the weight gradient: the rule book cut into pair ranges of equal length that never straddle
     an offset (the centre offset of a 3^3 kernel owns one pair per voxel, corner offsets a few per cent of
     that: equal splits per offset would leave most workgroups idle behind the centre ones).
     Returns (items int32 [3, n] on the device, n, item_off int32 [K+1] on the device); cached on the map
     (CoordinateManager.prefetch fills the cache ahead of the backward pass)."""
-    chunk = _wgrad_chunk(m.k_off_host, Cin, Cout)
+    chunk = _wgrad_chunk(m.k_off_host, Cin, Cout, bf16)
     cache = m.__dict__.setdefault("_wgrad_items", {})
     if chunk not in cache:
         items, total, item_off = _wgrad_items_host(m.k_off_host, chunk)
@@ -842,10 +860,16 @@ class _SparseConvFn(torch.autograd.Function):
     (k2 s2) -> the data gradient scatters straight into `gin`."""
 
     @staticmethod
-    def forward(ctx, x, W, bias, m, swap, single_out, single_in, stats=None, skip=False):
+    def forward(ctx, x, W, bias, m, swap, single_out, single_in, stats=None, skip=False, bf=None):
         """`stats`: optional StatsRequest of the BatchNorm that follows; when the output goes through the reduction
         pass, that pass also produces the fp64 sums of `out` (and, for a local BatchNorm, mean / invstd / running
-        statistics), returned in the request."""
+        statistics), returned in the request.
+        `bf`: None, or (precision.Bf16TrainContext, module, packed forward operand [K, Cout, Cin], packed data-gradient
+        operand [K, Cin, Cout]) of a mixed-precision training step: lidog_sconv_gemm_bf16 replaces the fp32 GEMM on the
+        identity, single-out and two-pass routes (a 3^3 convolution that would take the output-stationary kernel takes
+        the two-pass route: its bf16 form has no statistics epilogue and no mirrored data gradient); the reduction pass,
+        and with it the BatchNorm statistics, is the fp32 one.  backward() follows with the bf16 data and weight
+        gradients."""
         x = x.contiguous()
         W3 = W.contiguous().view(m.K, W.shape[-2], W.shape[-1])
         K, Cin, Cout = W3.shape
@@ -858,15 +882,21 @@ class _SparseConvFn(torch.autograd.Function):
         else:  # transposed convolution: the forward map used with in/out exchanged
             g_in, g_out, pos_o, n_out = m.pair_out, m.pair_in, m.pos_in, m.n_in
         out = torch.empty((n_out, Cout), dtype=torch.float32, device=x.device)
+        if bf is not None:
+            require_gpu(x, "features")
+            gemm = functools.partial(_gemm_bf16, wp=bf[2])
+            bf[0].count(bf[1], _precision.FWD_DIRECT if identity or single_out else _precision.FWD_REDUCE)
+        else:
+            gemm = _gemm
         if identity:
-            _gemm(x, None, W3, bias, m, Cin, Cout, out, None)
+            gemm(x, None, W3, bias, m, Cin, Cout, out, None)
         elif single_out:
-            _gemm(x, g_in, W3, bias, m, Cin, Cout, out, g_out)
+            gemm(x, g_in, W3, bias, m, Cin, Cout, out, g_out)
         elif Cin == 1 and not swap and Cout in (16, 32, 64) and K * Cout * 4 <= 48 * 1024 and m.nbr is not None:
             # the stem: straight from the neighbour table, no product rows (bit-identical to the two-pass path); the
             # BatchNorm statistics of its 32-channel output are then one small pass of their own
             call("lidog_sconv_cin1", ptr(x), ptr(m.nbr), ptr(W3), ptr(bias), n_out, K, Cout, ptr(out))
-        elif _os_rows(m, swap, Cin, Cout) is not None:
+        elif bf is None and _os_rows(m, swap, Cin, Cout) is not None:
             # sparse symmetric 3^3 map: output-stationary kernel, no product rows (bit-identical convolution; the
             # statistics are summed per tile instead of per row block)
             perm, wmask, order = _os_rows(m, swap, Cin, Cout)
@@ -891,7 +921,7 @@ class _SparseConvFn(torch.autograd.Function):
                      ptr(bias), None, Cin, Cout, ptr(out))
         else:
             T = torch.empty((m.P, Cout), dtype=torch.float32, device=x.device)
-            _gemm(x, g_in, W3, None, m, Cin, Cout, T, None)
+            gemm(x, g_in, W3, None, m, Cin, Cout, T, None)
             if Cout % 4 == 0:
                 row_ptr, row_list = m.rows("in" if swap else "out")
             if stats is not None and Cout % 4 == 0 and Cout <= 1024:
@@ -916,7 +946,7 @@ class _SparseConvFn(torch.autograd.Function):
                 call("lidog_sconv_reduce", ptr(T), ptr(pos_o), n_out, K, Cout, ptr(bias), None, ptr(out))
         ctx.save_for_backward(x, W3)
         ctx.m, ctx.swap, ctx.single_in, ctx.has_bias, ctx.w_shape = m, swap, single_in, bias is not None, W.shape
-        ctx.w_param, ctx.b_param = W, bias
+        ctx.w_param, ctx.b_param, ctx.bf = W, bias, bf
         if skip:
             # second output = the input itself (the residual branch of a BasicBlock): its gradient comes back to
             # this node and is added by the data gradient's reduction pass instead of by an autograd add kernel
@@ -939,14 +969,20 @@ class _SparseConvFn(torch.autograd.Function):
         else:
             g_in, g_out, pos_i, n_in = m.pair_out, m.pair_in, m.pos_out, m.n_out
         gx = gW = gb = None
+        bf = ctx.bf
+        wgrad = "lidog_sconv_wgrad_bf16" if bf is not None else "lidog_sconv_wgrad"
         lane_on = _WgradLane.active()
         # forked behind the data gradient's GEMM (see _WgradLane), or before everything in mode 1
         behind = lane_on and _WgradLane.mode == 2
 
         def queue_wgrad():
             gW = _grad_out(ctx.w_param, W3.shape)
-            items, n_items, item_off = _wgrad_items(m, Cin, Cout)
-            slabs = _lib.load().lidog_sconv_wgrad_slabs(Cin, Cout, n_items)
+            items, n_items, item_off = _wgrad_items(m, Cin, Cout, bf is not None)
+            if bf is not None:      # the bf16 kernel's own slab count (and, above, its own slots)
+                slabs = _lib.load().lidog_sconv_wgrad_bf16_slabs(Cin, Cout, n_items)
+                bf[0].count(bf[1], _precision.WGRAD)
+            else:
+                slabs = _lib.load().lidog_sconv_wgrad_slabs(Cin, Cout, n_items)
 
             partial = torch.empty((max(slabs, 1), Cin, Cout), dtype=torch.float32, device=x.device)
             if gW is not None and lane_on:
@@ -955,11 +991,11 @@ class _SparseConvFn(torch.autograd.Function):
                 # the lane has just been made to wait for everything queued on the main stream (fork)
                 lane = _WgradLane.get(x.device)
                 lane.fork(x, gout, m, partial)
-                call_on(lane.raw, "lidog_sconv_wgrad", ptr(x), ptr(g_in), ptr(gout), ptr(g_out), ptr(items), n_items,
+                call_on(lane.raw, wgrad, ptr(x), ptr(g_in), ptr(gout), ptr(g_out), ptr(items), n_items,
                         ptr(item_off), K, Cin, Cout, ptr(partial), ptr(gW))
             else:
                 gW = gW if gW is not None else torch.empty_like(W3)
-                call("lidog_sconv_wgrad", ptr(x), ptr(g_in), ptr(gout), ptr(g_out), ptr(items), n_items,
+                call(wgrad, ptr(x), ptr(g_in), ptr(gout), ptr(g_out), ptr(items), n_items,
                      ptr(item_off), K, Cin, Cout, ptr(partial), ptr(gW))
             return gW.view(ctx.w_shape)
 
@@ -967,17 +1003,21 @@ class _SparseConvFn(torch.autograd.Function):
             gW = queue_wgrad()
         if ctx.needs_input_grad[0]:
             wp = ctx.w_param
-            if getattr(wp, "_wt_version", -2) == wp._version:
-                Wt = wp._wt_view                     # refreshed after the optimiser step (optim.TransposedKernels)
+            if bf is not None:
+                # the packed transposed kernel (precision.Bf16Training); the reduction pass and its addend stay fp32
+                Wt, gemm = None, functools.partial(_gemm_bf16, wp=bf[3])
+                bf[0].count(bf[1], _precision.DGRAD_DIRECT if identity or ctx.single_in else _precision.DGRAD_REDUCE)
+            elif getattr(wp, "_wt_version", -2) == wp._version:
+                Wt, gemm = wp._wt_view, _gemm        # refreshed after the optimiser step (optim.TransposedKernels)
             else:
-                Wt = torch.empty((K, Cout, Cin), dtype=torch.float32, device=x.device)
+                Wt, gemm = torch.empty((K, Cout, Cin), dtype=torch.float32, device=x.device), _gemm
                 call("lidog_transpose_kernel", ptr(W3), K, Cin, Cout, ptr(Wt))
             gx = torch.empty((n_in, Cin), dtype=torch.float32, device=x.device)
             if identity:
-                _gemm(gout, None, Wt, None, m, Cout, Cin, gx, None)
+                gemm(gout, None, Wt, None, m, Cout, Cin, gx, None)
             elif ctx.single_in:
-                _gemm(gout, g_out, Wt, None, m, Cout, Cin, gx, g_in)
-            elif _os_rows(m, swap, Cin, Cout) is not None:
+                gemm(gout, g_out, Wt, None, m, Cout, Cin, gx, g_in)
+            elif bf is None and _os_rows(m, swap, Cin, Cout) is not None:
                 # the data gradient over the mirrored offsets of the same sorted rows (csrc/sconv_os.hip); the residual
                 # branch's gradient is added in its epilogue, as the reduction pass does
                 perm, wmask, order = _os_rows(m, swap, Cin, Cout)
@@ -988,7 +1028,7 @@ class _SparseConvFn(torch.autograd.Function):
                     gW = queue_wgrad()
             else:
                 T = torch.empty((m.P, Cin), dtype=torch.float32, device=x.device)
-                _gemm(gout, g_out, Wt, None, m, Cout, Cin, T, None)
+                gemm(gout, g_out, Wt, None, m, Cout, Cin, T, None)
                 if ctx.needs_input_grad[1] and behind:
                     gW = queue_wgrad()
                 add = gskip if (gskip is not None and Cin % 4 == 0) else None
@@ -1009,7 +1049,7 @@ class _SparseConvFn(torch.autograd.Function):
             call("lidog_colsum", ptr(gout), gout.shape[0], Cout, ptr(gb), ptr(ws))
         if gskip is not None:   # paths without a reduction pass (1x1, k2 s2) or no data gradient asked for
             gx = gskip if gx is None else gx + gskip
-        return gx, gW, gb, None, None, None, None, None, None
+        return gx, gW, gb, None, None, None, None, None, None, None
 
 
 def _bn_ws(C, hw, dev, images=1):
@@ -1221,11 +1261,11 @@ class _ConvBase(nn.Module):
             single_out = self.stride == self.kernel_size and self.stride > 1
         return m, s_out, swap, single_out, single_in
 
-    def _bf16(self):
+    def _bf16(self, ctx=False):
         """(context, packed bf16 kernel [K, Cout, Cin]) when this call takes the bf16 route -- a table is current
         (lidog_amd.precision.bf16_inference), autograd is off, the module is eligible and in the table -- else None.
-        With a table current the fp32 calls are counted too."""
-        ctx = _precision.current()
+        With a table current the fp32 calls are counted too.  `ctx`: the current context if the caller looked it up."""
+        ctx = _precision.current() if ctx is False else ctx
         if ctx is None or torch.is_grad_enabled():
             return None
         wp = ctx.kernels.get(self) if _precision.eligible(self) else None
@@ -1233,6 +1273,18 @@ class _ConvBase(nn.Module):
             ctx.count(self, _precision.FP32)
             return None
         return ctx, wp
+
+    def _bf16_train(self, ctx):
+        """(context, module, forward operand, data-gradient operand) when this grad-enabled call runs the bf16 training
+        kernels -- `ctx` is a precision.Bf16TrainContext, the module is eligible and in its table -- else None (counted
+        as fp32)"""
+        if not ctx.training:
+            return None
+        pair = ctx.kernels.pair(self) if _precision.eligible(self) else None
+        if pair is None:
+            ctx.count(self, _precision.FP32)
+            return None
+        return (ctx, self) + pair
 
     def _gemm_bf16(self, xf, gather, wp, bias, m, out, scatter):
         call("lidog_sconv_gemm_bf16", ptr(xf), ptr(gather), ptr(wp), ptr(bias), ptr(m.tiles[0]), ptr(m.tiles[1]),
@@ -1267,11 +1319,16 @@ class _ConvBase(nn.Module):
         so that the gradient of a residual branch taken from x' is added inside the data gradient's reduction"""
         cm, s_in = x.coordinate_manager, x.coordinate_map_key
         m, s_out, swap, single_out, single_in = self._resolve(x)
-        bf = self._bf16() if stats is None and not skip else None
-        if bf is not None:
-            out = self._forward_bf16(x.F.contiguous(), m, swap, single_out, *bf)
-            return SparseTensor(out, coordinate_manager=cm, coordinate_map_key=s_out)
-        out = _SparseConvFn.apply(x.F, self.kernel, self.bias, m, swap, single_out, single_in, stats, skip)
+        pctx, bf = _precision.current(), None       # the one look-up an fp32 call pays
+        if pctx is not None:
+            if torch.is_grad_enabled():
+                bf = self._bf16_train(pctx)
+            elif stats is None and not skip:
+                inf = self._bf16(pctx)
+                if inf is not None:
+                    out = self._forward_bf16(x.F.contiguous(), m, swap, single_out, *inf)
+                    return SparseTensor(out, coordinate_manager=cm, coordinate_map_key=s_out)
+        out = _SparseConvFn.apply(x.F, self.kernel, self.bias, m, swap, single_out, single_in, stats, skip, bf)
         if skip:
             return (SparseTensor(out[0], coordinate_manager=cm, coordinate_map_key=s_out),
                     SparseTensor(out[1], coordinate_manager=cm, coordinate_map_key=s_in))

@@ -269,12 +269,15 @@ class TransposedKernels:
         dev = flat.flat.device
         self.buf = torch.empty(off, dtype=torch.float32, device=dev)
         self.desc = torch.tensor(desc, dtype=torch.int64, device=dev).view(-1, 6) if desc else None
+        self.generation = 0     # refreshes so far (precision.Bf16Training packs from these copies and compares)
         for p, o, shape in self.items:
             p._wt_view = self.buf[o:o + p.numel()].view(shape)
             p._wt_version = -1
+            p._wt_owner = self
         self.refresh()
 
     def refresh(self):
+        self.generation += 1
         if not self.items or not self.buf.is_cuda:
             return
         call("lidog_transpose_batched", ptr(self.flat.flat), ptr(self.buf), ptr(self.desc), len(self.items),

@@ -1,17 +1,33 @@
-"""Opt-in bf16 inference: the evaluation passes' sparse convolutions on the bf16 matrix instruction.
+"""Opt-in bf16: the sparse convolutions of evaluation passes, or of whole training steps, on the bf16 matrix instruction.
 
-The reference passes `pipeline.precision` to Lightning's Trainer; here the knob covers evaluation only.  Activations stay
-fp32 in memory (every BatchNorm, residual, ReLU, concatenation, instance-norm and metric kernel is untouched); a
-convolution whose channel counts are multiples of 32 multiplies bf16 operands with fp32 accumulation
-(csrc/sconv_bf16.hip): the gathered rows are rounded as they are staged, the weights are packed once per run.
+The reference passes `pipeline.precision` to Lightning's Trainer.  Here only the two operands of the matrix instruction
+are bf16: activations, gradients, master weights, the flat gradient buffer and the optimiser state stay fp32 in memory
+(every BatchNorm, residual, ReLU, concatenation, instance-norm, loss and metric kernel and the 2-D BEV head are
+untouched); a convolution whose channel counts are multiples of 32 multiplies bf16 operands with fp32 accumulation
+(csrc/sconv_bf16.hip): gathered rows are rounded as they are staged, the weights are packed.  No loss scaling: bf16 has
+fp32's exponent range.
+
+Evaluation (autograd disabled):
 
     with bf16_inference(model) as ctx:            # packs; or bf16_inference(model, kernels) with a Bf16Kernels
         preds, logits = evaluate.predict(model, coords, feats)
     ctx.launches                                  # Counter: route -> convolutions that took it
 
+Training (autograd enabled; Fit(precision="bf16"), train --precision bf16, or a step class's precision="bf16"):
+
+    table = Bf16Training(model)                   # after the optimiser was built: it reads its transposed kernels
+    with bf16_training(model, table) as ctx:
+        loss = ...; loss.backward()               # forward, data gradient and weight gradient of the eligible convolutions
+    opt.step(); table.refresh()                   # what _Step.training_step does
+
+Inside a training context the trunk executor declines (it launches the fp32 kernels from C) and the step goes down the
+operator path; everything returns to it when the context exits.
+
 A packed table is a SNAPSHOT of the weights.  Its validity is not tied to the parameters' version counters: the
-optimiser's HIP kernels write through raw pointers and never advance them.  Whoever owns a Bf16Kernels calls refresh()
-after the weights change.  Without a current table (the default) no code path changes."""
+optimiser's HIP kernels write through raw pointers and never advance them.  Whoever owns a table calls refresh() after
+the weights change; a Bf16Training also notices, when it becomes current, that the optimiser's transposed copy it reads
+was refreshed behind its back (load_state_dict, resume) and packs again.  Without a current table (the default) no code
+path changes."""
 import collections
 import contextlib
 import threading
@@ -40,43 +56,67 @@ def eligible(conv):
         conv.in_channels % 32 == 0 and conv.out_channels % 32 == 0
 
 
+def table_layout(shapes, off=0, tiles=0):
+    """([(dst offset in bf16 elements, K, Cin, Cout, first 32 x 32 tile)] of kernels fp32 [K, Cin, Cout] packed back to
+    back from element `off` and tile `tiles` on, end offset, end tile): the last five columns of a descriptor row of
+    lidog_pack_kernels_bf16"""
+    layout = []
+    for K, Cin, Cout in shapes:
+        layout.append((off, K, Cin, Cout, tiles))
+        off += K * Cin * Cout
+        tiles += K * (Cin // 32) * (Cout // 32)
+    return layout, off, tiles
+
+
+def training_layout(shapes):
+    """(forward layout, data-gradient layout, elements, tiles) of a Bf16Training over kernels [K, Cin, Cout]: the
+    forward operands first, then the packs of the transposed kernels [K, Cout, Cin] (source `Cin` = Cout), in one
+    buffer and one tile range, so that ONE launch writes both"""
+    fwd, off, tiles = table_layout(shapes)
+    dgrad, off, tiles = table_layout([(K, Cout, Cin) for K, Cin, Cout in shapes], off, tiles)
+    return fwd, dgrad, off, tiles
+
+
+def _eligible_convs(model, what):
+    convs = [m for m in model.modules() if eligible(m)]
+    if not convs:
+        raise ValueError(f"{what}: the model has no convolution with channel counts that are multiples of 32")
+    for c in convs:
+        require_gpu(c.kernel, f"the model of {what}")
+    return convs
+
+
+def _pack(base, buf, sources, layout, total_tiles, what):
+    """one launch of lidog_pack_kernels_bf16: sources[i] (fp32, contiguous) -> layout[i] of buf; source offsets are taken
+    afresh (an optimiser may have moved the parameters into its flat buffer since the last call)"""
+    for k in sources:
+        if k.device != buf.device or k.dtype != torch.float32 or not k.is_contiguous():
+            raise ValueError(f"{what}: kernels must be contiguous float32 tensors on the table's device")
+    desc = [((k.data_ptr() - base.data_ptr()) // 4,) + tuple(row) for k, row in zip(sources, layout)]
+    desc = torch.tensor(desc, dtype=torch.int64).to(buf.device)
+    with torch.cuda.device(buf.device):
+        call("lidog_pack_kernels_bf16", ptr(base), ptr(buf), ptr(desc), len(sources), total_tiles)
+
+
 class Bf16Kernels:
     """bf16 [K, Cout, Cin] copies of the kernels [K, Cin, Cout] of every eligible convolution of `model` (transposed:
     a lane's eight k-values of the B operand are 16 contiguous bytes), written by ONE launch of lidog_pack_kernels_bf16
     on construction and on every refresh()."""
 
     def __init__(self, model):
-        self.convs = [m for m in model.modules() if eligible(m)]
-        if not self.convs:
-            raise ValueError("Bf16Kernels: the model has no convolution with channel counts that are multiples of 32")
-        for c in self.convs:
-            require_gpu(c.kernel, "the model of a bf16 evaluation")
-        off, tiles, self._layout, self._views = 0, 0, [], {}
-        for c in self.convs:
-            K, Cin, Cout = c.kernel_volume, c.in_channels, c.out_channels
-            self._layout.append((off, K, Cin, Cout, tiles))
-            off += K * Cin * Cout
-            tiles += K * (Cin // 32) * (Cout // 32)
-        self.total_tiles = tiles
+        self.convs = _eligible_convs(model, "a bf16 evaluation")
+        self._layout, off, self.total_tiles = table_layout(
+            [(c.kernel_volume, c.in_channels, c.out_channels) for c in self.convs])
         self.buf = torch.empty(off, dtype=torch.bfloat16, device=self.convs[0].kernel.device)
-        for c, (o, K, Cin, Cout, _) in zip(self.convs, self._layout):
-            self._views[c] = self.buf[o:o + K * Cin * Cout].view(K, Cout, Cin)
+        self._views = {c: self.buf[o:o + K * Cin * Cout].view(K, Cout, Cin)
+                       for c, (o, K, Cin, Cout, _) in zip(self.convs, self._layout)}
         self.packs = 0
         self.refresh()
 
     def refresh(self):
-        """pack the weights as they are now (source offsets are taken afresh: an optimiser may have moved the parameters
-        into its flat buffer since the last call)"""
+        """pack the weights as they are now"""
         kernels = [c.kernel.detach() for c in self.convs]
-        for k in kernels:
-            if k.device != self.buf.device or k.dtype != torch.float32 or not k.is_contiguous():
-                raise ValueError("Bf16Kernels: kernels must be contiguous float32 tensors on the table's device")
-        base = kernels[0]
-        desc = [((k.data_ptr() - base.data_ptr()) // 4, o, K, Cin, Cout, t)
-                for k, (o, K, Cin, Cout, t) in zip(kernels, self._layout)]
-        desc = torch.tensor(desc, dtype=torch.int64).to(self.buf.device)
-        with torch.cuda.device(self.buf.device):
-            call("lidog_pack_kernels_bf16", ptr(base), ptr(self.buf), ptr(desc), len(kernels), self.total_tiles)
+        _pack(kernels[0], self.buf, kernels, self._layout, self.total_tiles, "Bf16Kernels")
         self.packs += 1
 
     def get(self, conv):
@@ -84,8 +124,58 @@ class Bf16Kernels:
         return self._views.get(conv)
 
 
+class Bf16Training:
+    """The two bf16 operand tables of a mixed-precision training step over the eligible convolutions of `model`:
+    forward   [K, Cout, Cin]: the pack of the kernel W [K, Cin, Cout], as Bf16Kernels;
+    dgrad     [K, Cin, Cout]: the pack of the transposed kernel [K, Cout, Cin] that optim.TransposedKernels keeps for the
+              fp32 data gradient (the B operand of the gathered GEMM over the exchanged map).
+    Both are written by ONE launch of lidog_pack_kernels_bf16 (one descriptor table, source offsets relative to the
+    first kernel).  The model's optimiser must exist: the table reads its transposed copy, so refresh() belongs AFTER
+    TransposedKernels.refresh() -- i.e. after every optimiser step (_Step.training_step does that), and after
+    load_state_dict / resume, which refresh the transposed copy: stale() sees that and bf16_training packs again."""
+
+    def __init__(self, model):
+        self.convs = _eligible_convs(model, "bf16 training")
+        owners = {id(getattr(c.kernel, "_wt_owner", None)) for c in self.convs}
+        self.transposed = getattr(self.convs[0].kernel, "_wt_owner", None)
+        if self.transposed is None or len(owners) != 1:
+            raise ValueError("Bf16Training: build the model's optimiser first (the data-gradient table is packed from "
+                             "the transposed kernels it keeps, optim.TransposedKernels)")
+        self._fwd, self._dgrad, off, self.total_tiles = training_layout(
+            [(c.kernel_volume, c.in_channels, c.out_channels) for c in self.convs])
+        self.buf = torch.empty(off, dtype=torch.bfloat16, device=self.convs[0].kernel.device)
+        self._pairs = {}
+        for c, (of, K, Cin, Cout, _), (od, _, _, _, _) in zip(self.convs, self._fwd, self._dgrad):
+            n = K * Cin * Cout
+            self._pairs[c] = (self.buf[of:of + n].view(K, Cout, Cin), self.buf[od:od + n].view(K, Cin, Cout))
+        self.packs = 0
+        self.refresh()
+
+    def refresh(self):
+        """pack the weights and their transposed copies as they are now"""
+        kernels = [c.kernel.detach() for c in self.convs]
+        _pack(kernels[0], self.buf, kernels + [c.kernel._wt_view for c in self.convs], self._fwd + self._dgrad,
+              self.total_tiles, "Bf16Training")
+        self._seen = self.transposed.generation
+        self.packs += 1
+
+    def stale(self):
+        """the transposed copy was refreshed since the last pack (the weights were loaded or stepped without refresh())"""
+        return self._seen != self.transposed.generation
+
+    def pair(self, conv):
+        """(forward operand, data-gradient operand) of `conv`, or None when it is not in the table"""
+        return self._pairs.get(conv)
+
+    def get(self, conv):
+        """the forward operand of `conv` (what a no_grad call inside a training context takes), or None"""
+        p = self._pairs.get(conv)
+        return p[0] if p is not None else None
+
+
 class Bf16Context:
     """what bf16_inference yields: the table and the routes the convolutions took while it was current"""
+    training = False
 
     def __init__(self, kernels):
         self.kernels = kernels
@@ -97,10 +187,20 @@ class Bf16Context:
         self.routes.setdefault(conv, set()).add(route)
 
 
+class Bf16TrainContext(Bf16Context):
+    """what bf16_training yields: `kernels` is a Bf16Training; grad-enabled calls of the eligible convolutions take the
+    bf16 forward, data-gradient and weight-gradient kernels (the backward pass counts on the context its forward saw)"""
+    training = True
+
+
 # the routes of Bf16Context.launches
 OS_BN, GEMM_REDUCE_BN, GEMM_REDUCE, GEMM_DIRECT, FP32 = \
     "os_bn_bf16", "gemm_bf16+reduce_rows_bn", "gemm_bf16+reduce_rows", "gemm_bf16", "fp32"
 BF16_ROUTES = (OS_BN, GEMM_REDUCE_BN, GEMM_REDUCE, GEMM_DIRECT)
+# grad-enabled calls under a Bf16TrainContext (an fp32 convolution is counted once, as FP32, by its forward pass)
+FWD_DIRECT, FWD_REDUCE, DGRAD_DIRECT, DGRAD_REDUCE, WGRAD = \
+    "fwd:gemm_bf16", "fwd:gemm_bf16+reduce_rows", "dgrad:gemm_bf16", "dgrad:gemm_bf16+reduce_rows", "wgrad:wgrad_bf16"
+TRAIN_FWD_ROUTES, TRAIN_DGRAD_ROUTES = (FWD_DIRECT, FWD_REDUCE), (DGRAD_DIRECT, DGRAD_REDUCE)
 
 
 def current():
@@ -122,6 +222,27 @@ def bf16_inference(model, kernels=None):
     """Context manager: the eligible convolutions of `model` that run with autograd disabled inside it take the bf16
     kernels.  `kernels`: a Bf16Kernels of the model packed earlier (None: pack now).  Yields a Bf16Context."""
     return _set(Bf16Context(kernels if kernels is not None else Bf16Kernels(model)))
+
+
+def bf16_training(model, table=None):
+    """Context manager: grad-enabled calls of the eligible convolutions of `model` inside it run forward, data gradient
+    and weight gradient on the bf16 kernels, and the trunk executor declines.  `table`: a Bf16Training of the model (None:
+    pack now); one that went stale is packed again first.  Yields a Bf16TrainContext."""
+    if table is None:
+        table = Bf16Training(model)
+    elif table.stale():
+        table.refresh()
+    return _set(Bf16TrainContext(table))
+
+
+def check_single_rank(what="precision='bf16' training"):
+    """bf16 training steps go down the operator path; with more than one rank that is the SyncBatchNorm operator path,
+    which is not validated in this mode"""
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        raise NotImplementedError(
+            f"{what} with {dist.get_world_size()} ranks: a bf16 step leaves the trunk executor for the operator path, "
+            "and multi-rank training waits for the executor follow-up (csrc/trunk.hip learning the bf16 kernels)")
 
 
 def fp32_inference():

@@ -529,17 +529,20 @@ def build_model(kind="MinkUNet34BEV", bound_2d=50.0, in_channels=1, out_channels
 
 
 def build_step(model, kind="MinkUNet34BEV", optimizer="Adam", lr=1e-3, scheduler=None, weight_decay=1e-4,
-               momentum=0.98, warmup_epochs=0, source_weights=(0.5, 0.5), num_classes=7, ignore_label=-1, num_sources=1):
+               momentum=0.98, warmup_epochs=0, source_weights=(0.5, 0.5), num_classes=7, ignore_label=-1, num_sources=1,
+               precision=None):
     """SyncBN conversion when data-parallel (train_lidog.py:227-231), optimiser + scheduler
     (trainer_lighting_2d.py:349-394), step object (PLTTrainer2D / PLTRobustNet / PLTTrainer, on one or two sources).
-    Returns (model, step, scheduler)."""
+    `precision`: the training steps' (trainer._Step).  Returns (model, step, scheduler)."""
     if num_sources not in (1, 2):
         raise NotImplementedError(f"{num_sources} sources (the reference takes one or two)")
+    if _precision.resolve(precision):
+        _precision.check_single_rank()
     model = setup_data_parallel(model)
     model.train()
     opt = make_optimizer(optimizer, model, lr, weight_decay=weight_decay, momentum=momentum)
     sched = make_scheduler(scheduler, opt)
-    kw = dict(source_weights=source_weights, ignore_label=ignore_label, num_sources=num_sources)
+    kw = dict(source_weights=source_weights, ignore_label=ignore_label, num_sources=num_sources, precision=precision)
     if kind == "MinkUNet34BEV":
         step = LiDOGStep(model, opt, warmup_epochs=warmup_epochs, num_classes=num_classes, **kw)
     elif kind == "MinkUNet34Robust":
@@ -575,20 +578,26 @@ class Fit:
                  momentum=0.98, check_val_every_n_epoch=5, num_sanity_val_steps=2, save_dir=None, seed=1234,
                  train_data=None, val_data=None, shuffle=True, resume=None, auto_resume=False, prefetch=True,
                  device="cuda", log=None, state_dict=None, num_sources=None, log_every_n_steps=0, metric_sources=None,
-                 val_precision=None):
-        """`train_data` with `num_sources = 2` (MultiSynthScans) trains on two sources; `val_data` may then be a dict
+                 val_precision=None, precision=None):
+        """`precision`: None / "fp32" (the fp32 step, exactly what runs without it) or "bf16": mixed-precision training
+        steps (lidog_amd.precision: bf16 operands in the eligible sparse convolutions' forward, data-gradient and
+        weight-gradient kernels, everything else -- master weights, gradients, optimiser state, checkpoints -- fp32; the
+        step runs on the operator path, not the trunk executor; one rank only).  Independent of `val_precision`.
+        `train_data` with `num_sources = 2` (MultiSynthScans) trains on two sources; `val_data` may then be a dict
         {source name: dataset}: every source is validated on its own (the list of loaders of train_lidog.py:186-190),
         the results keyed by name.
         `val_precision`: None / "fp32" / "bf16" (lidog_amd.precision): the validation passes' convolutions; a bf16 pass
-        packs the weights once, when it starts.  Training steps are fp32 whatever it says.
+        packs the weights once, when it starts.  It does not touch the training steps.
         `log_every_n_steps` N > 0 (the reference's entry scripts: 50): every step whose number is a multiple of N is
         recorded by a metrics.StepMetrics (per-class IoU and occurrences of the point predictions and of every BEV level,
         losses, lr; nothing is launched on the other steps), read at the end of every epoch into the history record's
         `metrics` and, with `save_dir`, appended by rank 0 to <save_dir>/metrics.jsonl together with the validation
         results.  0: off.  `metric_sources`: the source names of the keys (default: training_source_names)"""
+        if _precision.resolve(precision):       # before anything is built
+            _precision.check_single_rank("Fit(precision='bf16')")
         self.rank, self.world = _rank_world()
         _precision.resolve(val_precision)
-        self.val_precision = val_precision
+        self.val_precision, self.precision = val_precision, precision
         self.kind, self.batch_size, self.epochs = model_kind, batch_size, epochs
         self.check_val, self.sanity = check_val_every_n_epoch, num_sanity_val_steps
         self.save_dir, self.seed, self.shuffle, self.prefetch = save_dir, seed, shuffle, prefetch
@@ -604,7 +613,7 @@ class Fit:
             num_sources = getattr(self.train_data, "num_sources", 1)
         self.model, self.step, self.sched = build_step(
             model, model_kind, optimizer, lr, scheduler, weight_decay, momentum, warmup_epochs, source_weights,
-            num_sources=num_sources)
+            num_sources=num_sources, precision=precision)
         self.opt = self.step.opt
         self.epoch, self.global_step = 0, 0
         self.history = []
@@ -796,7 +805,12 @@ def parse_args(argv=None):
                          "append them to <save-dir>/metrics.jsonl (the reference's entry scripts: 50; default 0: off)")
     ap.add_argument("--val-precision", default=argparse.SUPPRESS, choices=["fp32", "bf16"],
                     help="precision of the validation passes' convolutions (default fp32; bf16: lidog_amd.precision, the "
-                         "weights are packed once per validation pass); training is always fp32")
+                         "weights are packed once per validation pass); independent of --precision")
+    ap.add_argument("--precision", default=argparse.SUPPRESS, choices=["fp32", "bf16"],
+                    help="precision of the training steps (default fp32; bf16: the sparse convolutions with channel "
+                         "counts that are multiples of 32 run forward, data gradient and weight gradient on bf16 operands "
+                         "with fp32 accumulation, lidog_amd.precision; weights, gradients, optimiser state and "
+                         "checkpoints stay fp32; one GPU)")
     scans.add_file_arguments(ap, "--files", "train on")
     a = ap.parse_args(argv)
     source_augment = getattr(a, "source_augment", None)
@@ -882,6 +896,11 @@ def val_precision_of(a):
     return getattr(a, "val_precision", "fp32")
 
 
+def precision_of(a):
+    """--precision of parsed arguments (None, the fp32 step as it always ran, when it was not given)"""
+    return getattr(a, "precision", None)
+
+
 def main(argv=None):
     a = parse_args(argv)
     fit = _fit_from_args(a)
@@ -902,7 +921,7 @@ def _fit_from_args(a):
                source_weights=tuple(a.source_weights), check_val_every_n_epoch=a.check_val_every_n_epoch,
                save_dir=a.save_dir, seed=a.seed, train_data=train, val_data=val, resume=a.resume,
                auto_resume=a.auto_resume, log_every_n_steps=getattr(a, "log_every_n_steps", 0),
-               val_precision=val_precision_of(a))
+               val_precision=val_precision_of(a), precision=precision_of(a))
 
 
 def _data_from_args(a):

@@ -14,12 +14,14 @@ One process per GPU; gradients live in ONE contiguous fp32 buffer that is all-re
 a few large buckets launched as soon as their last gradient is produced (overlapping the rest of
 backward), then consumed by a single fused Adam kernel.
 """
+import contextlib as _contextlib
 import os as _os
 
 import torch
 import torch.distributed as dist
 
 from . import me as ME
+from . import precision as _precision
 from .losses import DICELoss, SoftDICELoss, iw_loss
 from .optim import (FlatAdam, FlatParams, FlatSGD, GradientBuckets, make_optimizer, make_scheduler,  # noqa: F401
                     shard_indices)
@@ -35,17 +37,28 @@ class _Step:
     Subclasses define `_losses(batch, epoch) -> (total, {name: loss}, [semantic output of each source])`.
     `metrics`: a lidog_amd.metrics.StepMetrics, or None (the default).  When set, training_step hands it the logits and
     labels of every source (LiDOGStep: and of every BEV level) and the step's losses; the step computes and returns
-    what it does without."""
+    what it does without.
+    `precision`: None / "fp32" (the fp32 step) or "bf16": the eligible sparse convolutions run forward, data gradient
+    and weight gradient on the bf16 matrix instruction (lidog_amd.precision; fp32 master weights, gradients and optimiser
+    state), the step leaves the trunk executor for the operator path, and the packed operand tables (`bf16`, a
+    precision.Bf16Training) are refreshed after every optimiser step.  `precision_ctx`: the context of the last bf16
+    step (its `.launches` count the routes).  One rank only."""
 
     metrics = None
+    bf16 = None                         # the packed tables of precision="bf16"
+    precision_ctx = None
     metric_losses = ("sem_loss",)       # the loss names of one source, in the order of the step's loss dict
     metric_bev = False                  # the BEV levels are logged too
     metric_count_ignored = True         # jaccard_score over all rows (the LiDOG trainers filter label == -1 first)
 
-    def __init__(self, model, optimizer, num_sources=1, ignore_label=-1):
+    def __init__(self, model, optimizer, num_sources=1, ignore_label=-1, precision=None):
         if num_sources not in (1, 2):
             raise NotImplementedError(f"{num_sources} sources (the reference takes one or two)")
         self.model, self.opt, self.num_sources = model, optimizer, num_sources
+        self.precision = precision
+        if _precision.resolve(precision):
+            _precision.check_single_rank()
+            self.bf16 = _precision.Bf16Training(model)
         self.sem_criterion = SoftDICELoss(ignore_label=ignore_label)
         self._prepared = {}
         if num_sources == 2:
@@ -85,6 +98,16 @@ class _Step:
             return {k: v[0] for k, v in losses.items()}
         return {f"{k}{s}": v[s] for k, v in losses.items() for s in (0, 1)}
 
+    @_contextlib.contextmanager
+    def _scope(self):
+        """the bf16 training context of a precision="bf16" step (a stale table is packed again first); else nothing"""
+        if self.bf16 is None:
+            yield None
+        else:
+            with _precision.bf16_training(self.model, self.bf16) as ctx:
+                self.precision_ctx = ctx
+                yield ctx
+
     def _forward(self, batch, epoch):
         total, losses, outs = self._losses(batch, epoch)
         # "_TrunkFnBackward": the trunk executor took the pass
@@ -94,7 +117,8 @@ class _Step:
 
     def forward_loss(self, batch, epoch=0):
         """one source: (total, *losses, output); two: {"loss": total, **losses, "outputs": [output0, output1]}"""
-        total, losses, outs = self._forward(batch, epoch)
+        with self._scope():
+            total, losses, outs = self._forward(batch, epoch)
         if self.num_sources == 2:
             return {"loss": total, **losses, "outputs": outs}
         return (total, *losses.values(), outs[0])
@@ -103,14 +127,17 @@ class _Step:
         """`prefetch`: the batch of the NEXT call (its coordinate maps are built while this step still runs on
         the GPU); `prefetch_ready`: event after which its coordinates are valid (None: everything queued so far).
         Returns the detached total and losses."""
-        total, losses, outs = self._forward(batch, epoch)
-        ready = self.metrics.mark() if self.metrics is not None else None
-        self.opt.zero_grad()
-        total.backward()
-        self.opt.step()
-        if ready is not None:       # here the host is ahead of the device: most of the metrics' host time hides (DESIGN 3q)
-            self._record_metrics(batch, total, losses, outs, ready)
-        self.prefetch_maps(prefetch, prefetch_ready)
+        with self._scope():
+            total, losses, outs = self._forward(batch, epoch)
+            ready = self.metrics.mark() if self.metrics is not None else None
+            self.opt.zero_grad()
+            total.backward()
+            self.opt.step()
+            if self.bf16 is not None:   # behind the step's TransposedKernels.refresh(): the dgrad table reads that copy
+                self.bf16.refresh()
+            if ready is not None:   # here the host is ahead of the device: most of the metrics' host time hides (DESIGN 3q)
+                self._record_metrics(batch, total, losses, outs, ready)
+            self.prefetch_maps(prefetch, prefetch_ready)     # inside the scope: work items cut for the bf16 kernel
         _check_transport(self)
         return {k: (v.detach() if torch.is_tensor(v) else v) for k, v in {"loss": total, **losses}.items()}
 
@@ -154,8 +181,8 @@ class LiDOGStep(_Step):
     metric_count_ignored = False
 
     def __init__(self, model, optimizer, source_weights=(0.5, 0.5), warmup_epochs=0, num_classes=7, ignore_label=-1,
-                 num_sources=1):
-        super().__init__(model, optimizer, num_sources, ignore_label)
+                 num_sources=1, precision=None):
+        super().__init__(model, optimizer, num_sources, ignore_label, precision)
         self.w, self.warmup, self.nc = source_weights, warmup_epochs, num_classes
         self.bev_criterion = DICELoss(ignore_label=ignore_label)
 
@@ -195,8 +222,8 @@ class SourceStep(_Step):
     """PLTTrainer.training_step (train_source.py / Mix3D; MinkUNet34 and MinkUNet34IBN): SoftDICE only.
     One source: total = sem, the only loss returned; two sources (trainer_lighting.py:92-116): w0 * sem0 + w1 * sem1."""
 
-    def __init__(self, model, optimizer, source_weights=(0.5, 0.5), ignore_label=-1, num_sources=1):
-        super().__init__(model, optimizer, num_sources, ignore_label)
+    def __init__(self, model, optimizer, source_weights=(0.5, 0.5), ignore_label=-1, num_sources=1, precision=None):
+        super().__init__(model, optimizer, num_sources, ignore_label, precision)
         self.w = source_weights
 
     def _losses(self, batch, epoch):
@@ -216,8 +243,9 @@ class RobustStep(_Step):
 
     metric_losses = ("sem_loss", "aux_loss")
 
-    def __init__(self, model, optimizer, source_weights=(0.5, 0.5), aux_epoch=5, ignore_label=-1, num_sources=1):
-        super().__init__(model, optimizer, num_sources, ignore_label)
+    def __init__(self, model, optimizer, source_weights=(0.5, 0.5), aux_epoch=5, ignore_label=-1, num_sources=1,
+                 precision=None):
+        super().__init__(model, optimizer, num_sources, ignore_label, precision)
         self.w, self.aux_epoch = source_weights, aux_epoch
 
     def _losses(self, batch, epoch):

@@ -19,7 +19,7 @@ import weakref
 import numpy as np
 import torch
 
-from . import _lib, me as ME
+from . import _lib, me as ME, precision as _precision
 from ._lib import call, call_on
 
 ENABLED = os.environ.get("LIDOG_TRUNK_EXEC", "1") != "0"
@@ -258,6 +258,9 @@ def _addr(t):
 
 def _eligible(model, prog, x):
     if not (ENABLED and prog is not None and torch.is_grad_enabled() and model.training):
+        return False
+    pctx = _precision.current()
+    if pctx is not None and pctx.training:      # the executor launches the fp32 kernels from C: bf16 steps decline it
         return False
     f = x.F
     if not (f.is_cuda and f.dtype == torch.float32 and not f.requires_grad and x.coordinate_map_key == 1):

@@ -15,7 +15,6 @@ Mirrors the surface of MinkowskiEngine 0.5.4 that LiDOG's models and pipelines u
 is no CPU path (tensors on the CPU raise).
 """
 import ctypes
-import functools
 import math
 import os
 import sys
@@ -724,8 +723,8 @@ def _gemm(A, gather, B, bias, m, Cin, Cout, out, scatter, tiles=None):
          n_tiles, Cin, Cout, ptr(out), ptr(scatter), A.shape[0])
 
 
-def _gemm_bf16(A, gather, B, bias, m, Cin, Cout, out, scatter, wp=None):
-    """_gemm's arguments on lidog_sconv_gemm_bf16; `wp`: the packed bf16 operand [K, Cout, Cin] that stands for B"""
+def _gemm_bf16(A, gather, wp, bias, m, Cin, Cout, out, scatter):
+    """_gemm's arguments on lidog_sconv_gemm_bf16; `wp`: the packed bf16 operand [K, Cout, Cin] in B's place"""
     call("lidog_sconv_gemm_bf16", ptr(A), ptr(gather), ptr(wp), ptr(bias), ptr(m.tiles[0]), ptr(m.tiles[1]),
          ptr(m.tiles[2]), m.n_tiles, Cin, Cout, ptr(out), ptr(scatter))
 
@@ -756,18 +755,14 @@ _WGRAD_FIT = int(os.environ.get("LIDOG_WGRAD_FIT", "-1"))
 _wgrad_slots_cache = {}
 
 
-def _wgrad_slots(Cin, Cout):
-    key = (Cin, Cout)
+def _wgrad_slots(Cin, Cout, bf16=False):
+    """resident workgroups of lidog_sconv_wgrad, or (`bf16`) of lidog_sconv_wgrad_bf16: another kernel, with its own
+    occupancy"""
+    key = (Cin, Cout, bf16)
     if key not in _wgrad_slots_cache:
-        _wgrad_slots_cache[key] = int(_lib.load().lidog_sconv_wgrad_slots(Cin, Cout, 0))
-    return _wgrad_slots_cache[key]
-
-
-def _wgrad_slots_bf16(Cin, Cout):
-    """the same for lidog_sconv_wgrad_bf16: another kernel, with its own occupancy"""
-    key = (Cin, Cout, "bf16")
-    if key not in _wgrad_slots_cache:
-        _wgrad_slots_cache[key] = int(_lib.load().lidog_sconv_wgrad_bf16_slots(Cin, Cout))
+        L = _lib.load()
+        _wgrad_slots_cache[key] = int(L.lidog_sconv_wgrad_bf16_slots(Cin, Cout) if bf16 else
+                                      L.lidog_sconv_wgrad_slots(Cin, Cout, 0))
     return _wgrad_slots_cache[key]
 
 
@@ -790,7 +785,7 @@ def _wgrad_chunk(k_off_host, Cin, Cout, bf16=False):
     target = max(1, blocks // tiles)
     max_items = max(1, (192 << 20) // (4 * Cin * Cout))             # at most ~192 MB of partial slots
     fit = _WGRAD_FIT if _WGRAD_FIT >= 0 else (0 if _WgradLane.enabled else 1)
-    slots = (_wgrad_slots_bf16(Cin, Cout) if bf16 else _wgrad_slots(Cin, Cout)) if fit else 0
+    slots = _wgrad_slots(Cin, Cout, bf16) if fit else 0
     if slots and blocks > slots:
         # Every offset ends in a partial item (P / chunk items are really ~K / 2 more) and the swept optimum is not a
         # multiple of the slots: 2 048 wanted on 768 slots = 2.7 rounds.  Cut so that the launch is `rounds` whole rounds.
@@ -854,6 +849,111 @@ def _os_rows(m, swap, Cin, Cout):
     return m.sorted()
 
 
+def _stats_tail(rows, C, dev, sync, eps, momentum, running_mean, running_var):
+    """(the trailing arguments of lidog_bn_stats, lidog_sconv_reduce_rows_stats and lidog_sconv_os_stats, mean, invstd)"""
+    if sync:    # the sums (and the row count behind them) still have to be all-reduced
+        return (rows, 0.0, 0.0, None, None, None, None), None, None
+    # local BatchNorm: mean / invstd / running statistics finalised in the same launch
+    mean = torch.empty(C, dtype=torch.float32, device=dev)
+    invstd = torch.empty(C, dtype=torch.float32, device=dev)
+    return (rows, float(eps), float(momentum), ptr(mean), ptr(invstd), ptr(running_mean), ptr(running_var)), mean, invstd
+
+
+def _conv_rows(x, B, m, swap, Cin, Cout, mirrored=False, direct=False, bias=None, bf16=False, add=None, stats=None,
+               bn=None, queued=lambda: None):
+    """out = sum_k x[gather_k] . B[k] (+ bias) over the rule book `m`: THE place that chooses the kernels of a sparse
+    convolution.  Returns (out, route); route: the precision.BF16_ROUTES name of what ran, precision.FP32 for fp32.
+    `swap`: the map is used with in/out exchanged (transposed convolution).  `mirrored`: the data-gradient direction:
+    x is the output's gradient, B the transposed kernel, Cin / Cout exchanged by the caller, the result rows are the
+    input's.  `direct`: every result row has exactly one pair (1x1; k2 s2 on its single side) -> the GEMM writes
+    straight into `out`.  `B`: fp32 [K, Cin, Cout], or with `bf16` the packed operand [K, Cout, Cin]:
+    lidog_sconv_gemm_bf16 replaces the fp32 GEMM, the reduction pass stays the fp32 one.
+    At most one epilogue:
+      `add`    [rows, Cout], the residual branch's gradient: added by the reduction pass or the output-stationary
+               kernel where there is one, else by a pass of its own;
+      `stats`  StatsRequest of the BatchNorm that follows: where the output goes through the reduction pass or the
+               output-stationary kernel, that also produces the fp64 sums of `out` (and, for a local BatchNorm, mean /
+               invstd / running statistics), returned in the request;
+      `bn`     (running_mean, invstd, weight, bias, residual or None, relu) of an evaluation-mode BatchNorm (+ residual
+               + ReLU) applied by the same two kernels -- no round trip of the convolution output.
+    `queued`: called once the matrix kernel is queued (the weight gradient forks there, see _WgradLane)."""
+    identity = isinstance(m, _IdentityMap)
+    if identity:
+        gather = scatter = None
+        n, side = m.n_out, "out"
+    elif swap == mirrored:
+        gather, scatter, n, side = m.pair_in, m.pair_out, m.n_out, "out"
+    else:       # transposed convolution, or the data gradient of a plain one: the map with in/out exchanged
+        gather, scatter, n, side = m.pair_out, m.pair_in, m.n_in, "in"
+    K, dev = m.K, x.device
+    if bf16:
+        require_gpu(x, "features")
+    gemm = _gemm_bf16 if bf16 else _gemm
+    out = torch.empty((n, Cout), dtype=torch.float32, device=dev)
+    if bn is not None:
+        bn_args = tuple(ptr(t) for t in bn[:5]) + (1 if bn[5] else 0, ptr(out))
+
+    def stats_args(ws_doubles):
+        """out, sums, workspace and trailing arguments of a kernel with the statistics epilogue; fills the request"""
+        stats.sums = stats.sums_out if stats.sums_out is not None else \
+            torch.empty(2 * Cout + 1, dtype=torch.float64, device=dev)
+        ws = torch.empty(ws_doubles, dtype=torch.float64, device=dev)
+        tail, stats.mean, stats.invstd = _stats_tail(float(n), Cout, dev, stats.sync, stats.eps, stats.momentum,
+                                                     stats.running_mean, stats.running_var)
+        return (ptr(out), ptr(stats.sums), ptr(ws)) + tail
+
+    if direct:
+        gemm(x, gather, B, bias, m, Cin, Cout, out, scatter)
+        queued()
+        route = _precision.GEMM_DIRECT
+    elif Cin == 1 and not (mirrored or swap or bf16) and bn is None and Cout in (16, 32, 64) and \
+            K * Cout * 4 <= 48 * 1024 and m.nbr is not None:
+        # the stem: straight from the neighbour table, no product rows (bit-identical to the two-pass path); the
+        # BatchNorm statistics of its 32-channel output are then one small pass of their own.  Forward only: a data
+        # gradient whose forward Cout is 1 arrives here with Cin = 1 too
+        call("lidog_sconv_cin1", ptr(x), ptr(m.nbr), ptr(B), ptr(bias), n, K, Cout, ptr(out))
+        route = _precision.FP32
+    elif (not bf16 or bn is not None) and _os_rows(m, swap, Cin, Cout) is not None:
+        # sparse symmetric 3^3 map: output-stationary kernel, no product rows (bit-identical convolution; the
+        # statistics are summed per tile instead of per row block); mirrored: the data gradient over the mirrored
+        # offsets of the same sorted rows (csrc/sconv_os.hip).  The epilogues are the reduction pass's (same bits).
+        # Its bf16 form has the BatchNorm epilogue only -- no statistics, no mirrored offsets: any other bf16
+        # convolution takes the two-pass route
+        perm, wmask, order = _os_rows(m, swap, Cin, Cout)
+        head = (ptr(x), ptr(m.nbr), n, K, ptr(perm), ptr(wmask), ptr(order), ptr(B))
+        if bn is not None:
+            call("lidog_sconv_os_bn_bf16" if bf16 else "lidog_sconv_os_bn", *head, ptr(bias), Cin, Cout, *bn_args)
+        elif stats is not None:
+            call("lidog_sconv_os_stats", *head, ptr(bias), Cin, Cout,
+                 *stats_args(_lib.load().lidog_sconv_os_stats_ws(n, Cout)))
+        else:
+            call("lidog_sconv_os", *head, 1 if mirrored else 0, ptr(bias), ptr(add), Cin, Cout, ptr(out))
+            add = None
+        queued()
+        route = _precision.OS_BN
+    else:
+        T = torch.empty((m.P, Cout), dtype=torch.float32, device=dev)
+        gemm(x, gather, B, None, m, Cin, Cout, T, None)
+        queued()
+        if Cout % 4 == 0:
+            row_ptr, row_list = m.rows(side)
+            head = (ptr(T), ptr(row_ptr), ptr(row_list), n, Cout, ptr(bias))
+        if bn is not None:      # (its callers send multiples of 4 only)
+            call("lidog_sconv_reduce_rows_bn", *head, *bn_args)
+        elif stats is not None and Cout % 4 == 0 and Cout <= 1024:
+            call("lidog_sconv_reduce_rows_stats", *head, *stats_args(_lib.load().lidog_sconv_reduce_stats_ws(n, Cout)))
+        elif Cout % 4 == 0:
+            call("lidog_sconv_reduce_rows", *head, ptr(add), ptr(out))
+            add = None
+        else:   # the dense position table [K, rows]; a map whose rows were sorted builds it on this first request
+            call("lidog_sconv_reduce", ptr(T), ptr(m.pos_out if side == "out" else m.pos_in), n, K, Cout, ptr(bias),
+                 None, ptr(out))
+        route = _precision.GEMM_REDUCE_BN if bn is not None else _precision.GEMM_REDUCE
+    if add is not None:     # no reduction pass took it (1x1, k2 s2, channel counts that are no multiple of 4)
+        out = out + add
+    return out, route if bf16 else _precision.FP32
+
+
 class _SparseConvFn(torch.autograd.Function):
     """out = conv(x) over a rule book.  `single_out`: every output row has exactly one pair (transposed
     k2 s2) -> the GEMM scatters straight into `out`; `single_in`: every input row has exactly one pair
@@ -861,89 +961,17 @@ class _SparseConvFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, W, bias, m, swap, single_out, single_in, stats=None, skip=False, bf=None):
-        """`stats`: optional StatsRequest of the BatchNorm that follows; when the output goes through the reduction
-        pass, that pass also produces the fp64 sums of `out` (and, for a local BatchNorm, mean / invstd / running
-        statistics), returned in the request.
+        """`stats`: optional StatsRequest of the BatchNorm that follows (_conv_rows fills it where it can).
         `bf`: None, or (precision.Bf16TrainContext, module, packed forward operand [K, Cout, Cin], packed data-gradient
-        operand [K, Cin, Cout]) of a mixed-precision training step: lidog_sconv_gemm_bf16 replaces the fp32 GEMM on the
-        identity, single-out and two-pass routes (a 3^3 convolution that would take the output-stationary kernel takes
-        the two-pass route: its bf16 form has no statistics epilogue and no mirrored data gradient); the reduction pass,
-        and with it the BatchNorm statistics, is the fp32 one.  backward() follows with the bf16 data and weight
-        gradients."""
+        operand [K, Cin, Cout]) of a mixed-precision training step: forward on the bf16 GEMM; backward() follows with
+        the bf16 data and weight gradients."""
         x = x.contiguous()
         W3 = W.contiguous().view(m.K, W.shape[-2], W.shape[-1])
         K, Cin, Cout = W3.shape
-        identity = isinstance(m, _IdentityMap)
-        if identity:
-            g_in = g_out = None
-            n_out = m.n_out
-        elif not swap:
-            g_in, g_out, pos_o, n_out = m.pair_in, m.pair_out, m.pos_out, m.n_out
-        else:  # transposed convolution: the forward map used with in/out exchanged
-            g_in, g_out, pos_o, n_out = m.pair_out, m.pair_in, m.pos_in, m.n_in
-        out = torch.empty((n_out, Cout), dtype=torch.float32, device=x.device)
+        out, route = _conv_rows(x, W3 if bf is None else bf[2], m, swap, Cin, Cout, bias=bias, bf16=bf is not None,
+                                direct=isinstance(m, _IdentityMap) or single_out, stats=stats)
         if bf is not None:
-            require_gpu(x, "features")
-            gemm = functools.partial(_gemm_bf16, wp=bf[2])
-            bf[0].count(bf[1], _precision.FWD_DIRECT if identity or single_out else _precision.FWD_REDUCE)
-        else:
-            gemm = _gemm
-        if identity:
-            gemm(x, None, W3, bias, m, Cin, Cout, out, None)
-        elif single_out:
-            gemm(x, g_in, W3, bias, m, Cin, Cout, out, g_out)
-        elif Cin == 1 and not swap and Cout in (16, 32, 64) and K * Cout * 4 <= 48 * 1024 and m.nbr is not None:
-            # the stem: straight from the neighbour table, no product rows (bit-identical to the two-pass path); the
-            # BatchNorm statistics of its 32-channel output are then one small pass of their own
-            call("lidog_sconv_cin1", ptr(x), ptr(m.nbr), ptr(W3), ptr(bias), n_out, K, Cout, ptr(out))
-        elif bf is None and _os_rows(m, swap, Cin, Cout) is not None:
-            # sparse symmetric 3^3 map: output-stationary kernel, no product rows (bit-identical convolution; the
-            # statistics are summed per tile instead of per row block)
-            perm, wmask, order = _os_rows(m, swap, Cin, Cout)
-            dev = x.device
-            if stats is not None:
-                sums = stats.sums_out if stats.sums_out is not None else \
-                    torch.empty(2 * Cout + 1, dtype=torch.float64, device=dev)
-                ws = torch.empty(_lib.load().lidog_sconv_os_stats_ws(n_out, Cout), dtype=torch.float64, device=dev)
-                if stats.sync:
-                    call("lidog_sconv_os_stats", ptr(x), ptr(m.nbr), n_out, K, ptr(perm), ptr(wmask), ptr(order), ptr(W3),
-                         ptr(bias), Cin, Cout, ptr(out), ptr(sums), ptr(ws), float(n_out), 0.0, 0.0, None, None, None,
-                         None)
-                else:
-                    stats.mean = torch.empty(Cout, dtype=torch.float32, device=dev)
-                    stats.invstd = torch.empty(Cout, dtype=torch.float32, device=dev)
-                    call("lidog_sconv_os_stats", ptr(x), ptr(m.nbr), n_out, K, ptr(perm), ptr(wmask), ptr(order), ptr(W3),
-                         ptr(bias), Cin, Cout, ptr(out), ptr(sums), ptr(ws), float(n_out), stats.eps, stats.momentum,
-                         ptr(stats.mean), ptr(stats.invstd), ptr(stats.running_mean), ptr(stats.running_var))
-                stats.sums = sums
-            else:
-                call("lidog_sconv_os", ptr(x), ptr(m.nbr), n_out, K, ptr(perm), ptr(wmask), ptr(order), ptr(W3), 0,
-                     ptr(bias), None, Cin, Cout, ptr(out))
-        else:
-            T = torch.empty((m.P, Cout), dtype=torch.float32, device=x.device)
-            gemm(x, g_in, W3, None, m, Cin, Cout, T, None)
-            if Cout % 4 == 0:
-                row_ptr, row_list = m.rows("in" if swap else "out")
-            if stats is not None and Cout % 4 == 0 and Cout <= 1024:
-                dev = x.device
-                sums = stats.sums_out if stats.sums_out is not None else \
-                    torch.empty(2 * Cout + 1, dtype=torch.float64, device=dev)
-                ws = torch.empty(_lib.load().lidog_sconv_reduce_stats_ws(n_out, Cout), dtype=torch.float64, device=dev)
-                if stats.sync:   # the sums (and the row count behind them) still have to be all-reduced
-                    call("lidog_sconv_reduce_rows_stats", ptr(T), ptr(row_ptr), ptr(row_list), n_out, Cout, ptr(bias),
-                         ptr(out), ptr(sums), ptr(ws), float(n_out), 0.0, 0.0, None, None, None, None)
-                else:            # local BatchNorm: mean / invstd / running statistics finalised in the same launch
-                    stats.mean = torch.empty(Cout, dtype=torch.float32, device=dev)
-                    stats.invstd = torch.empty(Cout, dtype=torch.float32, device=dev)
-                    call("lidog_sconv_reduce_rows_stats", ptr(T), ptr(row_ptr), ptr(row_list), n_out, Cout, ptr(bias),
-                         ptr(out), ptr(sums), ptr(ws), float(n_out), stats.eps, stats.momentum, ptr(stats.mean),
-                         ptr(stats.invstd), ptr(stats.running_mean), ptr(stats.running_var))
-                stats.sums = sums
-            elif Cout % 4 == 0:
-                call("lidog_sconv_reduce_rows", ptr(T), ptr(row_ptr), ptr(row_list), n_out, Cout, ptr(bias), None,
-                     ptr(out))
-            else:
-                call("lidog_sconv_reduce", ptr(T), ptr(pos_o), n_out, K, Cout, ptr(bias), None, ptr(out))
+            bf[0].count(bf[1], "fwd:" + route)
         ctx.save_for_backward(x, W3)
         ctx.m, ctx.swap, ctx.single_in, ctx.has_bias, ctx.w_shape = m, swap, single_in, bias is not None, W.shape
         ctx.w_param, ctx.b_param, ctx.bf = W, bias, bf
@@ -956,34 +984,27 @@ class _SparseConvFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout, gskip=None):
         x, W3 = ctx.saved_tensors
-        m, swap = ctx.m, ctx.swap
+        m, swap, bf = ctx.m, ctx.swap, ctx.bf
         K, Cin, Cout = W3.shape
         gout = gout.contiguous()
         gskip = gskip.contiguous() if gskip is not None else None
         identity = isinstance(m, _IdentityMap)
-        if identity:
-            g_in = g_out = m.rows
-            pos_i, n_in = None, m.n_in
-        elif not swap:
-            g_in, g_out, pos_i, n_in = m.pair_in, m.pair_out, m.pos_in, m.n_in
-        else:
-            g_in, g_out, pos_i, n_in = m.pair_out, m.pair_in, m.pos_out, m.n_out
+        g_in, g_out = (m.rows, m.rows) if identity else (m.pair_out, m.pair_in) if swap else (m.pair_in, m.pair_out)
         gx = gW = gb = None
-        bf = ctx.bf
         wgrad = "lidog_sconv_wgrad_bf16" if bf is not None else "lidog_sconv_wgrad"
         lane_on = _WgradLane.active()
-        # forked behind the data gradient's GEMM (see _WgradLane), or before everything in mode 1
-        behind = lane_on and _WgradLane.mode == 2
 
         def queue_wgrad():
+            """the weight gradient, if it is asked for and not queued yet"""
+            nonlocal gW
+            if gW is not None or not ctx.needs_input_grad[1]:
+                return
             gW = _grad_out(ctx.w_param, W3.shape)
+            # the bf16 kernel has its own slots (_wgrad_chunk) and its own slab count
             items, n_items, item_off = _wgrad_items(m, Cin, Cout, bf is not None)
-            if bf is not None:      # the bf16 kernel's own slab count (and, above, its own slots)
-                slabs = _lib.load().lidog_sconv_wgrad_bf16_slabs(Cin, Cout, n_items)
+            slabs = getattr(_lib.load(), wgrad + "_slabs")(Cin, Cout, n_items)
+            if bf is not None:
                 bf[0].count(bf[1], _precision.WGRAD)
-            else:
-                slabs = _lib.load().lidog_sconv_wgrad_slabs(Cin, Cout, n_items)
-
             partial = torch.empty((max(slabs, 1), Cin, Cout), dtype=torch.float32, device=x.device)
             if gW is not None and lane_on:
                 # launched on the lane's raw stream (no switch of torch's current stream: 2 x ~10 us of host time per
@@ -997,58 +1018,33 @@ class _SparseConvFn(torch.autograd.Function):
                 gW = gW if gW is not None else torch.empty_like(W3)
                 call(wgrad, ptr(x), ptr(g_in), ptr(gout), ptr(g_out), ptr(items), n_items,
                      ptr(item_off), K, Cin, Cout, ptr(partial), ptr(gW))
-            return gW.view(ctx.w_shape)
+            gW = gW.view(ctx.w_shape)
 
-        if ctx.needs_input_grad[1] and not behind:
-            gW = queue_wgrad()
+        # forked behind the data gradient's matrix kernel (see _WgradLane); in mode 1, or in line, before everything
+        if not (lane_on and _WgradLane.mode == 2):
+            queue_wgrad()
         if ctx.needs_input_grad[0]:
             wp = ctx.w_param
             if bf is not None:
-                # the packed transposed kernel (precision.Bf16Training); the reduction pass and its addend stay fp32
-                Wt, gemm = None, functools.partial(_gemm_bf16, wp=bf[3])
-                bf[0].count(bf[1], _precision.DGRAD_DIRECT if identity or ctx.single_in else _precision.DGRAD_REDUCE)
+                Wt = bf[3]      # the packed transposed kernel (precision.Bf16Training)
             elif getattr(wp, "_wt_version", -2) == wp._version:
-                Wt, gemm = wp._wt_view, _gemm        # refreshed after the optimiser step (optim.TransposedKernels)
+                Wt = wp._wt_view        # refreshed after the optimiser step (optim.TransposedKernels)
             else:
-                Wt, gemm = torch.empty((K, Cout, Cin), dtype=torch.float32, device=x.device), _gemm
+                Wt = torch.empty((K, Cout, Cin), dtype=torch.float32, device=x.device)
                 call("lidog_transpose_kernel", ptr(W3), K, Cin, Cout, ptr(Wt))
-            gx = torch.empty((n_in, Cin), dtype=torch.float32, device=x.device)
-            if identity:
-                gemm(gout, None, Wt, None, m, Cout, Cin, gx, None)
-            elif ctx.single_in:
-                gemm(gout, g_out, Wt, None, m, Cout, Cin, gx, g_in)
-            elif bf is None and _os_rows(m, swap, Cin, Cout) is not None:
-                # the data gradient over the mirrored offsets of the same sorted rows (csrc/sconv_os.hip); the residual
-                # branch's gradient is added in its epilogue, as the reduction pass does
-                perm, wmask, order = _os_rows(m, swap, Cin, Cout)
-                call("lidog_sconv_os", ptr(gout), ptr(m.nbr), n_in, K, ptr(perm), ptr(wmask), ptr(order), ptr(Wt), 1,
-                     None, ptr(gskip), Cout, Cin, ptr(gx))
-                gskip = None
-                if ctx.needs_input_grad[1] and behind:
-                    gW = queue_wgrad()
-            else:
-                T = torch.empty((m.P, Cin), dtype=torch.float32, device=x.device)
-                gemm(gout, g_out, Wt, None, m, Cout, Cin, T, None)
-                if ctx.needs_input_grad[1] and behind:
-                    gW = queue_wgrad()
-                add = gskip if (gskip is not None and Cin % 4 == 0) else None
-                if Cin % 4 == 0:
-                    row_ptr, row_list = m.rows("out" if swap else "in")
-                    call("lidog_sconv_reduce_rows", ptr(T), ptr(row_ptr), ptr(row_list), n_in, Cin, None, ptr(add),
-                         ptr(gx))
-                else:
-                    call("lidog_sconv_reduce", ptr(T), ptr(pos_i), n_in, K, Cin, None, None, ptr(gx))
-                if add is not None:
-                    gskip = None
-        if ctx.needs_input_grad[1] and gW is None:
-            gW = queue_wgrad()
+            # the residual branch's gradient is added in the data gradient's epilogue
+            gx, route = _conv_rows(gout, Wt, m, swap, Cout, Cin, mirrored=True, direct=identity or ctx.single_in,
+                                   bf16=bf is not None, add=gskip, queued=queue_wgrad)
+            if bf is not None:
+                bf[0].count(bf[1], "dgrad:" + route)
+        else:
+            gx = gskip
+        queue_wgrad()
         if ctx.has_bias and ctx.needs_input_grad[2]:
             gb = _grad_out(ctx.b_param, (1, Cout))
             gb = gb if gb is not None else torch.empty((1, Cout), dtype=torch.float32, device=x.device)
             ws = torch.empty(_lib.load().lidog_colsum_ws(Cout), dtype=torch.float64, device=x.device)
             call("lidog_colsum", ptr(gout), gout.shape[0], Cout, ptr(gb), ptr(ws))
-        if gskip is not None:   # paths without a reduction pass (1x1, k2 s2) or no data gradient asked for
-            gx = gskip if gx is None else gx + gskip
         return gx, gW, gb, None, None, None, None, None, None, None
 
 
@@ -1100,14 +1096,8 @@ class _BatchNormFn(torch.autograd.Function):
             sync = group is not None
             if sums is None:
                 sums = torch.empty(2 * C + 1, dtype=torch.float64, device=dev)
-                if sync:
-                    call("lidog_bn_stats", ptr(x), n, C, hw, ptr(sums), ptr(_bn_ws(C, hw, dev, n)), rows, 0.0, 0.0,
-                         None, None, None, None)
-                else:
-                    mean = torch.empty(C, dtype=torch.float32, device=dev)
-                    invstd = torch.empty(C, dtype=torch.float32, device=dev)
-                    call("lidog_bn_stats", ptr(x), n, C, hw, ptr(sums), ptr(_bn_ws(C, hw, dev, n)), rows, float(eps),
-                         float(momentum), ptr(mean), ptr(invstd), ptr(running_mean), ptr(running_var))
+                tail, mean, invstd = _stats_tail(rows, C, dev, sync, eps, momentum, running_mean, running_var)
+                call("lidog_bn_stats", ptr(x), n, C, hw, ptr(sums), ptr(_bn_ws(C, hw, dev, n)), *tail)
             if sync:
                 if not presynced:
                     from .comm import transport
@@ -1286,34 +1276,6 @@ class _ConvBase(nn.Module):
             return None
         return (ctx, self) + pair
 
-    def _gemm_bf16(self, xf, gather, wp, bias, m, out, scatter):
-        call("lidog_sconv_gemm_bf16", ptr(xf), ptr(gather), ptr(wp), ptr(bias), ptr(m.tiles[0]), ptr(m.tiles[1]),
-             ptr(m.tiles[2]), m.n_tiles, self.in_channels, self.out_channels, ptr(out), ptr(scatter))
-
-    def _forward_bf16(self, xf, m, swap, single_out, ctx, wp):
-        """plain forward on the bf16 kernels: straight into the output for 1x1 and single-pair maps, else product rows
-        + the fp32 reduction pass"""
-        require_gpu(xf, "features")
-        Cout = self.out_channels
-        bias = self.bias.detach() if self.bias is not None else None
-        if isinstance(m, _IdentityMap):
-            out = torch.empty((m.n_out, Cout), dtype=torch.float32, device=xf.device)
-            self._gemm_bf16(xf, None, wp, bias, m, out, None)
-            ctx.count(self, _precision.GEMM_DIRECT)
-            return out
-        g_in, g_out, n_out = (m.pair_in, m.pair_out, m.n_out) if not swap else (m.pair_out, m.pair_in, m.n_in)
-        out = torch.empty((n_out, Cout), dtype=torch.float32, device=xf.device)
-        if single_out:
-            self._gemm_bf16(xf, g_in, wp, bias, m, out, g_out)
-            ctx.count(self, _precision.GEMM_DIRECT)
-            return out
-        T = torch.empty((m.P, Cout), dtype=torch.float32, device=xf.device)
-        self._gemm_bf16(xf, g_in, wp, None, m, T, None)
-        row_ptr, row_list = m.rows("in" if swap else "out")
-        call("lidog_sconv_reduce_rows", ptr(T), ptr(row_ptr), ptr(row_list), n_out, Cout, ptr(bias), None, ptr(out))
-        ctx.count(self, _precision.GEMM_REDUCE)
-        return out
-
     def forward(self, x, stats=None, skip=False):
         """`skip=True` returns (conv(x), x'): x' is x again, but routed through this convolution's autograd node
         so that the gradient of a residual branch taken from x' is added inside the data gradient's reduction"""
@@ -1325,8 +1287,11 @@ class _ConvBase(nn.Module):
                 bf = self._bf16_train(pctx)
             elif stats is None and not skip:
                 inf = self._bf16(pctx)
-                if inf is not None:
-                    out = self._forward_bf16(x.F.contiguous(), m, swap, single_out, *inf)
+                if inf is not None:     # plain forward on the bf16 kernels
+                    out, route = _conv_rows(x.F.contiguous(), inf[1], m, swap, self.in_channels, self.out_channels,
+                                            direct=isinstance(m, _IdentityMap) or single_out, bf16=True,
+                                            bias=self.bias.detach() if self.bias is not None else None)
+                    inf[0].count(self, route)
                     return SparseTensor(out, coordinate_manager=cm, coordinate_map_key=s_out)
         out = _SparseConvFn.apply(x.F, self.kernel, self.bias, m, swap, single_out, single_in, stats, skip, bf)
         if skip:
@@ -1335,52 +1300,26 @@ class _ConvBase(nn.Module):
         return SparseTensor(out, coordinate_manager=cm, coordinate_map_key=s_out)
 
     def forward_eval_bn(self, x, bn, relu, residual):
-        """Validation path, no autograd: convolution whose reduction pass applies the evaluation-mode BatchNorm
-        (+ residual + ReLU) in its epilogue (lidog_sconv_reduce_rows_bn) -- no separate BatchNorm kernel, no round
+        """Validation path, no autograd: convolution whose reduction pass (or output-stationary kernel) applies the
+        evaluation-mode BatchNorm (+ residual + ReLU) in its epilogue -- no separate BatchNorm kernel, no round
         trip of the convolution output.  Returns None when this convolution does not go through the reduction
         pass (1x1, transposed k2 s2, the 5^3 stem, channel counts not a multiple of 4): the caller falls back."""
         if self.kernel_volume == 1 or self.transposed or self.in_channels == 1 or self.out_channels % 4:
             return None
-        cm = x.coordinate_manager
         m, s_out, swap, single_out, single_in = self._resolve(x)
         xf = x.F.contiguous()
-        W3 = self.kernel.detach().contiguous().view(m.K, self.in_channels, self.out_channels)
-        Cin, Cout, dev = self.in_channels, self.out_channels, xf.device
-        invstd = torch.empty(Cout, dtype=torch.float32, device=dev)
+        Cin, Cout = self.in_channels, self.out_channels
+        invstd = torch.empty(Cout, dtype=torch.float32, device=xf.device)
         call("lidog_bn_eval_invstd", ptr(bn.running_var), float(bn.eps), Cout, ptr(invstd))
-        out = torch.empty((m.n_out, Cout), dtype=torch.float32, device=dev)
         res = residual.F.contiguous() if residual is not None else None
-        srt = _os_rows(m, swap, Cin, Cout)
         bf = self._bf16()
+        out, route = _conv_rows(xf, bf[1] if bf is not None else self.kernel.detach().contiguous().view(m.K, Cin, Cout),
+                                m, swap, Cin, Cout, bias=self.bias.detach() if self.bias is not None else None,
+                                bf16=bf is not None,
+                                bn=(bn.running_mean, invstd, bn.weight.detach(), bn.bias.detach(), res, relu))
         if bf is not None:
-            ctx, wp = bf
-            require_gpu(xf, "features")
-            bias = self.bias.detach() if self.bias is not None else None
-            tail = (ptr(bn.running_mean), ptr(invstd), ptr(bn.weight.detach()), ptr(bn.bias.detach()), ptr(res),
-                    1 if relu else 0, ptr(out))
-            if srt is not None and not single_out:
-                call("lidog_sconv_os_bn_bf16", ptr(xf), ptr(m.nbr), m.n_out, m.K, ptr(srt[0]), ptr(srt[1]), ptr(srt[2]),
-                     ptr(wp), ptr(bias), Cin, Cout, *tail)
-                ctx.count(self, _precision.OS_BN)
-            else:
-                T = torch.empty((m.P, Cout), dtype=torch.float32, device=dev)
-                self._gemm_bf16(xf, m.pair_in, wp, None, m, T, None)
-                row_ptr, row_list = m.rows("out")
-                call("lidog_sconv_reduce_rows_bn", ptr(T), ptr(row_ptr), ptr(row_list), m.n_out, Cout, ptr(bias), *tail)
-                ctx.count(self, _precision.GEMM_REDUCE_BN)
-            return SparseTensor(out, coordinate_manager=cm, coordinate_map_key=s_out)
-        if srt is not None and not single_out:      # sorted rows: output-stationary kernel, same epilogue (same bits)
-            call("lidog_sconv_os_bn", ptr(xf), ptr(m.nbr), m.n_out, m.K, ptr(srt[0]), ptr(srt[1]), ptr(srt[2]), ptr(W3),
-                 ptr(self.bias.detach()) if self.bias is not None else None, Cin, Cout, ptr(bn.running_mean), ptr(invstd),
-                 ptr(bn.weight.detach()), ptr(bn.bias.detach()), ptr(res), 1 if relu else 0, ptr(out))
-            return SparseTensor(out, coordinate_manager=cm, coordinate_map_key=s_out)
-        T = torch.empty((m.P, Cout), dtype=torch.float32, device=dev)
-        _gemm(xf, m.pair_in, W3, None, m, Cin, Cout, T, None)
-        row_ptr, row_list = m.rows("out")
-        call("lidog_sconv_reduce_rows_bn", ptr(T), ptr(row_ptr), ptr(row_list), m.n_out, Cout,
-             ptr(self.bias.detach()) if self.bias is not None else None, ptr(bn.running_mean), ptr(invstd),
-             ptr(bn.weight.detach()), ptr(bn.bias.detach()), ptr(res), 1 if relu else 0, ptr(out))
-        return SparseTensor(out, coordinate_manager=cm, coordinate_map_key=s_out)
+            bf[0].count(self, route)
+        return SparseTensor(out, coordinate_manager=x.coordinate_manager, coordinate_map_key=s_out)
 
 
 class MinkowskiConvolution(_ConvBase):

@@ -102,29 +102,45 @@ class Bf16Kernels:
     """bf16 [K, Cout, Cin] copies of the kernels [K, Cin, Cout] of every eligible convolution of `model` (transposed:
     a lane's eight k-values of the B operand are 16 contiguous bytes), written by ONE launch of lidog_pack_kernels_bf16
     on construction and on every refresh()."""
+    what, dgrad = "a bf16 evaluation", False    # Bf16Training: the data-gradient operands behind the forward ones
 
     def __init__(self, model):
-        self.convs = _eligible_convs(model, "a bf16 evaluation")
-        self._layout, off, self.total_tiles = table_layout(
-            [(c.kernel_volume, c.in_channels, c.out_channels) for c in self.convs])
+        self.convs = _eligible_convs(model, self.what)
+        shapes = [(c.kernel_volume, c.in_channels, c.out_channels) for c in self.convs]
+        if not self.dgrad:
+            self._layout, off, self.total_tiles = table_layout(shapes)
+        else:
+            owners = {id(getattr(c.kernel, "_wt_owner", None)) for c in self.convs}
+            self.transposed = getattr(self.convs[0].kernel, "_wt_owner", None)
+            if self.transposed is None or len(owners) != 1:
+                raise ValueError("Bf16Training: build the model's optimiser first (the data-gradient table is packed "
+                                 "from the transposed kernels it keeps, optim.TransposedKernels)")
+            fwd, dgrad, off, self.total_tiles = training_layout(shapes)
+            self._layout = fwd + dgrad
         self.buf = torch.empty(off, dtype=torch.bfloat16, device=self.convs[0].kernel.device)
-        self._views = {c: self.buf[o:o + K * Cin * Cout].view(K, Cout, Cin)
-                       for c, (o, K, Cin, Cout, _) in zip(self.convs, self._layout)}
+        # a layout row's view is [K, its Cout, its Cin]: [K, Cout, Cin] forward, [K, Cin, Cout] for the data gradient
+        views = [self.buf[o:o + K * Cin * Cout].view(K, Cout, Cin) for o, K, Cin, Cout, _ in self._layout]
+        self._views = {c: tuple(views[i::len(self.convs)]) for i, c in enumerate(self.convs)}
         self.packs = 0
         self.refresh()
 
     def refresh(self):
-        """pack the weights as they are now"""
-        kernels = [c.kernel.detach() for c in self.convs]
-        _pack(kernels[0], self.buf, kernels, self._layout, self.total_tiles, "Bf16Kernels")
+        """pack the weights (Bf16Training: and their transposed copies) as they are now"""
+        sources = [c.kernel.detach() for c in self.convs]
+        if self.dgrad:
+            sources += [c.kernel._wt_view for c in self.convs]
+            self._seen = self.transposed.generation
+        _pack(sources[0], self.buf, sources, self._layout, self.total_tiles, type(self).__name__)
         self.packs += 1
 
     def get(self, conv):
-        """the packed kernel of `conv`, or None when it is not in the table"""
-        return self._views.get(conv)
+        """the packed kernel of `conv` -- the forward operand, also what a no_grad call inside a training context
+        takes -- or None when it is not in the table"""
+        views = self._views.get(conv)
+        return views[0] if views is not None else None
 
 
-class Bf16Training:
+class Bf16Training(Bf16Kernels):
     """The two bf16 operand tables of a mixed-precision training step over the eligible convolutions of `model`:
     forward   [K, Cout, Cin]: the pack of the kernel W [K, Cin, Cout], as Bf16Kernels;
     dgrad     [K, Cin, Cout]: the pack of the transposed kernel [K, Cout, Cin] that optim.TransposedKernels keeps for the
@@ -133,31 +149,7 @@ class Bf16Training:
     first kernel).  The model's optimiser must exist: the table reads its transposed copy, so refresh() belongs AFTER
     TransposedKernels.refresh() -- i.e. after every optimiser step (_Step.training_step does that), and after
     load_state_dict / resume, which refresh the transposed copy: stale() sees that and bf16_training packs again."""
-
-    def __init__(self, model):
-        self.convs = _eligible_convs(model, "bf16 training")
-        owners = {id(getattr(c.kernel, "_wt_owner", None)) for c in self.convs}
-        self.transposed = getattr(self.convs[0].kernel, "_wt_owner", None)
-        if self.transposed is None or len(owners) != 1:
-            raise ValueError("Bf16Training: build the model's optimiser first (the data-gradient table is packed from "
-                             "the transposed kernels it keeps, optim.TransposedKernels)")
-        self._fwd, self._dgrad, off, self.total_tiles = training_layout(
-            [(c.kernel_volume, c.in_channels, c.out_channels) for c in self.convs])
-        self.buf = torch.empty(off, dtype=torch.bfloat16, device=self.convs[0].kernel.device)
-        self._pairs = {}
-        for c, (of, K, Cin, Cout, _), (od, _, _, _, _) in zip(self.convs, self._fwd, self._dgrad):
-            n = K * Cin * Cout
-            self._pairs[c] = (self.buf[of:of + n].view(K, Cout, Cin), self.buf[od:od + n].view(K, Cin, Cout))
-        self.packs = 0
-        self.refresh()
-
-    def refresh(self):
-        """pack the weights and their transposed copies as they are now"""
-        kernels = [c.kernel.detach() for c in self.convs]
-        _pack(kernels[0], self.buf, kernels + [c.kernel._wt_view for c in self.convs], self._fwd + self._dgrad,
-              self.total_tiles, "Bf16Training")
-        self._seen = self.transposed.generation
-        self.packs += 1
+    what, dgrad = "bf16 training", True
 
     def stale(self):
         """the transposed copy was refreshed since the last pack (the weights were loaded or stepped without refresh())"""
@@ -165,12 +157,7 @@ class Bf16Training:
 
     def pair(self, conv):
         """(forward operand, data-gradient operand) of `conv`, or None when it is not in the table"""
-        return self._pairs.get(conv)
-
-    def get(self, conv):
-        """the forward operand of `conv` (what a no_grad call inside a training context takes), or None"""
-        p = self._pairs.get(conv)
-        return p[0] if p is not None else None
+        return self._views.get(conv)
 
 
 class Bf16Context:

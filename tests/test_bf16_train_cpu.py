@@ -103,8 +103,7 @@ def test_wgrad_chunk_reads_the_bf16_kernels_own_slots(monkeypatch):
     cnt = (352_000 * np.concatenate([rng.uniform(0.05, 0.4, 13), [1.0], rng.uniform(0.05, 0.4, 13)])).astype(np.int64)
     k_off = np.concatenate([[0], np.cumsum(cnt)])
     items = lambda chunk: int(np.sum((cnt + chunk - 1) // chunk))   # noqa: E731
-    monkeypatch.setattr(ME, "_wgrad_slots", lambda cin, cout: 768)
-    monkeypatch.setattr(ME, "_wgrad_slots_bf16", lambda cin, cout: 1280)
+    monkeypatch.setattr(ME, "_wgrad_slots", lambda cin, cout, bf16=False: 1280 if bf16 else 768)
     monkeypatch.setattr(ME, "_WGRAD_FIT", 1)
     fp32, bf16 = ME._wgrad_chunk(k_off, 128, 128), ME._wgrad_chunk(k_off, 128, 128, bf16=True)
     assert fp32 % 32 == 0 and bf16 % 32 == 0 and fp32 != bf16

@@ -225,7 +225,7 @@ def test_weight_gradient_work_items_fill_whole_rounds_when_asked(monkeypatch):
     cnt = (n * np.concatenate([rng.uniform(0.05, 0.4, 13), [1.0], rng.uniform(0.05, 0.4, 13)])).astype(np.int64)
     k_off = np.concatenate([[0], np.cumsum(cnt)])
     items = lambda chunk: int(np.sum((cnt + chunk - 1) // chunk))   # noqa: E731
-    monkeypatch.setattr(ME, "_wgrad_slots", lambda cin, cout: {96: 512, 128: 768, 256: 768}[cin])
+    monkeypatch.setattr(ME, "_wgrad_slots", lambda cin, cout, bf16=False: {96: 512, 128: 768, 256: 768}[cin])
     monkeypatch.setattr(ME, "_WGRAD_FIT", 0)
     old = ME._wgrad_chunk(k_off, 128, 128)
     assert old % 32 == 0 and 2048 - 40 < items(old) < 2048 + 40   # ~2 048 +- partial items: 2.67 rounds of 768 slots

@@ -214,6 +214,49 @@ def test_program_follows_structural_changes_of_the_model():
     assert p2 is not p1 and all(type(b) is ME.MinkowskiSyncBatchNorm for b in p2.bns)
 
 
+EDGE_ROWS = {       # rows per level (tensor strides 1, 2, 4, 8, 16) of the scenes tests/test_gpu_trunk_edge.py steps on
+    "tiny_1": [1, 1, 1, 1, 1],
+    "tiny_2": [2, 2, 2, 2, 2],
+    "tiny_127": [127, 102, 46, 15, 4],
+    "tiny_128": [128, 103, 46, 15, 4],
+    "tiny_129": [129, 104, 46, 15, 4],
+    "line_x129": [129, 65, 33, 17, 9],
+    "isolated": [385, 385, 385, 72, 16],
+    "checkerboard": [864, 252, 48, 8, 2],
+    "dense_cube_odd": [2000, 432, 54, 16, 8],
+    "one_and_many": [2477, 2165, 1350, 349, 92],
+    "range_ends": [54, 16, 2, 2, 2],
+    "twin_scans": [4044, 3666, 2494, 690, 190],
+}
+
+
+def test_edge_scenes_keep_the_row_counts_the_executor_tests_rely_on():
+    """tests/test_gpu_trunk_edge.py takes the executor through levels of 1 and 2 rows, the 128-row tile edge at level 0,
+    maps with centre pairs only and a scan without voxels: all of that is a property of the scenes of tests/sconv_ref.py.
+    If a scene is edited, this says which edge went away."""
+    import sconv_ref as R
+    for name, rows in EDGE_ROWS.items():
+        c = R.scene(name)
+        assert [R.strided(c, 2 ** lv).shape[0] for lv in range(5)] == rows, name
+    batches = {name: sorted(set(R.scene(name)[:, 0].tolist())) for name in EDGE_ROWS}
+    assert batches["tiny_1"] == [1]                        # scan 0 has no voxel: its BEV image is empty
+    assert batches["tiny_2"] == [0, 1]                     # two scans of one voxel
+    assert batches["range_ends"] == [0, 4095]
+    c = R.scene("range_ends")
+    assert c[:, 1:].max() == 65535 and c[:, 1:].min() == -65536
+    c = R.scene("one_and_many")
+    assert (c[:, 0] == 0).sum() == 1 and (c[:, 0] == 1).sum() == 2476
+    # isolated (a grid of pitch 4): no voxel has a 3^3 neighbour at strides 1 and 2 (centre pairs only), one child per
+    # parent down to stride 4, where the grid is dense
+    c = R.scene("isolated")
+    for s in (1, 2):
+        lv = R.strided(c, s)
+        assert (R.neighbours(lv, lv, 3, s, s) >= 0).sum() == lv.shape[0]
+    # dense_cube_odd: full 27-neighbour rows exist
+    c = R.scene("dense_cube_odd")
+    assert (R.neighbours(c, c, 3, 1, 1) >= 0).sum(axis=0).max() == 27
+
+
 def test_weight_gradient_work_items_fill_whole_rounds_when_asked(monkeypatch):
     """me._wgrad_chunk: with LIDOG_WGRAD_FIT the items of a launch (one partial item per offset included) fit a whole
     number of rounds of the kernel's resident workgroups, tightly; without it the round-4 rule (pairs / optimum, which

@@ -42,7 +42,9 @@ int64_t lidog_hash_capacity(int64_t n);
 
 /* Build the hash table of a coordinate map: keys[cap] (uint64), vals[cap] (int32 row of the FIRST
  * occurrence of that coordinate).  first_row[i] = vals of row i's key (== i for unique input).
- * n_unique_dev receives the number of distinct coordinates (device int64). */
+ * n_unique_dev receives the number of distinct coordinates (device int64).
+ * Range: -65536 <= x, y, z <= 65535 and 0 <= batch <= 4095.  A row outside it sets *err_flag = 1, enters no key,
+ * counts as a distinct coordinate of its own and gets first_row[i] = i; the caller reads the flag and refuses the map. */
 int lidog_coords_insert(const int32_t *coords, int64_t n, uint64_t *keys, int32_t *vals, int64_t cap,
                         int32_t *first_row, int64_t *n_unique_dev, int32_t *err_flag, void *stream);
 /* the same, and in the same pass what a caller needs to size occupancy bitmaps and batch loops:
@@ -52,7 +54,10 @@ int lidog_coords_insert_info(const int32_t *coords, int64_t n, uint64_t *keys, i
                              int32_t *first_row, int64_t *info, int32_t *err_flag, void *stream);
 
 /* Compact a map with duplicates: unique_rows[j] = first-occurrence row of output row j (ascending),
- * inverse[i] = output row of input row i; rewrites vals to output rows.  scan_ws: int32[n + 2048]. */
+ * inverse[i] = output row of input row i; rewrites vals to output rows.  scan_ws: int32[n + 2048].
+ * Terminates on any input: a row that lidog_coords_insert flagged as out of range keeps its unique_rows / inverse
+ * entries (every output is defined) and rewrites no slot, and a probe ends at an empty slot.  A caller may therefore
+ * launch it before it has read the range flag (lidog_amd.data.quantize_rows: one read-back after the last launch). */
 int lidog_coords_compact(const int32_t *first_row, int64_t n, const uint64_t *keys, int32_t *vals, int64_t cap,
                          const int32_t *coords, int32_t *unique_rows, int32_t *inverse, int32_t *scan_ws,
                          void *stream);
@@ -366,7 +371,10 @@ int lidog_dice_bwd(const float *logits, const int64_t *target, int64_t n, int32_
  * ME.utils.sparse_quantize (utils/datasets/semantickitti_bev.py:232-238) = lidog_voxel_floor +
  * lidog_coords_insert + lidog_coords_compact + lidog_label_vote; PC2ImgConverter.getBEVImageNew
  * (utils/datasets/semantickitti_bev.py:433-464) = lidog_bev_label_raster. */
-/* rows[i] = (batch, floor(x/qx), floor(y/qy), floor(z/qz)) in float32 arithmetic; points [n,3] */
+/* rows[i] = (batch, floor(x/qx), floor(y/qy), floor(z/qz)) in float32 arithmetic (a true division, as numpy's on a
+ * float32 array); points [n,3].  A quotient that is NaN, infinite or beyond int32 gives INT32_MIN, which
+ * lidog_coords_insert flags as out of range: such a point is refused, never put into voxel 0.  lidog_augment_points
+ * and lidog_mix_gather_aug write their voxel rows by the same rule. */
 int lidog_voxel_floor(const float *points, int64_t n, float qx, float qy, float qz, int32_t batch, int32_t *rows,
                       void *stream);
 /* voxel_labels[j] = label of the voxel's first point, or ignore_label when its points disagree */

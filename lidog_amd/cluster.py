@@ -39,7 +39,7 @@ def dbscan_count(coords, voxel_size, eps=0.5, min_samples=10):
          ptr(ws), ws_bytes)
     err, k = info.tolist()                      # the one device -> host read
     if err == 1:
-        raise ValueError("voxel coordinates out of the supported range |c| <= 65535")
+        raise ValueError("dbscan: voxel coordinates out of the supported range -65535 <= x, y, z <= 65535")
     if err:
         raise ValueError(f"dbscan: the grid of eps-sized cells ({eps} / {voxel_size} voxels) over the input's bounding "
                          "box has more than 2^32 cells")

@@ -59,7 +59,9 @@ __device__ __forceinline__ AugPoint aug_transform(const float *__restrict__ pts,
 // (batch, floor(p / q)): np.floor(c / q) on a float64 array with q = float64(quantization_size); on a float32 array with
 // q = float32(quantization_size), as k_voxel_floor
 __device__ __forceinline__ int4 aug_voxel_row(const AugPoint &a, int32_t batch, double qx, double qy, double qz) {
-    if (a.is64) return make_int4(batch, (int)floor(a.d[0] / qx), (int)floor(a.d[1] / qy), (int)floor(a.d[2] / qz));
-    return make_int4(batch, (int)floorf(a.f[0] / (float)qx), (int)floorf(a.f[1] / (float)qy),
-                     (int)floorf(a.f[2] / (float)qz));
+    if (a.is64)
+        return make_int4(batch, lidog_voxel_coord(floor(a.d[0] / qx)), lidog_voxel_coord(floor(a.d[1] / qy)),
+                         lidog_voxel_coord(floor(a.d[2] / qz)));
+    return make_int4(batch, lidog_voxel_coord(floorf(a.f[0] / (float)qx)), lidog_voxel_coord(floorf(a.f[1] / (float)qy)),
+                     lidog_voxel_coord(floorf(a.f[2] / (float)qz)));
 }

@@ -54,6 +54,17 @@ __device__ __forceinline__ uint64_t lidog_pack(int b, int x, int y, int z, int *
     return ((uint64_t)(unsigned)b << 51) | ((uint64_t)ux << 34) | ((uint64_t)uy << 17) | (uint64_t)uz;
 }
 
+// Voxel coordinate of an already floored quotient.  A NaN, an infinity or a value that no int32 holds becomes INT_MIN
+// (what numpy's astype(int32) gives for them on x86), which lidog_pack reports as out of range: such a point raises in
+// the caller instead of landing in voxel 0, where a bare (int) cast of NaN puts it.
+#define LIDOG_COORD_BAD (-2147483647 - 1)
+__device__ __forceinline__ int lidog_voxel_coord(float f) {
+    return (f >= -2147483648.0f && f < 2147483648.0f) ? (int)f : LIDOG_COORD_BAD;
+}
+__device__ __forceinline__ int lidog_voxel_coord(double f) {
+    return (f >= -2147483648.0 && f < 2147483648.0) ? (int)f : LIDOG_COORD_BAD;
+}
+
 __device__ __forceinline__ uint64_t lidog_mix(uint64_t k) {
     k ^= k >> 33;
     k *= 0xff51afd7ed558ccdull;

@@ -267,9 +267,20 @@ __global__ __launch_bounds__(256) void k_compact_rows(const int32_t *__restrict_
         int4 c = coords[i];
         int bad = 0;
         uint64_t key = lidog_pack(c.x, c.y, c.z, c.w, &bad);
+        // an out-of-range row (k_insert: slot -1, its own first occurrence) has no key in the table: nothing to rewrite,
+        // its unique_rows / inverse entries above keep every output defined and the caller raises on the range flag
+        if (bad) return;
+        // the probe ends at an empty slot, as lidog_find: the kernel terminates whatever the table holds
         uint64_t slot = lidog_mix(key) & mask;
-        while (keys[slot] != key) slot = (slot + 1) & mask;
-        vals[slot] = r;
+        for (;;) {
+            uint64_t k = keys[slot];
+            if (k == key) {
+                vals[slot] = r;
+                break;
+            }
+            if (k == LIDOG_EMPTY_KEY) break;
+            slot = (slot + 1) & mask;
+        }
     }
 }
 

@@ -5,13 +5,15 @@
 #include "common.h"
 
 // rows[i] = (batch, floor(x/q), floor(y/q), floor(z/q)); float32 division and floor exactly as
-// np.floor(points / quantization_size) on a float32 array
+// np.floor(points / quantization_size) on a float32 array; a non-finite quotient gives LIDOG_COORD_BAD (common.h), which
+// the range check of lidog_coords_insert refuses
 __global__ __launch_bounds__(256) void k_voxel_floor(const float *__restrict__ pts, int64_t n, float qx, float qy,
                                                      float qz, int batch, int4 *__restrict__ rows) {
     int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     float x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
-    rows[i] = make_int4(batch, (int)floorf(x / qx), (int)floorf(y / qy), (int)floorf(z / qz));
+    rows[i] = make_int4(batch, lidog_voxel_coord(floorf(x / qx)), lidog_voxel_coord(floorf(y / qy)),
+                        lidog_voxel_coord(floorf(z / qz)));
 }
 
 extern "C" int lidog_voxel_floor(const float *points, int64_t n, float qx, float qy, float qz, int32_t batch,

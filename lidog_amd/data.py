@@ -56,7 +56,8 @@ def quantize_rows(rows, features=None, labels=None, ignore_label=-100, return_in
     call("lidog_coords_compact", ptr(first), n, ptr(keys), ptr(vals), cap, ptr(rows), ptr(uniq), ptr(inv), ptr(ws))
     m, bad = sizes.cpu().tolist()
     if bad:
-        raise ValueError("voxel coordinates out of the supported range |c| <= 65535")
+        raise ValueError("voxel coordinates out of the supported range: -65536 <= x, y, z <= 65535, 0 <= batch <= 4095 "
+                         "(a NaN or infinite point counts as out of range)")
     uniq = uniq[:m]
     index = uniq.long()
     out = [rows[index][:, 1:].contiguous()]

@@ -399,7 +399,7 @@ class CoordinateManager:
             raise RuntimeError("occupancy bitmap: a coordinate lies outside the bounding box the bitmap was sized for "
                                "(kernel maps built through it would drop neighbours); LIDOG_MAP_BITMAPS=0 disables them")
         if code != 0:
-            raise ValueError("coordinates out of the supported range: |x|,|y|,|z| <= 65535, 0 <= batch <= 4095")
+            raise ValueError("coordinates out of the supported range: -65536 <= x, y, z <= 65535, 0 <= batch <= 4095")
 
     def insert(self, coords):
         _lib.require_gpu(coords, "coordinates")

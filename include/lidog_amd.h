@@ -883,6 +883,45 @@ int lidog_sconv_wgrad_bf16(const float *A, const int32_t *pair_a, const float *G
                            const int32_t *items, int32_t n_items, const int32_t *item_off, int32_t K, int32_t Cin,
                            int32_t Cout, float *partial, float *gW, void *stream);
 
+/* ------------------------------------------------------------------ sparse pooling (csrc/pool.hip)
+ * Replaces ME.Minkowski{Sum,Avg,Max}Pooling, MinkowskiPoolingTranspose and MinkowskiGlobal{Sum,Avg,Max}Pooling of
+ * MinkowskiEngine 0.5.4 (utils/models/resnet_old.py:28,53; utils/models/common.py:126,180,208).  Features fp32 [rows, C],
+ * any C >= 1 (float4 kernels when C % 4 == 0, scalar ones otherwise).  Every entry is a gather written with plain
+ * stores: no atomics, the same bits on every call.  n == 0 returns without a launch.
+ *
+ * Local pooling walks the per-row lists of lidog_kernel_map_rows of the RESULT side: row r owns the pair positions
+ * row_list[row_ptr[r] .. row_ptr[r + 1]) (ascending offset), other[p] is the row on the other side of pair p (pair_in
+ * when the result rows are the map's output rows, pair_out when they are its input rows).
+ *
+ * lidog_pool_rows: y[r] = sum over p of x[other[p]]; avg != 0: divided by the number of pairs of r (the neighbours
+ * that exist, not the kernel volume); other_row_ptr != NULL: every term x[o] is divided by the pair count of o on ITS
+ * side (other_row_ptr[o + 1] - other_row_ptr[o]) before it is added -- the gradient of an average, gathered from the
+ * input side.  A row without pairs gets exact zeros.  Serves the forward pass (output rows), the gradients of sum and
+ * avg (input rows), the transposed pooling (input rows, avg) and its gradient (output rows, other_row_ptr). */
+int lidog_pool_rows(const float *x, const int32_t *row_ptr, const int32_t *row_list, const int32_t *other, int64_t n,
+                    int32_t C, int32_t avg, const int32_t *other_row_ptr, float *y, void *stream);
+/* y[r][c] = max over p of x[other[p]][c], arg[r][c] = other[p] of the FIRST maximum in list order (strict >: a tie
+ * stays with the lowest offset).  A NaN wins over every number and the first NaN stays (torch.amax's value).  A row
+ * without pairs gets y = 0, arg = -1. */
+int lidog_pool_rows_max(const float *x, const int32_t *row_ptr, const int32_t *row_list, const int32_t *other,
+                        int64_t n, int32_t C, float *y, int32_t *arg, void *stream);
+/* gx[i][c] = sum over the pairs p of INPUT row i of gy[other[p]][c] where arg[other[p]][c] == i (row lists of the
+ * input side, other = the output row of a pair; arg [n_out, C] of lidog_pool_rows_max). */
+int lidog_pool_rows_max_bwd(const float *gy, const int32_t *arg, const int32_t *row_ptr, const int32_t *row_list,
+                            const int32_t *other, int64_t n, int32_t C, float *gx, void *stream);
+/* Global pooling: one reduction per scan over the segments of lidog_in_segments (perm, seg_off [B + 1], bid).
+ * mode 0 = sum, 1 = avg (sum / rows of the scan), 2 = max with arg [B, C] = the row of the maximum (ties and two NaNs
+ * go to the smaller row index = the first in the scan's order).  y [B, C]; a batch index without rows gets zeros (and
+ * arg = -1).  The sums are per-workgroup partials added in workgroup order; the cut into workgroups depends on
+ * (n, B, C) alone.
+ * ws: lidog_pool_global_ws(n, B, C) bytes. */
+int64_t lidog_pool_global_ws(int64_t n, int32_t B, int32_t C);
+int lidog_pool_global(const float *x, int64_t n, int32_t C, int32_t B, const int32_t *perm, const int32_t *seg_off,
+                      int32_t mode, float *y, int32_t *arg /* mode 2 only */, void *ws, int64_t ws_bytes, void *stream);
+/* gx[i] = gy[bid[i]] (sum), gy[bid[i]] / rows of that scan (avg), gy[b][c] where arg[b][c] == i else 0 (max) */
+int lidog_pool_global_bwd(const float *gy, const int32_t *arg, int64_t n, int32_t C, int32_t B, const int32_t *bid,
+                          const int32_t *seg_off, int32_t mode, float *gx, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

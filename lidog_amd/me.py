@@ -7,14 +7,21 @@ Mirrors the surface of MinkowskiEngine 0.5.4 that LiDOG's models and pipelines u
   MinkowskiBatchNorm(.bn) / MinkowskiSyncBatchNorm   minkunet_bev.py:60,406-408; train_lidog.py:228
   MinkowskiReLU(inplace=True), cat, +=               minkunet_bev.py:124,337; resnet_block.py:52
   MinkowskiInstanceNorm                              utils/models/minkunet_ibn.py:26,38-40
+  MinkowskiMaxPooling / AvgPooling / SumPooling,     utils/models/resnet_old.py:28; common.py:180,208
+    MinkowskiPoolingTranspose, MinkowskiGlobal{Sum,Avg,Max}Pooling (MinkowskiGlobalPooling)   resnet_old.py:53
+  MinkowskiLinear, MinkowskiGELU, MinkowskiNetwork   resnet_old.py:50,55; utils/models/resunet.py:86
+  RegionType, KernelGenerator (HYPER_CUBE only)      utils/models/common.py:52-61,126
+  MinkowskiFunctional.relu                           utils/models/resunet.py:4,39
   utils.kaiming_normal_                              minkunet_bev.py:404
   modules.resnet_block.BasicBlock                    minkunet_bev.py:4,425-439
 
 `install_as_minkowski_engine()` registers this module as `MinkowskiEngine` so the reference's
 `import MinkowskiEngine as ME` resolves to it.  Everything runs on the GPU through the C ABI; there
-is no CPU path (tensors on the CPU raise).
+is no CPU path (tensors on the CPU raise).  The pooling operators are HIP gathers over the rule book's per-row lists
+and over the scans of a map (csrc/pool.hip): no weights, no atomics, the same bits on every call.
 """
 import ctypes
+import enum
 import math
 import os
 import sys
@@ -326,12 +333,15 @@ class CoordinateManager:
         """Build every map of `trace` that is missing with ONE host synchronisation for all kernel maps and ONE
         host-to-device copy for all tile / work-item tables (the lazy path costs one of each per map, each with
         the GPU idle while the host prepares the tables)."""
-        want, shapes = [], {}
+        want, shapes, pooled = [], {}, []
         for key, cin, cout in trace:
             if key not in shapes:
                 shapes[key] = []
                 want.append(key)
-            if (cin, cout) not in shapes[key]:
+            if cin == 0:    # a pooling layer: no weights, so no weight-gradient items; it walks both sides' row lists
+                if key not in pooled:
+                    pooled.append(key)
+            elif (cin, cout) not in shapes[key]:
                 shapes[key].append((cin, cout))
         pending = []
         for key in want:
@@ -343,6 +353,8 @@ class CoordinateManager:
             if s_out != s_in:
                 self.stride(s_in, s_out)
             pending.append((key, self._kernel_map_launch(key)))
+        # a 1x1 on a map that only exists once the network runs (the origin map of a global pooling) stays lazy
+        want = [key for key in want if key[0] != "identity" or key[1] in self.maps]
         # the error word rides along: k_bitmap_set flags a coordinate outside the box its bitmap was sized for
         hosts = torch.cat([pd[3] for _, pd in pending] + [self.err.long()]).tolist() if pending else []
         if pending and hosts[-1] != 0:
@@ -392,6 +404,8 @@ class CoordinateManager:
         for key, chunk, islot, total, oslot in items_todo:
             m = self.identity[self.maps[key[1]].n] if key[0] == "identity" else self.kmaps[key]
             m.__dict__.setdefault("_wgrad_items", {})[chunk] = (views[islot], total, views[oslot])
+        for key in pooled:
+            self._own(*self.kmaps[key].rows("out"), *self.kmaps[key].rows("in"))
 
     def _check(self, code=None):
         code = int(self.err.item()) if code is None else code
@@ -1211,6 +1225,7 @@ class _ConvBase(nn.Module):
             raise ValueError("lidog_amd implements the 3-D operators of the LiDOG hot path")
         self.in_channels, self.out_channels = in_channels, out_channels
         self.kernel_size, self.stride, self.dilation = int(kernel_size), int(stride), int(dilation)
+        _check_generator(kernel_generator, self.kernel_size, self.stride, self.dilation, type(self).__name__)
         self.dimension = dimension
         self.kernel_volume = self.kernel_size ** 3
         shape = (self.kernel_volume, in_channels, out_channels) if self.kernel_volume > 1 else \
@@ -1576,6 +1591,299 @@ class MinkowskiDropout(nn.Module):
         return x._like(self.drop(x.F))
 
 
+class MinkowskiGELU(nn.Module):
+    """ME.MinkowskiGELU (utils/models/resnet_old.py:50): torch's GELU on the feature matrix"""
+
+    def __init__(self, approximate="none"):
+        super().__init__()
+        self.gelu = nn.GELU(approximate=approximate)
+
+    def forward(self, x):
+        return x._like(self.gelu(x.F))
+
+
+class MinkowskiNetwork(nn.Module):
+    """ME.MinkowskiNetwork (utils/models/resunet.py:86): the base class that remembers the dimension"""
+
+    def __init__(self, D):
+        super().__init__()
+        self.D = D
+
+
+# ------------------------------------------------------------------ kernel regions
+class RegionType(enum.Enum):
+    """ME.RegionType (utils/models/common.py:52-61); only HYPER_CUBE regions are implemented"""
+    HYPER_CUBE = 0
+    HYPER_CROSS = 1
+    CUSTOM = 2
+
+
+class KernelGenerator:
+    """ME.KernelGenerator (utils/models/common.py:126,150,177): stores its arguments.  The convolution and pooling
+    modules accept one that describes the plain hyper-cube they build anyway (_check_generator)."""
+
+    def __init__(self, kernel_size=-1, stride=1, dilation=1, is_transpose=False, region_type=RegionType.HYPER_CUBE,
+                 region_offsets=None, expand_coordinates=False, axis_types=None, dimension=-1):
+        self.kernel_size, self.stride, self.dilation = kernel_size, stride, dilation
+        self.is_transpose = is_transpose
+        self.region_type = region_type
+        self.region_offsets = region_offsets
+        self.expand_coordinates = expand_coordinates
+        self.axis_types = axis_types
+        self.dimension = dimension
+
+
+def _one_size(v, what, who):
+    """a kernel size / stride / dilation given per axis -> the one value, if the axes agree"""
+    if isinstance(v, (list, tuple)) or (torch.is_tensor(v) and v.dim() > 0) or isinstance(v, np.ndarray):
+        vals = [int(a) for a in v]
+        if len(set(vals)) != 1:
+            raise NotImplementedError(f"{who}: a HYPER_CUBE region with per-axis {what} {vals} is not implemented")
+        return vals[0]
+    return int(v)
+
+
+def _check_generator(gen, kernel_size, stride, dilation, who):
+    """None or a plain hyper-cube that agrees with the module's own arguments passes; any other region raises"""
+    if gen is None:
+        return
+    region = gen.region_type if isinstance(gen.region_type, RegionType) else RegionType(gen.region_type)
+    if region is not RegionType.HYPER_CUBE:
+        raise NotImplementedError(f"{who}: kernel region {region.name} is not implemented (RegionType.HYPER_CUBE only)")
+    for name in ("axis_types", "region_offsets"):
+        if getattr(gen, name, None) is not None:
+            raise NotImplementedError(f"{who}: a {region.name} kernel region with {name} is not implemented")
+    if getattr(gen, "expand_coordinates", False):
+        raise NotImplementedError(f"{who}: a {region.name} kernel region with expand_coordinates is not implemented")
+    have = tuple(_one_size(getattr(gen, n), n, who) for n in ("kernel_size", "stride", "dilation"))
+    if have != (kernel_size, stride, dilation):
+        raise NotImplementedError(f"{who}: a {region.name} kernel generator with (kernel_size, stride, dilation) = {have} "
+                                  f"on a module with {(kernel_size, stride, dilation)} is not implemented")
+
+
+# ------------------------------------------------------------------ pooling (csrc/pool.hip)
+# [ME-mem] the pooling operators of MinkowskiEngine 0.5.4, restated from memory (unpinned like every ME convention here,
+# SURVEY.md 8(c)): the output map and the kernel region are those of a MinkowskiConvolution with the same arguments;
+# MinkowskiAvgPooling divides by the number of neighbours that exist, not by the kernel volume; MinkowskiPoolingTranspose
+# averages the coarse rows that reach a fine row; the global forms return one row per batch index on the origin map
+# (coordinates (b, 0, 0, 0), tensor stride 0).  include/lidog_amd.h states the formulas the kernels are tested against.
+_POOL_MODES = {"sum": 0, "avg": 1, "max": 2}
+_OTHER_SIDE = {"out": "in", "in": "out"}
+
+
+def _pool_side(m, side):
+    """(row_ptr, row_list, the row on the other side of each pair, rows) of the side of rule book `m` that is written"""
+    row_ptr, row_list = m.rows(side)
+    if side == "out":
+        return row_ptr, row_list, m.pair_in, m.n_out
+    return row_ptr, row_list, m.pair_out, m.n_in
+
+
+def _pool_features(x):
+    require_gpu(x, "features")
+    if x.dtype != torch.float32 or x.dim() != 2:
+        raise ValueError("pooling takes a float32 feature matrix [rows, channels]")
+    return x.contiguous()
+
+
+class _PoolRowsFn(torch.autograd.Function):
+    """Local pooling over rule book `m`; `side`: the rows that are written ("out": pooling, "in": transposed pooling).
+    Forward and every gradient are gathers over the per-row lists (KernelMap.rows); max saves only its argmax."""
+
+    @staticmethod
+    def forward(ctx, x, m, side, mode):
+        x = _pool_features(x)
+        row_ptr, row_list, other, n = _pool_side(m, side)
+        C = x.shape[1]
+        y = torch.empty((n, C), dtype=torch.float32, device=x.device)
+        if mode == "max":
+            arg = torch.empty((n, C), dtype=torch.int32, device=x.device)
+            call("lidog_pool_rows_max", ptr(x), ptr(row_ptr), ptr(row_list), ptr(other), n, C, ptr(y), ptr(arg))
+            ctx.save_for_backward(arg)
+        else:
+            call("lidog_pool_rows", ptr(x), ptr(row_ptr), ptr(row_list), ptr(other), n, C, 1 if mode == "avg" else 0,
+                 None, ptr(y))
+        ctx.m, ctx.side, ctx.mode = m, side, mode
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        m, side, mode = ctx.m, ctx.side, ctx.mode
+        gy = gy.contiguous()
+        row_ptr, row_list, other, n = _pool_side(m, _OTHER_SIDE[side])
+        C = gy.shape[1]
+        gx = torch.empty((n, C), dtype=torch.float32, device=gy.device)
+        if mode == "max":
+            (arg,) = ctx.saved_tensors
+            call("lidog_pool_rows_max_bwd", ptr(gy), ptr(arg), ptr(row_ptr), ptr(row_list), ptr(other), n, C, ptr(gx))
+        else:   # avg: every term divided by the pair count of the row it comes from (the forward pass's divisor)
+            counts = m.rows(side)[0] if mode == "avg" else None
+            call("lidog_pool_rows", ptr(gy), ptr(row_ptr), ptr(row_list), ptr(other), n, C, 0, ptr(counts), ptr(gx))
+        return gx, None, None, None
+
+
+class _PoolBase(nn.Module):
+    mode = None
+
+    def __init__(self, kernel_size, stride=1, dilation=1, kernel_generator=None, dimension=None):
+        super().__init__()
+        if dimension != 3:
+            raise ValueError("lidog_amd implements the 3-D operators of the LiDOG hot path")
+        who = type(self).__name__
+        self.kernel_size = _one_size(kernel_size, "kernel_size", who)
+        self.stride = _one_size(stride, "stride", who)
+        self.dilation = _one_size(dilation, "dilation", who)
+        _check_generator(kernel_generator, self.kernel_size, self.stride, self.dilation, who)
+        self.dimension = dimension
+
+    def forward(self, x):
+        """the output map and the kernel region of a MinkowskiConvolution with the same arguments; the use is recorded in
+        the manager's trace with zero channel counts (CoordinateManager.prefetch builds the map and both row lists)"""
+        cm, s_in = x.coordinate_manager, x.coordinate_map_key
+        key = (s_in, s_in * self.stride, self.kernel_size, self.dilation)
+        m = cm.kernel_map(*key)
+        cm.trace.append((key, 0, 0))
+        return SparseTensor(_PoolRowsFn.apply(x.F, m, "out", self.mode), coordinate_manager=cm,
+                            coordinate_map_key=key[1])
+
+    def extra_repr(self):
+        return f"kernel_size={self.kernel_size}, stride={self.stride}, dilation={self.dilation}"
+
+
+class MinkowskiSumPooling(_PoolBase):
+    """y[o] = sum of the input rows in o's kernel region (utils/models/common.py:208)"""
+    mode = "sum"
+
+
+class MinkowskiAvgPooling(_PoolBase):
+    """the same sum divided by the number of rows that are there (utils/models/common.py:180)"""
+    mode = "avg"
+
+
+class MinkowskiMaxPooling(_PoolBase):
+    """per-channel maximum over the kernel region (utils/models/resnet_old.py:28); a tie goes to the lowest offset"""
+    mode = "max"
+
+
+class MinkowskiPoolingTranspose(_PoolBase):
+    """y[fine] = average of the coarse rows whose kernel region holds `fine`; lands on the existing finer map, as
+    MinkowskiConvolutionTranspose does"""
+    mode = "avg"
+
+    def __init__(self, kernel_size, stride, dilation=1, kernel_generator=None, dimension=None):
+        super().__init__(kernel_size, stride, dilation, kernel_generator, dimension)
+
+    def forward(self, x):
+        cm, s_in = x.coordinate_manager, x.coordinate_map_key
+        if s_in % self.stride != 0 or (s_in // self.stride) not in cm.maps:
+            raise ValueError("transposed convolution must land on an existing finer coordinate map")
+        key = (s_in // self.stride, s_in, self.kernel_size, self.dilation)
+        m = cm.kernel_map(*key)
+        cm.trace.append((key, 0, 0))
+        return SparseTensor(_PoolRowsFn.apply(x.F, m, "in", self.mode), coordinate_manager=cm,
+                            coordinate_map_key=key[0])
+
+
+ORIGIN_KEY = 0      # coordinate-map key of the origin map: one row (b, 0, 0, 0) per batch index, tensor stride 0
+
+
+def _origin_map(cm):
+    """the origin map of a manager, created once"""
+    if ORIGIN_KEY not in cm.maps:
+        B = int(cm.batch_size or 0)
+        coords = torch.zeros((B, 4), dtype=torch.int32, device=cm.device)
+        coords[:, 0] = torch.arange(B, dtype=torch.int32, device=cm.device)
+        cm.maps[ORIGIN_KEY] = _CoordMap(cm._own(coords), None, None, 0)
+    return cm.maps[ORIGIN_KEY]
+
+
+class _GlobalPoolFn(torch.autograd.Function):
+    """one reduction per scan over CoordinateManager.segments; `segs` = (perm, seg_off, bid, B)"""
+
+    @staticmethod
+    def forward(ctx, x, segs, mode):
+        x = _pool_features(x)
+        perm, seg_off, bid, B = segs
+        n, C = x.shape
+        dev = x.device
+        y = torch.empty((B, C), dtype=torch.float32, device=dev)
+        arg = torch.empty((B, C), dtype=torch.int32, device=dev) if mode == "max" else None
+        nbytes = _lib.load().lidog_pool_global_ws(n, B, C)
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        call("lidog_pool_global", ptr(x), n, C, B, ptr(perm), ptr(seg_off), _POOL_MODES[mode], ptr(y), ptr(arg), ptr(ws),
+             nbytes)
+        ctx.save_for_backward(arg)
+        ctx.segs, ctx.mode, ctx.n = segs, mode, n
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        (arg,) = ctx.saved_tensors
+        perm, seg_off, bid, B = ctx.segs
+        gy = gy.contiguous()
+        C = gy.shape[1]
+        gx = torch.empty((ctx.n, C), dtype=torch.float32, device=gy.device)
+        call("lidog_pool_global_bwd", ptr(gy), ptr(arg), ctx.n, C, B, ptr(bid), ptr(seg_off), _POOL_MODES[ctx.mode],
+             ptr(gx))
+        return gx, None, None
+
+
+class _GlobalPoolBase(nn.Module):
+    """One row per batch index, in batch order whatever the order of the input rows, on the manager's origin map
+    (coordinate-map key 0, coordinates (b, 0, 0, 0), tensor_stride [0, 0, 0]).  A batch index without rows gives a row
+    of zeros and receives no gradient; MinkowskiEngine emits no row for it -- collated batches never have one."""
+    mode = None
+
+    def __init__(self, mode=None):     # `mode`: ME's PoolingMode argument, which chooses among its own algorithms
+        super().__init__()
+
+    def forward(self, x):
+        cm = x.coordinate_manager
+        _origin_map(cm)
+        n = x.F.shape[0]
+        segs = cm.segments(x.coordinate_map_key) if n else (None, None, None, int(cm.batch_size or 0))
+        return SparseTensor(_GlobalPoolFn.apply(x.F, segs, self.mode), coordinate_manager=cm,
+                            coordinate_map_key=ORIGIN_KEY)
+
+
+class MinkowskiGlobalSumPooling(_GlobalPoolBase):
+    mode = "sum"
+
+
+class MinkowskiGlobalAvgPooling(_GlobalPoolBase):
+    mode = "avg"
+
+
+class MinkowskiGlobalMaxPooling(_GlobalPoolBase):
+    """utils/models/resnet_old.py:53"""
+    mode = "max"
+
+
+MinkowskiGlobalPooling = MinkowskiGlobalAvgPooling      # ME 0.5.4's alias
+
+
+class MinkowskiLinear(nn.Module):
+    """ME.MinkowskiLinear (utils/models/resnet_old.py:55): nn.Linear on the feature rows, parameters `linear.weight` /
+    `linear.bias` as in ME.  Runs as the library's 1x1 convolution (the gathered GEMM over the identity map) with the
+    transposed weight: the bits of a MinkowskiConvolution(kernel_size=1, bias=True) that holds the same numbers.  Always
+    fp32: a bf16 context counts it as precision.FP32."""
+
+    def __init__(self, in_features, out_features, bias=True):
+        super().__init__()
+        self.linear = nn.Linear(in_features, out_features, bias=bias)
+
+    def forward(self, x):
+        cm, key = x.coordinate_manager, x.coordinate_map_key
+        lin = self.linear
+        pctx = _precision.current()
+        if pctx is not None:
+            pctx.count(self, _precision.FP32)
+        m = cm.identity_map(x.F.shape[0])
+        cm.trace.append((("identity", key), lin.in_features, lin.out_features))
+        bias = lin.bias.view(1, -1) if lin.bias is not None else None
+        return x._like(_SparseConvFn.apply(x.F, lin.weight.t(), bias, m, False, True, True))
+
+
 # ------------------------------------------------------------------ utils
 def _fans(t):
     if t.dim() == 2:
@@ -1751,6 +2059,14 @@ class Bottleneck(nn.Module):
         return conv_bn(self.conv3, self.norm3, out, relu=True, residual=residual)
 
 
+def _functional_relu(x, inplace=False):
+    """MEF.relu (utils/models/resunet.py:39-255): MinkowskiReLU as a function"""
+    return MinkowskiReLU(inplace)(x)
+
+
+MinkowskiFunctional = types.ModuleType(__name__ + ".MinkowskiFunctional")
+MinkowskiFunctional.relu = _functional_relu
+
 modules = types.ModuleType(__name__ + ".modules")
 resnet_block = types.ModuleType(__name__ + ".modules.resnet_block")
 resnet_block.BasicBlock = BasicBlock
@@ -1763,5 +2079,6 @@ def install_as_minkowski_engine():
     sys.modules["MinkowskiEngine"] = me
     sys.modules["MinkowskiEngine.utils"] = utils
     sys.modules["MinkowskiEngine.modules"] = modules
+    sys.modules["MinkowskiEngine.MinkowskiFunctional"] = MinkowskiFunctional
     sys.modules["MinkowskiEngine.modules.resnet_block"] = resnet_block
     return me

@@ -307,7 +307,9 @@ int lidog_bev_pool_fwd(const float *feats, int32_t C, const int32_t *winner, con
                        void *stream);
 /* Backward of lidog_bev_pool_fwd as a gather over (voxel row, channel), no atomics (bit-reproducible): every row that
  * targets a pixel receives the gradient of the pixel's winning row's cells (index_put's backward, minkunet_bev.py:217),
- * a cell's gradient is the sum over the windows whose arg-max it was, in ascending window order. */
+ * a cell's gradient is the sum over the windows whose arg-max it was, in ascending window order.  Only the (argsrc, gout)
+ * pairs of windows that cover a cell of an occupied pixel enter the result; the kernel may LOAD a neighbouring pair of
+ * the same plane (index clamped) and drop it, so both images must be allocated in full but need not be initialised there. */
 int lidog_bev_pool_bwd(const float *gout /*[B,C,Ho,Wo]*/, const int32_t *argsrc, const int32_t *winner,
                        const int32_t *pixel, int64_t n, int32_t C, int32_t B, int32_t H, int32_t W, int32_t pk,
                        int32_t ps, int32_t pp, int32_t Ho, int32_t Wo, float *gfeats /*[n,C]*/, void *stream);

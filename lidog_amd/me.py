@@ -856,9 +856,20 @@ def _wgrad_items(m, Cin, Cout, bf16=False):
     return cache[chunk]
 
 
+def os_takes(Cin, Cout):
+    """the output-stationary 3^3 kernel (csrc/sconv_os.hip) takes these channel counts; THE owner of that choice, for
+    the operator path and the trunk executor's tables alike (the map needs sorted rows and sparse core 1 besides)"""
+    return Cin % 32 == 0 and Cout % 32 == 0
+
+
+def stem_takes(Cin, Cout, K):
+    """the stem kernel (lidog_sconv_cin1: one input channel, at most 48 KB of weights) takes this convolution"""
+    return Cin == 1 and Cout in (16, 32, 64) and K * Cout * 4 <= 48 * 1024
+
+
 def _os_rows(m, swap, Cin, Cout):
     """the sorted rows of the map if this convolution takes the output-stationary kernel, else None"""
-    if swap or isinstance(m, _IdentityMap) or Cin % 32 or Cout % 32 or _lib.load().lidog_get_sparse_core() != 1:
+    if swap or isinstance(m, _IdentityMap) or not os_takes(Cin, Cout) or _lib.load().lidog_get_sparse_core() != 1:
         return None
     return m.sorted()
 
@@ -920,8 +931,7 @@ def _conv_rows(x, B, m, swap, Cin, Cout, mirrored=False, direct=False, bias=None
         gemm(x, gather, B, bias, m, Cin, Cout, out, scatter)
         queued()
         route = _precision.GEMM_DIRECT
-    elif Cin == 1 and not (mirrored or swap or bf16) and bn is None and Cout in (16, 32, 64) and \
-            K * Cout * 4 <= 48 * 1024 and m.nbr is not None:
+    elif stem_takes(Cin, Cout, K) and not (mirrored or swap or bf16) and bn is None and m.nbr is not None:
         # the stem: straight from the neighbour table, no product rows (bit-identical to the two-pass path); the
         # BatchNorm statistics of its 32-channel output are then one small pass of their own.  Forward only: a data
         # gradient whose forward Cout is 1 arrives here with Cin = 1 too

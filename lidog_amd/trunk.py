@@ -34,6 +34,9 @@ OP_CONVBN, OP_CAT, OP_CONV = range(3)
 TC_COLS, TM_COLS, TO_COLS, TB_COLS, REC_COLS = 20, 20, 8, 4, 4
 (TC_KIND, TC_MAP, TC_CIN, TC_COUT, TC_K, TC_W, TC_WT, TC_GW, TC_BIAS, TC_GBIAS, TC_BNW, TC_BNB, TC_BNRM, TC_BNRV,
  TC_GBNW, TC_GBNB, TC_ITEMS, TC_NITEMS, TC_ITEMOFF, TC_ACC) = range(20)
+# the map table's columns, in the order of the enum in csrc/trunk.hip
+(TM_K, TM_NIN, TM_NOUT, TM_P, TM_PAIR_IN, TM_PAIR_OUT, TM_RP_OUT, TM_RL_OUT, TM_RP_IN, TM_RL_IN, TM_TILES, TM_NTILES,
+ TM_NBR, TM_IDENT, TM_PERM, TM_WMASK, TM_ORDER) = range(17)
 # external buffers: the input features and the tensors the model hands back
 EXT_X, EXT_OUT, EXT_LOGITS, EXT_BOTTLE, EXT_LV_BOTTLE, EXT_LV_BLOCK6, EXT_LV_BLOCK7 = range(7)
 N_EXT = 7
@@ -79,8 +82,7 @@ def _kind_of(conv):
     if ks == 2 and st == 2 and conv.in_channels % 4 == 0:
         return KIND_DOWN
     if ks % 2 == 1 and st == 1:
-        if conv.in_channels == 1 and conv.out_channels in (16, 32, 64) and \
-                conv.kernel_volume * conv.out_channels * 4 <= 48 * 1024:
+        if ME.stem_takes(conv.in_channels, conv.out_channels, conv.kernel_volume):
             return KIND_STEM
         if conv.in_channels % 4 == 0 and conv.out_channels % 4 == 0:
             return KIND_K3
@@ -187,7 +189,7 @@ class Program:
         for (cv, _, kind, _, _), mi in zip(self.convs, self.conv_map):
             if kind == KIND_K3:
                 self.rows_need[mi] |= {"out", "in"}
-                if cv.in_channels % 32 or cv.out_channels % 32:
+                if not ME.os_takes(cv.in_channels, cv.out_channels):
                     self.os_ok[mi] = False
             elif kind in (KIND_DOWN, KIND_UP):
                 self.rows_need[mi].add("out")
@@ -330,7 +332,7 @@ def _build_tables(prog, x, run):
             if key[1] not in cm.maps:
                 return None
             m = cm.identity_map(cm.maps[key[1]].n)
-            row = [1, m.n_in, m.n_out, m.P, 0, 0, 0, 0, 0, 0, _addr(m.tiles), m.n_tiles, 0, _addr(m.rows)]
+            row = {TM_K: 1, TM_IDENT: _addr(m.rows)}
         else:
             m = cm.kernel_map(*key)
             rp_o = rl_o = rp_i = rl_i = None
@@ -340,12 +342,13 @@ def _build_tables(prog, x, run):
                 rp_o, rl_o = m.rows("out")
             if "in" in prog.rows_need[i] and by_rows:
                 rp_i, rl_i = m.rows("in")
-            row = [m.K, m.n_in, m.n_out, m.P, _addr(m.pair_in), _addr(m.pair_out), _addr(rp_o), _addr(rl_o),
-                   _addr(rp_i), _addr(rl_i), _addr(m.tiles), m.n_tiles, _addr(m.nbr), 0, _addr(srt[0]), _addr(srt[1]),
-                   _addr(srt[2])]
+            row = {TM_K: m.K, TM_PAIR_IN: _addr(m.pair_in), TM_PAIR_OUT: _addr(m.pair_out), TM_RP_OUT: _addr(rp_o),
+                   TM_RL_OUT: _addr(rl_o), TM_RP_IN: _addr(rp_i), TM_RL_IN: _addr(rl_i), TM_NBR: _addr(m.nbr),
+                   TM_PERM: _addr(srt[0]), TM_WMASK: _addr(srt[1]), TM_ORDER: _addr(srt[2])}
         if m.P == 0 or m.n_tiles == 0 or not m.tiles.is_contiguous():
             return None
-        maps[i, :len(row)] = row
+        row.update({TM_NIN: m.n_in, TM_NOUT: m.n_out, TM_P: m.P, TM_TILES: _addr(m.tiles), TM_NTILES: m.n_tiles})
+        maps[i, list(row)] = list(row.values())
         mobjs.append(m)
     levels = []
     for lv in range(N_LEVELS):

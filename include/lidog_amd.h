@@ -358,7 +358,7 @@ int lidog_conv2d_wgrad_sparse(const float *x, const float *gy, const int32_t *ac
 /* ------------------------------------------------------------------ DICE losses
  * utils/losses/losses.py:56-97 (DICELoss: soft = 0) and :100-187 (SoftDICELoss: soft = 1, label smoothing eps,
  * powerize, present-class mask), as called by trainer_lighting_2d.py:172-190.  logits [n, C] float32 (C in
- * {2, 7, 8, 16}), target [n] int64; rows with target == ignore_label are skipped when has_ignore != 0.
+ * 2..20), target [n] int64; rows with target == ignore_label are skipped when has_ignore != 0.
  * fwd: loss[0] = 1 - mean present-class DICE + offset (offset = -1 for neg_range); coef [2C] receives the
  * per-class gradient coefficients bwd needs; ws: lidog_dice_ws(C) doubles.  bwd: glogits = d loss / d logits * gout[0]. */
 int64_t lidog_dice_ws(int32_t C);
@@ -368,6 +368,34 @@ int lidog_dice_fwd(const float *logits, const int64_t *target, int64_t n, int32_
 int lidog_dice_bwd(const float *logits, const int64_t *target, int64_t n, int32_t C, int64_t ignore_label,
                    int32_t has_ignore, float eps, int32_t soft, int32_t powerize, const float *coef, const float *gout,
                    float *glogits, void *stream);
+/* SoftDICELoss(is_kitti=True) (get_kitti_soft, losses.py:112-126): the label-smoothed targets, except that a row
+ * labelled 1 or 6 carries (1 - eps) / 2 on classes 1 and 6 both; the present-class mask still counts the hard label.
+ * Same workspace, coefficients and contract as lidog_dice_fwd / _bwd with soft = 1; C in 7..20, anything else returns 2
+ * before any launch. */
+int lidog_dice_kitti_fwd(const float *logits, const int64_t *target, int64_t n, int32_t C, int64_t ignore_label,
+                         int32_t has_ignore, float eps, int32_t powerize, int32_t use_tmask, float offset, double *ws,
+                         float *loss, float *coef, void *stream);
+int lidog_dice_kitti_bwd(const float *logits, const int64_t *target, int64_t n, int32_t C, int64_t ignore_label,
+                         int32_t has_ignore, float eps, int32_t powerize, const float *coef, const float *gout,
+                         float *glogits, void *stream);
+
+/* ------------------------------------------------------------------ weighted cross-entropy and focal loss
+ * utils/losses/losses.py:8-25 (CELoss = nn.CrossEntropyLoss(weight, ignore_index), mean reduction) and :423-436
+ * (FocalLoss: alpha (1 - exp(-ce))^gamma ce, a scalar function of that mean).  logits [n, C] float32 (C in 2..20),
+ * target [n] int64, weight [C] float32 or NULL (all ones).  A row takes part when its label is not ignore_label (with
+ * has_ignore != 0) and lies in [0, C); torch asserts on the device for a label outside, here such a row has zero weight
+ * and a zero gradient, and weight is never read for it.
+ * fwd: ce = sum w[t] (lse(x) - x[t]) / sum w[t]; loss[0] = ce (focal = 0) or the focal loss; coef[0] =
+ * (d loss / d ce) / sum w[t]; ws: lidog_ce_ws(C) doubles (per-workgroup partials, added in a fixed order).
+ * bwd: glogits[r][c] = gout[0] * coef[0] * w[t] * (softmax(x_r)[c] - [c == t]); +0 in the rows that take no part.
+ * Both return 2 on a bad shape before any launch; bwd returns 0 for n == 0. */
+int64_t lidog_ce_ws(int32_t C);
+int lidog_ce_fwd(const float *logits, const int64_t *target, int64_t n, int32_t C, int64_t ignore_label,
+                 int32_t has_ignore, const float *weight, int32_t focal, double alpha, double gamma, double *ws,
+                 float *loss, float *coef, void *stream);
+int lidog_ce_bwd(const float *logits, const int64_t *target, int64_t n, int32_t C, int64_t ignore_label,
+                 int32_t has_ignore, const float *weight, const float *coef, const float *gout, float *glogits,
+                 void *stream);
 
 /* ------------------------------------------------------------------ data path next to the hot path
  * ME.utils.sparse_quantize (utils/datasets/semantickitti_bev.py:232-238) = lidog_voxel_floor +

@@ -99,6 +99,11 @@ SIGNATURES = {
     "lidog_dice_ws": [_i32],
     "lidog_dice_fwd": [_p, _p, _i64, _i32, _i64, _i32, _f, _i32, _i32, _i32, _f, _p, _p, _p, _p],
     "lidog_dice_bwd": [_p, _p, _i64, _i32, _i64, _i32, _f, _i32, _i32, _p, _p, _p, _p],
+    "lidog_dice_kitti_fwd": [_p, _p, _i64, _i32, _i64, _i32, _f, _i32, _i32, _f, _p, _p, _p, _p],
+    "lidog_dice_kitti_bwd": [_p, _p, _i64, _i32, _i64, _i32, _f, _i32, _p, _p, _p, _p],
+    "lidog_ce_ws": [_i32],
+    "lidog_ce_fwd": [_p, _p, _i64, _i32, _i64, _i32, _p, _i32, _d, _d, _p, _p, _p, _p],
+    "lidog_ce_bwd": [_p, _p, _i64, _i32, _i64, _i32, _p, _p, _p, _p, _p],
     "lidog_adam_step": [_p, _p, _p, _p, _i64, _f, _f, _f, _f, _f, _i32, _f, _p],
     "lidog_sgd_step": [_p, _p, _p, _i64, _f, _f, _f, _i32, _f, _p],
     "lidog_comm_unique_id_bytes": [],
@@ -176,7 +181,7 @@ SIGNATURES = {
     "lidog_pool_global_bwd": [_p, _p, _i64, _i32, _i32, _p, _p, _i32, _p, _p],
 }
 _RESTYPES = {"lidog_hash_capacity": _i64, "lidog_sconv_reduce_stats_ws": _i64, "lidog_bn_reduce_ws": _i64,
-             "lidog_dice_ws": _i64, "lidog_colsum_ws": _i64, "lidog_conv2d_support_ws": _i64, "lidog_conv2d_wgrad_sparse_ws": _i64,
+             "lidog_dice_ws": _i64, "lidog_ce_ws": _i64, "lidog_colsum_ws": _i64, "lidog_conv2d_support_ws": _i64, "lidog_conv2d_wgrad_sparse_ws": _i64,
              "lidog_tiles_host": _i64, "lidog_wgrad_items_host": _i64, "lidog_bitmap_words": _i64,
              "lidog_bn_bwd_reduce_blocks": _i64, "lidog_relu_bits_words": _i64,
              "lidog_peer_mailbox_bytes": _i64, "lidog_peer_calls": _i64,

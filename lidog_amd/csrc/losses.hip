@@ -8,6 +8,11 @@
 //   loss = 1 - sum_c present_c * 2 I_c / U_c / (sum_c present_c + 1e-12),
 //   I_c = sum_r p_rc t_rc,  U_c = sum_r (p_rc^2 or p_rc) + sum_r t_rc + 1e-12,
 //   t = one-hot (DICE) or label-smoothed one-hot (soft: 1-eps / eps/(C-1)); rows with the ignore label are skipped.
+//   KITTI soft labels (get_kitti_soft, losses.py:112-126; `kitti` != 0): a row labelled 1 or 6 carries (1-eps)/2 on
+//   classes 1 and 6 both; the present-class count still takes the hard label.
+// Weighted cross-entropy and the focal loss on top of it (CELoss losses.py:8-25, FocalLoss :423-436), further down:
+//   ce = sum_r w[t_r] (lse(x_r) - x_r[t_r]) / sum_r w[t_r] over the rows whose label is neither the ignore label nor
+//   outside [0, C);  focal = alpha (1 - exp(-ce))^gamma ce, a scalar function of ce: one pass each way for both.
 #include "common.h"
 
 #define DL_MAXC 20
@@ -33,7 +38,7 @@ __device__ __forceinline__ void softmax_row(const float *__restrict__ x, float (
 template <int C>
 __global__ __launch_bounds__(256) void k_dice_sums(const float *__restrict__ logits, const int64_t *__restrict__ target,
                                                    int64_t n, int64_t ignore, int has_ignore, float t_on, float t_off,
-                                                   int powerize, double *__restrict__ partial) {
+                                                   int powerize, int kitti, double *__restrict__ partial) {
     __shared__ double red[4][4 * C];
     float acc[4 * C];
 #pragma unroll
@@ -43,10 +48,11 @@ __global__ __launch_bounds__(256) void k_dice_sums(const float *__restrict__ log
         if (has_ignore && t == ignore) continue;
         float p[C];
         softmax_row<C>(logits + r * C, p);
+        const bool pair = kitti && (t == 1 || t == 6);   // classes 1 and 6 share the row's mass
 #pragma unroll
         for (int c = 0; c < C; ++c) {
             const bool on = (t == c);
-            const float tw = on ? t_on : t_off;
+            const float tw = (pair && (c == 1 || c == 6)) ? 0.5f * t_on : (on ? t_on : t_off);
             acc[c] += p[c] * tw;
             acc[C + c] += powerize ? p[c] * p[c] : p[c];
             acc[2 * C + c] += tw;
@@ -111,7 +117,7 @@ __global__ __launch_bounds__(1024) void k_dice_finish(const double *__restrict__
 template <int C>
 __global__ __launch_bounds__(256) void k_dice_bwd(const float *__restrict__ logits, const int64_t *__restrict__ target,
                                                   int64_t n, int64_t ignore, int has_ignore, float t_on, float t_off,
-                                                  int powerize, const float *__restrict__ coef,
+                                                  int powerize, int kitti, const float *__restrict__ coef,
                                                   const float *__restrict__ gout, float *__restrict__ glogits) {
     float a[C], b[C];
 #pragma unroll
@@ -131,9 +137,10 @@ __global__ __launch_bounds__(256) void k_dice_bwd(const float *__restrict__ logi
         float p[C], gp[C];
         softmax_row<C>(logits + r * C, p);
         float dot = 0.f;
+        const bool pair = kitti && (t == 1 || t == 6);
 #pragma unroll
         for (int c = 0; c < C; ++c) {
-            const float tw = (t == c) ? t_on : t_off;
+            const float tw = (pair && (c == 1 || c == 6)) ? 0.5f * t_on : ((t == c) ? t_on : t_off);
             gp[c] = a[c] * tw + b[c] * (powerize ? 2.f * p[c] : 1.f);
             dot += p[c] * gp[c];
         }
@@ -176,15 +183,14 @@ extern "C" int64_t lidog_dice_ws(int32_t C) { return (int64_t)DL_MAX_BLOCKS * 4 
         default: LIDOG_REQUIRE(false, "dice: C must be in [2, 20]");            \
     }
 
-extern "C" int lidog_dice_fwd(const float *logits, const int64_t *target, int64_t n, int32_t C, int64_t ignore_label,
-                              int32_t has_ignore, float eps, int32_t soft, int32_t powerize, int32_t use_tmask,
-                              float offset, double *ws, float *loss, float *coef, void *stream) {
-    hipStream_t st = (hipStream_t)stream;
+static int dice_fwd(const float *logits, const int64_t *target, int64_t n, int32_t C, int64_t ignore_label,
+                    int32_t has_ignore, float eps, int32_t soft, int32_t powerize, int32_t use_tmask, float offset,
+                    int32_t kitti, double *ws, float *loss, float *coef, hipStream_t st) {
     LIDOG_REQUIRE(n >= 0 && C >= 2 && C <= DL_MAXC, "dice: bad shape");
     const float t_on = soft ? 1.f - eps : 1.f, t_off = soft ? eps / (float)(C - 1) : 0.f;
     const int nb = dice_blocks(n);
 #define CALL(C_) \
-    k_dice_sums<C_><<<nb, 256, 0, st>>>(logits, target, n, ignore_label, has_ignore, t_on, t_off, powerize, ws)
+    k_dice_sums<C_><<<nb, 256, 0, st>>>(logits, target, n, ignore_label, has_ignore, t_on, t_off, powerize, kitti, ws)
     DICE_DISPATCH(CALL)
 #undef CALL
     k_dice_finish<<<1, 1024, 0, st>>>(ws, nb, C, use_tmask, offset, loss, coef);   // 8 lanes x 4C <= 80 columns
@@ -192,17 +198,187 @@ extern "C" int lidog_dice_fwd(const float *logits, const int64_t *target, int64_
     return 0;
 }
 
-extern "C" int lidog_dice_bwd(const float *logits, const int64_t *target, int64_t n, int32_t C, int64_t ignore_label,
-                              int32_t has_ignore, float eps, int32_t soft, int32_t powerize, const float *coef,
-                              const float *gout, float *glogits, void *stream) {
-    hipStream_t st = (hipStream_t)stream;
+static int dice_bwd(const float *logits, const int64_t *target, int64_t n, int32_t C, int64_t ignore_label,
+                    int32_t has_ignore, float eps, int32_t soft, int32_t powerize, int32_t kitti, const float *coef,
+                    const float *gout, float *glogits, hipStream_t st) {
     if (n == 0) return 0;
     const float t_on = soft ? 1.f - eps : 1.f, t_off = soft ? eps / (float)(C - 1) : 0.f;
     int64_t nb = cdiv64(n, 256);
     if (nb > 4096) nb = 4096;
 #define CALL(C_)                                                                                                \
     k_dice_bwd<C_><<<(unsigned)nb, 256, 0, st>>>(logits, target, n, ignore_label, has_ignore, t_on, t_off, powerize, \
-                                                 coef, gout, glogits)
+                                                 kitti, coef, gout, glogits)
+    DICE_DISPATCH(CALL)
+#undef CALL
+    LIDOG_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int lidog_dice_fwd(const float *logits, const int64_t *target, int64_t n, int32_t C, int64_t ignore_label,
+                              int32_t has_ignore, float eps, int32_t soft, int32_t powerize, int32_t use_tmask,
+                              float offset, double *ws, float *loss, float *coef, void *stream) {
+    return dice_fwd(logits, target, n, C, ignore_label, has_ignore, eps, soft, powerize, use_tmask, offset, 0, ws, loss,
+                    coef, (hipStream_t)stream);
+}
+
+extern "C" int lidog_dice_bwd(const float *logits, const int64_t *target, int64_t n, int32_t C, int64_t ignore_label,
+                              int32_t has_ignore, float eps, int32_t soft, int32_t powerize, const float *coef,
+                              const float *gout, float *glogits, void *stream) {
+    return dice_bwd(logits, target, n, C, ignore_label, has_ignore, eps, soft, powerize, 0, coef, gout, glogits,
+                    (hipStream_t)stream);
+}
+
+// SoftDICELoss(is_kitti=True): always the label-smoothed targets; classes 1 and 6 must exist
+extern "C" int lidog_dice_kitti_fwd(const float *logits, const int64_t *target, int64_t n, int32_t C,
+                                    int64_t ignore_label, int32_t has_ignore, float eps, int32_t powerize,
+                                    int32_t use_tmask, float offset, double *ws, float *loss, float *coef,
+                                    void *stream) {
+    LIDOG_REQUIRE(C >= 7, "dice_kitti: the soft labels pair classes 1 and 6: C must be in [7, 20]");
+    return dice_fwd(logits, target, n, C, ignore_label, has_ignore, eps, 1, powerize, use_tmask, offset, 1, ws, loss,
+                    coef, (hipStream_t)stream);
+}
+
+extern "C" int lidog_dice_kitti_bwd(const float *logits, const int64_t *target, int64_t n, int32_t C,
+                                    int64_t ignore_label, int32_t has_ignore, float eps, int32_t powerize,
+                                    const float *coef, const float *gout, float *glogits, void *stream) {
+    LIDOG_REQUIRE(n >= 0 && C >= 7 && C <= DL_MAXC, "dice_kitti: bad shape (C must be in [7, 20])");
+    return dice_bwd(logits, target, n, C, ignore_label, has_ignore, eps, 1, powerize, 1, coef, gout, glogits,
+                    (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------ weighted cross-entropy, focal loss
+// A row takes part when its label is not the ignore label and lies in [0, C) (torch asserts on the device for any other
+// label; a kernel cannot raise without a synchronisation, so such a row gets zero weight and a zero gradient, and the
+// weight table is never read for it).
+// partial[block][2] = (sum w[t] nll, sum w[t])
+template <int C>
+__global__ __launch_bounds__(256) void k_ce_sums(const float *__restrict__ logits, const int64_t *__restrict__ target,
+                                                 int64_t n, int64_t ignore, int has_ignore,
+                                                 const float *__restrict__ weight, double *__restrict__ partial) {
+    __shared__ double red[4][2];
+    float acc_s = 0.f, acc_w = 0.f;
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n; r += (int64_t)gridDim.x * 256) {
+        const int64_t t = target[r];
+        if ((has_ignore && t == ignore) || t < 0 || t >= C) continue;
+        const float *x = logits + r * C;
+        float v[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) v[c] = x[c];
+        float m = v[0], xt = v[0];
+#pragma unroll
+        for (int c = 1; c < C; ++c) {
+            m = fmaxf(m, v[c]);
+            xt = (t == c) ? v[c] : xt;
+        }
+        float s = 0.f;
+#pragma unroll
+        for (int c = 0; c < C; ++c) s += expf(v[c] - m);
+        const float nll = logf(s) - (xt - m);
+        const float w = weight ? weight[t] : 1.f;
+        acc_s += w * nll;
+        acc_w += w;
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double vs = (double)acc_s, vw = (double)acc_w;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        vs += __shfl_down(vs, d);
+        vw += __shfl_down(vw, d);
+    }
+    if (lane == 0) {
+        red[wave][0] = vs;
+        red[wave][1] = vw;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2)
+        partial[(size_t)blockIdx.x * 2 + threadIdx.x] =
+            red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+}
+
+// one block: (S, W) over the partials in a fixed order; ce = S / W; loss = ce or alpha (1 - exp(-ce))^gamma ce;
+// coef[0] = (d loss / d ce) / W, the one coefficient the backward pass needs
+__global__ __launch_bounds__(256) void k_ce_finish(const double *__restrict__ partial, int nb, int focal, double alpha,
+                                                   double gamma, float *__restrict__ loss, float *__restrict__ coef) {
+    __shared__ double part[256][2];
+    double s = 0, w = 0;
+    for (int b = threadIdx.x; b < nb; b += 256) {
+        s += partial[(size_t)b * 2];
+        w += partial[(size_t)b * 2 + 1];
+    }
+    part[threadIdx.x][0] = s;
+    part[threadIdx.x][1] = w;
+    __syncthreads();
+    for (int d = 128; d >= 1; d >>= 1) {      // a fixed tree: bit-reproducible
+        if ((int)threadIdx.x < d) {
+            part[threadIdx.x][0] += part[threadIdx.x + d][0];
+            part[threadIdx.x][1] += part[threadIdx.x + d][1];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double S = part[0][0], W = part[0][1];
+        const double ce = S / W;
+        double l = ce, dl = 1.0;
+        if (focal) {
+            const double pt = exp(-ce), q = 1.0 - pt;
+            const double qg = pow(q, gamma);
+            l = alpha * qg * ce;
+            // d/dce: gamma q^(gamma-1) pt ce + q^gamma; a zero exponent has a zero derivative whatever q is
+            dl = alpha * ((gamma == 0.0 ? 0.0 : gamma * pow(q, gamma - 1.0) * pt * ce) + qg);
+        }
+        loss[0] = (float)l;
+        coef[0] = (float)(dl / W);
+    }
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void k_ce_bwd(const float *__restrict__ logits, const int64_t *__restrict__ target,
+                                                int64_t n, int64_t ignore, int has_ignore,
+                                                const float *__restrict__ weight, const float *__restrict__ coef,
+                                                const float *__restrict__ gout, float *__restrict__ glogits) {
+    const float gk = gout[0] * coef[0];
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n; r += (int64_t)gridDim.x * 256) {
+        const int64_t t = target[r];
+        float *g = glogits + r * C;
+        if ((has_ignore && t == ignore) || t < 0 || t >= C) {
+#pragma unroll
+            for (int c = 0; c < C; ++c) g[c] = 0.f;
+            continue;
+        }
+        float p[C];
+        softmax_row<C>(logits + r * C, p);
+        const float s = gk * (weight ? weight[t] : 1.f);
+#pragma unroll
+        for (int c = 0; c < C; ++c) g[c] = s * (p[c] - ((t == c) ? 1.f : 0.f));
+    }
+}
+
+extern "C" int64_t lidog_ce_ws(int32_t C) { return (int64_t)DL_MAX_BLOCKS * 2; }
+
+extern "C" int lidog_ce_fwd(const float *logits, const int64_t *target, int64_t n, int32_t C, int64_t ignore_label,
+                            int32_t has_ignore, const float *weight, int32_t focal, double alpha, double gamma,
+                            double *ws, float *loss, float *coef, void *stream) {
+    hipStream_t st = (hipStream_t)stream;
+    LIDOG_REQUIRE(n >= 0 && C >= 2 && C <= DL_MAXC, "ce: bad shape");
+    const int nb = dice_blocks(n);
+#define CALL(C_) k_ce_sums<C_><<<nb, 256, 0, st>>>(logits, target, n, ignore_label, has_ignore, weight, ws)
+    DICE_DISPATCH(CALL)
+#undef CALL
+    k_ce_finish<<<1, 256, 0, st>>>(ws, nb, focal, alpha, gamma, loss, coef);
+    LIDOG_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int lidog_ce_bwd(const float *logits, const int64_t *target, int64_t n, int32_t C, int64_t ignore_label,
+                            int32_t has_ignore, const float *weight, const float *coef, const float *gout,
+                            float *glogits, void *stream) {
+    hipStream_t st = (hipStream_t)stream;
+    LIDOG_REQUIRE(n >= 0 && C >= 2 && C <= DL_MAXC, "ce: bad shape");
+    if (n == 0) return 0;
+    int64_t nb = cdiv64(n, 256);
+    if (nb > 4096) nb = 4096;
+#define CALL(C_) \
+    k_ce_bwd<C_><<<(unsigned)nb, 256, 0, st>>>(logits, target, n, ignore_label, has_ignore, weight, coef, gout, glogits)
     DICE_DISPATCH(CALL)
 #undef CALL
     LIDOG_LAUNCH_CHECK();

@@ -1,7 +1,11 @@
-"""DICE losses of the LiDOG step, kept on the device (the reference moves logits to the CPU first).
+"""The training criteria, kept on the device (the reference moves logits to the CPU first).
 
-  SoftDICELoss  utils/losses/losses.py:100-109,129-187  (powerize, present-class mask, eps = 0.05)
+  SoftDICELoss  utils/losses/losses.py:100-126,129-187  (powerize, present-class mask, eps = 0.05; is_kitti: the
+                                                         19-class soft labels that pair classes 1 and 6)
   DICELoss      utils/losses/losses.py:56-97            (hard one-hot, no mask)
+  CELoss        utils/losses/losses.py:8-25             (nn.CrossEntropyLoss(weight, ignore_index), mean)
+  FocalLoss     utils/losses/losses.py:423-436          (alpha (1 - exp(-ce))^gamma ce on that mean)
+  make_criterion / make_bev_criterion                   (init_losses of utils/pipelines/trainer_lighting*.py)
   IWLoss        utils/losses/losses.py:464-485          (RobustNet's instance-whitening loss, csrc/iwloss.hip)
   CovMatrix_IRW utils/models/cov_settings.py:4-25        (its eye / mask helper)
 Same formulas as the reference, as HIP kernels (csrc/losses.hip; there is no torch formula behind them: CPU tensors and
@@ -24,7 +28,7 @@ class _DiceFn(torch.autograd.Function):
     """csrc/losses.hip: softmax + the per-class sums in one pass, the gradient in one pass"""
 
     @staticmethod
-    def forward(ctx, logits, target, ignore_label, eps, soft, powerize, use_tmask, offset):
+    def forward(ctx, logits, target, ignore_label, eps, soft, powerize, use_tmask, offset, kitti=False):
         logits, target = logits.contiguous(), target.contiguous()
         if target.dtype != torch.int64:
             target = target.long()
@@ -34,24 +38,25 @@ class _DiceFn(torch.autograd.Function):
         loss = torch.empty((), dtype=torch.float32, device=dev)
         coef = torch.empty(2 * C, dtype=torch.float32, device=dev)
         has_ignore = ignore_label is not None
-        cfg = (n, C, int(ignore_label) if has_ignore else 0, 1 if has_ignore else 0, float(eps), 1 if soft else 0,
-               1 if powerize else 0)
-        call("lidog_dice_fwd", ptr(logits), ptr(target), *cfg, 1 if use_tmask else 0, float(offset), ptr(ws),
-             ptr(loss), ptr(coef))
+        cfg = (n, C, int(ignore_label) if has_ignore else 0, 1 if has_ignore else 0, float(eps))
+        cfg += (1 if powerize else 0,) if kitti else (1 if soft else 0, 1 if powerize else 0)   # the KITTI entry is soft
+        call("lidog_dice_kitti_fwd" if kitti else "lidog_dice_fwd", ptr(logits), ptr(target), *cfg,
+             1 if use_tmask else 0, float(offset), ptr(ws), ptr(loss), ptr(coef))
         ctx.save_for_backward(logits, target, coef)
-        ctx.cfg = cfg
+        ctx.cfg, ctx.kitti = cfg, kitti
         return loss
 
     @staticmethod
     def backward(ctx, gout):
         logits, target, coef = ctx.saved_tensors
         g = torch.empty_like(logits)
-        call("lidog_dice_bwd", ptr(logits), ptr(target), *ctx.cfg, ptr(coef), ptr(gout.contiguous()), ptr(g))
-        return g, None, None, None, None, None, None, None
+        call("lidog_dice_kitti_bwd" if ctx.kitti else "lidog_dice_bwd", ptr(logits), ptr(target), *ctx.cfg, ptr(coef),
+             ptr(gout.contiguous()), ptr(g))
+        return g, None, None, None, None, None, None, None, None
 
 
 def _check(output):
-    """the DICE losses exist as HIP kernels only (csrc/losses.hip): no torch formula behind them"""
+    """the criteria exist as HIP kernels only (csrc/losses.hip): no torch formula behind them"""
     _lib.require_gpu(output, "logits")
     if output.dim() != 2 or output.shape[1] not in _FUSED_CLASSES or output.dtype != torch.float32:
         raise NotImplementedError(f"lidog_amd DICE losses take float32 logits [n, C] with C in {_FUSED_CLASSES}, "
@@ -61,15 +66,18 @@ def _check(output):
 class SoftDICELoss(nn.Module):
     def __init__(self, ignore_label=None, powerize=True, use_tmask=True, neg_range=False, eps=0.05, is_kitti=False):
         super().__init__()
-        if is_kitti:
-            raise NotImplementedError("the 19-class KITTI soft-label variant is not on the LiDOG hot path")
-        self.ignore_label, self.powerize, self.use_tmask, self.neg_range, self.eps = \
-            ignore_label, powerize, use_tmask, neg_range, eps
+        self.ignore_label, self.powerize, self.use_tmask, self.neg_range, self.eps, self.is_kitti = \
+            ignore_label, powerize, use_tmask, neg_range, eps, is_kitti
 
-    def forward(self, output, target):
+    def forward(self, output, target, is_kitti=False):
+        """`is_kitti` here or in the constructor: get_kitti_soft's targets (a row labelled 1 or 6 carries (1 - eps) / 2
+        on classes 1 and 6 both), which need C >= 7"""
         _check(output)
+        kitti = bool(self.is_kitti or is_kitti)
+        if kitti and output.shape[1] < 7:
+            raise ValueError(f"SoftDICELoss(is_kitti=True) pairs classes 1 and 6: C = {output.shape[1]} < 7")
         return _DiceFn.apply(output, target, self.ignore_label, self.eps, True, self.powerize, self.use_tmask,
-                             -1.0 if self.neg_range else 0.0)
+                             -1.0 if self.neg_range else 0.0, kitti)
 
 
 class DICELoss(nn.Module):
@@ -80,6 +88,117 @@ class DICELoss(nn.Module):
     def forward(self, output, target):
         _check(output)
         return _DiceFn.apply(output, target, self.ignore_label, 0.0, False, self.powerize, self.use_tmask, 0.0)
+
+
+# ------------------------------------------------------------------ cross-entropy and focal loss
+class _CEFn(torch.autograd.Function):
+    """csrc/losses.hip: the weighted log-sum-exp sums in one pass, the gradient in one pass; `focal`: None or
+    (alpha, gamma)"""
+
+    @staticmethod
+    def forward(ctx, logits, target, ignore_label, weight, focal):
+        logits, target = logits.contiguous(), target.contiguous()
+        if target.dtype != torch.int64:
+            target = target.long()
+        n, C = logits.shape
+        dev = logits.device
+        ws = torch.empty(_lib.load().lidog_ce_ws(C), dtype=torch.float64, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        coef = torch.empty(1, dtype=torch.float32, device=dev)
+        has_ignore = ignore_label is not None
+        cfg = (n, C, int(ignore_label) if has_ignore else 0, 1 if has_ignore else 0, ptr(weight))
+        alpha, gamma = focal if focal is not None else (1.0, 0.0)
+        call("lidog_ce_fwd", ptr(logits), ptr(target), *cfg, 0 if focal is None else 1, float(alpha), float(gamma),
+             ptr(ws), ptr(loss), ptr(coef))
+        ctx.save_for_backward(logits, target, coef)
+        ctx.cfg, ctx.weight = cfg, weight       # the table itself: cfg holds its address only
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        logits, target, coef = ctx.saved_tensors
+        g = torch.empty_like(logits)
+        call("lidog_ce_bwd", ptr(logits), ptr(target), *ctx.cfg, ptr(coef), ptr(gout.contiguous()), ptr(g))
+        return g, None, None, None, None
+
+
+class _WeightedCE(nn.Module):
+    """what CELoss and FocalLoss share: the class-weight table, uploaded once, and the checks"""
+
+    def __init__(self, ignore_label, weight):
+        super().__init__()
+        self.ignore_label = ignore_label
+        if weight is not None:
+            weight = torch.as_tensor(weight).detach().float().contiguous()
+            if weight.dim() != 1:
+                raise ValueError(f"the class weights are a vector [C], got {tuple(weight.shape)}")
+            if not weight.is_cuda:
+                weight = weight.cuda() if torch.cuda.is_available() else weight
+        self.register_buffer("weight", weight, persistent=False)
+
+    def _apply_fn(self, output, target, focal):
+        _check(output)
+        w = self.weight
+        if w is not None:
+            if w.shape[0] != output.shape[1]:
+                raise ValueError(f"{w.shape[0]} class weights for logits with C = {output.shape[1]}")
+            if w.device != output.device:       # a module built before the GPU was there, or moved
+                self.weight = w = w.to(output.device)
+        return _CEFn.apply(output, target, self.ignore_label, w, focal)
+
+
+class CELoss(_WeightedCE):
+    """nn.CrossEntropyLoss(weight, ignore_index=ignore_label), mean reduction.  `weight`: numpy array (as in the
+    reference) or tensor [C]; `ignore_label=None`: no row is ignored.  A label outside [0, C) other than the ignore label
+    takes no part (torch asserts on the device)."""
+
+    def __init__(self, ignore_label=None, weight=None):
+        super().__init__(ignore_label, weight)
+
+    def forward(self, preds, gt):
+        return self._apply_fn(preds, gt, None)
+
+
+class FocalLoss(_WeightedCE):
+    """-(1 - pt)^gamma alpha log pt with log pt = -CE(preds, labels), the mean cross-entropy: a scalar function of it"""
+
+    def __init__(self, alpha=0.5, gamma=2, weight=None, ignore_index=-1):
+        super().__init__(ignore_index, weight)
+        self.alpha, self.gamma, self.ignore_index = alpha, gamma, ignore_index
+
+    def forward(self, preds, labels):
+        return self._apply_fn(preds, labels, (self.alpha, self.gamma))
+
+
+POINT_CRITERIA = ("CELoss", "DICELoss", "SoftDICELoss", "FocalLoss")
+BEV_CRITERIA = ("DICELoss", "SoftDICELoss", "CELoss")
+
+
+def make_criterion(name, ignore_label=-1, num_classes=7):
+    """losses.sem_criterion of init_losses (trainer_lighting.py:73-90): FocalLoss is (alpha 0.25, gamma 2) and keeps its
+    own default ignore_index of -1, as there; SoftDICELoss takes the KITTI soft labels as soon as num_classes == 19; any
+    other name raises"""
+    if name == "CELoss":
+        return CELoss(ignore_label=ignore_label, weight=None)
+    if name == "DICELoss":
+        return DICELoss(ignore_label=ignore_label)
+    if name == "SoftDICELoss":
+        return SoftDICELoss(ignore_label=ignore_label, is_kitti=num_classes == 19)
+    if name == "FocalLoss":
+        return FocalLoss(alpha=0.25, gamma=2)
+    raise NotImplementedError(f"sem_criterion {name!r}: one of {POINT_CRITERIA}")
+
+
+def make_bev_criterion(name, ignore_label=-1):
+    """losses.sem_bev_criterion of init_losses (trainer_lighting_2d.py:107-116; SoftDICELoss without the KITTI rule, as
+    there).  The reference falls through to CELoss for every other name; here another name raises."""
+    if name == "DICELoss":
+        return DICELoss(ignore_label=ignore_label)
+    if name == "SoftDICELoss":
+        return SoftDICELoss(ignore_label=ignore_label)
+    if name == "CELoss":
+        return CELoss(ignore_label=ignore_label, weight=None)
+    raise NotImplementedError(f"sem_bev_criterion {name!r}: one of {BEV_CRITERIA}")
 
 
 # ------------------------------------------------------------------ instance-whitening loss (RobustNet)

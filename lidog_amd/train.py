@@ -43,6 +43,7 @@ from .data import (augment_item, check_augmentations, collate_items, cosmix_merg
                    draw_scaling, draw_source, mix3d_merge, on_merge_stream, pointcutmix_merge, scaling_params, sn_scale)
 from . import precision as _precision
 from .evaluate import CLASS_NAMES, per_class_iou
+from .losses import BEV_CRITERIA, POINT_CRITERIA
 from .metrics import MetricLayout, MetricsWriter, StepMetrics
 from .optim import make_optimizer, make_scheduler, shard_indices
 from .trainer import LiDOGStep, RobustStep, SourceStep, setup_data_parallel
@@ -530,21 +531,26 @@ def build_model(kind="MinkUNet34BEV", bound_2d=50.0, in_channels=1, out_channels
 
 def build_step(model, kind="MinkUNet34BEV", optimizer="Adam", lr=1e-3, scheduler=None, weight_decay=1e-4,
                momentum=0.98, warmup_epochs=0, source_weights=(0.5, 0.5), num_classes=7, ignore_label=-1, num_sources=1,
-               precision=None):
+               precision=None, sem_criterion="SoftDICELoss", sem_bev_criterion=None):
     """SyncBN conversion when data-parallel (train_lidog.py:227-231), optimiser + scheduler
     (trainer_lighting_2d.py:349-394), step object (PLTTrainer2D / PLTRobustNet / PLTTrainer, on one or two sources).
-    `precision`: the training steps' (trainer._Step).  Returns (model, step, scheduler)."""
+    `precision`: the training steps' (trainer._Step).  `sem_criterion` / `sem_bev_criterion`: the point and BEV losses by
+    name (losses.make_criterion / make_bev_criterion); the BEV one (None: DICELoss) belongs to MinkUNet34BEV alone.
+    Returns (model, step, scheduler)."""
     if num_sources not in (1, 2):
         raise NotImplementedError(f"{num_sources} sources (the reference takes one or two)")
+    if sem_bev_criterion is not None and kind != "MinkUNet34BEV":
+        raise ValueError(f"sem_bev_criterion={sem_bev_criterion!r}: {kind} has no BEV head")
     if _precision.resolve(precision):
         _precision.check_single_rank()
     model = setup_data_parallel(model)
     model.train()
     opt = make_optimizer(optimizer, model, lr, weight_decay=weight_decay, momentum=momentum)
     sched = make_scheduler(scheduler, opt)
-    kw = dict(source_weights=source_weights, ignore_label=ignore_label, num_sources=num_sources, precision=precision)
+    kw = dict(source_weights=source_weights, ignore_label=ignore_label, num_sources=num_sources, precision=precision,
+              sem_criterion=sem_criterion, num_classes=num_classes)
     if kind == "MinkUNet34BEV":
-        step = LiDOGStep(model, opt, warmup_epochs=warmup_epochs, num_classes=num_classes, **kw)
+        step = LiDOGStep(model, opt, warmup_epochs=warmup_epochs, sem_bev_criterion=sem_bev_criterion or "DICELoss", **kw)
     elif kind == "MinkUNet34Robust":
         step = RobustStep(model, opt, **kw)
     else:
@@ -578,8 +584,10 @@ class Fit:
                  momentum=0.98, check_val_every_n_epoch=5, num_sanity_val_steps=2, save_dir=None, seed=1234,
                  train_data=None, val_data=None, shuffle=True, resume=None, auto_resume=False, prefetch=True,
                  device="cuda", log=None, state_dict=None, num_sources=None, log_every_n_steps=0, metric_sources=None,
-                 val_precision=None, precision=None):
-        """`precision`: None / "fp32" (the fp32 step, exactly what runs without it) or "bf16": mixed-precision training
+                 val_precision=None, precision=None, sem_criterion="SoftDICELoss", sem_bev_criterion=None):
+        """`sem_criterion` / `sem_bev_criterion`: losses.sem_criterion / sem_bev_criterion of the reference's
+        configurations, by name (build_step); the validation loss is the point criterion's.
+        `precision`: None / "fp32" (the fp32 step, exactly what runs without it) or "bf16": mixed-precision training
         steps (lidog_amd.precision: bf16 operands in the eligible sparse convolutions' forward, data-gradient and
         weight-gradient kernels, everything else -- master weights, gradients, optimiser state, checkpoints -- fp32; the
         step runs on the operator path, not the trunk executor; one rank only).  Independent of `val_precision`.
@@ -613,7 +621,8 @@ class Fit:
             num_sources = getattr(self.train_data, "num_sources", 1)
         self.model, self.step, self.sched = build_step(
             model, model_kind, optimizer, lr, scheduler, weight_decay, momentum, warmup_epochs, source_weights,
-            num_sources=num_sources, precision=precision)
+            num_sources=num_sources, precision=precision, sem_criterion=sem_criterion,
+            sem_bev_criterion=sem_bev_criterion)
         self.opt = self.step.opt
         self.epoch, self.global_step = 0, 0
         self.history = []
@@ -811,8 +820,14 @@ def parse_args(argv=None):
                          "counts that are multiples of 32 run forward, data gradient and weight gradient on bf16 operands "
                          "with fp32 accumulation, lidog_amd.precision; weights, gradients, optimiser state and "
                          "checkpoints stay fp32; one GPU)")
+    ap.add_argument("--sem-criterion", default=argparse.SUPPRESS, choices=list(POINT_CRITERIA),
+                    help="the point loss (losses.sem_criterion of the reference's configurations; default SoftDICELoss)")
+    ap.add_argument("--sem-bev-criterion", default=argparse.SUPPRESS, choices=list(BEV_CRITERIA),
+                    help="the BEV loss of MinkUNet34BEV (losses.sem_bev_criterion; default DICELoss)")
     scans.add_file_arguments(ap, "--files", "train on")
     a = ap.parse_args(argv)
+    if getattr(a, "sem_bev_criterion", None) is not None and a.model != "MinkUNet34BEV":
+        ap.error(f"--sem-bev-criterion is the loss of the BEV head: --model MinkUNet34BEV, not {a.model}")
     source_augment = getattr(a, "source_augment", None)
     sn_target_files = getattr(a, "sn_target_files", None)
     sn_target_label_maps = getattr(a, "sn_target_label_maps", None)
@@ -901,6 +916,17 @@ def precision_of(a):
     return getattr(a, "precision", None)
 
 
+def sem_criterion_of(a):
+    """--sem-criterion of parsed arguments ("SoftDICELoss" when it was not given)"""
+    return getattr(a, "sem_criterion", "SoftDICELoss")
+
+
+def sem_bev_criterion_of(a):
+    """--sem-bev-criterion of parsed arguments; not given: "DICELoss" for MinkUNet34BEV, None for a model without the
+    BEV head"""
+    return getattr(a, "sem_bev_criterion", "DICELoss" if a.model == "MinkUNet34BEV" else None)
+
+
 def main(argv=None):
     a = parse_args(argv)
     fit = _fit_from_args(a)
@@ -921,7 +947,8 @@ def _fit_from_args(a):
                source_weights=tuple(a.source_weights), check_val_every_n_epoch=a.check_val_every_n_epoch,
                save_dir=a.save_dir, seed=a.seed, train_data=train, val_data=val, resume=a.resume,
                auto_resume=a.auto_resume, log_every_n_steps=getattr(a, "log_every_n_steps", 0),
-               val_precision=val_precision_of(a), precision=precision_of(a))
+               val_precision=val_precision_of(a), precision=precision_of(a), sem_criterion=sem_criterion_of(a),
+               sem_bev_criterion=sem_bev_criterion_of(a))
 
 
 def _data_from_args(a):

@@ -22,7 +22,7 @@ import torch.distributed as dist
 
 from . import me as ME
 from . import precision as _precision
-from .losses import DICELoss, SoftDICELoss, iw_loss
+from .losses import iw_loss, make_bev_criterion, make_criterion
 from .optim import (FlatAdam, FlatParams, FlatSGD, GradientBuckets, make_optimizer, make_scheduler,  # noqa: F401
                     shard_indices)
 
@@ -42,7 +42,10 @@ class _Step:
     and weight gradient on the bf16 matrix instruction (lidog_amd.precision; fp32 master weights, gradients and optimiser
     state), the step leaves the trunk executor for the operator path, and the packed operand tables (`bf16`, a
     precision.Bf16Training) are refreshed after every optimiser step.  `precision_ctx`: the context of the last bf16
-    step (its `.launches` count the routes).  One rank only."""
+    step (its `.launches` count the routes).  One rank only.
+    `sem_criterion`: the point loss by name, losses.sem_criterion of the reference's configurations
+    (losses.make_criterion: CELoss, DICELoss, SoftDICELoss, FocalLoss); `num_classes` = 19 gives SoftDICELoss the KITTI
+    soft labels."""
 
     metrics = None
     bf16 = None                         # the packed tables of precision="bf16"
@@ -51,7 +54,8 @@ class _Step:
     metric_bev = False                  # the BEV levels are logged too
     metric_count_ignored = True         # jaccard_score over all rows (the LiDOG trainers filter label == -1 first)
 
-    def __init__(self, model, optimizer, num_sources=1, ignore_label=-1, precision=None):
+    def __init__(self, model, optimizer, num_sources=1, ignore_label=-1, precision=None, sem_criterion="SoftDICELoss",
+                 num_classes=7):
         if num_sources not in (1, 2):
             raise NotImplementedError(f"{num_sources} sources (the reference takes one or two)")
         self.model, self.opt, self.num_sources = model, optimizer, num_sources
@@ -59,7 +63,7 @@ class _Step:
         if _precision.resolve(precision):
             _precision.check_single_rank()
             self.bf16 = _precision.Bf16Training(model)
-        self.sem_criterion = SoftDICELoss(ignore_label=ignore_label)
+        self.sem_criterion = make_criterion(sem_criterion, ignore_label, num_classes)
         self._prepared = {}
         if num_sources == 2:
             optimizer.buckets.set_uses(2)
@@ -174,17 +178,18 @@ class LiDOGStep(_Step):
     is the mean over levels of DICE on .view(-1, C) (trainer_lighting_2d_multi.py:176-189);
     one source:  total = w0 * sem + w1 * bev,                          during warm-up total = bev;
     two sources: total = w0 * (sem0 + bev0) + w1 * (sem1 + bev1)  (:191-197), during warm-up w0 * bev0 + w1 * bev1
-    (:198-205).  During warm-up the sem losses are zero tensors."""
+    (:198-205).  During warm-up the sem losses are zero tensors.
+    `sem_bev_criterion`: the BEV loss by name (losses.make_bev_criterion: DICELoss, SoftDICELoss, CELoss)."""
 
     metric_losses = ("sem_loss", "bev_loss")
     metric_bev = True
     metric_count_ignored = False
 
     def __init__(self, model, optimizer, source_weights=(0.5, 0.5), warmup_epochs=0, num_classes=7, ignore_label=-1,
-                 num_sources=1, precision=None):
-        super().__init__(model, optimizer, num_sources, ignore_label, precision)
+                 num_sources=1, precision=None, sem_criterion="SoftDICELoss", sem_bev_criterion="DICELoss"):
+        super().__init__(model, optimizer, num_sources, ignore_label, precision, sem_criterion, num_classes)
         self.w, self.warmup, self.nc = source_weights, warmup_epochs, num_classes
-        self.bev_criterion = DICELoss(ignore_label=ignore_label)
+        self.bev_criterion = make_bev_criterion(sem_bev_criterion, ignore_label)
 
     def _bev_loss(self, bev, labels):
         loss = 0.0
@@ -219,11 +224,12 @@ class LiDOGStep(_Step):
 
 
 class SourceStep(_Step):
-    """PLTTrainer.training_step (train_source.py / Mix3D; MinkUNet34 and MinkUNet34IBN): SoftDICE only.
+    """PLTTrainer.training_step (train_source.py / Mix3D; MinkUNet34 and MinkUNet34IBN): the point loss only.
     One source: total = sem, the only loss returned; two sources (trainer_lighting.py:92-116): w0 * sem0 + w1 * sem1."""
 
-    def __init__(self, model, optimizer, source_weights=(0.5, 0.5), ignore_label=-1, num_sources=1, precision=None):
-        super().__init__(model, optimizer, num_sources, ignore_label, precision)
+    def __init__(self, model, optimizer, source_weights=(0.5, 0.5), ignore_label=-1, num_sources=1, precision=None,
+                 sem_criterion="SoftDICELoss", num_classes=7):
+        super().__init__(model, optimizer, num_sources, ignore_label, precision, sem_criterion, num_classes)
         self.w = source_weights
 
     def _losses(self, batch, epoch):
@@ -244,8 +250,8 @@ class RobustStep(_Step):
     metric_losses = ("sem_loss", "aux_loss")
 
     def __init__(self, model, optimizer, source_weights=(0.5, 0.5), aux_epoch=5, ignore_label=-1, num_sources=1,
-                 precision=None):
-        super().__init__(model, optimizer, num_sources, ignore_label, precision)
+                 precision=None, sem_criterion="SoftDICELoss", num_classes=7):
+        super().__init__(model, optimizer, num_sources, ignore_label, precision, sem_criterion, num_classes)
         self.w, self.aux_epoch = source_weights, aux_epoch
 
     def _losses(self, batch, epoch):

@@ -876,6 +876,46 @@ int lidog_scan_load(const float *points_raw, int32_t point_stride, const void *l
                     float radius_sq, float *points_out, int32_t *labels_out, int64_t *counts, int32_t num_classes,
                     int32_t *info, int32_t *ws, void *stream);
 
+/* ------------------------------------------------------------------ one label per point of a scan file (csrc/pointlabels.hip)
+ * What the SemanticKITTI and nuScenes-lidarseg benchmarks score: a class for every record of the file, in file order.
+ * The voxel logits go back to the points through the row every record has in lidog_scan_load's output (keep_row) and
+ * the voxel every kept row fell into (inverse_map).  Positions come from lidog_mix_split and the counts are integers:
+ * the same bytes on every run.  No allocation, synchronisation or blocking copy inside. */
+/* int32 workspace of lidog_scan_keep_rows for a file of n rows */
+int64_t lidog_scan_keep_rows_ws(int64_t n);
+/* points_raw, point_stride, n, use_radius, radius_sq: as lidog_scan_load takes them (the same radius test, the same
+ * stable compaction).  keep_row [n] int32: the row of record i among lidog_scan_load's kept rows, -1 for a record the
+ * mask dropped (without use_radius: i itself).  info [1] int32 (device): the number of kept rows.  n = 0 launches
+ * nothing and writes info = 0.  ws: lidog_scan_keep_rows_ws(n) int32 (not read without use_radius). */
+int lidog_scan_keep_rows(const float *points_raw, int32_t point_stride, int64_t n, int32_t use_radius, float radius_sq,
+                         int32_t *keep_row, int32_t *info, int32_t *ws, void *stream);
+/* int32 workspace of lidog_point_labels: the arg-max of every voxel row */
+int64_t lidog_point_labels_ws(int64_t n_voxels);
+/* A loader batch of n_scans (1..64) files.  logits [n_voxels, n_classes] float32 (n_classes <= 32): the batch's voxel
+ * rows, scan after scan.  row_off / kept_off / vox_off [n_scans + 1] int64, HOST arrays (they travel as a kernel
+ * argument: nothing is copied in front of the launch): where every scan's file rows, kept rows and voxel rows start in the
+ * concatenated arrays, from 0, non-decreasing, ending at n_rows / n_kept / n_voxels (checked here); any of a scan's
+ * three ranges may be empty.  keep_row [n_rows]
+ * int32: lidog_scan_keep_rows' output of every file, concatenated.  inverse_map [n_kept] int64: the voxel row, within
+ * its scan, of every kept row.  Prediction of a voxel row = the first maximal index, the first NaN in a row holding one
+ * (lidog_eval_confusion's rule), taken once per voxel row into ws.
+ * labels_out [n_rows] uint32: out_lut[prediction] (out_lut [n_classes] int32) of the record's voxel, `fill` for a
+ * record with keep_row = -1.
+ * label_kind 1 / 2 (0: no labels, counts is not touched): labels_raw [n_rows], label_mask, lut, lut_len as
+ * lidog_scan_load takes them, the files' label words concatenated.  counts [n_scans, n_classes, n_classes] int64 is
+ * ADDED to: counts[scan, label, prediction] over the kept records whose mapped label lies in [0, n_classes) and is not
+ * ignore_label.
+ * err [1] int32 (device, never cleared here) collects bits: 1 a file row outside every scan's range (excluded by the
+ * offset checks), 2 a raw label outside the table, 4 an inverse_map entry outside its scan's voxel rows, 8 a keep_row entry
+ * outside its scan's kept rows.  Such a record keeps `fill` and is counted nowhere; no value is used as an index before
+ * it is checked.  ws: lidog_point_labels_ws(n_voxels) int32. */
+int lidog_point_labels(const float *logits, int64_t n_voxels, int32_t n_classes, int32_t n_scans,
+                       const int64_t *row_off, const int64_t *kept_off, const int64_t *vox_off, int64_t n_rows,
+                       int64_t n_kept, const int32_t *keep_row, const int64_t *inverse_map, const int32_t *out_lut,
+                       uint32_t fill, const void *labels_raw, int32_t label_kind, int32_t label_mask,
+                       const int32_t *lut, int32_t lut_len, int64_t ignore_label, uint32_t *labels_out, int64_t *counts,
+                       int32_t *err, int32_t *ws, void *stream);
+
 /* ------------------------------------------------------------------ bf16-operand forward kernels (csrc/sconv_bf16.hip)
  * Opt-in evaluation path (lidog_amd/precision.py): activations stay fp32 in memory, the gathered rows are rounded to bf16
  * (nearest even) as they are staged, the weights are packed once, accumulation is fp32 (v_mfma_f32_32x32x16_bf16).

@@ -173,6 +173,11 @@ SIGNATURES = {
     "lidog_train_confusion": [_p, _p, _p, _i32, _i32, _i64, _p, _p, _p],
     "lidog_scan_load_ws": [_i64],
     "lidog_scan_load": [_p, _i32, _p, _i32, _i32, _i64, _p, _i32, _i32, _f, _p, _p, _p, _i32, _p, _p, _p],
+    "lidog_scan_keep_rows_ws": [_i64],
+    "lidog_scan_keep_rows": [_p, _i32, _i64, _i32, _f, _p, _p, _p, _p],
+    "lidog_point_labels_ws": [_i64],
+    "lidog_point_labels": [_p, _i64, _i32, _i32, _p, _p, _p, _i64, _i64, _p, _p, _p, ctypes.c_uint32, _p, _i32, _i32, _p,
+                           _i32, _i64, _p, _p, _p, _p, _p],
     "lidog_pool_rows": [_p, _p, _p, _p, _i64, _i32, _i32, _p, _p, _p],
     "lidog_pool_rows_max": [_p, _p, _p, _p, _i64, _i32, _p, _p, _p],
     "lidog_pool_rows_max_bwd": [_p, _p, _p, _p, _p, _i64, _i32, _p, _p],
@@ -188,7 +193,8 @@ _RESTYPES = {"lidog_hash_capacity": _i64, "lidog_sconv_reduce_stats_ws": _i64, "
              "lidog_kernel_map_sorted_ws": _i64, "lidog_sconv_os_stats_ws": _i64, "lidog_in_segments_ws": _i64,
              "lidog_in_reduce_ws": _i64, "lidog_iw_ws": _i64, "lidog_mix_split_ws": _i64,
              "lidog_dbscan_ws": _i64, "lidog_augment_ws": _i64, "lidog_eval_pack_ws": _i64,
-             "lidog_scan_load_ws": _i64, "lidog_pool_global_ws": _i64}
+             "lidog_scan_load_ws": _i64, "lidog_pool_global_ws": _i64, "lidog_scan_keep_rows_ws": _i64,
+             "lidog_point_labels_ws": _i64}
 
 # lidog_abi_version() of the library these signatures were written against: a stale .so (or a header an external caller
 # compiled against long ago) would take mis-sized arguments without any diagnostic

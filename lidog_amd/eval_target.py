@@ -4,6 +4,8 @@
     python -m lidog_amd.eval_target --checkpoint ... --model MinkUNet34 --targets nusc35k --save-predictions
     python -m lidog_amd.eval_target --checkpoint ... --precision bf16
     python -m lidog_amd.eval_target --checkpoint ... --target-files SemanticKITTI=/data/SemanticKITTI --label-maps semantickitti2common.yaml
+    python -m lidog_amd.eval_target --checkpoint ... --target-files ... --label-maps ... --point-level
+    python -m lidog_amd.eval_target --checkpoint ... --target-files ... --label-maps ... --save-labels --inverse-label-map common2semantickitti.yaml
 
 What the reference does through pytorch-lightning's trainer.test, as plain arguments:
   get_model / get_target_domains / loaders with batch_size * 2, shuffle=False        eval_target.py:46-89,119-167
@@ -15,6 +17,11 @@ What the reference does through pytorch-lightning's trainer.test, as plain argum
 The metric runs on the device up to integer confusion counts (lidog_amd.evaluate.TargetEvaluator); the counts cross to
 the host once per target.  Target scans are synthetic (lidog_amd.synth), drawn as train.py draws validation scans: scan
 i of target t has seed 10**6 + t * synth.SOURCE1_SEED + i.  `main(argv)` returns the per-target results.
+
+Point level (--point-level / --save-labels, file targets only; the voxel-level outputs stay what they are): every record
+of every scan file gets the class of its voxel (lidog_amd.evaluate.point_labels), records beyond the radius a fill id;
+`<sources>-TO-<targets>-points.csv` holds the IoU over the labelled points, and --save-labels writes one uint32 id per
+record in file order, for SemanticKITTI as `predictions/<target>/sequences/SS/predictions/NNNNNN.label`.
 """
 import argparse
 import json
@@ -25,7 +32,8 @@ import torch
 
 from . import synth
 from .checkpoint import load_lightning_checkpoint
-from .evaluate import (CLASS_NAMES, TargetEvaluator, dataset_batches, palette, write_ply, write_results_csv)
+from .evaluate import (CLASS_NAMES, PointLabelWriter, PointPath, TargetEvaluator, dataset_batches, inverse_lut,
+                       load_inverse_label_map, palette, write_ply, write_results_csv)
 from . import scans
 from .train import SynthScans, bev_image_size, build_model, source_names
 
@@ -53,6 +61,15 @@ def parse_args(argv=None):
                     help="bf16: convolutions with channel counts that are multiples of 32 multiply bf16 operands "
                          "(fp32 accumulation, fp32 activations); the weights are packed once per target")
     scans.add_file_arguments(ap, "--target-files", "evaluate on the validation")
+    ap.add_argument("--point-level", action="store_true",
+                    help="with --target-files: also score one label per point of every scan file (records beyond the "
+                         "radius are left out) into <sources>-TO-<targets>-points.csv")
+    ap.add_argument("--save-labels", action="store_true",
+                    help="with --target-files: write one uint32 id per record of every scan file, in file order "
+                         "(SemanticKITTI: predictions/<target>/sequences/SS/predictions/NNNNNN.label)")
+    ap.add_argument("--inverse-label-map", nargs="+", default=None, metavar="FILE",
+                    help="one per target: a .yaml / .json file with a learning_map_inv (common class -> id to write; "
+                         "entry -1: the id of records beyond the radius, default 0).  Default: the class itself")
     a = ap.parse_args(argv)
     if a.checkpoint is None:
         ap.error(NO_CHECKPOINT)
@@ -61,6 +78,12 @@ def parse_args(argv=None):
         a.targets = [n for n, _ in a.target_files]               # the CSV's target names
     elif a.label_maps is not None or a.synth4d_splits is not None or a.limit_files is not None:
         ap.error("--label-maps, --synth4d-splits and --limit-files go with --target-files")
+    if (a.point_level or a.save_labels or a.inverse_label_map is not None) and a.target_files is None:
+        ap.error("--point-level, --save-labels and --inverse-label-map go with --target-files (a synthetic target has no "
+                 "file whose order the labels could follow)")
+    if a.inverse_label_map is not None:
+        if len(a.inverse_label_map) != len(a.target_files):
+            ap.error("--inverse-label-map needs one file per --target-files entry")
     if len(a.targets) > 2:
         raise NotImplementedError(f"{len(a.targets)} targets (the reference takes one or two)")
     if a.scans < 1 or a.batch < 1:
@@ -115,21 +138,42 @@ def main(argv=None):
                                                  synth4d_splits=a.synth4d_splits, limit=a.limit_files), luts[t])
         else:
             data = SynthScans(a.scans, config, first=10 ** 6 + t * synth.SOURCE1_SEED, bev_size=bev)
+        points = None
+        if a.point_level or a.save_labels:
+            lut, fill = inverse_lut(load_inverse_label_map(a.inverse_label_map[t]) if a.inverse_label_map else None,
+                                    len(CLASS_NAMES), 0xFFFF if config == "SemanticKITTI" else 2 ** 31 - 1)
+            label_writer = None
+            if a.save_labels:
+                label_writer = PointLabelWriter(os.path.join(save_dir, "predictions"), name, config,
+                                                data.listings[0].files)
+            points = PointPath.of(data, device, out_lut=torch.from_numpy(lut).to(device), fill=fill,
+                                  with_labels=a.point_level, on_point_labels=label_writer)
         writer = None
         if a.save_predictions:
             writer = PredictionWriter(os.path.join(save_dir, "predictions"), name, a.model != "MinkUNet34BEV",
                                       len(CLASS_NAMES))
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        res = ev.run(dataset_batches(data, a.batch, device), len(data), rows=a.rows, on_predictions=writer)
+        res = ev.run(dataset_batches(data, a.batch, device), len(data), rows=a.rows, on_predictions=writer,
+                     points=points)
         dt = time.perf_counter() - t0                                # run() ends with the host copy of the counts
         path = write_results_csv(save_dir, sources, name, res["rows"], CLASS_NAMES, first_target=t == 0,
                                  file_targets=file_targets)
         out = {"target": name, "checkpoint_epoch": epoch, "per_class_iou": [float(x) for x in res["per_class"]],
                "mean_iou": res["mean"], "rows": int(res["rows"].shape[0]), "rows_per": a.rows,
                "scans": int(res["scans"]), "scans_per_s": res["scans"] / dt, "csv": path}
+        extra = {}
+        if a.point_level:
+            out["points_csv"] = write_results_csv(save_dir, sources, name, res["point_rows"], CLASS_NAMES,
+                                                  first_target=t == 0, file_targets=file_targets + "-points")
+            out["point_per_class_iou"] = [float(x) for x in res["point_per_class"]]
+            out["point_mean_iou"] = res["point_mean"]
+            extra = {"point_iou_rows": res["point_rows"], "point_counts": res["point_counts"]}
+        if a.save_labels:
+            out["label_files"] = len(points.on_point_labels.written)
+            extra["label_paths"] = list(points.on_point_labels.written)
         print(json.dumps(out), flush=True)
-        results.append(dict(out, iou_rows=res["rows"], counts=res["counts"]))
+        results.append(dict(out, iou_rows=res["rows"], counts=res["counts"], **extra))
     return results
 
 

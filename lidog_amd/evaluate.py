@@ -9,7 +9,11 @@ Everything stays on the device (the reference moves predictions to the CPU for s
 
 eval_target (second half of this file): confusion / TargetEvaluator take the metric from logits to integer counts in
 one HIP kernel (csrc/evalstats.hip) and read the counts once per target; iou_rows turns them into test_step's rows on
-the host, per loader batch as the reference or per scan as evaluate() above."""
+the host, per loader batch as the reference or per scan as evaluate() above.
+
+Point level (third part): point_labels takes a batch's voxel logits back to every record of the scan files, in file order
+(csrc/pointlabels.hip), with the per-scan confusion counts over the kept, labelled points; TargetEvaluator.run(points=...)
+adds both to a target's evaluation, and the label-file helpers write what the SemanticKITTI API reads."""
 import torch
 
 from . import me as ME
@@ -230,6 +234,159 @@ def unpack_predictions(buf, n_scans):
     return [rec[start[s]:start[s + 1]] for s in range(n_scans)]
 
 
+# ------------------------------------------------------------------ point level: one label per record of a scan file
+MAX_POINT_SCANS = 64      # of one point_labels call: the scans' offsets travel with the launch
+POINT_ERRORS = ((1, "a file row outside every scan's range of rows"),
+                (2, "a raw label outside the label map's table"),
+                (4, "an inverse_map entry outside its scan's voxel rows"),
+                (8, "a keep_row entry outside its scan's kept rows"))
+
+
+def check_point_error(err, what="point_labels"):
+    """raises when lidog_point_labels set a bit of its error word (one read of a device word)"""
+    e = int(err.item())
+    if e:
+        raise ValueError(f"{what}: " + "; ".join(m for b, m in POINT_ERRORS if e & b) +
+                         f" (error word {e}); such records keep the fill id and were not counted")
+
+
+def _offsets(name, off, n_scans, total, what):
+    import numpy as np
+    o = np.asarray(off, dtype=np.int64).reshape(-1)
+    if o.shape[0] != n_scans + 1 or o[0] != 0 or (np.diff(o) < 0).any() or int(o[-1]) != total:
+        raise ValueError(f"point_labels: {name} must hold {n_scans + 1} non-decreasing offsets from 0 to the {total} "
+                         f"{what}, got {o.tolist()}")
+    return o
+
+
+def point_labels(logits, row_off, kept_off, vox_off, keep_row, inverse_map, out_lut=None, fill=0, labels_raw=None,
+                 lut=None, label_mask=None, ignore_label=-1, counts=None, err=None):
+    """(labels_out uint32 [N], counts) of lidog_point_labels, on the device: one id per record of every file of a loader
+    batch, in file order.  logits float32 [V, C]: the batch's voxel rows, scan after scan; row_off / kept_off / vox_off:
+    B + 1 host integers each (B <= 64; they travel with the launch, no copy is queued), where every scan's file rows,
+    kept rows (load_scan's output) and voxel rows start;
+    keep_row int32 [N] (scans.keep_rows of every file, concatenated); inverse_map int64 or int32 [kept] (kept row ->
+    voxel row within its item).  labels_out = out_lut[arg-max of the record's voxel] (out_lut int32 [C] on the device,
+    None: the class itself), `fill` for a record the radius mask dropped.  The arg-max is confusion()'s: the first
+    maximal index, the first NaN.
+    labels_raw (int32 or uint8 [N], the files' label words concatenated) with lut / label_mask as scans.load_scan takes
+    them: counts [B, C, C] int64 (`counts`: a contiguous tensor or slice to ADD to, else zeros) += the confusion (label,
+    prediction) over the kept records whose mapped label is a class other than ignore_label; without labels_raw the
+    counts are returned as given.  `err`: an int32 [1] device word the caller checks later with check_point_error
+    (nothing is read back here); without it this call checks, which costs one synchronisation."""
+    import numpy as np
+    from . import _lib
+    from ._lib import call, ptr, require_gpu
+    require_gpu(logits, "logits")
+    dev = logits.device
+    if logits.dim() != 2 or logits.dtype != torch.float32:
+        raise ValueError(f"point_labels: logits must be float32 [V, C], got {logits.dtype} {tuple(logits.shape)}")
+    v, c = logits.shape
+    if not 1 <= c <= MAX_CLASSES:
+        raise ValueError(f"point_labels: {c} classes (at most {MAX_CLASSES})")
+    for name, t, dtypes in (("keep_row", keep_row, (torch.int32,)), ("inverse_map", inverse_map, (torch.int32, torch.int64))):
+        require_gpu(t, name)
+        if t.dim() != 1 or t.dtype not in dtypes or t.device != dev:
+            raise ValueError(f"point_labels: {name} must be a 1-d {' or '.join(str(d) for d in dtypes)} tensor on {dev}, "
+                             f"got {t.dtype} {tuple(t.shape)} on {t.device}")
+    n, kept = keep_row.shape[0], inverse_map.shape[0]
+    b = len(row_off) - 1
+    if not 1 <= b <= MAX_POINT_SCANS:
+        raise ValueError(f"point_labels: {b} scans (1..{MAX_POINT_SCANS})")
+    offs = np.stack([_offsets("row_off", row_off, b, n, "file rows"), _offsets("kept_off", kept_off, b, kept, "kept rows"),
+                     _offsets("vox_off", vox_off, b, v, "voxel rows")])
+    if out_lut is None:
+        out_lut = torch.arange(c, dtype=torch.int32, device=dev)
+    require_gpu(out_lut, "out_lut")
+    if out_lut.shape != (c,) or out_lut.dtype != torch.int32 or out_lut.device != dev:
+        raise ValueError(f"point_labels: out_lut must be int32 [{c}] on {dev}")
+    fill = int(fill)
+    if not 0 <= fill < 2 ** 32:
+        raise ValueError(f"point_labels: fill = {fill} is no uint32")
+    kind, mask = 0, -1
+    if labels_raw is not None:
+        require_gpu(labels_raw, "labels_raw")
+        kinds = {torch.int32: 1, torch.uint8: 2}
+        if labels_raw.dtype not in kinds or labels_raw.shape != (n,) or labels_raw.device != dev:
+            raise ValueError(f"point_labels: labels_raw must be int32 or uint8 [{n}] on {dev}, got {labels_raw.dtype} "
+                             f"{tuple(labels_raw.shape)}")
+        kind = kinds[labels_raw.dtype]
+        if lut is None or not lut.is_cuda or lut.dtype != torch.int32 or lut.dim() != 1 or lut.shape[0] < 1:
+            raise ValueError("point_labels: lut must be a non-empty int32 [L] tensor on the GPU")
+        if label_mask is not None:
+            mask = int(np.array(label_mask, dtype=np.uint32).astype(np.int32))
+        if counts is None:
+            counts = torch.zeros((b, c, c), dtype=torch.int64, device=dev)
+        elif counts.shape != (b, c, c) or counts.dtype != torch.int64 or not counts.is_contiguous() or \
+                counts.device != dev:
+            raise ValueError(f"point_labels: counts must be a contiguous int64 [{b}, {c}, {c}] tensor on {dev}")
+    own_err = err is None
+    if own_err:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    out = torch.empty(n, dtype=torch.uint32, device=dev)
+    ws = torch.empty(_lib.load().lidog_point_labels_ws(v), dtype=torch.int32, device=dev)
+    call("lidog_point_labels", ptr(logits.contiguous()), v, c, b, offs[0].ctypes.data, offs[1].ctypes.data, offs[2].ctypes.data, n, kept,
+         ptr(keep_row.contiguous()), ptr(inverse_map.long().contiguous()), ptr(out_lut.contiguous()), fill,
+         ptr(labels_raw.contiguous()) if kind else None, kind, mask, ptr(lut.contiguous()) if kind else None,
+         lut.shape[0] if kind else 0, int(ignore_label), ptr(out), ptr(counts) if kind else None, ptr(err), ptr(ws))
+    if own_err:
+        check_point_error(err)
+    return out, counts
+
+
+def point_inputs(items, with_labels=True):
+    """The arguments of point_labels for a loader batch from its scans' FileScans.point_item dicts, in batch order: the
+    keep index of every file (scans.keep_rows, on the words already uploaded) and the concatenations.  Nothing is read
+    back: every offset is a size the host already knows.  A dict of row_off, kept_off, vox_off, keep_row, inverse_map,
+    labels_raw, lut, label_mask; labels_raw is None unless with_labels, and a file without labels is a ValueError then."""
+    import numpy as np
+    from . import scans as _scans
+    if not items:
+        raise ValueError("point_inputs: no scans")
+    keep = [_scans.keep_rows(it["points_raw"], it["stride"], it["in_radius"], name=it["path"])[0] for it in items]
+    out = {"row_off": np.concatenate([[0], np.cumsum([it["rows"] for it in items])]).astype(np.int64),
+           "kept_off": np.concatenate([[0], np.cumsum([it["kept"] for it in items])]).astype(np.int64),
+           "vox_off": np.concatenate([[0], np.cumsum([it["voxels"] for it in items])]).astype(np.int64),
+           "keep_row": torch.cat(keep), "inverse_map": torch.cat([it["inverse_map"] for it in items]),
+           "labels_raw": None, "lut": None, "label_mask": None}
+    if with_labels:
+        missing = [it["path"] for it in items if it["labels_raw"] is None]
+        if missing:
+            raise ValueError(f"{missing[0]}: no label file, so no point-level confusion (labels can still be saved)")
+        if len({(it["labels_raw"].dtype, it["mask"], it["lut"].data_ptr()) for it in items}) != 1:
+            raise ValueError("point_inputs: the scans of a batch must share label dtype, mask and look-up table")
+        out.update(labels_raw=torch.cat([it["labels_raw"] for it in items]), lut=items[0]["lut"],
+                   label_mask=items[0]["mask"])
+    return out
+
+
+class PointPath:
+    """What TargetEvaluator.run(points=...) needs for the point level.  `items(ids)`: the FileScans.point_item dicts of a
+    batch's dataset indices (the dataset has `keep_raw` set); `out_lut`: int32 [C] class -> id to write (None: the class
+    itself) and `fill`: the id of records beyond the radius; `with_labels`: count the point confusion (needs every
+    file's labels); `on_point_labels(first_scan, labels_out, row_off)`: called per batch with the dataset index of its
+    first scan, the host copy of its ids (numpy uint32, file order) and the B + 1 row offsets of its scans; asking for it
+    costs one device -> host copy per batch."""
+
+    def __init__(self, items, out_lut=None, fill=0, with_labels=True, on_point_labels=None):
+        self.items, self.out_lut, self.fill = items, out_lut, int(fill)
+        self.with_labels, self.on_point_labels = bool(with_labels), on_point_labels
+
+    @classmethod
+    def of(cls, data, device="cuda", **kw):
+        """over a scans.FileScans validation dataset, which from here on keeps the uploaded files of the items it makes"""
+        data.keep_raw = True
+        return cls(lambda ids: [data.point_item(i, device) for i in ids], **kw)
+
+
+def point_iou_counts(point_counts):
+    """[n, C, C] point confusion -> the [n, C + 1, C] layout iou_rows takes; row 0 (labels outside the classes) stays
+    empty: the point level leaves unlabelled points out altogether"""
+    import numpy as np
+    m = np.asarray(point_counts, dtype=np.int64)
+    return np.concatenate([np.zeros((m.shape[0], 1, m.shape[2]), np.int64), m], axis=1)
+
+
 def iou_rows(counts, rows="batch", batch_of_scan=None):
     """IoU rows of test_step from confusion counts [n_scans, C + 1, C], on the host in float64.  Per row and class:
     tp / (true + pred - tp) as one division, 0 where the denominator is 0, -1 where the class is absent from the row's
@@ -299,9 +456,13 @@ class TargetEvaluator:
         self.precision, self.kernels = precision, None
 
     @torch.no_grad()
-    def run(self, batches, n_scans, rows="batch", on_predictions=None):
+    def run(self, batches, n_scans, rows="batch", on_predictions=None, points=None):
         """`batches`: iterable of (batch dict, scan indices); `n_scans`: scans of all batches together.  Returns a dict:
-        counts [n_scans, C + 1, C] (numpy), batch_of_scan, rows (IoU rows), per_class (percent), mean, scans."""
+        counts [n_scans, C + 1, C] (numpy), batch_of_scan, rows (IoU rows), per_class (percent), mean, scans.
+        `points` (a PointPath; None changes nothing): every batch's logits also go through point_labels; the dict then
+        carries point_counts [n_scans, C, C], point_rows / point_per_class / point_mean (iou_rows / mean_iou_rows with
+        the same `rows`), and points.on_point_labels sees every batch's ids.  The point counts and their error word
+        cross to the host at the end, with the voxel ones."""
         import numpy as np
         if rows not in ("batch", "scan"):
             raise ValueError(f"rows={rows!r} (one of 'batch', 'scan')")
@@ -310,7 +471,7 @@ class TargetEvaluator:
         self.kernels = run.kernels
         it = iter(batches)
         cur = next(it, None)
-        counts = err = None
+        counts = err = pcounts = perr = None
         batch_of_scan = []
         done = 0
         nb = 0
@@ -321,6 +482,9 @@ class TargetEvaluator:
             if counts is None:
                 counts = torch.zeros((int(n_scans), c + 1, c), dtype=torch.int64, device=coords.device)
                 err = torch.zeros(1, dtype=torch.int32, device=coords.device)
+                if points is not None:
+                    pcounts = torch.zeros((int(n_scans), c, c), dtype=torch.int64, device=coords.device)
+                    perr = torch.zeros(1, dtype=torch.int32, device=coords.device)
             k = len(ids)
             if done + k > counts.shape[0]:
                 raise ValueError(f"TargetEvaluator: more than n_scans = {n_scans} scans in the batches")
@@ -332,6 +496,13 @@ class TargetEvaluator:
                 buf = pack_predictions(coords, preds, labels, k, self.ignore_label, err=err)
                 for idx, rec in zip(ids, unpack_predictions(buf, k)):
                     on_predictions(idx, rec)
+            if points is not None:
+                pin = point_inputs(points.items(ids), points.with_labels)
+                ids_out, _ = point_labels(logits, pin["row_off"], pin["kept_off"], pin["vox_off"], pin["keep_row"],
+                                          pin["inverse_map"], points.out_lut, points.fill, pin["labels_raw"], pin["lut"],
+                                          pin["label_mask"], self.ignore_label, pcounts[done:done + k], perr)
+                if points.on_point_labels is not None:
+                    points.on_point_labels(ids[0], ids_out.cpu().numpy(), pin["row_off"])
             batch_of_scan += [nb] * k
             done += k
             nb += 1
@@ -343,8 +514,15 @@ class TargetEvaluator:
         batch_of_scan = np.asarray(batch_of_scan, dtype=np.int64)
         r = iou_rows(counts, rows, batch_of_scan)
         per_class, mean = mean_iou_rows(r)
-        return {"counts": counts, "batch_of_scan": batch_of_scan, "rows": r, "per_class": per_class, "mean": mean,
-                "scans": done}
+        res = {"counts": counts, "batch_of_scan": batch_of_scan, "rows": r, "per_class": per_class, "mean": mean,
+               "scans": done}
+        if points is not None:
+            check_point_error(perr, "TargetEvaluator")
+            pc = pcounts[:done].cpu().numpy()
+            pr = iou_rows(point_iou_counts(pc), rows, batch_of_scan)
+            p_class, p_mean = mean_iou_rows(pr)
+            res.update(point_counts=pc, point_rows=pr, point_per_class=p_class, point_mean=p_mean)
+        return res
 
 
 # ------------------------------------------------------------------ point clouds of the prediction dump
@@ -389,3 +567,80 @@ def read_ply(path):
     v = np.frombuffer(raw, dtype=np.dtype([(name, t) for name, t, _ in _PLY_FIELDS]), count=n, offset=end)
     return (np.stack([v["x"], v["y"], v["z"]], axis=1).reshape(-1, 3),
             np.stack([v["red"], v["green"], v["blue"]], axis=1).reshape(-1, 3))
+
+
+# ------------------------------------------------------------------ label files of the point level
+def load_inverse_label_map(path):
+    """the `learning_map_inv` of a label-map file ({common class: id to write}; entry -1, if present, is the id of the
+    records beyond the radius): a .json or .yaml file, read as scans.load_label_map reads its own"""
+    import json
+    if path.lower().endswith(".json"):
+        with open(path) as f:
+            maps = json.load(f)
+    else:
+        try:
+            import yaml
+        except ImportError as e:
+            raise ImportError(f"{path}: reading a YAML label map needs PyYAML; convert the file to JSON instead") from e
+        with open(path) as f:
+            maps = yaml.safe_load(f)
+    if not isinstance(maps, dict) or "learning_map_inv" not in maps:
+        raise ValueError(f"{path}: no 'learning_map_inv' entry")
+    return {int(k): int(v) for k, v in maps["learning_map_inv"].items()}
+
+
+def inverse_lut(mapping=None, num_classes=7, max_id=2 ** 31 - 1):
+    """(out_lut int32 [num_classes] numpy, fill) of an inverse label map: the identity where the map says nothing, fill =
+    its entry -1 or 0.  Keys outside -1 .. num_classes - 1 and ids outside 0 .. max_id (0xFFFF for a SemanticKITTI label
+    file, whose upper half is the instance id) are a ValueError."""
+    import numpy as np
+    lut = np.arange(num_classes, dtype=np.int32)
+    fill = 0
+    for k, v in (mapping or {}).items():
+        if not -1 <= k < num_classes:
+            raise ValueError(f"inverse label map: class {k} outside -1 .. {num_classes - 1}")
+        if not 0 <= v <= max_id:
+            raise ValueError(f"inverse label map: id {v} of class {k} outside 0 .. {max_id}")
+        if k == -1:
+            fill = int(v)
+        else:
+            lut[k] = v
+    return lut, fill
+
+
+def label_file_path(folder, target, dataset, idx, points_path):
+    """where the ids of scan `idx` go.  SemanticKITTI (points file .../sequences/SS/velodyne/NNNNNN.bin):
+    `<folder>/<target>/sequences/SS/predictions/NNNNNN.label`, the layout the SemanticKITTI API reads; any other
+    dataset: `<folder>/<target>/point_labels/<idx>.label`"""
+    import os
+    if dataset == "SemanticKITTI":
+        parts = os.path.normpath(points_path).split(os.sep)
+        if len(parts) < 4 or parts[-4] != "sequences" or parts[-2] != "velodyne":
+            raise ValueError(f"{points_path}: not a .../sequences/SS/velodyne/NNNNNN.bin path")
+        return os.path.join(folder, target, "sequences", parts[-3], "predictions",
+                            os.path.splitext(parts[-1])[0] + ".label")
+    return os.path.join(folder, target, "point_labels", f"{idx}.label")
+
+
+def write_label_file(path, ids):
+    """little-endian uint32, one per record, in file order: exactly 4 bytes per record"""
+    import os
+    import numpy as np
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    np.ascontiguousarray(ids).astype("<u4").tofile(path)
+    return path
+
+
+class PointLabelWriter:
+    """PointPath's on_point_labels: one label file per scan of a batch (label_file_path), from the batch's one host copy.
+    `files`: the listing's (points file, label file) pairs."""
+
+    def __init__(self, folder, target, dataset, files):
+        self.folder, self.target, self.dataset, self.files = folder, target, dataset, list(files)
+        self.written = []
+
+    def __call__(self, first_scan, labels_out, row_off):
+        for s in range(len(row_off) - 1):
+            idx = int(first_scan) + s
+            path = label_file_path(self.folder, self.target, self.dataset, idx, self.files[idx][0])
+            self.written.append(write_label_file(path, labels_out[int(row_off[s]):int(row_off[s + 1])]))

@@ -9,6 +9,9 @@ synth4d.py and their *_bev.py training forms), with the per-point work on the GP
                               per-class label statistics (csrc/scanload.hip, lidog_scan_load).  One device -> host read
                               per scan: the four words of `info`.
   label_counts                get_dataset_stats on a label file alone (semantickitti.py:199-213)
+  keep_rows                   the row every record of a file has in load_scan's output, -1 where the radius mask dropped
+                              it (csrc/pointlabels.hip, lidog_scan_keep_rows): the way back from a voxel to the file's
+                              points, for lidog_amd.evaluate.point_labels
   semantickitti_files, synth4d_files, pair_list_files, listing     the file listings, in the reference's order
   FileScans                   a dataset over one or two listings: validation form (every kept point, voxelised) and
                               training form (sub_p / augmentations, bounds filter and BEV labels), items through
@@ -171,6 +174,30 @@ def label_counts(labels_raw, lut, counts, label_mask=None, name="labels"):
     return _launch(None, labels_raw, lut, 0, label_mask, None, counts, labels_raw.shape[0], labels_raw.device)[2]
 
 
+def keep_rows(points_raw, point_stride, in_radius=None, name="scan"):
+    """(keep_row int32 [n], m int32 [1]) on the device (lidog_scan_keep_rows): keep_row[i] = the row record i of the file
+    has in load_scan's `points`, -1 if the radius mask dropped it; m = the number of kept rows.  points_raw, point_stride
+    and in_radius as load_scan takes them: the same float32 test, the same stable compaction, so
+    points[keep_row >= 0] is load_scan's `points` bit for bit.  Nothing is read back."""
+    stride = int(point_stride)
+    if stride < 3:
+        raise ValueError(f"{name}: point_stride = {stride} (at least 3)")
+    words = _as_words(points_raw, "points", name)
+    if words.shape[0] % stride:
+        raise ValueError(f"{name}: {words.shape[0] * 4} bytes of points are no multiple of the {4 * stride}-byte record")
+    n = words.shape[0] // stride
+    dev = words.device
+    keep = torch.empty(n, dtype=torch.int32, device=dev)
+    m = torch.empty(1, dtype=torch.int32, device=dev)
+    ws = None
+    if in_radius is not None and n:
+        ws = torch.empty(_lib.load().lidog_scan_keep_rows_ws(n), dtype=torch.int32, device=dev)
+    r2 = float(np.float32(float(in_radius) ** 2)) if in_radius is not None else 0.0
+    call("lidog_scan_keep_rows", ptr(words), stride, n, 1 if in_radius is not None else 0, r2, ptr(keep), ptr(m),
+         ptr(ws))
+    return keep, m
+
+
 # ------------------------------------------------------------------ file listings
 class Listing:
     """`files`: [(points file, label file)] of one dataset and phase, in the reference's order"""
@@ -302,10 +329,12 @@ class FileScans:
     listing from pair's own generator, which moves with every call: only for i < min(len) is a batch made twice the same
     batch, before and after a resume included.  `luts`: one int32 look-up table per listing.  `use_cache` keeps loaded
     scans on the device (the reference's CACHE of the `data` dict; off in every configuration).
+    `keep_raw` (validation only, an attribute that may be set later): every item made also leaves what the point-level
+    evaluation needs, the uploaded file included, for point_item to hand out once.
     Items are made on data.merge_stream; per scan the host waits once for `info`, then for the sizes augment_item reads."""
 
     def __init__(self, listings, luts, voxel_size=0.05, augmentations=None, sub_p=0.8, seed=1234, bev=None,
-                 ignore_label=-1, in_radius=50.0, use_cache=False, use_intensity=False):
+                 ignore_label=-1, in_radius=50.0, use_cache=False, use_intensity=False, keep_raw=False):
         listings = [listings] if isinstance(listings, Listing) else list(listings)
         luts = [luts] if isinstance(luts, np.ndarray) else list(luts)
         if len(listings) not in (1, 2):
@@ -334,6 +363,9 @@ class FileScans:
             from .train import MultiSynthScans       # the pairing rule lives with the synthetic datasets
             self.pairs = MultiSynthScans(len(listings[0]), len(listings[1]), seed=seed)
         self._cache, self._dev_luts = {}, {}
+        if keep_raw and self.train:
+            raise ValueError("keep_raw: only the validation form keeps every point of a file")
+        self.keep_raw, self._raw, self._point_items = bool(keep_raw), {}, {}
 
     def __len__(self):
         return max(len(l) for l in self.listings)
@@ -359,9 +391,15 @@ class FileScans:
         fmt = lst.format
         points_path, labels_path = lst.files[j]
         pts, labels, stride = read_files(fmt, points_path, labels_path)
-        scan = load_scan(torch.from_numpy(pts).to(device), torch.from_numpy(labels).to(device) if labels is not None
-                         else None, self._lut(s, device), stride, fmt["mask"],
-                         self.in_radius if fmt["radius"] else None, name=points_path)
+        pts = torch.from_numpy(pts).to(device)
+        labels = torch.from_numpy(labels).to(device) if labels is not None else None
+        radius = self.in_radius if fmt["radius"] else None
+        scan = load_scan(pts, labels, self._lut(s, device), stride, fmt["mask"], radius, name=points_path)
+        if self.keep_raw:       # the uploaded words themselves: the point path reads them again, nothing is copied
+            words = _as_words(pts, "points", points_path)
+            self._raw[key] = {"points_raw": words, "labels_raw": _check_labels(labels, points_path),
+                              "stride": int(stride), "mask": fmt["mask"], "lut": self._lut(s, device),
+                              "in_radius": radius, "rows": words.shape[0] // int(stride), "path": points_path}
         if self.use_cache:
             self._cache[key] = scan
         return scan
@@ -381,7 +419,29 @@ class FileScans:
             row.append(augment_item(scan, self.draws(rng, scan["points"].shape[0]), voxel_size=self.voxel_size,
                                     bounds=self.bev is not None, ignore_label=self.ignore_label, bev=self.bev,
                                     bev_from=self.listings[s].format["bev_from"]))
+            raw = self._raw.get((s, j, str(device))) if self.keep_raw else None
+            if raw is not None:
+                if not self.use_cache:
+                    del self._raw[(s, j, str(device))]
+                self._point_items[int(i)] = dict(raw, inverse_map=row[-1]["inverse_map"],
+                                                 kept=int(scan["points"].shape[0]),
+                                                 voxels=int(row[-1]["coordinates"].shape[0]))
         return row
+
+    def point_item(self, i, device="cuda"):
+        """What the point-level evaluation needs of validation item i, made by the last item(i) / batch([.. i ..]) with
+        `keep_raw` set; nothing is read or uploaded again.  A dict: `points_raw` (the file's float32 words), `labels_raw`
+        (int32 / uint8 [rows] or None), `stride`, `mask`, `lut` (device int32), `in_radius` (None: no mask), `rows`,
+        `kept`, `voxels` (the sizes of the file, of load_scan's output and of the item), `inverse_map` (kept row -> voxel
+        row of the item), `path`.  Handed out once: the file's words are dropped with the caller's reference."""
+        if int(i) not in self._point_items:
+            raise KeyError(f"item {i} was not made with keep_raw set (or its point inputs were taken already)")
+        item = self._point_items.pop(int(i))
+        cur = torch.cuda.current_stream(torch.device(device))
+        for t in item.values():         # made on the merge stream, read on the caller's
+            if torch.is_tensor(t) and t.is_cuda:
+                t.record_stream(cur)
+        return item
 
     # ---- the item provider of lidog_amd.train.MixedSynthScans / ScaledSynthScans (see train.PlainSynthItems)
     @property

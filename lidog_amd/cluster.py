@@ -56,7 +56,9 @@ def dbscan(coords, voxel_size, eps=0.5, min_samples=10):
 
 def cluster_boxes(coords, labels, k=None):
     """(counts int64 [k], lo int32 [k, 3], hi int32 [k, 3]): rows and per-axis minimum / maximum coordinate of every
-    label 0..k-1 (k = labels.max() + 1 when not given: one read); noise (-1) is left out"""
+    label 0..k-1 (k = labels.max() + 1 when not given: one read); noise (-1) is left out, and so is every label from k
+    on when a smaller k is passed.  A label without rows (also: every label when n = 0) has count 0, lo INT_MAX and hi
+    INT_MIN, the values the kernels start from."""
     coords = _coords(coords)
     _lib.require_gpu(labels, "labels")
     labels = labels.to(torch.int32).contiguous()

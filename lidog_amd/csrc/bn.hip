@@ -9,28 +9,14 @@
 #include <map>
 #include <unordered_map>
 
+#include "bn_math.h"
 #include "common.h"
 #include "stats_tail.h"
 
-// MODE 0: (x, x*x)            -> statistics
-// MODE 1: (dy', dy' * xhat)   -> backward reductions, dy' = dy * (relu_y > 0) when relu_y given
-template <int MODE>
-__device__ __forceinline__ void red_terms(float x, float dy, float ry, bool has_relu, float mean, float invstd,
-                                          double &t0, double &t1) {
-    if (MODE == 0) {
-        t0 += (double)x;
-        t1 += (double)x * (double)x;
-    } else {
-        float g = (has_relu && !(ry > 0.f)) ? 0.f : dy;
-        float xh = (x - mean) * invstd;
-        t0 += (double)g;
-        t1 += (double)g * (double)xh;
-    }
-}
-
+// MODE: the terms of bn_math.h:bn_red_terms.
 // rw / rb (MODE 1, ry == NULL): BatchNorm weight and bias -- the ReLU mask is then recomputed from x with the forward
-// pass's own expression ((x - mean) * invstd * w + b > 0, same operation order, contraction off: the same bits)
-// instead of being read from the saved output: one tensor less to stream for a BatchNorm + ReLU without residual
+// pass's own expression (bn_affine > 0: the same bits) instead of being read from the saved output: one tensor less
+// to stream for a BatchNorm + ReLU without residual
 template <int MODE>
 __global__ __launch_bounds__(256) void k_colreduce_nc4(const float4 *__restrict__ x, const float4 *__restrict__ dy,
                                                        const float4 *__restrict__ ry, int64_t n, int C4,
@@ -82,28 +68,13 @@ __global__ __launch_bounds__(256) void k_colreduce_nc4(const float4 *__restrict_
                 float4 vv = (MODE == 0 && !ok) ? z : v[u];
                 float4 gg = ok ? g[u] : z;
                 float4 yy = y[u];
-                if (from_x) {   // the forward pass's pre-activation, bit for bit (k_bn_apply4)
-                    yy.x = (vv.x - m[0]) * is[0] * gw[0] + gb[0];
-                    yy.y = (vv.y - m[1]) * is[1] * gw[1] + gb[1];
-                    yy.z = (vv.z - m[2]) * is[2] * gw[2] + gb[2];
-                    yy.w = (vv.w - m[3]) * is[3] * gw[3] + gb[3];
-                }
+                if (from_x) yy = bn_affine4(vv, bn_f4(m), bn_f4(is), bn_f4(gw), bn_f4(gb));   // the pre-activation
                 const bool has_relu = ry != nullptr || from_x || rbits != nullptr;
-                red_terms<MODE>(vv.x, gg.x, yy.x, has_relu, m[0], is[0], a[0], a[4]);
-                red_terms<MODE>(vv.y, gg.y, yy.y, has_relu, m[1], is[1], a[1], a[5]);
-                red_terms<MODE>(vv.z, gg.z, yy.z, has_relu, m[2], is[2], a[2], a[6]);
-                red_terms<MODE>(vv.w, gg.w, yy.w, has_relu, m[3], is[3], a[3], a[7]);
+                bn_red_terms4<MODE>(vv, gg, yy, has_relu, bn_f4(m), bn_f4(is), a);
             }
         }
     }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) red[tid * 8 + j] = a[j];
-    __syncthreads();
-    if (active && r == 0) {
-        for (int rr = 1; rr < RB; ++rr)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) a[j] += red[(rr * C4 + c4) * 8 + j];
-    }
+    lidog_stats_wg_reduce(red, tid, RB, C4, c4, active && r == 0, a);
     // one partial row per workgroup, added in a fixed order by the last workgroup to arrive (stats_tail.h): no atomics
     // on the sums (512 workgroups adding to the same 2C addresses cost ~25 us of serialised L2 atomics),
     // bit-reproducible, and no finishing launch behind this one
@@ -116,8 +87,6 @@ __global__ __launch_bounds__(256) void k_colreduce_nc4(const float4 *__restrict_
 //   count > 0   -> sums[2C] = count   (SyncBatchNorm all-reduces the row count together with the sums)
 //   fin.mean    -> mean / invstd / running statistics from (sum x, sum x^2) and count  (= k_bn_finalize)
 //   fin.db / dw -> float copies of (first sums, second sums)                            (= k_bn_param_grads)
-#define bn_finalize_channel lidog_bn_finalize_channel   // stats_tail.h
-
 __global__ __launch_bounds__(256) void k_sums_finish(const double *__restrict__ partial, int nb, int C,
                                                      double *__restrict__ sums, double count, BnFinish fin) {
     __shared__ double red[256];
@@ -145,7 +114,7 @@ __global__ __launch_bounds__(256) void k_sums_finish(const double *__restrict__ 
         sums[col] = red[cl];
         if (fin.db && half == 0) fin.db[ch] = (float)red[cl];
         if (fin.dw && half == 1) fin.dw[ch] = (float)red[cl];
-        if (fin.mean && half == 0) bn_finalize_channel(red[cl], red[cl + 2], count, ch, fin);
+        if (fin.mean && half == 0) lidog_bn_finalize_channel(red[cl], red[cl + 2], count, ch, fin);
     }
     if (blockIdx.x == 0 && threadIdx.x == 0 && count > 0) sums[C2] = count;
 }
@@ -163,7 +132,7 @@ __global__ void k_sums_post(double *__restrict__ sums, int C, double count, BnFi
     if (c >= C) return;
     if (fin.db) fin.db[c] = (float)sums[c];
     if (fin.dw) fin.dw[c] = (float)sums[C + c];
-    if (fin.mean) bn_finalize_channel(sums[c], sums[C + c], count, c, fin);
+    if (fin.mean) lidog_bn_finalize_channel(sums[c], sums[C + c], count, c, fin);
 }
 
 // generic layout (NCHW planes, or [n,C] with C % 4 != 0 as hw = 1 "planes" of strided access)
@@ -197,7 +166,7 @@ __global__ __launch_bounds__(256) void k_colreduce_plane(const float *__restrict
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u)
-            if (i + 256 * u < i1) red_terms<MODE>(xv[u], gv[u], yv[u], ry != nullptr, m, is, t0, t1);
+            if (i + 256 * u < i1) bn_red_terms<MODE>(xv[u], gv[u], yv[u], ry != nullptr, m, is, t0, t1);
     }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
@@ -228,7 +197,7 @@ __global__ __launch_bounds__(256) void k_colreduce_strided(const float *__restri
     float m = 0.f, is = 1.f;
     if (MODE == 1) { m = mean[c]; is = invstd[c]; }
     for (int64_t i = threadIdx.x; i < n; i += 256)
-        red_terms<MODE>(x[i * C + c], MODE ? dy[i * C + c] : 0.f, (MODE && ry) ? ry[i * C + c] : 1.f, ry != nullptr, m,
+        bn_red_terms<MODE>(x[i * C + c], MODE ? dy[i * C + c] : 0.f, (MODE && ry) ? ry[i * C + c] : 1.f, ry != nullptr, m,
                         is, t0, t1);
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
@@ -319,7 +288,6 @@ static bool colreduce_uses_partials(int C, int64_t hw) { return hw == 1 && C % 4
 // accumulate the same partials in its epilogue, bit for bit (sconv.hip:k_sconv_reduce_rows4_bwdstats)
 #define COLREDUCE_BWD_MAX_BLOCKS 2048
 
-#include <stdlib.h>
 // workgroups of the per-row statistics reductions (forward and backward); measured in the step: 1024 (two rows in flight
 // per thread) 50.4 ms, 2048 50.8, 512 50.6; at bs 2 1536 / 2048 lose too (round 5)
 extern "C" int32_t lidog_stats_max_blocks(void) { return 1024; }
@@ -405,9 +373,7 @@ extern "C" int lidog_bn_bwd_reduce_bits(const float *dy, const float *x, const f
                                         const uint32_t *relu_bits, int64_t n, int32_t C, int64_t hw,
                                         const float *mean, const float *invstd, double *sums, double *ws, double count,
                                         float *dw, float *db, const float *relu_w, const float *relu_b, void *stream) {
-    LIDOG_REQUIRE((relu_w == nullptr) == (relu_b == nullptr) && (relu_y != nullptr) + (relu_w != nullptr) +
-                                                                        (relu_bits != nullptr) <= 1,
-                  "bn_bwd_reduce: pass at most one of relu_y, relu_bits, (relu_w, relu_b)");
+    if (int e = lidog_require_one_relu_source("bn_bwd_reduce", relu_y, relu_bits, relu_w, relu_b)) return e;
     BnFinish fin = {0.f, 0.f, nullptr, nullptr, nullptr, nullptr, dw, db};
     return launch_colreduce<1>(x, dy, relu_y, n, C, hw, mean, invstd, sums, ws, count, fin, (hipStream_t)stream,
                                relu_w, relu_b, relu_bits);
@@ -419,16 +385,8 @@ __global__ void k_bn_finalize(const double *__restrict__ sums, double count, int
     int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     if (!(count > 0)) count = sums[2 * C];  // SyncBatchNorm: the all-reduced row count rides behind the sums
-    double m = sums[c] / count;
-    double var = sums[C + c] / count - m * m;
-    if (var < 0) var = 0;
-    mean[c] = (float)m;
-    invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-    if (running_mean) {
-        double unb = (count > 1) ? var * count / (count - 1) : var;
-        running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)m;
-        running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unb;
-    }
+    lidog_bn_finalize_channel(sums[c], sums[C + c], count, c,
+                              BnFinish{eps, momentum, mean, invstd, running_mean, running_var, nullptr, nullptr});
 }
 
 extern "C" int lidog_bn_finalize(const double *sums, double count, int32_t C, float eps, float momentum, float *mean,
@@ -450,10 +408,26 @@ __global__ __launch_bounds__(256) void k_bn_apply(const float *__restrict__ x, i
                                                   const float *__restrict__ res, int relu, float *__restrict__ y) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         int c = chan_of(i, C, hw);
-        float v = (x[i] - mean[c]) * invstd[c] * w[c] + b[c];
-        if (res) v += res[i];
-        if (relu) v = v > 0.f ? v : 0.f;
-        y[i] = v;
+        y[i] = bn_res_relu<true>(bn_affine(x[i], mean[c], invstd[c], w[c], b[c]), res, i, relu);
+    }
+}
+
+// The row loop of the [rows, C] apply pass; mean / invstd come from global memory (k_bn_apply4) or from LDS
+// (k_bn_apply4_sync).  The loop is uniform per workgroup (the tail iteration masks lanes instead of leaving): the ReLU
+// bit mask is assembled from 8 neighbouring lanes with shuffles
+__device__ __forceinline__ void bn_apply4_rows(const float4 *x, int64_t total4, int C4, const float4 *mean,
+                                               const float4 *invstd, const float4 *w, const float4 *b, const float4 *res,
+                                               int relu, float4 *y, uint32_t *bits) {
+    for (int64_t base = (int64_t)blockIdx.x * 256; base < total4; base += (int64_t)gridDim.x * 256) {
+        const int64_t i = base + threadIdx.x;
+        const bool ok = i < total4;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (ok) {
+            int c4 = (int)(i % C4);
+            v = bn_res_relu4(bn_affine4(x[i], mean[c4], invstd[c4], w[c4], b[c4]), res, i, relu);
+            y[i] = v;
+        }
+        if (bits) lidog_relu_bits_store(bits, i, ok, v);
     }
 }
 
@@ -462,39 +436,13 @@ __global__ __launch_bounds__(256) void k_bn_apply4(const float4 *__restrict__ x,
                                                    const float4 *__restrict__ w, const float4 *__restrict__ b,
                                                    const float4 *__restrict__ res, int relu, float4 *__restrict__ y,
                                                    uint32_t *__restrict__ bits) {
-    // the loop is uniform per workgroup (the tail iteration masks lanes instead of leaving): the ReLU bit mask is
-    // assembled from 8 neighbouring lanes with shuffles
-    for (int64_t base = (int64_t)blockIdx.x * 256; base < total4; base += (int64_t)gridDim.x * 256) {
-        const int64_t i = base + threadIdx.x;
-        const bool ok = i < total4;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (ok) {
-            int c4 = (int)(i % C4);
-            v = x[i];
-            const float4 m = mean[c4], s = invstd[c4], ww = w[c4], bb = b[c4];
-            v.x = (v.x - m.x) * s.x * ww.x + bb.x;
-            v.y = (v.y - m.y) * s.y * ww.y + bb.y;
-            v.z = (v.z - m.z) * s.z * ww.z + bb.z;
-            v.w = (v.w - m.w) * s.w * ww.w + bb.w;
-            if (res) { float4 r = res[i]; v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w; }
-            if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-            y[i] = v;
-        }
-        if (bits) {   // 4 bits per float4 (element > 0), 8 float4 per 32-bit word: bit 4 * (i % 8) + component
-            uint32_t nib = (v.x > 0.f ? 1u : 0u) | (v.y > 0.f ? 2u : 0u) | (v.z > 0.f ? 4u : 0u) | (v.w > 0.f ? 8u : 0u);
-            uint32_t wv = nib << (4 * (threadIdx.x & 7));
-            wv |= __shfl_xor(wv, 1);
-            wv |= __shfl_xor(wv, 2);
-            wv |= __shfl_xor(wv, 4);
-            if (ok && (threadIdx.x & 7) == 0) bits[i >> 3] = wv;
-        }
-    }
+    bn_apply4_rows(x, total4, C4, mean, invstd, w, b, res, relu, y, bits);
 }
 
 // The same pass for SyncBatchNorm: mean / invstd are derived from the ALL-REDUCED (sum x, sum x^2, rows) vector inside
-// the launch -- k_bn_finalize's arithmetic, by the first C threads of every workgroup into LDS -- instead of by a
-// launch of their own between the all-reduce and this pass (62 per step on the dependent chain of a data-parallel
-// rank).  Workgroup 0 also stores mean / invstd (backward reads them) and updates the running statistics.
+// the launch -- by the first C threads of every workgroup into LDS -- instead of by a launch of their own between the
+// all-reduce and this pass (62 per step on the dependent chain of a data-parallel rank).  Workgroup 0 also stores
+// mean / invstd (backward reads them) and updates the running statistics.
 __global__ __launch_bounds__(256) void k_bn_apply4_sync(const float4 *__restrict__ x, int64_t total4, int C4,
                                                         const double *__restrict__ sums, float eps, float momentum,
                                                         float *__restrict__ mean_out, float *__restrict__ invstd_out,
@@ -505,50 +453,21 @@ __global__ __launch_bounds__(256) void k_bn_apply4_sync(const float4 *__restrict
     extern __shared__ float s_ms[];   // [C] mean, [C] invstd
     const int C = C4 * 4;
     const double count = sums[2 * C];
+    const BnFinish fin = {eps, momentum, mean_out, invstd_out, running_mean, running_var, nullptr, nullptr};
     for (int c = threadIdx.x; c < C; c += 256) {
-        const double m = sums[c] / count;
-        double var = sums[C + c] / count - m * m;
-        if (var < 0) var = 0;
-        const float mf = (float)m, isf = (float)(1.0 / sqrt(var + (double)eps));
+        const BnMoments mo = bn_moments(sums[c], sums[C + c], count);
+        const float mf = (float)mo.mean, isf = bn_invstd(mo.var, eps);
         s_ms[c] = mf;
         s_ms[C + c] = isf;
         if (blockIdx.x == 0) {
             mean_out[c] = mf;
             invstd_out[c] = isf;
-            if (running_mean) {
-                const double unb = (count > 1) ? var * count / (count - 1) : var;
-                running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mf;
-                running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unb;
-            }
+            bn_running_update(mo, count, c, fin);
         }
     }
     __syncthreads();
-    const float4 *mean4 = reinterpret_cast<const float4 *>(s_ms), *is4 = reinterpret_cast<const float4 *>(s_ms + C);
-    for (int64_t base = (int64_t)blockIdx.x * 256; base < total4; base += (int64_t)gridDim.x * 256) {
-        const int64_t i = base + threadIdx.x;
-        const bool ok = i < total4;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (ok) {
-            int c4 = (int)(i % C4);
-            v = x[i];
-            const float4 m = mean4[c4], s = is4[c4], ww = w[c4], bb = b[c4];
-            v.x = (v.x - m.x) * s.x * ww.x + bb.x;
-            v.y = (v.y - m.y) * s.y * ww.y + bb.y;
-            v.z = (v.z - m.z) * s.z * ww.z + bb.z;
-            v.w = (v.w - m.w) * s.w * ww.w + bb.w;
-            if (res) { float4 r = res[i]; v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w; }
-            if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-            y[i] = v;
-        }
-        if (bits) {
-            uint32_t nib = (v.x > 0.f ? 1u : 0u) | (v.y > 0.f ? 2u : 0u) | (v.z > 0.f ? 4u : 0u) | (v.w > 0.f ? 8u : 0u);
-            uint32_t wv = nib << (4 * (threadIdx.x & 7));
-            wv |= __shfl_xor(wv, 1);
-            wv |= __shfl_xor(wv, 2);
-            wv |= __shfl_xor(wv, 4);
-            if (ok && (threadIdx.x & 7) == 0) bits[i >> 3] = wv;
-        }
-    }
+    bn_apply4_rows(x, total4, C4, reinterpret_cast<const float4 *>(s_ms), reinterpret_cast<const float4 *>(s_ms + C), w,
+                   b, res, relu, y, bits);
 }
 
 static unsigned ew_grid(int64_t n) {
@@ -566,8 +485,7 @@ __global__ __launch_bounds__(256) void k_bn_apply_plane(const float *__restrict_
                                                         float *__restrict__ y) {
     const int64_t plane = blockIdx.x;
     const int c = (int)(plane % C);
-    const float m = mean[c], sc = invstd[c] * w[c], sh = b[c], is = invstd[c], ww = w[c];
-    (void)sc;
+    const float m = mean[c], sh = b[c], is = invstd[c], ww = w[c];
     const int64_t chunk = (hw + gridDim.y - 1) / gridDim.y;
     const int64_t i0 = plane * hw + (int64_t)blockIdx.y * chunk;
     const int64_t i1 = (blockIdx.y + 1) * chunk < hw ? i0 + chunk : plane * hw + hw;
@@ -581,9 +499,7 @@ __global__ __launch_bounds__(256) void k_bn_apply_plane(const float *__restrict_
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            float v = (xv[u] - m) * is * ww + sh;   // same operation order as k_bn_apply
-            if (res) v += rv[u];
-            if (relu) v = v > 0.f ? v : 0.f;
+            const float v = bn_res_relu<true>(bn_affine(xv[u], m, is, ww, sh), res != nullptr, rv[u], relu);
             if (i + 256 * u < i1) y[i + 256 * u] = v;
         }
     }
@@ -617,9 +533,8 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply_plane(const float *__restr
         for (int u = 0; u < 4; ++u) {
             float g = gv[u];
             if (ry && !(yv[u] > 0.f)) g = 0.f;
-            const float xh = (xv[u] - m) * is;
             if (i + 256 * u < i1) {
-                dx[i + 256 * u] = (g - m0 - xh * m1) * is * ww;   // same operation order as k_bn_bwd_apply
+                dx[i + 256 * u] = bn_dx(g, xv[u], m, is, ww, m0, m1);
                 if (dres) dres[i + 256 * u] = g;
             }
         }
@@ -688,11 +603,10 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply(const float *__restrict__ 
         int c = chan_of(i, C, hw);
         float g = dy[i];
         if (ry && !(ry[i] > 0.f)) g = 0.f;
-        float is = invstd[c];
-        float xh = (x[i] - mean[c]) * is;
+        const float is = invstd[c], xv = x[i], mu = mean[c];
         const double ic = (inv_count > 0) ? inv_count : 1.0 / sums[2 * C];
         float m0 = (float)(sums[c] * ic), m1 = (float)(sums[C + c] * ic);
-        dx[i] = (g - m0 - xh * m1) * is * w[c];
+        dx[i] = bn_dx(g, xv, mu, is, w[c], m0, m1);
         if (dres) dres[i] = g;
     }
 }
@@ -721,26 +635,15 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply4(const float4 *__restrict_
         is[j] = invstd[c];
         gw[j] = w[c];
         gb[j] = rb ? rb[c] : 0.f;
-        sc[j] = is[j] * w[c];
+        sc[j] = bn_scale(is[j], w[c]);
         m0[j] = (float)(sums[c] * ic);
         m1[j] = (float)(sums[C + c] * ic);
     }
     auto one = [&](int64_t at, float4 g, const float4 xv, const float4 y) {
-        if (ry || rbits) {
-            g.x = y.x > 0.f ? g.x : 0.f; g.y = y.y > 0.f ? g.y : 0.f;
-            g.z = y.z > 0.f ? g.z : 0.f; g.w = y.w > 0.f ? g.w : 0.f;
-        } else if (rb) {   // ReLU mask from the forward pass's pre-activation, recomputed bit for bit from x
-            g.x = ((xv.x - mu[0]) * is[0] * gw[0] + gb[0]) > 0.f ? g.x : 0.f;
-            g.y = ((xv.y - mu[1]) * is[1] * gw[1] + gb[1]) > 0.f ? g.y : 0.f;
-            g.z = ((xv.z - mu[2]) * is[2] * gw[2] + gb[2]) > 0.f ? g.z : 0.f;
-            g.w = ((xv.w - mu[3]) * is[3] * gw[3] + gb[3]) > 0.f ? g.w : 0.f;
-        }
-        float4 o;
-        o.x = (g.x - m0[0] - (xv.x - mu[0]) * is[0] * m1[0]) * sc[0];
-        o.y = (g.y - m0[1] - (xv.y - mu[1]) * is[1] * m1[1]) * sc[1];
-        o.z = (g.z - m0[2] - (xv.z - mu[2]) * is[2] * m1[2]) * sc[2];
-        o.w = (g.w - m0[3] - (xv.w - mu[3]) * is[3] * m1[3]) * sc[3];
-        dx[at] = o;
+        if (ry || rbits) g = bn_relu_mask4(g, y);
+        else if (rb)   // ReLU mask from the forward pass's pre-activation, recomputed from x
+            g = bn_relu_mask4(g, bn_affine4(xv, bn_f4(mu), bn_f4(is), bn_f4(gw), bn_f4(gb)));
+        dx[at] = bn_dx_scaled4(g, xv, bn_f4(mu), bn_f4(is), bn_f4(sc), bn_f4(m0), bn_f4(m1));
         if (dres) dres[at] = g;
     };
     const float4 none = make_float4(1.f, 1.f, 1.f, 1.f);

@@ -36,6 +36,14 @@ struct BnFinish {
     float *mean, *invstd, *running_mean, *running_var;
     float *dw, *db;
 };
+// the ReLU mask of a BatchNorm-backward reduction has at most one source; `who`: the entry point, for the message
+static inline int lidog_require_one_relu_source(const char *who, const float *relu_y, const uint32_t *relu_bits,
+                                                const float *relu_w, const float *relu_b) {
+    LIDOG_REQUIRE((relu_w == nullptr) == (relu_b == nullptr) &&
+                      (relu_y != nullptr) + (relu_w != nullptr) + (relu_bits != nullptr) <= 1,
+                  "%s: pass at most one of relu_y, relu_bits, (relu_w, relu_b)", who);
+    return 0;
+}
 int lidog_launch_sums_finish(const double *partial, int nb, int C, double *sums, double count, BnFinish fin,
                              hipStream_t st);
 
@@ -84,11 +92,4 @@ __device__ __forceinline__ int lidog_find(const uint64_t *__restrict__ keys, con
         if (k == LIDOG_EMPTY_KEY) return -1;
         slot = (slot + 1) & mask;
     }
-}
-
-// ReLU bit mask of a [rows, C] matrix (C % 4 == 0) written by lidog_bn_apply_bits: bit 4 * (q % 8) + j of word q / 8 is
-// (element j of float4 number q) > 0.  Read back as a float4 of 1 / 0 so that the consumers keep their `y > 0` tests.
-__device__ __forceinline__ float4 lidog_relu_bits_as_float4(const uint32_t *__restrict__ bits, int64_t q) {
-    const uint32_t nib = bits[q >> 3] >> (4 * (int)(q & 7));
-    return make_float4((float)(nib & 1u), (float)((nib >> 1) & 1u), (float)((nib >> 2) & 1u), (float)((nib >> 3) & 1u));
 }

@@ -19,6 +19,7 @@
 //
 // [rows, C] with C % 4 == 0 streams float4 rows as bn.hip does; any other C takes plain scalar kernels (the module is
 // public; no performance target there).
+#include "bn_math.h"
 #include "common.h"
 #include "stats_tail.h"
 
@@ -170,38 +171,18 @@ __global__ __launch_bounds__(256) void k_in_reduce4(const float4 *__restrict__ x
                     const int64_t pr = perm[row];
                     v[u] = x[pr * C4 + c4];
                     g[u] = MODE == 1 ? dy[pr * dy_s4 + c4] : make_float4(0, 0, 0, 0);
-                    if (MODE == 1 && bits) {
-                        const float4 k = lidog_relu_bits_as_float4(bits, pr * bits_s4 + bits_o4 + c4);
-                        g[u].x = k.x > 0.f ? g[u].x : 0.f; g[u].y = k.y > 0.f ? g[u].y : 0.f;
-                        g[u].z = k.z > 0.f ? g[u].z : 0.f; g[u].w = k.w > 0.f ? g[u].w : 0.f;
-                    }
+                    if (MODE == 1 && bits)
+                        g[u] = bn_relu_mask4(g[u], lidog_relu_bits_as_float4(bits, pr * bits_s4 + bits_o4 + c4));
                 }
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     if (row0 + u * RB >= e) continue;
-                    const float vv[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-                    const float gg[4] = {g[u].x, g[u].y, g[u].z, g[u].w};
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        if (MODE == 0) {
-                            a[j] += (double)vv[j];
-                            a[4 + j] += (double)vv[j] * (double)vv[j];
-                        } else {
-                            const float xh = (vv[j] - m[j]) * is[j];
-                            a[j] += (double)gg[j];
-                            a[4 + j] += (double)gg[j] * (double)xh;
-                        }
-                    }
+                    bn_red_terms4<MODE>(v[u], g[u], g[u], false, bn_f4(m), bn_f4(is), a);   // g is masked already
                 }
             }
         }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) red[tid * 8 + j] = a[j];
-        __syncthreads();
+        lidog_stats_wg_reduce(red, tid, RB, C4, c4, active && r == 0, a);
         if (active && r == 0) {
-            for (int rr = 1; rr < RB; ++rr)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) a[j] += red[(rr * C4 + c4) * 8 + j];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 lidog_store_sc1(prow + b * C + c4 * 4 + j, a[j]);
@@ -243,15 +224,7 @@ __global__ __launch_bounds__(256) void k_in_reduce_scalar(const float *__restric
     double t0 = 0, t1 = 0;
     for (int64_t i = s + threadIdx.x; i < e; i += 256) {
         const int64_t pr = perm[i];
-        const float v = x[pr * C + c];
-        if (MODE == 0) {
-            t0 += (double)v;
-            t1 += (double)v * (double)v;
-        } else {
-            const float g = dy[pr * C + c], xh = (v - m) * is;
-            t0 += (double)g;
-            t1 += (double)g * (double)xh;
-        }
+        bn_red_terms<MODE>(x[pr * C + c], MODE ? dy[pr * C + c] : 0.f, 1.f, false, m, is, t0, t1);
     }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
@@ -338,20 +311,6 @@ static unsigned in_grid(int64_t n) {
     return (unsigned)(g > 4096 ? 4096 : (g < 1 ? 1 : g));
 }
 
-// the normalisation gradient of one element: k_bn_bwd_apply4's expression and operation order (bn.hip), so that the
-// BatchNorm half of the IBN backward pass below equals lidog_bn_bwd_apply bit for bit
-__device__ __forceinline__ float norm_dx(float g, float x, float mu, float is, float sc, float m0, float m1) {
-    return (g - m0 - (x - mu) * is * m1) * sc;
-}
-
-__device__ __forceinline__ float4 in_affine4(float4 v, float4 m, float4 s, float4 w, float4 b) {
-    v.x = (v.x - m.x) * s.x * w.x + b.x;
-    v.y = (v.y - m.y) * s.y * w.y + b.y;
-    v.z = (v.z - m.z) * s.z * w.z + b.z;
-    v.w = (v.w - m.w) * s.w * w.w + b.w;
-    return v;
-}
-
 __global__ __launch_bounds__(256) void k_in_apply4(const float4 *__restrict__ x, int64_t total4, int C4,
                                                    const int32_t *__restrict__ bid, const float4 *__restrict__ mean,
                                                    const float4 *__restrict__ invstd, const float4 *__restrict__ w,
@@ -360,7 +319,7 @@ __global__ __launch_bounds__(256) void k_in_apply4(const float4 *__restrict__ x,
         const int64_t row = i / C4;
         const int c4 = (int)(i - row * C4);
         const int64_t k = (int64_t)bid[row] * C4 + c4;
-        y[i] = in_affine4(x[i], mean[k], invstd[k], w[c4], b[c4]);
+        y[i] = bn_affine4(x[i], mean[k], invstd[k], w[c4], b[c4]);
     }
 }
 
@@ -372,7 +331,7 @@ __global__ __launch_bounds__(256) void k_in_apply(const float *__restrict__ x, i
         const int64_t row = i / C;
         const int c = (int)(i - row * C);
         const int64_t k = (int64_t)bid[row] * C + c;
-        y[i] = (x[i] - mean[k]) * invstd[k] * w[c] + b[c];
+        y[i] = bn_affine(x[i], mean[k], invstd[k], w[c], b[c]);
     }
 }
 
@@ -387,12 +346,7 @@ __global__ __launch_bounds__(256) void k_in_bwd_apply4(const float4 *__restrict_
         const int c4 = (int)(i - row * C4);
         const int64_t k = (int64_t)bid[row] * C4 + c4;
         const float4 g = dy[i], xv = x[i], mu = mean[k], is = invstd[k], ww = w[c4], m0 = coef[k], m1 = coef[BC4 + k];
-        float4 o;
-        o.x = norm_dx(g.x, xv.x, mu.x, is.x, is.x * ww.x, m0.x, m1.x);
-        o.y = norm_dx(g.y, xv.y, mu.y, is.y, is.y * ww.y, m0.y, m1.y);
-        o.z = norm_dx(g.z, xv.z, mu.z, is.z, is.z * ww.z, m0.z, m1.z);
-        o.w = norm_dx(g.w, xv.w, mu.w, is.w, is.w * ww.w, m0.w, m1.w);
-        dx[i] = o;
+        dx[i] = bn_dx_scaled4(g, xv, mu, is, bn_scale4(is, ww), m0, m1);
     }
 }
 
@@ -406,7 +360,7 @@ __global__ __launch_bounds__(256) void k_in_bwd_apply(const float *__restrict__ 
         const int64_t row = i / C;
         const int c = (int)(i - row * C);
         const int64_t k = (int64_t)bid[row] * C + c;
-        dx[i] = norm_dx(dy[i], x[i], mean[k], invstd[k], invstd[k] * w[c], coef[k], coef[BC + k]);
+        dx[i] = bn_dx_scaled(dy[i], x[i], mean[k], invstd[k], bn_scale(invstd[k], w[c]), coef[k], coef[BC + k]);
     }
 }
 
@@ -444,9 +398,9 @@ extern "C" int lidog_in_bwd_apply(const float *dy, const float *x, int64_t n, in
 
 // ------------------------------------------------------------------ the IBN block: ReLU(BN(x)) | ReLU(IN(x))
 // y [n, 2C]: float4 q = row * 2 C4 + c of y is BatchNorm (c < C4) or instance norm (c >= C4) of x's float4 row * C4 +
-// c mod C4, then max(., 0); bits: lidog_bn_apply_bits' layout over y.  Both halves use the expression of their own
-// apply pass (bn.hip:k_bn_apply4, k_in_apply4): the result equals lidog_bn_apply + lidog_in_apply + lidog_cat2 +
-// lidog_relu_fwd bit for bit.  The two halves of a row are read by neighbouring lanes: x comes from HBM once.
+// c mod C4, then max(., 0); bits: lidog_bn_apply_bits' layout over y.  The result equals lidog_bn_apply +
+// lidog_in_apply + lidog_cat2 + lidog_relu_fwd bit for bit.  The two halves of a row are read by neighbouring lanes: x
+// comes from HBM once.
 __global__ __launch_bounds__(256) void k_ibn_apply4(const float4 *__restrict__ x, int64_t total4, int C4,
                                                     const float4 *__restrict__ bn_mean,
                                                     const float4 *__restrict__ bn_invstd, const float4 *__restrict__ bn_w,
@@ -464,21 +418,16 @@ __global__ __launch_bounds__(256) void k_ibn_apply4(const float4 *__restrict__ x
             const int64_t row = i / C8;
             const int c = (int)(i - row * C8);
             if (c < C4) {
-                v = in_affine4(x[row * C4 + c], bn_mean[c], bn_invstd[c], bn_w[c], bn_b[c]);
+                v = bn_affine4(x[row * C4 + c], bn_mean[c], bn_invstd[c], bn_w[c], bn_b[c]);
             } else {
                 const int c4 = c - C4;
                 const int64_t k = (int64_t)bid[row] * C4 + c4;
-                v = in_affine4(x[row * C4 + c4], in_mean[k], in_invstd[k], in_w[c4], in_b[c4]);
+                v = bn_affine4(x[row * C4 + c4], in_mean[k], in_invstd[k], in_w[c4], in_b[c4]);
             }
-            v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+            v = bn_res_relu4(v, nullptr, i, 1);
             y[i] = v;
         }
-        uint32_t nib = (v.x > 0.f ? 1u : 0u) | (v.y > 0.f ? 2u : 0u) | (v.z > 0.f ? 4u : 0u) | (v.w > 0.f ? 8u : 0u);
-        uint32_t wv = nib << (4 * (threadIdx.x & 7));
-        wv |= __shfl_xor(wv, 1);
-        wv |= __shfl_xor(wv, 2);
-        wv |= __shfl_xor(wv, 4);
-        if (ok && (threadIdx.x & 7) == 0) bits[i >> 3] = wv;
+        lidog_relu_bits_store(bits, i, ok, v);
     }
 }
 
@@ -507,39 +456,22 @@ __global__ __launch_bounds__(256) void k_ibn_bn_reduce4(const float4 *__restrict
                 int64_t row = row0 + u * step;
                 row = row < n ? row : n - 1;
                 v[u] = x[row * C4 + c4];
-                g[u] = dy[row * 2 * C4 + c4];
-                const float4 k = lidog_relu_bits_as_float4(bits, row * 2 * C4 + c4);
-                g[u].x = k.x > 0.f ? g[u].x : 0.f; g[u].y = k.y > 0.f ? g[u].y : 0.f;
-                g[u].z = k.z > 0.f ? g[u].z : 0.f; g[u].w = k.w > 0.f ? g[u].w : 0.f;
+                g[u] = bn_relu_mask4(dy[row * 2 * C4 + c4], lidog_relu_bits_as_float4(bits, row * 2 * C4 + c4));
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const bool ok = row0 + u * step < n;
-                const float4 z = make_float4(0, 0, 0, 0);
-                const float4 vv = v[u], gg = ok ? g[u] : z;
-                const float vx[4] = {vv.x, vv.y, vv.z, vv.w}, gx[4] = {gg.x, gg.y, gg.z, gg.w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float xh = (vx[j] - m[j]) * is[j];
-                    a[j] += (double)gx[j];
-                    a[4 + j] += (double)gx[j] * (double)xh;
-                }
+                const float4 gg = ok ? g[u] : make_float4(0, 0, 0, 0);
+                bn_red_terms4<1>(v[u], gg, gg, false, bn_f4(m), bn_f4(is), a);   // g is masked already
             }
         }
     }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) red[tid * 8 + j] = a[j];
-    __syncthreads();
-    if (active && r == 0) {
-        for (int rr = 1; rr < RB; ++rr)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) a[j] += red[(rr * C4 + c4) * 8 + j];
-    }
+    lidog_stats_wg_reduce(red, tid, RB, C4, c4, active && r == 0, a);
     lidog_stats_tail(tail, active && r == 0, c4, a);
 }
 
-// dx = dx_BN + dx_IN from dy [n, 2C] and the mask bits of the forward pass: each half is k_bn_bwd_apply4's /
-// k_in_bwd_apply4's expression, and their sum is what autograd adds for the two readers of x
+// dx = dx_BN + dx_IN from dy [n, 2C] and the mask bits of the forward pass: the sum autograd adds for the two readers
+// of x
 __global__ __launch_bounds__(256) void k_ibn_bwd_apply4(const float4 *__restrict__ dy, const uint32_t *__restrict__ bits,
                                                         const float4 *__restrict__ x, int64_t total4, int C4, int B,
                                                         const float *__restrict__ bn_mean,
@@ -559,7 +491,7 @@ __global__ __launch_bounds__(256) void k_ibn_bwd_apply4(const float4 *__restrict
             const int c = 4 * q + j;
             t[0][j] = bn_mean[c];
             t[1][j] = bn_invstd[c];
-            t[2][j] = bn_invstd[c] * bn_w[c];
+            t[2][j] = bn_scale(bn_invstd[c], bn_w[c]);
             t[3][j] = (float)(bn_sums[c] * bn_ic);
             t[4][j] = (float)(bn_sums[C + c] * bn_ic);
         }
@@ -574,20 +506,14 @@ __global__ __launch_bounds__(256) void k_ibn_bwd_apply4(const float4 *__restrict
         const int64_t qb = row * 2 * C4 + c4, qi = qb + C4;
         float4 gb = dy[qb], gi = dy[qi];
         const float4 xv = x[i];
-        const float4 kb = lidog_relu_bits_as_float4(bits, qb), ki = lidog_relu_bits_as_float4(bits, qi);
-        gb.x = kb.x > 0.f ? gb.x : 0.f; gb.y = kb.y > 0.f ? gb.y : 0.f; gb.z = kb.z > 0.f ? gb.z : 0.f;
-        gb.w = kb.w > 0.f ? gb.w : 0.f;
-        gi.x = ki.x > 0.f ? gi.x : 0.f; gi.y = ki.y > 0.f ? gi.y : 0.f; gi.z = ki.z > 0.f ? gi.z : 0.f;
-        gi.w = ki.w > 0.f ? gi.w : 0.f;
+        gb = bn_relu_mask4(gb, lidog_relu_bits_as_float4(bits, qb));
+        gi = bn_relu_mask4(gi, lidog_relu_bits_as_float4(bits, qi));
         const float4 mu = s_bn[0][c4], is = s_bn[1][c4], sc = s_bn[2][c4], m0 = s_bn[3][c4], m1 = s_bn[4][c4];
         const int64_t k = (int64_t)bid[row] * C4 + c4;
         const float4 imu = in_mean[k], iis = in_invstd[k], iw = in_w[c4], im0 = coef[k], im1 = coef[BC4 + k];
-        float4 o;
-        o.x = norm_dx(gb.x, xv.x, mu.x, is.x, sc.x, m0.x, m1.x) + norm_dx(gi.x, xv.x, imu.x, iis.x, iis.x * iw.x, im0.x, im1.x);
-        o.y = norm_dx(gb.y, xv.y, mu.y, is.y, sc.y, m0.y, m1.y) + norm_dx(gi.y, xv.y, imu.y, iis.y, iis.y * iw.y, im0.y, im1.y);
-        o.z = norm_dx(gb.z, xv.z, mu.z, is.z, sc.z, m0.z, m1.z) + norm_dx(gi.z, xv.z, imu.z, iis.z, iis.z * iw.z, im0.z, im1.z);
-        o.w = norm_dx(gb.w, xv.w, mu.w, is.w, sc.w, m0.w, m1.w) + norm_dx(gi.w, xv.w, imu.w, iis.w, iis.w * iw.w, im0.w, im1.w);
-        dx[i] = o;
+        const float4 ob = bn_dx_scaled4(gb, xv, mu, is, sc, m0, m1);
+        const float4 oi = bn_dx_scaled4(gi, xv, imu, iis, bn_scale4(iis, iw), im0, im1);
+        dx[i] = make_float4(ob.x + oi.x, ob.y + oi.y, ob.z + oi.z, ob.w + oi.w);
     }
 }
 

@@ -2,6 +2,7 @@
 // waves) -> per-output-row reduction in ascending kernel-offset order (no atomics, bit-reproducible),
 // weight gradient by split reduction over pairs.  CPU restatement: oracle/me_oracle.c
 // (orc_conv_fwd / orc_conv_bwd_data / orc_conv_bwd_weight).
+#include "bn_math.h"
 #include "common.h"
 #include "stats_tail.h"
 #include "sconv_mfma.h"
@@ -472,14 +473,7 @@ __global__ __launch_bounds__(256) void k_sconv_reduce4_stats(const float4 *__res
             a[6] += (double)acc.z * acc.z; a[7] += (double)acc.w * acc.w;
         }
     }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) red[tid * 8 + j] = a[j];
-    __syncthreads();
-    if (active && r == 0) {
-        for (int rr = 1; rr < RB; ++rr)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) a[j] += red[(rr * C4 + c4) * 8 + j];
-    }
+    lidog_stats_wg_reduce(red, tid, RB, C4, c4, active && r == 0, a);
     lidog_stats_tail(tail, active && r == 0, c4, a);   // partial row + in-kernel finish by the last workgroup
 }
 
@@ -600,14 +594,7 @@ __global__ __launch_bounds__(256) void k_sconv_reduce_rows4_stats(const float4 *
             }
         }
     }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) red[tid * 8 + j] = a[j];
-    __syncthreads();
-    if (active && r == 0) {
-        for (int rr = 1; rr < RB; ++rr)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) a[j] += red[(rr * C4 + c4) * 8 + j];
-    }
+    lidog_stats_wg_reduce(red, tid, RB, C4, c4, active && r == 0, a);
     lidog_stats_tail(tail, active && r == 0, c4, a);   // partial row + in-kernel finish by the last workgroup
 }
 
@@ -615,9 +602,8 @@ __global__ __launch_bounds__(256) void k_sconv_reduce_rows4_stats(const float4 *
 // writes: out[o] = sum of T rows (+ addend) is the complete gradient dy of that layer's BatchNorm output, so
 // (sum dy', sum dy' * xhat) -- dy' = dy masked by the layer's ReLU, xhat from its saved pre-normalisation rows -- can be
 // accumulated while dy is still in registers instead of by a second pass over dy (bn.hip:k_colreduce_nc4<1>, which then
-// is not launched).  Same row -> (workgroup, thread) assignment, same per-thread order, same LDS tree and the same
-// terms (red_terms<1>) as that kernel at the same grid size, and the partials go through the same finishing kernel:
-// the sums are bit-identical to the two-pass path.
+// is not launched).  Same row -> (workgroup, thread) assignment and same per-thread order as that kernel at the same
+// grid size, and the partials go through the same finishing kernel: the sums are bit-identical to the two-pass path.
 __global__ __launch_bounds__(256) void k_sconv_reduce_rows4_bwdstats(
     const float4 *__restrict__ T, const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ row_list, int64_t n,
     int C4, const float4 *__restrict__ addend, float4 *__restrict__ out, const float4 *__restrict__ pre,
@@ -645,20 +631,8 @@ __global__ __launch_bounds__(256) void k_sconv_reduce_rows4_bwdstats(
         auto emit = [&](int64_t idx, float4 g, float4 x, float4 y, float4 ad) {
             g.x += ad.x; g.y += ad.y; g.z += ad.z; g.w += ad.w;   // no addend: + 0 (a sum of products is never -0 ... and
             out[idx] = g;                                          // -0 + 0 = +0 compares equal anyway)
-            if (from_x) {   // the forward pass's pre-activation, bit for bit (bn.hip:k_bn_apply4)
-                y.x = (x.x - m[0]) * is[0] * gw[0] + gb[0];
-                y.y = (x.y - m[1]) * is[1] * gw[1] + gb[1];
-                y.z = (x.z - m[2]) * is[2] * gw[2] + gb[2];
-                y.w = (x.w - m[3]) * is[3] * gw[3] + gb[3];
-            }
-            const float xv[4] = {x.x, x.y, x.z, x.w}, gv[4] = {g.x, g.y, g.z, g.w}, yv[4] = {y.x, y.y, y.z, y.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {   // = bn.hip:red_terms<1>
-                const float gg = (has_relu && !(yv[j] > 0.f)) ? 0.f : gv[j];
-                const float xh = (xv[j] - m[j]) * is[j];
-                a[j] += (double)gg;
-                a[4 + j] += (double)gg * (double)xh;
-            }
+            if (from_x) y = bn_affine4(x, bn_f4(m), bn_f4(is), bn_f4(gw), bn_f4(gb));   // the pre-activation
+            bn_red_terms4<1>(x, g, y, has_relu, bn_f4(m), bn_f4(is), a);
         };
         // two rows of this thread in flight (rows o and o + step), accumulated in row order
         for (int64_t o = (int64_t)blockIdx.x * RB + r; o < n; o += 2 * step) {
@@ -681,14 +655,7 @@ __global__ __launch_bounds__(256) void k_sconv_reduce_rows4_bwdstats(
             }
         }
     }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) red[tid * 8 + j] = a[j];
-    __syncthreads();
-    if (active && r == 0) {
-        for (int rr = 1; rr < RB; ++rr)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) a[j] += red[(rr * C4 + c4) * 8 + j];
-    }
+    lidog_stats_wg_reduce(red, tid, RB, C4, c4, active && r == 0, a);
     lidog_stats_tail(tail, active && r == 0, c4, a);   // partial row + in-kernel finish by the last workgroup
 }
 
@@ -701,9 +668,7 @@ extern "C" int lidog_sconv_reduce_rows_bwdstats(const float *T, const int32_t *r
     hipStream_t st = (hipStream_t)stream;
     LIDOG_REQUIRE(C % 4 == 0 && C / 4 <= 256, "sconv_reduce_rows_bwdstats: C must be a multiple of 4, <= 1024");
     LIDOG_REQUIRE(pre && mean && invstd && sums && partial_ws, "sconv_reduce_rows_bwdstats: null argument");
-    LIDOG_REQUIRE((relu_w == nullptr) == (relu_b == nullptr) &&
-                      (relu_y != nullptr) + (relu_w != nullptr) + (relu_bits != nullptr) <= 1,
-                  "sconv_reduce_rows_bwdstats: pass at most one of relu_y, relu_bits, (relu_w, relu_b)");
+    if (int e = lidog_require_one_relu_source("sconv_reduce_rows_bwdstats", relu_y, relu_bits, relu_w, relu_b)) return e;
     if (n == 0) return hipMemsetAsync(sums, 0, sizeof(double) * (2 * C + 1), st) == hipSuccess ? 0 : 1;
     const int C4 = C / 4;
     const int64_t nb = lidog_bn_bwd_reduce_blocks(n, C);   // the grid of lidog_bn_bwd_reduce: same partials
@@ -720,7 +685,7 @@ extern "C" int lidog_sconv_reduce_rows_bwdstats(const float *T, const int32_t *r
 
 // The same reduction with an evaluation-mode BatchNorm (+ residual + ReLU) applied in the epilogue: the validation path
 // (minkunet_bev.py:376-393, running statistics) needs no statistics pass, so the separate BatchNorm kernel and one
-// write + read of the convolution output go away.  Same expression and operation order as bn.hip:k_bn_apply4.
+// write + read of the convolution output go away.
 __global__ __launch_bounds__(256) void k_sconv_reduce_rows4_bn(const float4 *__restrict__ T,
                                                                const int32_t *__restrict__ row_ptr,
                                                                const int32_t *__restrict__ row_list, int64_t n, int C4,
@@ -740,14 +705,7 @@ __global__ __launch_bounds__(256) void k_sconv_reduce_rows4_bn(const float4 *__r
         float4 bb = bias[c4];
         v.x += bb.x; v.y += bb.y; v.z += bb.z; v.w += bb.w;
     }
-    const float4 m = mean[c4], s = invstd[c4], ww = w[c4], bb = b[c4];
-    v.x = (v.x - m.x) * s.x * ww.x + bb.x;
-    v.y = (v.y - m.y) * s.y * ww.y + bb.y;
-    v.z = (v.z - m.z) * s.z * ww.z + bb.z;
-    v.w = (v.w - m.w) * s.w * ww.w + bb.w;
-    if (res) { float4 r = res[idx]; v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w; }
-    if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-    out[idx] = v;
+    out[idx] = bn_res_relu4(bn_affine4(v, mean[c4], invstd[c4], w[c4], b[c4]), res, idx, relu);
 }
 
 extern "C" int lidog_sconv_reduce_rows_bn(const float *T, const int32_t *row_ptr, const int32_t *row_list, int64_t n,

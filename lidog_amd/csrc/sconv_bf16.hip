@@ -383,8 +383,8 @@ __global__ __launch_bounds__(256) void k_sconv_os_bn_bf16(const float *__restric
         }
     }
 
-    // epilogue: bn.hip:k_bn_apply4's expression and operation order; rows in two batches of eight, the residual loads of
-    // a batch issued before the first use (a row behind the end of the map reads row 0 and is masked afterwards)
+    // epilogue: rows in two batches of eight, the residual loads of a batch issued before the first use (a row behind
+    // the end of the map reads row 0 and is masked afterwards)
 #pragma unroll
     for (int eb = 0; eb < 16; eb += 8) {
         int dst[8];
@@ -401,12 +401,9 @@ __global__ __launch_bounds__(256) void k_sconv_os_bn_bf16(const float *__restric
         for (int u = 0; u < 8; ++u) {
             float v[NT];
 #pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                float y = ((acc[t][eb + u] + bv[t]) - e_m[t]) * e_is[t] * e_w[t] + e_b[t];
-                if (bn.res) y += resv[u][t];
-                if (bn.relu) y = fmaxf(y, 0.f);
-                v[t] = y;
-            }
+            for (int t = 0; t < NT; ++t)
+                v[t] = bn_res_relu(bn_affine(acc[t][eb + u] + bv[t], e_m[t], e_is[t], e_w[t], e_b[t]), bn.res != nullptr,
+                                   resv[u][t], bn.relu);
             if (dst[u] >= 0) bf_store_row<NT>(out + (size_t)dst[u] * Cout + col0 + li * NT, v);
         }
     }

@@ -3,9 +3,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bn_math.h"
+
 // BatchNorm (+ ReLU) of the layer that produced the gathered rows, applied while they are staged: the consumer reads the
-// producer's raw convolution output and never needs the normalised copy (bn.hip:k_bn_apply4's expression and operation
-// order, so the staged values are that kernel's bits).  mean == NULL: rows taken as they are.
+// producer's raw convolution output and never needs the normalised copy (the staged values are the bits lidog_bn_apply
+// would have written).  mean == NULL: rows taken as they are.
 struct InBn {
     const float *mean, *invstd, *w, *b;
     int relu;
@@ -13,10 +15,7 @@ struct InBn {
 
 __device__ __forceinline__ float4 in_bn_apply(float4 v, const float4 &m, const float4 &s, const float4 &w, const float4 &b,
                                               int relu) {
-    v.x = (v.x - m.x) * s.x * w.x + b.x;
-    v.y = (v.y - m.y) * s.y * w.y + b.y;
-    v.z = (v.z - m.z) * s.z * w.z + b.z;
-    v.w = (v.w - m.w) * s.w * w.w + b.w;
+    v = bn_affine4(v, m, s, w, b);
     const float lo = relu ? 0.f : -__builtin_inff();   // one max either way: no branch in the staging loop
     v.x = fmaxf(v.x, lo); v.y = fmaxf(v.y, lo); v.z = fmaxf(v.z, lo); v.w = fmaxf(v.w, lo);
     return v;

@@ -321,7 +321,7 @@ __device__ __forceinline__ void os_frag_load(const float *p, float (&f)[NT]) {
 // and mask re-read per tile row -- costs what the stand-alone reduction costs, 0.047 vs 0.055 ms on a stride-1
 // 96-channel layer, and its sums are not the operator path's bits; the data gradient therefore stays plain + addend.)
 //   mode 3 = an evaluation-mode BatchNorm (+ residual + ReLU) applied to the result before it is stored: the validation
-// path's fused form (sconv.hip:k_sconv_reduce_rows4_bn), same expression and operation order as bn.hip:k_bn_apply4.
+// path's fused form (sconv.hip:k_sconv_reduce_rows4_bn).
 struct OsStats {
     int mode;
     StatsTail tail;
@@ -387,12 +387,9 @@ __device__ __forceinline__ void os_epilogue(f32x16 (&acc)[NT], const float (&bv)
             for (int t = 0; t < NT; ++t) v[t] = acc[t][e] + adv[u][t];   // no addend: + 0
             if (st.mode == 3) {
 #pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    float y = (v[t] - e_m[t]) * e_is[t] * e_w[t] + e_b[t];
-                    if (st.bn_res) y += resv[u][t];
-                    if (st.bn_relu) y = fmaxf(y, 0.f);
-                    v[t] = y;
-                }
+                for (int t = 0; t < NT; ++t)
+                    v[t] = bn_res_relu(bn_affine(v[t], e_m[t], e_is[t], e_w[t], e_b[t]), st.bn_res != nullptr, resv[u][t],
+                                       st.bn_relu);
             }
             if (ok) {
                 float *o = out + (size_t)dst[u] * Cout + col0 + li * NT;

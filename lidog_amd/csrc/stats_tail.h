@@ -16,6 +16,7 @@
 // an agent-scope ticket, and the workgroup whose add returned the last ticket reads -- the guide's counter form.
 // Ticket words are zero between launches: the final workgroup resets them (the buffer is zeroed when it is created).
 #pragma once
+#include "bn_math.h"   // lidog_bn_finalize_channel
 #include "common.h"
 
 #define STATS_GROUP 32
@@ -41,17 +42,19 @@ struct StatsTail {
     BnFinish fin;
 };
 
-__device__ __forceinline__ void lidog_bn_finalize_channel(double sx, double sxx, double count, int c,
-                                                          const BnFinish &fin) {
-    double m = sx / count;
-    double var = sxx / count - m * m;
-    if (var < 0) var = 0;
-    fin.mean[c] = (float)m;
-    fin.invstd[c] = (float)(1.0 / sqrt(var + (double)fin.eps));
-    if (fin.running_mean) {
-        double unb = (count > 1) ? var * count / (count - 1) : var;
-        fin.running_mean[c] = (1.f - fin.momentum) * fin.running_mean[c] + fin.momentum * (float)m;
-        fin.running_var[c] = (1.f - fin.momentum) * fin.running_var[c] + fin.momentum * (float)unb;
+// The workgroup reduction in front of the tail, for 256 threads laid out as RB = 256 / C4 rows of C4 channel quads
+// (tid = r * C4 + c4; threads with r >= RB idle): every thread puts its eight sums into red [256 * 8], and the
+// thread of row 0 (`lead`) adds rows 1 .. RB - 1 to its own in ascending order.  Every kernel that ends in
+// lidog_stats_tail reduces this way, which is why the fused and the stand-alone reductions produce the same partials.
+__device__ __forceinline__ void lidog_stats_wg_reduce(double *red, int tid, int RB, int C4, int c4, bool lead,
+                                                      double (&a)[8]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) red[tid * 8 + j] = a[j];
+    __syncthreads();
+    if (lead) {
+        for (int rr = 1; rr < RB; ++rr)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) a[j] += red[(rr * C4 + c4) * 8 + j];
     }
 }
 

@@ -108,7 +108,7 @@ def in_dx64(g, x, batch, mean, invstd, w, m0, m1):
 
 def ibn_dx64(g_bn, g_in, x, batch, bn_mean, bn_invstd, bn_w, bn_m0, bn_m1, in_mean, in_invstd, in_w, in_m0, in_m1):
     """dx of relu(cat(bn(x), in(x))): the BatchNorm half ([C] statistics) plus the instance-norm half ([B, C]);
-    g_* are the ReLU-masked halves of dy.  Returns (dx, bar): every half is the 8-rounding expression of norm_dx
+    g_* are the ReLU-masked halves of dy.  Returns (dx, bar): every half is the 8-rounding expression of bn_dx_scaled
     (C_DX u scale; the fp32 casts of m0 / m1 are among the eight), the final add rounds their sum once more:
     bar = C_DX u (scale_bn + scale_in) + u (|dx_bn| + |dx_in|)."""
     d_bn, s_bn = norm_dx64(g_bn, x, bn_mean[None], bn_invstd[None], bn_w[None], bn_m0[None], bn_m1[None])

@@ -256,6 +256,45 @@ def test_sync_apply_on_one_shard_vs_float64_of_the_whole_batch(C, record_propert
             _bits_match(bits, y, rows, C, f"sync C{C}")
 
 
+@pytest.mark.parametrize("residual", [True, False], ids=["residual", "no_residual"])
+@pytest.mark.parametrize("rows", [0, 1, 70])
+@pytest.mark.parametrize("C", [8, 96])
+def test_sync_apply_equals_finalize_then_apply_bit_for_bit(C, rows, residual):
+    """lidog_bn_apply_sync against lidog_bn_finalize(count = -1) + lidog_bn_apply_bits from the same all-reduced sums
+    vector (ReLU on): y, the bit words, mean, invstd and the running statistics with torch.equal.  70 rows leave a
+    partial last bit word and a partial last workgroup; an empty shard compares the statistics only."""
+    from lidog_amd import _lib
+    from lidog_amd._lib import call, ptr
+    L = _lib.load()
+    n = 141                                  # rows of the whole batch behind the sums; this shard holds `rows` of them
+    x, p = _data(n, C, 31 * C + rows)
+    sums = torch.full((2 * C + 1,), NAN, dtype=torch.float64, device="cuda")
+    ws = torch.empty(L.lidog_bn_reduce_ws(C, 1), dtype=torch.float64, device="cuda")
+    call("lidog_bn_stats", ptr(x), n, C, 1, ptr(sums), ptr(ws), float(n), 0.0, 0.0, None, None, None, None)
+    res = p["res"] if residual else None
+    got = {}
+    for form in ("sync", "two_pass"):
+        o = dict(mean=torch.full((C,), NAN, device="cuda"), invstd=torch.full((C,), NAN, device="cuda"),
+                 rm=p["rm"].clone(), rv=p["rv"].clone(), y=torch.full((max(rows, 1), C), NAN, device="cuda"),
+                 bits=torch.full((max(L.lidog_relu_bits_words(rows, C), 1),), -1, dtype=torch.int32, device="cuda"))
+        if form == "sync":
+            call("lidog_bn_apply_sync", ptr(x), rows, C, ptr(sums), EPS, MOM, ptr(o["mean"]), ptr(o["invstd"]), ptr(o["rm"]),
+                 ptr(o["rv"]), ptr(p["w"]), ptr(p["b"]), ptr(res), 1, ptr(o["y"]), ptr(o["bits"]))
+        else:
+            call("lidog_bn_finalize", ptr(sums), -1.0, C, EPS, MOM, ptr(o["mean"]), ptr(o["invstd"]), ptr(o["rm"]),
+                 ptr(o["rv"]))
+            call("lidog_bn_apply_bits", ptr(x), rows, C, 1, ptr(o["mean"]), ptr(o["invstd"]), ptr(p["w"]), ptr(p["b"]),
+                 ptr(res), 1, ptr(o["y"]), ptr(o["bits"]))
+        torch.cuda.synchronize()
+        got[form] = o
+    assert bool(torch.isfinite(got["sync"]["mean"]).all()) and bool(torch.isfinite(got["sync"]["invstd"]).all())
+    for key in ("mean", "invstd", "rm", "rv") + (("y", "bits") if rows else ()):
+        assert torch.equal(got["sync"][key], got["two_pass"][key]), f"C{C} rows {rows}: {key} differs from the two-pass form"
+    if rows:
+        assert bool(torch.isfinite(got["sync"]["y"]).all())
+        _bits_match(got["sync"]["bits"], got["sync"]["y"], rows, C, f"sync C{C} rows {rows}")
+
+
 def _bench_map():
     cm = _bench()["cm"]
     return cm.kernel_map(1, 1, 3)

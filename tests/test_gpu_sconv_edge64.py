@@ -400,6 +400,9 @@ class Forms:
         res = {"reduce_rows_bn": _nan(n, Cout)}
         call("lidog_sconv_reduce_rows_bn", ptr(T), ptr(rp), ptr(rl), n, Cout, ptr(self.b), ptr(mean), ptr(invstd), ptr(w),
              ptr(b), ptr(residual), relu, ptr(res["reduce_rows_bn"]))
+        res["reduce_rows + bn_apply"] = _nan(n, Cout)     # the two-pass sequence the fused forms replace
+        call("lidog_bn_apply", ptr(self.reduce_rows(T, "out", Cout, self.b, None)), n, Cout, 1, ptr(mean), ptr(invstd),
+             ptr(w), ptr(b), ptr(residual), relu, ptr(res["reduce_rows + bn_apply"]))
         if self.mfma and x is not None:
             perm, wm, order = self.sorted
             res["os_bn"] = _nan(n, Cout)
@@ -605,7 +608,8 @@ def test_fused_epilogues(name, Cin, Cout, record_property):
     """The statistics forms (lidog_sconv_reduce_rows_stats, lidog_sconv_reduce_stats -- the `pos` form, which no caller
     uses -- and lidog_sconv_os_stats): the convolution bit-equal to the plain reduction, the sums to the bars of
     tests/test_gpu_sconv_os.py.  The evaluation-mode BatchNorm forms (lidog_sconv_reduce_rows_bn, lidog_sconv_os_bn;
-    residual and ReLU on and off): bit-equal, and against float64 of the formula
+    residual and ReLU on and off): bit-equal to each other and to the two-pass sequence lidog_sconv_reduce_rows +
+    lidog_bn_apply, and against float64 of the formula
 
         y = relu(((c - mean) * invstd) * w + b + residual),          c = the convolution with its bias,
 

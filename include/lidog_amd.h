@@ -992,6 +992,60 @@ int lidog_pool_global(const float *x, int64_t n, int32_t C, int32_t B, const int
 int lidog_pool_global_bwd(const float *gy, const int32_t *arg, int64_t n, int32_t C, int32_t B, const int32_t *bid,
                           const int32_t *seg_off, int32_t mode, float *gx, void *stream);
 
+/* ------------------------------------------------------------------ point <-> voxel family (csrc/field.hip)
+ * ME.TensorField / TensorField.sparse, SparseTensor.slice / cat_slice / features_at_coordinates / interpolate and
+ * MinkowskiInterpolation of MinkowskiEngine 0.5.  The reference never calls them and MinkowskiEngine's sources were not
+ * at hand: every rule below is restated from memory [ME-mem] and THIS text is the contract the tests hold the kernels to.
+ * Features fp32 [rows, C], any C >= 1 (float4 kernels when C % 4 == 0).  Plain stores in a stated order everywhere: no
+ * atomics on floats, the same bits on every call.  An entry with nothing to do returns without a launch.
+ *
+ * lidog_field_floor [ME-mem]: points [n, 4] float32 rows (batch, x, y, z) -> rows [n, 4] int32.  Spatial columns:
+ * floor(v / s) * s in float32 (a true division, s = (float)stride), then lidog_voxel_floor's conversion: NaN, an infinity
+ * or a value no int32 holds gives INT32_MIN, which matches no map row.  The batch column must be integer-valued in
+ * 0 .. 4095, else the row gets batch -1 (matches no map row).  err [1] int32 (device, never cleared here) collects bits:
+ * 1 a bad batch column, 2 a NaN or infinite spatial column.  A finite value beyond the coordinate range sets no bit: such
+ * a point simply has no neighbours. */
+int lidog_field_floor(const float *points, int64_t n, int32_t stride, int32_t *rows, int32_t *err, void *stream);
+/* Per-row lists of an index table (a stable counting sort): inv [n] names a row in [0, m) per entry (any other value:
+ * the entry is in no list).  row_ptr [m + 1], row_list [n]: the entries j with inv[j] == v are
+ * row_list[row_ptr[v] .. row_ptr[v + 1]) in ASCENDING j; row_ptr[m] entries are listed, what lies behind them in
+ * row_list is unspecified.  Serves a field (inv = point -> voxel row) and the interpolation gradient (inv = the neighbour
+ * table nbr [8][Q] read flat: entry j = k * Q + q, so a list ascends in k and then in q).
+ * ws: lidog_field_lists_ws(n, m) bytes. */
+int64_t lidog_field_lists_ws(int64_t n, int64_t m);
+int lidog_field_lists(const int32_t *inv, int64_t n, int64_t m, int32_t *row_ptr, int32_t *row_list, void *ws,
+                      int64_t ws_bytes, void *stream);
+/* Ordered segment sum [ME-mem: UNWEIGHTED_SUM / UNWEIGHTED_AVERAGE]: y[v][c] = x[l0][c] + x[l1][c] + ... over the list of
+ * v in list order, float32, starting FROM the first element (not from 0); mean != 0: followed by ONE division by
+ * (float)count.  An empty list gives exact zeros.  x [n_x, C]; an entry outside [0, n_x) is never used as an address.
+ * TensorField.sparse() forward and the gradient of slice. */
+int lidog_field_reduce(const float *x, int64_t n_x, const int32_t *row_ptr, const int32_t *row_list, int64_t m, int32_t C,
+                       int32_t mean, float *y, void *stream);
+/* y[p][c] = x[inv[p]][c], row_ptr != NULL: divided by (float)(row_ptr[inv[p] + 1] - row_ptr[inv[p]]).  x [m, C]; an
+ * inv[p] outside [0, m) gives a row of zeros.  slice forward and the gradient of TensorField.sparse(). */
+int lidog_field_gather(const float *x, const int32_t *inv, int64_t n, int64_t m, int32_t C, const int32_t *row_ptr,
+                       float *y, void *stream);
+/* Trilinear interpolation [ME-mem: features_at_coordinates / MinkowskiInterpolation] of F [m, C], the features of a map
+ * of tensor stride s, at query [Q, 4] float32 rows (batch, x, y, z).  Per axis: lo = floor(x / s) * s,
+ * t = (x - lo) / s; a lower neighbour has factor 1 - t, an upper one t.  In float32 (s a power of two: everything
+ * but one subtraction is exact) the fraction is taken from the lattice point on the side of zero, whose distance is exact:
+ *   x >= 0: t = (x - lo) / s, factors (1 - t, t);      x < 0: r = ((lo + s) - x) / s, factors (r, 1 - r).
+ * (x - lo itself rounds below zero: -4e-14 - (-1) = 1, which would leave the point's own cell without weight.)  So one
+ * factor of an axis is exact, the other rounds once, and the factor of the cell that holds the point is never 0.
+ * The 8 neighbours are lo + bit * s with k = bx + 2 by + 4 bz (x fastest, the order of
+ * the 2^3 kernel offsets {0, s}^3), weight w_k = f_x * f_y * f_z multiplied in that order.  nbr [8][Q]: row of F holding neighbour k of query q or -1 -- lidog_kernel_map[_bits]
+ * of the floored queries (lidog_field_floor) with those 8 offsets; a neighbour in another batch index is never found.
+ *   y[q][c] = 0, then y = fmaf(w_k, F[nbr[k][q]][c], y) over the neighbours that exist, ascending k.
+ * Missing neighbours add nothing and nothing is renormalised; a query without neighbours gives a row of zeros.  The
+ * weights are recomputed from the query, never stored.  Q < 2^28. */
+int lidog_interp_fwd(const float *F, int64_t m, int32_t C, const float *query, const int32_t *nbr, int64_t n_query,
+                     int32_t stride, float *y, void *stream);
+/* gF[i][c] = 0, then gF = fmaf(w_k(q), gy[q][c], gF) over the pairs (k, q) with nbr[k][q] == i, ascending k and then
+ * ascending q: the list of row i from lidog_field_lists(nbr, 8 Q, m).  A row nobody hits gets zeros.  No gradient with
+ * respect to the coordinates. */
+int lidog_interp_bwd(const float *gy, const float *query, int64_t n_query, const int32_t *row_ptr,
+                     const int32_t *row_list, int64_t m, int32_t C, int32_t stride, float *gF, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

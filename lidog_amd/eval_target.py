@@ -22,6 +22,8 @@ Point level (--point-level / --save-labels, file targets only; the voxel-level o
 of every scan file gets the class of its voxel (lidog_amd.evaluate.point_labels), records beyond the radius a fill id;
 `<sources>-TO-<targets>-points.csv` holds the IoU over the labelled points, and --save-labels writes one uint32 id per
 record in file order, for SemanticKITTI as `predictions/<target>/sequences/SS/predictions/NNNNNN.label`.
+--point-interp trilinear: a point takes the class of the logits interpolated at its own position between the voxels
+(lidog_amd.evaluate.point_logits over csrc/field.hip) instead of its voxel's; the default, nearest, changes nothing.
 """
 import argparse
 import json
@@ -67,6 +69,9 @@ def parse_args(argv=None):
     ap.add_argument("--save-labels", action="store_true",
                     help="with --target-files: write one uint32 id per record of every scan file, in file order "
                          "(SemanticKITTI: predictions/<target>/sequences/SS/predictions/NNNNNN.label)")
+    ap.add_argument("--point-interp", default="nearest", choices=["nearest", "trilinear"],
+                    help="with --point-level / --save-labels: a point takes its voxel's class (nearest) or the class of the "
+                         "logits interpolated trilinearly at its own position (missing neighbours add nothing)")
     ap.add_argument("--inverse-label-map", nargs="+", default=None, metavar="FILE",
                     help="one per target: a .yaml / .json file with a learning_map_inv (common class -> id to write; "
                          "entry -1: the id of records beyond the radius, default 0).  Default: the class itself")
@@ -81,6 +86,8 @@ def parse_args(argv=None):
     if (a.point_level or a.save_labels or a.inverse_label_map is not None) and a.target_files is None:
         ap.error("--point-level, --save-labels and --inverse-label-map go with --target-files (a synthetic target has no "
                  "file whose order the labels could follow)")
+    if a.point_interp != "nearest" and not (a.point_level or a.save_labels):
+        ap.error("--point-interp goes with --point-level or --save-labels")
     if a.inverse_label_map is not None:
         if len(a.inverse_label_map) != len(a.target_files):
             ap.error("--inverse-label-map needs one file per --target-files entry")
@@ -147,7 +154,7 @@ def main(argv=None):
                 label_writer = PointLabelWriter(os.path.join(save_dir, "predictions"), name, config,
                                                 data.listings[0].files)
             points = PointPath.of(data, device, out_lut=torch.from_numpy(lut).to(device), fill=fill,
-                                  with_labels=a.point_level, on_point_labels=label_writer)
+                                  with_labels=a.point_level, on_point_labels=label_writer, interp=a.point_interp)
         writer = None
         if a.save_predictions:
             writer = PredictionWriter(os.path.join(save_dir, "predictions"), name, a.model != "MinkUNet34BEV",

@@ -51,6 +51,12 @@ def predict(model, coords, feats, manager=None, precision=None, kernels=None):
     (ME.CoordinateManager.prepare: one host synchronisation instead of one per kernel map); `manager`: a manager
     prepared ahead of time for these coordinates (Predictor / evaluate() build the next batch's while the current
     forward pass runs)."""
+    out = _forward(model, coords, feats, manager, precision, kernels)
+    return out.F.max(dim=1)[1], out.F
+
+
+def _forward(model, coords, feats, manager=None, precision=None, kernels=None):
+    """predict()'s forward pass; returns the model's output SparseTensor (the stride-1 logits on the batch's manager)"""
     scope = _precision.scope(model, precision, kernels)
     was_training = model.training
     model.eval()
@@ -64,9 +70,8 @@ def predict(model, coords, feats, manager=None, precision=None, kernels=None):
     with scope:
         out = model(st)
     model._lidog_eval_trace = st.coordinate_manager.trace
-    logits = (out[0] if isinstance(out, tuple) else out).F
     model.train(was_training)
-    return logits.max(dim=1)[1], logits
+    return out[0] if isinstance(out, tuple) else out
 
 
 class Predictor:
@@ -77,6 +82,7 @@ class Predictor:
 
     def __init__(self, model, precision=None):
         self.model, self._next, self.precision = model, None, precision
+        self.output = None      # the last call's output SparseTensor (point_logits interpolates on its map)
         self.kernels = _precision.Bf16Kernels(model) if _precision.resolve(precision) else None
 
     def __call__(self, coords, feats, next_coords=None):
@@ -88,7 +94,8 @@ class Predictor:
         # forward pass that is about to be launched
         ready = torch.cuda.Event()
         ready.record()
-        out = predict(self.model, coords, feats, mgr, self.precision, self.kernels)
+        self.output = _forward(self.model, coords, feats, mgr, self.precision, self.kernels)
+        out = (self.output.F.max(dim=1)[1], self.output.F)
         trace = getattr(self.model, "_lidog_eval_trace", None)
         if next_coords is not None and trace is not None:
             self._next = (next_coords, ME.CoordinateManager.prepare(next_coords, trace, ready))
@@ -334,6 +341,39 @@ def point_labels(logits, row_off, kept_off, vox_off, keep_row, inverse_map, out_
     return out, counts
 
 
+POINT_INTERP = ("nearest", "trilinear")
+
+
+def point_queries(items):
+    """float32 [kept, 4] rows (scan's position in the batch, x, y, z): the kept points of every scan of a loader batch
+    (FileScans.point_item's `points`, load_scan's output) divided by the voxel size in the float32 true division the
+    voxeliser uses, so the floor of a query is the voxel its point was put into.  An item that cannot supply one such
+    query per kept row (not a FileScans validation item, an augmented one, or one whose rows were cut to the BEV bounds)
+    is a ValueError."""
+    import numpy as np
+    out = []
+    for b, it in enumerate(items):
+        pts = it.get("points")
+        if pts is None or not it.get("plain", False) or pts.shape[0] != it["kept"] or \
+                it["inverse_map"].shape[0] != pts.shape[0]:
+            raise ValueError(f"{it.get('path', f'scan {b}')}: trilinear point labels need one query per kept row: a "
+                             "FileScans validation item without augmentations and without the BEV bounds cut "
+                             "(use interp='nearest' for this dataset)")
+        q = np.broadcast_to(np.asarray(it["voxel_size"], dtype=np.float64), (3,)).astype(np.float32)
+        rows = torch.empty((pts.shape[0], 4), dtype=torch.float32, device=pts.device)
+        rows[:, 0] = float(b)
+        rows[:, 1:] = pts / torch.from_numpy(q).to(pts.device)        # tensor / tensor: a true division per element
+        out.append(rows)
+    return torch.cat(out) if out else None
+
+
+def point_logits(logits, items, err=None):
+    """float32 [kept, C]: the stride-1 logits of a loader batch (`logits`: the model's output ME.SparseTensor)
+    interpolated trilinearly at its kept points (point_queries of the batch's point_item dicts, scan after scan).
+    Missing neighbours add nothing; `err` as SparseTensor.features_at_coordinates takes it."""
+    return logits.features_at_coordinates(point_queries(items), err=err)
+
+
 def point_inputs(items, with_labels=True):
     """The arguments of point_labels for a loader batch from its scans' FileScans.point_item dicts, in batch order: the
     keep index of every file (scans.keep_rows, on the words already uploaded) and the concatenations.  Nothing is read
@@ -366,9 +406,13 @@ class PointPath:
     itself) and `fill`: the id of records beyond the radius; `with_labels`: count the point confusion (needs every
     file's labels); `on_point_labels(first_scan, labels_out, row_off)`: called per batch with the dataset index of its
     first scan, the host copy of its ids (numpy uint32, file order) and the B + 1 row offsets of its scans; asking for it
-    costs one device -> host copy per batch."""
+    costs one device -> host copy per batch.  `interp`: "nearest" (every point takes its voxel's class) or "trilinear" (the
+    class of the logits interpolated at the point's own position between the voxels, point_logits)."""
 
-    def __init__(self, items, out_lut=None, fill=0, with_labels=True, on_point_labels=None):
+    def __init__(self, items, out_lut=None, fill=0, with_labels=True, on_point_labels=None, interp="nearest"):
+        if interp not in POINT_INTERP:
+            raise ValueError(f"PointPath: interp={interp!r} (one of {', '.join(POINT_INTERP)})")
+        self.interp = interp
         self.items, self.out_lut, self.fill = items, out_lut, int(fill)
         self.with_labels, self.on_point_labels = bool(with_labels), on_point_labels
 
@@ -471,7 +515,7 @@ class TargetEvaluator:
         self.kernels = run.kernels
         it = iter(batches)
         cur = next(it, None)
-        counts = err = pcounts = perr = None
+        counts = err = pcounts = perr = ferr = None
         batch_of_scan = []
         done = 0
         nb = 0
@@ -485,6 +529,7 @@ class TargetEvaluator:
                 if points is not None:
                     pcounts = torch.zeros((int(n_scans), c, c), dtype=torch.int64, device=coords.device)
                     perr = torch.zeros(1, dtype=torch.int32, device=coords.device)
+                    ferr = torch.zeros(1, dtype=torch.int32, device=coords.device)
             k = len(ids)
             if done + k > counts.shape[0]:
                 raise ValueError(f"TargetEvaluator: more than n_scans = {n_scans} scans in the batches")
@@ -497,9 +542,15 @@ class TargetEvaluator:
                 for idx, rec in zip(ids, unpack_predictions(buf, k)):
                     on_predictions(idx, rec)
             if points is not None:
-                pin = point_inputs(points.items(ids), points.with_labels)
-                ids_out, _ = point_labels(logits, pin["row_off"], pin["kept_off"], pin["vox_off"], pin["keep_row"],
-                                          pin["inverse_map"], points.out_lut, points.fill, pin["labels_raw"], pin["lut"],
+                items = points.items(ids)
+                pin = point_inputs(items, points.with_labels)
+                plogits, vox_off, inverse = logits, pin["vox_off"], pin["inverse_map"]
+                if points.interp == "trilinear":    # one row of logits per kept point: every kept row is its own "voxel"
+                    plogits, vox_off = point_logits(run.output, items, err=ferr), pin["kept_off"]
+                    inverse = torch.cat([torch.arange(it["kept"], dtype=torch.int64, device=coords.device)
+                                         for it in items])
+                ids_out, _ = point_labels(plogits, pin["row_off"], pin["kept_off"], vox_off, pin["keep_row"],
+                                          inverse, points.out_lut, points.fill, pin["labels_raw"], pin["lut"],
                                           pin["label_mask"], self.ignore_label, pcounts[done:done + k], perr)
                 if points.on_point_labels is not None:
                     points.on_point_labels(ids[0], ids_out.cpu().numpy(), pin["row_off"])
@@ -518,6 +569,8 @@ class TargetEvaluator:
                "scans": done}
         if points is not None:
             check_point_error(perr, "TargetEvaluator")
+            if points.interp == "trilinear":
+                ME.field_error(ferr.item(), "TargetEvaluator: point queries")
             pc = pcounts[:done].cpu().numpy()
             pr = iou_rows(point_iou_counts(pc), rows, batch_of_scan)
             p_class, p_mean = mean_iou_rows(pr)

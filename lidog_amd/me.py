@@ -640,6 +640,30 @@ class SparseTensor:
         self._same_map(other)
         return self._like(_AddFn.apply(self._F, other._F))
 
+    # ---- point <-> voxel family (csrc/field.hip; the classes are further down, next to the pooling operators)
+    def slice(self, field):
+        """TensorField of F[inverse]: every point of `field` takes its voxel's row.  Valid for the stride-1 map of the
+        manager that field.sparse() made."""
+        return field._like(_slice_features(self, field))
+
+    def cat_slice(self, field):
+        """TensorField of [F[inverse] | field.F]"""
+        left, right = _slice_features(self, field), field.F
+        if left.shape[1] % 4 == 0 and right.shape[1] % 4 == 0:      # lidog_cat2 copies float4 columns
+            return field._like(_Cat2Fn.apply(left, right))
+        return field._like(torch.cat([left, right], dim=1))
+
+    def features_at_coordinates(self, query, err=None):
+        """[Q, C] trilinear interpolation of the features at float coordinates query [Q, 4] (batch, x, y, z); works on a
+        map of any tensor stride.  Missing neighbours add nothing (no renormalisation).  Non-finite queries or a bad
+        batch column raise ValueError after one read-back; `err`: an int32 [1] device word that collects the bits
+        instead (lidog_field_floor), to be checked by the caller later."""
+        return _interpolate_features(self, query, err)
+
+    def interpolate(self, field, err=None):
+        """TensorField of the features interpolated at the coordinates of `field`"""
+        return field._like(_interpolate_features(self, field.C, err))
+
 
 def cat(*tensors):
     """ME.cat: feature matrices of tensors on ONE coordinate map side by side (minkunet_bev.py:337,348,359,370)"""
@@ -1870,6 +1894,306 @@ class MinkowskiGlobalMaxPooling(_GlobalPoolBase):
 
 
 MinkowskiGlobalPooling = MinkowskiGlobalAvgPooling      # ME 0.5.4's alias
+
+
+# ------------------------------------------------------------------ point <-> voxel family (csrc/field.hip)
+# MinkowskiEngine 0.5's TensorField / slice / interpolation, restated from memory [ME-mem]; the formulas and the order of
+# every sum are in include/lidog_amd.h.  All gathers over lists from one stable sort: no atomics, the same bits on every call.
+class SparseTensorQuantizationMode(enum.Enum):
+    RANDOM_SUBSAMPLE = 0
+    UNWEIGHTED_AVERAGE = 1
+    UNWEIGHTED_SUM = 2
+    MAX_POOL = 3
+
+
+_FIELD_ERR_BATCH, _FIELD_ERR_NONFINITE = 1, 2
+
+
+def field_error(code, who="coordinates"):
+    """raise for the bits lidog_field_floor collected in an error word (`code`: its value on the host)"""
+    code = int(code)
+    if code & _FIELD_ERR_NONFINITE:
+        raise ValueError(f"{who}: a NaN or infinite coordinate")
+    if code & _FIELD_ERR_BATCH:
+        raise ValueError(f"{who}: the batch column must hold integers in 0 .. 4095")
+    if code:
+        raise ValueError(f"{who}: error word {code}")
+
+
+def _field_rows(coords, stride, err):
+    """int32 [N, 4] = lidog_field_floor of float32 [N, 4] rows (batch, x, y, z); the bits go to `err`"""
+    n = coords.shape[0]
+    rows = torch.empty((n, 4), dtype=torch.int32, device=coords.device)
+    call("lidog_field_floor", ptr(coords), n, int(stride), ptr(rows), ptr(err))
+    return rows
+
+
+def _field_coordinates(coords, who):
+    require_gpu(coords, who)
+    if coords.dim() != 2 or coords.shape[1] != 4:
+        raise ValueError(f"{who} must be [N, 4] rows (batch, x, y, z), got {tuple(coords.shape)}")
+    if coords.dtype == torch.int32:
+        coords = coords.float()
+    if coords.dtype != torch.float32:
+        raise ValueError(f"{who} must be float32 or int32 (got {coords.dtype})")
+    return coords.contiguous()
+
+
+def _field_lists(inv, m):
+    """(row_ptr [m + 1], row_list [n]) of lidog_field_lists: the entries of `inv` that name row v, ascending"""
+    inv = inv.reshape(-1)
+    n, dev = inv.shape[0], inv.device
+    row_ptr = torch.empty(m + 1, dtype=torch.int32, device=dev)
+    row_list = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    nbytes = _lib.load().lidog_field_lists_ws(n, m)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    call("lidog_field_lists", ptr(inv), n, m, ptr(row_ptr), ptr(row_list), ptr(ws), nbytes)
+    return row_ptr, row_list
+
+
+class _FieldMap:
+    """what TensorField.sparse() built: the manager, point -> voxel row, the first point of every voxel, the lists"""
+    __slots__ = ("cm", "inverse", "first", "row_ptr", "row_list", "n", "m")
+
+
+class _FieldReduceFn(torch.autograd.Function):
+    """voxel rows from point rows: the ordered segment sum (mean = 1: divided by the count); gradient = a gather"""
+
+    @staticmethod
+    def forward(ctx, x, fm, mean):
+        x = _pool_features(x)
+        C = x.shape[1]
+        y = torch.empty((fm.m, C), dtype=torch.float32, device=x.device)
+        call("lidog_field_reduce", ptr(x), fm.n, ptr(fm.row_ptr), ptr(fm.row_list), fm.m, C, mean, ptr(y))
+        ctx.fm, ctx.mean = fm, mean
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        fm = ctx.fm
+        gy = gy.contiguous()
+        C = gy.shape[1]
+        gx = torch.empty((fm.n, C), dtype=torch.float32, device=gy.device)
+        call("lidog_field_gather", ptr(gy), ptr(fm.inverse), fm.n, fm.m, C, ptr(fm.row_ptr) if ctx.mean else None,
+             ptr(gx))
+        return gx, None, None
+
+
+class _FieldGatherFn(torch.autograd.Function):
+    """point rows from voxel rows (slice); gradient = the ordered segment sum"""
+
+    @staticmethod
+    def forward(ctx, x, fm):
+        x = _pool_features(x)
+        C = x.shape[1]
+        y = torch.empty((fm.n, C), dtype=torch.float32, device=x.device)
+        call("lidog_field_gather", ptr(x), ptr(fm.inverse), fm.n, fm.m, C, None, ptr(y))
+        ctx.fm = fm
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        fm = ctx.fm
+        gy = gy.contiguous()
+        C = gy.shape[1]
+        gx = torch.empty((fm.m, C), dtype=torch.float32, device=gy.device)
+        call("lidog_field_reduce", ptr(gy), fm.n, ptr(fm.row_ptr), ptr(fm.row_list), fm.m, C, 0, ptr(gx))
+        return gx, None
+
+
+class _FieldFirstFn(torch.autograd.Function):
+    """RANDOM_SUBSAMPLE: the first point of every voxel, what SparseTensor does with duplicates; the gradient of a voxel
+    goes to that point alone"""
+
+    @staticmethod
+    def forward(ctx, x, fm):
+        x = _pool_features(x)
+        C = x.shape[1]
+        y = torch.empty((fm.m, C), dtype=torch.float32, device=x.device)
+        call("lidog_field_gather", ptr(x), ptr(fm.first), fm.m, fm.n, C, None, ptr(y))
+        ctx.fm = fm
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        fm = ctx.fm
+        gy = gy.contiguous()
+        C = gy.shape[1]
+        # point p reads row inverse[p] when it is that voxel's first point, a row of zeros (index -1) otherwise
+        point = torch.arange(fm.n, dtype=torch.int32, device=gy.device)
+        src = torch.where(fm.first[fm.inverse.long()] == point, fm.inverse, torch.full_like(fm.inverse, -1))
+        gx = torch.empty((fm.n, C), dtype=torch.float32, device=gy.device)
+        call("lidog_field_gather", ptr(gy), ptr(src), fm.n, fm.m, C, None, ptr(gx))
+        return gx, None
+
+
+class TensorField:
+    """ME.TensorField [ME-mem]: features on continuous points.  coordinates float32 (or int32, converted) [N, 4] rows
+    (batch, x, y, z) on the GPU.  `.sparse()` puts the points onto the voxels floor(coordinate) of a manager of its own
+    and reduces their features per `quantization_mode`; `SparseTensor.slice` / `.interpolate` bring voxel features back
+    to the points.  A `coordinate_manager` is what `.sparse()` made for a field with the same coordinates (the fields
+    that slice / interpolate return carry it); a foreign one is not accepted."""
+
+    def __init__(self, features, coordinates, tensor_stride=1, coordinate_manager=None,
+                 quantization_mode=SparseTensorQuantizationMode.UNWEIGHTED_AVERAGE, device=None, **unsupported):
+        if unsupported:
+            raise TypeError(f"lidog_amd.me.TensorField: unsupported arguments {sorted(unsupported)}")
+        if not isinstance(quantization_mode, SparseTensorQuantizationMode):
+            raise TypeError("quantization_mode must be a SparseTensorQuantizationMode")
+        if int(tensor_stride) != 1:
+            raise NotImplementedError("TensorField: only tensor_stride=1 is supported")
+        if coordinate_manager is not None:
+            raise NotImplementedError("TensorField: a field builds its coordinate manager in .sparse(); passing one in "
+                                      "is not supported")
+        if device is not None:
+            features, coordinates = features.to(device), coordinates.to(device)
+        require_gpu(features, "features")
+        coordinates = _field_coordinates(coordinates, "coordinates")
+        if features.dim() != 2 or features.shape[0] != coordinates.shape[0]:
+            raise ValueError(f"features {tuple(features.shape)} do not match {coordinates.shape[0]} coordinate rows")
+        self._F, self._C = features, coordinates
+        self.quantization_mode = quantization_mode
+        self.coordinate_manager = None
+        self._map = None
+
+    F = property(lambda self: self._F)
+    features = F
+    C = property(lambda self: self._C)
+    coordinates = C
+    device = property(lambda self: self._F.device)
+    shape = property(lambda self: self._F.shape)
+    tensor_stride = property(lambda self: [1, 1, 1])
+
+    def _like(self, feats):
+        """a field over the same points (and the same voxel map, once built) with other features"""
+        out = TensorField.__new__(TensorField)
+        out._F, out._C, out.quantization_mode = feats, self._C, self.quantization_mode
+        out.coordinate_manager, out._map = self.coordinate_manager, self._map
+        return out
+
+    def _field_map(self):
+        if self._map is None:
+            dev, n = self._C.device, self._C.shape[0]
+            err = torch.zeros(1, dtype=torch.int32, device=dev)
+            rows = _field_rows(self._C, 1, err)
+            field_error(err.item(), "TensorField coordinates")
+            fm = _FieldMap()
+            fm.cm = CoordinateManager(dev)
+            first, inv = fm.cm.insert(rows)      # rows beyond the coordinate range raise here
+            fm.cm.uniq = None                    # the rows of this manager's input tensors are voxel rows already
+            point = torch.arange(n, dtype=torch.int32, device=dev)
+            fm.inverse = inv if inv is not None else point
+            fm.first = first.contiguous() if first is not None else point
+            fm.n, fm.m = n, fm.cm.maps[1].n
+            fm.row_ptr, fm.row_list = _field_lists(fm.inverse, fm.m)
+            self._map, self.coordinate_manager = fm, fm.cm
+        return self._map
+
+    def sparse(self, tensor_stride=1, quantization_mode=None):
+        """SparseTensor on the voxels floor(coordinate), rows in first-occurrence order, differentiable in the features.
+        UNWEIGHTED_AVERAGE / UNWEIGHTED_SUM: the ordered segment sum of lidog_field_reduce; RANDOM_SUBSAMPLE: the first
+        point of every voxel.  The map is built once per field; every call reduces the field's features anew."""
+        if int(tensor_stride) != 1:
+            raise NotImplementedError("TensorField.sparse: only tensor_stride=1 is supported")
+        mode = self.quantization_mode if quantization_mode is None else quantization_mode
+        if not isinstance(mode, SparseTensorQuantizationMode):
+            raise TypeError("quantization_mode must be a SparseTensorQuantizationMode")
+        if mode is SparseTensorQuantizationMode.MAX_POOL:
+            raise NotImplementedError("TensorField.sparse: MAX_POOL is not implemented")
+        fm = self._field_map()
+        if mode is SparseTensorQuantizationMode.RANDOM_SUBSAMPLE:
+            feats = _FieldFirstFn.apply(self._F, fm)
+        else:
+            feats = _FieldReduceFn.apply(self._F, fm, 1 if mode is SparseTensorQuantizationMode.UNWEIGHTED_AVERAGE else 0)
+        return SparseTensor(feats, coordinate_manager=fm.cm, coordinate_map_key=1)
+
+    def inverse_mapping(self):
+        """int64 [N]: the voxel row of every point in the tensor .sparse() returns"""
+        return self._field_map().inverse.long()
+
+
+def _slice_features(x, field):
+    if not isinstance(field, TensorField):
+        raise TypeError("slice takes a TensorField")
+    if field._map is None or x.coordinate_manager is not field.coordinate_manager or x.coordinate_map_key != 1:
+        raise ValueError("slice: valid only for the stride-1 map of the coordinate manager that this field's .sparse() "
+                         "made (got a tensor of another manager or tensor stride)")
+    return _FieldGatherFn.apply(x.F, field._map)
+
+
+class _InterpFn(torch.autograd.Function):
+    """lidog_interp_fwd over the neighbour table nbr [8][Q]; the gradient walks per-row lists of that table, built on
+    the first backward pass"""
+
+    @staticmethod
+    def forward(ctx, F, query, nbr, stride):
+        F = _pool_features(F)
+        m, C = F.shape
+        nq = query.shape[0]
+        y = torch.empty((nq, C), dtype=torch.float32, device=F.device)
+        call("lidog_interp_fwd", ptr(F), m, C, ptr(query), ptr(nbr), nq, stride, ptr(y))
+        ctx.query, ctx.nbr, ctx.stride, ctx.m = query, nbr, stride, m
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        gy = gy.contiguous()
+        C, nq, m = gy.shape[1], ctx.query.shape[0], ctx.m
+        row_ptr, row_list = _field_lists(ctx.nbr, m)
+        gF = torch.empty((m, C), dtype=torch.float32, device=gy.device)
+        call("lidog_interp_bwd", ptr(gy), ptr(ctx.query), nq, ptr(row_ptr), ptr(row_list), m, C, ctx.stride, ptr(gF))
+        return gF, None, None, None
+
+
+def interpolation_neighbours(cm, key, query, err=None):
+    """nbr int32 [8, Q]: the row of coordinate map `key` of manager `cm` that holds neighbour k = bx + 2 by + 4 bz of
+    every query (float32 [Q, 4], contiguous), or -1.  The floored queries are the output coordinates of the map's own
+    neighbour search with the offsets {0, s}^3 (through the occupancy bitmap where the map has one).  `err` as
+    SparseTensor.features_at_coordinates takes it."""
+    if key not in cm.maps or int(key) < 1:
+        raise ValueError(f"no coordinate map of tensor stride {key} to interpolate on")
+    cmap, s, nq, dev = cm.maps[key], int(key), query.shape[0], query.device
+    word = err if err is not None else torch.zeros(1, dtype=torch.int32, device=dev)
+    rows = _field_rows(query, s, word)
+    if err is None:
+        field_error(word.item(), "query coordinates")
+    nbr = torch.empty((8, nq), dtype=torch.int32, device=dev)
+    if cmap.n == 0:
+        return nbr.fill_(-1)
+    offs = kernel_offsets(2, s)
+    bits, box = cm._bitmap(key)
+    if bits is not None:
+        call("lidog_kernel_map_bits", ptr(rows), nq, ptr(cmap.keys), ptr(cmap.vals), cmap.cap, offs.ctypes.data, 8,
+             ptr(bits), *box, ptr(nbr))
+    else:
+        call("lidog_kernel_map", ptr(rows), nq, ptr(cmap.keys), ptr(cmap.vals), cmap.cap, offs.ctypes.data, 8, ptr(nbr))
+    return nbr
+
+
+def _interpolate_features(x, query, err=None):
+    query = _field_coordinates(query, "query coordinates")
+    if err is not None and (not err.is_cuda or err.dtype != torch.int32 or err.numel() != 1):
+        raise ValueError("err must be an int32 [1] tensor on the GPU")
+    cm = x.coordinate_manager
+    cm.handover()
+    nbr = interpolation_neighbours(cm, x.coordinate_map_key, query, err)
+    return _InterpFn.apply(x.F, query, nbr, int(x.coordinate_map_key))
+
+
+class MinkowskiInterpolation(nn.Module):
+    """ME.MinkowskiInterpolation [ME-mem]: forward(input, tfield) = the features of `input` interpolated trilinearly at
+    the coordinates `tfield` (float [Q, 4] rows (batch, x, y, z)), a [Q, C] tensor"""
+
+    def __init__(self, return_kernel_map=False, return_weights=False):
+        super().__init__()
+        if return_kernel_map or return_weights:
+            raise NotImplementedError("MinkowskiInterpolation: return_kernel_map / return_weights are not implemented "
+                                      "(the weights are recomputed in the kernels, never stored)")
+
+    def forward(self, input, tfield):
+        if isinstance(tfield, TensorField):
+            tfield = tfield.C
+        return input.features_at_coordinates(tfield)
 
 
 class MinkowskiLinear(nn.Module):

@@ -423,8 +423,10 @@ class FileScans:
             if raw is not None:
                 if not self.use_cache:
                     del self._raw[(s, j, str(device))]
+                # `points`: load_scan's kept points themselves (no second upload), `plain`: rows in file order, untouched
                 self._point_items[int(i)] = dict(raw, inverse_map=row[-1]["inverse_map"],
-                                                 kept=int(scan["points"].shape[0]),
+                                                 kept=int(scan["points"].shape[0]), points=scan["points"],
+                                                 voxel_size=self.voxel_size, plain=self.augmentations is None,
                                                  voxels=int(row[-1]["coordinates"].shape[0]))
         return row
 
@@ -433,7 +435,8 @@ class FileScans:
         `keep_raw` set; nothing is read or uploaded again.  A dict: `points_raw` (the file's float32 words), `labels_raw`
         (int32 / uint8 [rows] or None), `stride`, `mask`, `lut` (device int32), `in_radius` (None: no mask), `rows`,
         `kept`, `voxels` (the sizes of the file, of load_scan's output and of the item), `inverse_map` (kept row -> voxel
-        row of the item), `path`.  Handed out once: the file's words are dropped with the caller's reference."""
+        row of the item), `path`, and for evaluate.point_queries `points` (load_scan's kept points, float32 [kept, 3]),
+        `voxel_size` and `plain` (no augmentation touched the rows).  Handed out once: the file's words are dropped with the caller's reference."""
         if int(i) not in self._point_items:
             raise KeyError(f"item {i} was not made with keep_raw set (or its point inputs were taken already)")
         item = self._point_items.pop(int(i))

@@ -1046,6 +1046,27 @@ int lidog_interp_fwd(const float *F, int64_t m, int32_t C, const float *query, c
 int lidog_interp_bwd(const float *gy, const float *query, int64_t n_query, const int32_t *row_ptr,
                      const int32_t *row_list, int64_t m, int32_t C, int32_t stride, float *gF, void *stream);
 
+/* ---- the Raycast baseline's resampler (raycast.hip): a scan re-sampled onto a target sensor's
+ * (beam, azimuth) grid; every cell keeps the nearest source point that falls into it (a point-splat range image).
+ * int32 workspace (8-byte aligned) of lidog_raycast for n points and n_cells = n_beams * n_az cells */
+int64_t lidog_raycast_ws(int64_t n, int64_t n_cells);
+/* points [n, 3] float32; origin [3] float32 on the device (NULL: 0): q = points - origin in float32.
+ * r2 = (qx qx + qy qy) + qz qz in float32, unfused; a row is dropped if r2 == 0, r2 < min2, or use_max and r2 >= max2.
+ * az = atan2(qy, qx), el = atan2(qz, sqrt(qx^2 + qy^2)) in float64 from the float32 q.
+ * column c = floor((az - az0) / (2 pi / n_az) + 0.5) mod n_az (non-negative); row b: edges[b] <= el < edges[b + 1],
+ * edges [n_beams + 1] float64 ascending; a row outside [edges[0], edges[n_beams]) is dropped.  cell = b n_az + c.
+ * The winner of a cell has the smallest r2, among equal r2 bits the smallest row (one 64-bit integer atomicMin).
+ * cell_out [n] int32 (may be NULL): the cell of every row, -1 for a dropped one.  Output row k is the winner of the
+ * k-th occupied cell in ascending cell order: rows_out [k] its source row, points_out [k] q of that row (snap == 0) or,
+ * with r = sqrt(qx^2 + qy^2 + qz^2) in float64, float32 of ((r cos_el[b]) cos_az[c], (r cos_el[b]) sin_az[c],
+ * r sin_el[b]) (snap != 0; the four float64 tables [n_beams] / [n_az] come from the host).  points_out and rows_out
+ * hold min(n, n_cells) rows; m_dev [1] int32 = the number of output rows.  Nothing is read back or synchronised.
+ * n, n_cells < 2^31 - 1, n_beams >= 2, |az0| <= 2 pi. */
+int lidog_raycast(const float *points, int64_t n, const float *origin, const double *edges, int32_t n_beams,
+                  int32_t n_az, double az0, float min2, int32_t use_max, float max2, int32_t snap,
+                  const double *cos_el, const double *sin_el, const double *cos_az, const double *sin_az,
+                  int32_t *cell_out, float *points_out, int32_t *rows_out, int32_t *m_dev, int32_t *ws, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -191,6 +191,8 @@ SIGNATURES = {
     "lidog_field_gather": [_p, _p, _i64, _i64, _i32, _p, _p, _p],
     "lidog_interp_fwd": [_p, _i64, _i32, _p, _p, _i64, _i32, _p, _p],
     "lidog_interp_bwd": [_p, _p, _i64, _p, _p, _i64, _i32, _i32, _p, _p],
+    "lidog_raycast_ws": [_i64, _i64],
+    "lidog_raycast": [_p, _i64, _p, _p, _i32, _i32, _d, _f, _i32, _f, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
 }
 _RESTYPES = {"lidog_hash_capacity": _i64, "lidog_sconv_reduce_stats_ws": _i64, "lidog_bn_reduce_ws": _i64,
              "lidog_dice_ws": _i64, "lidog_ce_ws": _i64, "lidog_colsum_ws": _i64, "lidog_conv2d_support_ws": _i64, "lidog_conv2d_wgrad_sparse_ws": _i64,
@@ -201,7 +203,7 @@ _RESTYPES = {"lidog_hash_capacity": _i64, "lidog_sconv_reduce_stats_ws": _i64, "
              "lidog_in_reduce_ws": _i64, "lidog_iw_ws": _i64, "lidog_mix_split_ws": _i64,
              "lidog_dbscan_ws": _i64, "lidog_augment_ws": _i64, "lidog_eval_pack_ws": _i64,
              "lidog_scan_load_ws": _i64, "lidog_pool_global_ws": _i64, "lidog_scan_keep_rows_ws": _i64,
-             "lidog_point_labels_ws": _i64, "lidog_field_lists_ws": _i64}
+             "lidog_point_labels_ws": _i64, "lidog_field_lists_ws": _i64, "lidog_raycast_ws": _i64}
 
 # lidog_abi_version() of the library these signatures were written against: a stale .so (or a header an external caller
 # compiled against long ago) would take mis-sized arguments without any diagnostic

@@ -17,6 +17,10 @@ synth4d.py and their *_bev.py training forms), with the per-point work on the GP
                               training form (sub_p / augmentations, bounds filter and BEV labels), items through
                               lidog_amd.data.augment_item, batches with the keys of synth.make_batch
 
+FakeKITTI / FakeSynth4D-kitti / FakeSynth4D-nuscenes are the Raycast baseline's pre-generated datasets (fake_kitti.py,
+fake_synth4d.py): SemanticKITTI-layout records, written by `python -m lidog_amd.raycast`.  FileScans(raycast=) resamples
+the scans of any training listing on the fly instead (lidog_amd.raycast).
+
 The library ships no label map of its own: the user passes the reference's *2common.yaml (or the same as JSON).
 """
 import json
@@ -31,7 +35,8 @@ from ._lib import call, ptr
 from .data import (NUSCENES_NAME, augment_item, check_augmentations, collate_items, draw_augmentation, merge_stream,
                    on_merge_stream)
 
-NAMES = ("SemanticKITTI", "Synth4D-kitti", "Synth4D-nuscenes", "nuScenes")
+NAMES = ("SemanticKITTI", "Synth4D-kitti", "Synth4D-nuscenes", "nuScenes", "FakeKITTI", "FakeSynth4D-kitti",
+         "FakeSynth4D-nuscenes")
 # per dataset: how a file is laid out and what the reference's dataset does with it.  `stride`: floats per point record
 # (None: whatever the .npy array holds); `labels`: the label file's dtype; `mask`: AND-mask on the raw label (the
 # instance id sits in SemanticKITTI's upper 16 bits); `radius`: the reference masks SemanticKITTI (semantickitti.py:110)
@@ -43,6 +48,15 @@ FORMATS = {
     "Synth4D-kitti": dict(stride=None, labels=np.int32, mask=None, radius=False, bev_from="voted", folder="kitti_synth"),
     "Synth4D-nuscenes": dict(stride=None, labels=np.int32, mask=None, radius=False, bev_from="voted",
                              folder="nuscenes_synth"),
+    # the Raycast baseline's pre-generated data (lidog_amd.raycast writes it): plain SemanticKITTI-layout records.
+    # FakeKITTI masks by radius (fake_kitti.py:110), FakeSynth4D never does; the hdl32e form of fake_synth4d.py reads
+    # its labels as int8 (:119), raw ids up to 127, read here as uint8.  `fake`: <town>/velodyne/<id:06d>.bin directly
+    # under the root, labels in <town>/labels/<id:06d>.label (fake_synth4d.py:79-83)
+    "FakeKITTI": dict(stride=4, labels=np.int32, mask=0xFFFF, radius=True, bev_from="voted"),
+    "FakeSynth4D-kitti": dict(stride=4, labels=np.int32, mask=None, radius=False, bev_from="voted",
+                              folder="kitti_synth", fake=True),
+    "FakeSynth4D-nuscenes": dict(stride=4, labels=np.uint8, mask=None, radius=False, bev_from="voted",
+                                 folder="nuscenes_synth", fake=True),
 }
 SEMANTICKITTI_SPLITS = {      # semantickitti.py:42-50, semantickitti_bev.py:73-79
     "full": {"train": ["00", "01", "02", "03", "04", "05", "06", "07", "09", "10"], "validation": ["08"]},
@@ -249,6 +263,12 @@ def synth4d_files(root, name, splits_dir, phase="train"):
     split = load_obj(os.path.join(splits_dir, folder,
                                   "training_split.pkl" if _phase(phase) == "train" else "validation_split.pkl"))
     files = []
+    if FORMATS[name].get("fake"):       # fake_synth4d.py:79-83: the same split, SemanticKITTI-style records
+        for town in split.keys():
+            for f in np.sort(split[town]):
+                files.append((os.path.join(root, town, "velodyne", str(f).zfill(6) + ".bin"),
+                              os.path.join(root, town, "labels", str(f).zfill(6) + ".label")))
+        return files
     for town in split.keys():
         pc_path = os.path.join(root, folder, town, "velodyne")
         for f in np.sort(split[town]):
@@ -275,7 +295,7 @@ def pair_list_files(root, phase="train"):
 def listing(name, root, phase="train", version="full", synth4d_splits=None, limit=None):
     """the Listing of a dataset and phase, its first `limit` files.  `version` is SemanticKITTI's split; Synth4D's
     'mini' (a random draw of 100 scans per town, synth4d.py:66-70) is not restated: --limit-files serves that end."""
-    if name == "SemanticKITTI":
+    if name in ("SemanticKITTI", "FakeKITTI"):
         files = semantickitti_files(root, phase, version)
     elif name == "nuScenes":
         files = pair_list_files(root, phase)
@@ -302,6 +322,8 @@ def read_files(fmt, points_path, labels_path, points=True):
     file means None"""
     if fmt["stride"] is not None:
         pts = _read_bytes(points_path, 4 * fmt["stride"], "point") if points else None
+        if fmt.get("fake") and not os.path.exists(labels_path):     # fake_synth4d.py:111-112: zeros, unmapped
+            return pts, None, fmt["stride"]
         labels = _read_bytes(labels_path, np.dtype(fmt["labels"]).itemsize, "label").view(fmt["labels"])
         return pts, labels, fmt["stride"]
     pts = stride = None
@@ -329,12 +351,16 @@ class FileScans:
     listing from pair's own generator, which moves with every call: only for i < min(len) is a batch made twice the same
     batch, before and after a resume included.  `luts`: one int32 look-up table per listing.  `use_cache` keeps loaded
     scans on the device (the reference's CACHE of the `data` dict; off in every configuration).
+    `raycast` (training only; a raycast.SensorSpec, a sensor's name or JSON file) resamples every scan to that sensor as
+    seen from `raycast_origin` right after load_scan, before the cache, the draws and augment_item: the draws see the
+    resampled point count (lidog_amd.raycast).
     `keep_raw` (validation only, an attribute that may be set later): every item made also leaves what the point-level
     evaluation needs, the uploaded file included, for point_item to hand out once.
     Items are made on data.merge_stream; per scan the host waits once for `info`, then for the sizes augment_item reads."""
 
     def __init__(self, listings, luts, voxel_size=0.05, augmentations=None, sub_p=0.8, seed=1234, bev=None,
-                 ignore_label=-1, in_radius=50.0, use_cache=False, use_intensity=False, keep_raw=False):
+                 ignore_label=-1, in_radius=50.0, use_cache=False, use_intensity=False, keep_raw=False, raycast=None,
+                 raycast_origin=None):
         listings = [listings] if isinstance(listings, Listing) else list(listings)
         luts = [luts] if isinstance(luts, np.ndarray) else list(luts)
         if len(listings) not in (1, 2):
@@ -366,6 +392,12 @@ class FileScans:
         if keep_raw and self.train:
             raise ValueError("keep_raw: only the validation form keeps every point of a file")
         self.keep_raw, self._raw, self._point_items = bool(keep_raw), {}, {}
+        self.raycast, self.raycast_origin = None, raycast_origin
+        if raycast is not None:
+            if not self.train:
+                raise ValueError("raycast: only training scans are resampled, a target is validated as it is")
+            from .raycast import sensor
+            self.raycast = sensor(raycast)
 
     def __len__(self):
         return max(len(l) for l in self.listings)
@@ -395,6 +427,9 @@ class FileScans:
         labels = torch.from_numpy(labels).to(device) if labels is not None else None
         radius = self.in_radius if fmt["radius"] else None
         scan = load_scan(pts, labels, self._lut(s, device), stride, fmt["mask"], radius, name=points_path)
+        if self.raycast is not None:    # the Raycast baseline: the scan as the target's sensor would have recorded it
+            from .raycast import raycast_scan
+            scan = raycast_scan(scan, self.raycast, self.raycast_origin)
         if self.keep_raw:       # the uploaded words themselves: the point path reads them again, nothing is copied
             words = _as_words(pts, "points", points_path)
             self._raw[key] = {"points_raw": words, "labels_raw": _check_labels(labels, points_path),
@@ -535,7 +570,8 @@ def add_file_arguments(ap, flag, what):
     """--files / --target-files and what goes with them (shared with lidog_amd.eval_target)"""
     ap.add_argument(flag, nargs="+", default=None, metavar="NAME=PATH",
                     help=f"{what} scans read from files (lidog_amd.scans): one or two entries, NAME one of SemanticKITTI, "
-                         "Synth4D-kitti, Synth4D-nuscenes, nuScenes (a pair list train.txt / val.txt under PATH)")
+                         "Synth4D-kitti, Synth4D-nuscenes, nuScenes (a pair list train.txt / val.txt under PATH), or "
+                         "FakeKITTI, FakeSynth4D-kitti, FakeSynth4D-nuscenes (written by lidog_amd.raycast)")
     ap.add_argument("--label-maps", nargs="+", default=None, metavar="FILE",
                     help="one label map per entry: a .yaml / .json file with a learning_map (the reference's *2common.yaml)")
     ap.add_argument("--synth4d-splits", default=None, metavar="DIR",
@@ -554,7 +590,7 @@ def check_file_arguments(ap, entries, a, flag):
         ap.error(f"{flag}: {len(files)} entries (the reference takes one or two)")
     if a.label_maps is None or len(a.label_maps) != len(files):
         ap.error(f"{flag} needs --label-maps with one file per entry")
-    if any(n.startswith("Synth4D") for n, _ in files) and a.synth4d_splits is None:
+    if any("Synth4D" in n for n, _ in files) and a.synth4d_splits is None:
         ap.error(f"{flag}: a Synth4D entry needs --synth4d-splits")
     if a.limit_files is not None and a.limit_files < 1:
         ap.error("--limit-files must be positive")

@@ -20,6 +20,8 @@ What the reference's entry scripts do through pytorch-lightning, as plain argume
                                                                        /tmp/run/metrics.jsonl: lidog_amd.metrics)
     python -m lidog_amd.train --files SemanticKITTI=/data/SemanticKITTI --label-maps semantickitti2common.yaml ...
                                                                        (scans from files: lidog_amd.scans)
+    python -m lidog_amd.train --model MinkUNet34 --config kitti120k --raycast-to nusc35k --lr 0.01 --scheduler ExponentialLR
+                                              (the Raycast baseline, configs/raycast: lidog_amd.raycast)
 
 Scans are synthetic (lidog_amd.synth; there are no datasets on the box) unless --files names a dataset on disk
 (lidog_amd.scans: SemanticKITTI, Synth4D, a nuScenes pair list); anything with `__len__` and
@@ -381,16 +383,30 @@ class AugmentedSynthScans:
     (Synth4DDataset).  One configuration: a one-source batch; two: paired as MultiSynthScans.pair, each source's item
     augmented on its own, source 0 first (MultiBEVSourceDataset.__getitem__).  The draws of item i in epoch e come from
     np.random.RandomState([seed, e, i]) in the reference's sequence: a batch does not depend on the world size, the
-    batch split or a resume (Fit calls set_epoch).  Items are made on data.merge_stream."""
+    batch split or a resume (Fit calls set_epoch).  Items are made on data.merge_stream.
+    `raycast` (a raycast.SensorSpec, a sensor's name or JSON file): the Raycast baseline.  Every scan is resampled to
+    that sensor on the GPU (lidog_amd.raycast.raycast_scan) before anything is drawn, as seen from `raycast_origin`
+    (default: raycast.origin_between(configuration, sensor) when the sensor is a configuration's, else 0); the draws see
+    the resampled point count.  Only then may `augmentations` be None: nothing is drawn, every point in order, as
+    scans.FileScans.draws."""
 
     CACHE_SCANS = 256
 
-    def __init__(self, n, configs, augmentations, sub_p=0.8, seed=1234, first=0, bev=None, ignore_label=-1):
+    def __init__(self, n, configs, augmentations, sub_p=0.8, seed=1234, first=0, bev=None, ignore_label=-1,
+                 raycast=None, raycast_origin=None):
         configs = (configs,) if isinstance(configs, str) else tuple(configs)
         if len(configs) not in (1, 2):
             raise NotImplementedError(f"{len(configs)} sources (the reference takes one or two)")
         self.configs, self.num_sources = configs, len(configs)
-        self.augmentations = check_augmentations(augmentations)
+        self.raycast, self.raycast_origins = None, None
+        if raycast is not None:
+            from . import raycast as _raycast
+            self.raycast = _raycast.sensor(raycast)
+            between = self.raycast.name in synth.CONFIGS
+            self.raycast_origins = [raycast_origin if raycast_origin is not None else
+                                    (_raycast.origin_between(c, self.raycast.name) if between else None) for c in configs]
+        self.augmentations = None if (augmentations is None and raycast is not None) else \
+            check_augmentations(augmentations)
         self.sub_p, self.bev, self.ignore_label = sub_p, bev, ignore_label
         self.n, self.seed, self.first, self.epoch = int(n), int(seed), int(first), 0
         self.pairs = MultiSynthScans(n, n, configs, seed=seed, first=first) if self.num_sources == 2 else None
@@ -413,8 +429,28 @@ class AugmentedSynthScans:
             self._cache[(s, j)] = synth.scan_points_labels(self.first + j + s * synth.SOURCE1_SEED, self.configs[s])
         return self._cache[(s, j)]
 
+    def scan(self, s, j, device):
+        """the scan dict of scan j of source s on `device`, uploaded (and with `raycast` resampled) on the current
+        stream"""
+        pts, labels = self.points(s, j)
+        scan = {"points": torch.from_numpy(pts).to(device), "sem_labels": torch.from_numpy(labels).to(device),
+                "features": torch.ones((pts.shape[0], 1), dtype=torch.float32, device=device)}
+        if self.raycast is not None:
+            from .raycast import raycast_scan
+            scan = raycast_scan(scan, self.raycast, self.raycast_origins[s])
+        return scan
+
+    def draws(self, rng, m):
+        """the draws of one item of m points: the reference's sequence with an augmentation list, nothing otherwise"""
+        if self.augmentations is None:
+            return {"sampled_idx": np.arange(m), "ops": []}
+        return draw_augmentation(rng, m, self.sub_p, self.augmentations)
+
     def item(self, i):
-        """[(source, scan index, draws)] of item i in the current epoch"""
+        """[(source, scan index, draws)] of item i in the current epoch (without `raycast`: with it the number of
+        points is known on the device only, see _batch)"""
+        if self.raycast is not None:
+            raise RuntimeError("item: with raycast the draws follow the resampled scan, ask for batch()")
         rng = self.item_rng(i)
         js = (int(i),) if self.pairs is None else self.pairs.pair(i)
         return [(s, j, draw_augmentation(rng, self.points(s, j)[0].shape[0], self.sub_p, self.augmentations))
@@ -426,9 +462,22 @@ class AugmentedSynthScans:
         return synth.CONFIGS[self.configs[0]]["voxel"]
 
     def draw_item(self, s, j, rng, device=None):
+        if self.raycast is not None:    # the resampled point count is known once the scan is on the device
+            device = torch.device("cuda" if device is None else device)
+            scan = on_merge_stream(lambda: self.scan(s, j, device), device, wait=False)
+            self._last = ((s, int(j), str(device)), scan)
+            return self.draws(rng, scan["points"].shape[0])
         return draw_augmentation(rng, self.points(s, j)[0].shape[0], self.sub_p, self.augmentations)
 
     def make_item(self, s, j, draws, device):
+        if self.raycast is not None:
+            device = torch.device(device)
+            key, scan = getattr(self, "_last", (None, None))
+            if key != (s, int(j), str(device)):
+                scan = self.scan(s, j, device)
+            self._last = (None, None)
+            return merge_scan(augment_item(scan, draws, voxel_size=synth.CONFIGS[self.configs[s]]["voxel"],
+                                           bounds=self.bev is not None, ignore_label=self.ignore_label), j)
         pts, labels = self.points(s, j)
         scan = {"points": torch.from_numpy(pts).to(device), "sem_labels": torch.from_numpy(labels).to(device),
                 "features": torch.ones((pts.shape[0], 1), dtype=torch.float32, device=device)}
@@ -449,7 +498,22 @@ class AugmentedSynthScans:
     def face_name(self, s):
         return synth.CONFIGS[self.configs[s]].get("dataset", self.configs[s])
 
+    def _raycast_batch(self, indices, device):
+        items = []
+        for i in indices:
+            rng = self.item_rng(i)
+            row = []
+            for s, j in enumerate((int(i),) if self.pairs is None else self.pairs.pair(i)):
+                scan = self.scan(s, j, device)
+                row.append(augment_item(scan, self.draws(rng, scan["points"].shape[0]),
+                                        voxel_size=synth.CONFIGS[self.configs[s]]["voxel"], bounds=self.bev is not None,
+                                        ignore_label=self.ignore_label, bev=self.bev))
+            items.append(row)
+        return collate_items(items, self.bev is not None)
+
     def _batch(self, indices, device):
+        if self.raycast is not None:
+            return self._raycast_batch(indices, device)
         items = []
         for i in indices:
             row = []
@@ -793,6 +857,13 @@ def parse_args(argv=None):
                     help="SN car-size scaling (train_scaling_based.py): every scan of --config (or of the two --sources) "
                          "is scaled to the car size of these target configurations and re-quantised; the car sizes "
                          "are clustered on the GPU at start-up; trained with SoftDICE (use the *_cars configurations)")
+    ap.add_argument("--raycast-to", default=argparse.SUPPRESS, metavar="NAME|FILE.json",
+                    help="the Raycast baseline (configs/raycast): every training scan is resampled on the GPU as the "
+                         "target's sensor would have recorded it (lidog_amd.raycast): a configuration's sensor, hdl32e, "
+                         "or a JSON file; --augment runs after the resampling; validation data is never resampled")
+    ap.add_argument("--raycast-origin", nargs=3, type=float, default=argparse.SUPPRESS, metavar=("X", "Y", "Z"),
+                    help="the target sensor's position in the source frame (default: the height difference of two "
+                         "synthetic configurations, else 0 0 0)")
     ap.add_argument("--check-val-every-n-epoch", type=int, default=5)
     ap.add_argument("--save-dir", default=None)
     ap.add_argument("--resume", default=None)
@@ -853,7 +924,7 @@ def parse_args(argv=None):
             ap.error(f"--sn-target-files: {e}")
         if sn_target_label_maps is None or len(sn_target_label_maps) != len(sn_target_files):
             ap.error("--sn-target-files needs --sn-target-label-maps with one file per entry")
-        if any(n.startswith("Synth4D") for n, _ in sn_target_files) and a.synth4d_splits is None:
+        if any("Synth4D" in n for n, _ in sn_target_files) and a.synth4d_splits is None:
             ap.error("--sn-target-files: a Synth4D entry needs --synth4d-splits")
     elif sn_target_label_maps is not None:
         ap.error("--sn-target-label-maps goes with --sn-target-files")
@@ -889,6 +960,16 @@ def parse_args(argv=None):
                      f"MinkUNet34IBN, not {a.model}")
         if a.mix is not None or a.mix3d:
             ap.error(f"{flag}, --mix and --mix3d are different methods: pass one of them")
+    if getattr(a, "raycast_to", None) is not None:
+        if a.mix is not None or a.mix3d or sn:
+            ap.error("--raycast-to, --mix, --mix3d and --sn-targets are different methods: pass one of them")
+        from .raycast import sensor
+        try:
+            sensor(a.raycast_to)
+        except ValueError as e:
+            ap.error(f"--raycast-to: {e}")
+    elif getattr(a, "raycast_origin", None) is not None:
+        ap.error("--raycast-origin goes with --raycast-to")
     if a.augment is not None:
         check_augmentations(a.augment)       # NotImplementedError for another name, as get_augmentations
         if a.mix is not None or a.mix3d or sn:
@@ -973,9 +1054,11 @@ def _data_from_args(a):
         train = ScaledSynthScans(a.scans, configs, a.sn_targets, seed=a.seed, items=items)
         val = per_source_val() if a.sources else (
             SynthScans(a.val_scans, a.config, first=10 ** 6, bev_size=bev) if a.val_scans else None)
-    elif getattr(a, "augment", None) is not None:
+    elif getattr(a, "augment", None) is not None or getattr(a, "raycast_to", None) is not None:
         train = AugmentedSynthScans(a.scans, a.sources or a.config, a.augment, sub_p=a.sub_p, seed=a.seed,
-                                    bev=(a.bound, bev) if a.model == "MinkUNet34BEV" else None)
+                                    bev=(a.bound, bev) if a.model == "MinkUNet34BEV" else None,
+                                    raycast=getattr(a, "raycast_to", None),
+                                    raycast_origin=getattr(a, "raycast_origin", None))
         if a.sources:                       # validation data is never augmented (phase == 'train' only)
             val = {name: SynthScans(a.val_scans, c, first=10 ** 6 + i * synth.SOURCE1_SEED, bev_size=bev)
                    for i, (name, c) in enumerate(zip(source_names(a.sources), a.sources))} if a.val_scans else None
@@ -1026,7 +1109,9 @@ def _file_data(a, bev):
                                      items=items, target_faces=faces)
     else:
         train = scans.FileScans(listings, luts, augmentations=a.augment, sub_p=a.sub_p, seed=a.seed,
-                                bev=(a.bound, bev) if a.model == "MinkUNet34BEV" else None)
+                                bev=(a.bound, bev) if a.model == "MinkUNet34BEV" else None,
+                                raycast=getattr(a, "raycast_to", None),
+                                raycast_origin=getattr(a, "raycast_origin", None))
     val = {name: scans.FileScans(scans.listing(n, p, "validation", **kw), lut, seed=a.seed)
            for name, (n, p), lut in zip(source_names([n for n, _ in a.files]), a.files, luts)}
     return train, val

@@ -30,6 +30,8 @@ extern "C" {
 #endif
 
 const char *lidog_last_error(void);
+/* 9.  Bumped whenever an entry point changes its arguments or their meaning (additive entries leave it alone);
+ * 8 -> 9: the workspaces of lidog_coords_compact / lidog_coords_stride are sized by their _ws functions. */
 int lidog_abi_version(void);
 
 /* ------------------------------------------------------------------ coordinate maps
@@ -49,15 +51,19 @@ int lidog_coords_insert(const int32_t *coords, int64_t n, uint64_t *keys, int32_
                         int32_t *first_row, int64_t *n_unique_dev, int32_t *err_flag, void *stream);
 /* the same, and in the same pass what a caller needs to size occupancy bitmaps and batch loops:
  * info [9] int64 (device) = (unique rows, error flag, largest batch index, lowest x, y, z, highest x, y, z) -- one
- * read-back instead of n_unique + err + three device-wide min / max reductions of the caller's own. */
+ * read-back instead of n_unique + err + three device-wide min / max reductions of the caller's own.  The extrema are
+ * taken over ALL n rows, out-of-range ones included (the caller refuses such a map anyway); for n = 0 they are the
+ * placeholders -2^40 (largest batch index, highest x, y, z) and 2^40 (lowest x, y, z). */
 int lidog_coords_insert_info(const int32_t *coords, int64_t n, uint64_t *keys, int32_t *vals, int64_t cap,
                              int32_t *first_row, int64_t *info, int32_t *err_flag, void *stream);
 
 /* Compact a map with duplicates: unique_rows[j] = first-occurrence row of output row j (ascending),
- * inverse[i] = output row of input row i; rewrites vals to output rows.  scan_ws: int32[n + 2048].
+ * inverse[i] = output row of input row i; rewrites vals to output rows.  scan_ws: int32[lidog_coords_compact_ws(n)]
+ * (the required size: n + ceil(n / 1024) + 1 words, n < 0 counting as 0; the entry point cannot check it).
  * Terminates on any input: a row that lidog_coords_insert flagged as out of range keeps its unique_rows / inverse
  * entries (every output is defined) and rewrites no slot, and a probe ends at an empty slot.  A caller may therefore
  * launch it before it has read the range flag (lidog_amd.data.quantize_rows: one read-back after the last launch). */
+int64_t lidog_coords_compact_ws(int64_t n);
 int lidog_coords_compact(const int32_t *first_row, int64_t n, const uint64_t *keys, int32_t *vals, int64_t cap,
                          const int32_t *coords, int32_t *unique_rows, int32_t *inverse, int32_t *scan_ws,
                          void *stream);
@@ -65,7 +71,9 @@ int lidog_coords_compact(const int32_t *first_row, int64_t n, const uint64_t *ke
 /* Strided map (conv kernel 2 stride 2, minkunet_bev.py:62,69,76,83): out coordinate =
  * floor(c / new_stride) * new_stride per spatial dim, duplicates collapsed, rows in first-occurrence
  * order of the parent.  coords_out has room for n_in rows; n_out_dev (device int64) gets the count.
- * parent2child[i] = output row of parent row i.  ws: int32[2 * n_in + 2048]. */
+ * parent2child[i] = output row of parent row i.  ws: int32[lidog_coords_stride_ws(n_in)] (the required size:
+ * 2 n_in + ceil(n_in / 1024) + 1 words, n_in < 0 counting as 0). */
+int64_t lidog_coords_stride_ws(int64_t n_in);
 int lidog_coords_stride(const int32_t *coords_in, int64_t n_in, int32_t new_stride, uint64_t *keys,
                         int32_t *vals, int64_t cap, int32_t *parent2child, int32_t *coords_out,
                         int64_t *n_out_dev, int32_t *ws, int32_t *err_flag, void *stream);

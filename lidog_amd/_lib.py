@@ -18,6 +18,8 @@ SIGNATURES = {
     "lidog_hash_capacity": [_i64],
     "lidog_coords_insert": [_p, _i64, _p, _p, _i64, _p, _p, _p, _p],
     "lidog_coords_insert_info": [_p, _i64, _p, _p, _i64, _p, _p, _p, _p],
+    "lidog_coords_compact_ws": [_i64],
+    "lidog_coords_stride_ws": [_i64],
     "lidog_coords_compact": [_p, _i64, _p, _p, _i64, _p, _p, _p, _p, _p],
     "lidog_coords_stride": [_p, _i64, _i32, _p, _p, _i64, _p, _p, _p, _p, _p, _p],
     "lidog_kernel_map": [_p, _i64, _p, _p, _i64, _p, _i32, _p, _p],
@@ -194,7 +196,8 @@ SIGNATURES = {
     "lidog_raycast_ws": [_i64, _i64],
     "lidog_raycast": [_p, _i64, _p, _p, _i32, _i32, _d, _f, _i32, _f, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
 }
-_RESTYPES = {"lidog_hash_capacity": _i64, "lidog_sconv_reduce_stats_ws": _i64, "lidog_bn_reduce_ws": _i64,
+_RESTYPES = {"lidog_hash_capacity": _i64, "lidog_coords_compact_ws": _i64, "lidog_coords_stride_ws": _i64,
+             "lidog_sconv_reduce_stats_ws": _i64, "lidog_bn_reduce_ws": _i64,
              "lidog_dice_ws": _i64, "lidog_ce_ws": _i64, "lidog_colsum_ws": _i64, "lidog_conv2d_support_ws": _i64, "lidog_conv2d_wgrad_sparse_ws": _i64,
              "lidog_tiles_host": _i64, "lidog_wgrad_items_host": _i64, "lidog_bitmap_words": _i64,
              "lidog_bn_bwd_reduce_blocks": _i64, "lidog_relu_bits_words": _i64,
@@ -207,7 +210,7 @@ _RESTYPES = {"lidog_hash_capacity": _i64, "lidog_sconv_reduce_stats_ws": _i64, "
 
 # lidog_abi_version() of the library these signatures were written against: a stale .so (or a header an external caller
 # compiled against long ago) would take mis-sized arguments without any diagnostic
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 _lib = None
 

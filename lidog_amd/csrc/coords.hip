@@ -17,7 +17,8 @@ void lidog_set_error(const char *fmt, ...) {
 extern "C" const char *lidog_last_error(void) { return g_err; }
 // bumped whenever an entry point changes its arguments or their meaning (lidog_amd/_lib.py checks it at load time);
 // 4 = round 4: in-kernel statistics finish (workspace sizes), peer all-reduce stream binding / fault hooks
-extern "C" int lidog_abi_version(void) { return 8; }
+// 9 = the scan workspaces of lidog_coords_compact / lidog_coords_stride are sized by lidog_coords_compact_ws / _stride_ws
+extern "C" int lidog_abi_version(void) { return 9; }
 
 extern "C" int64_t lidog_hash_capacity(int64_t n) {
     int64_t cap = 1024;
@@ -97,6 +98,9 @@ __global__ __launch_bounds__(256) void scan_apply(int32_t *__restrict__ data, in
         ex += v[j];
     }
 }
+
+// ints of `sums` the scan of n entries writes: one per 1024-entry block and the total behind them
+static int64_t scan_sums_ints(int64_t n) { return cdiv64(n, 1024) + 1; }
 
 static int device_exclusive_scan(int32_t *data, int64_t n, int32_t *sums, hipStream_t st) {
     int64_t nb = cdiv64(n, 1024);
@@ -282,6 +286,18 @@ __global__ __launch_bounds__(256) void k_compact_rows(const int32_t *__restrict_
             slot = (slot + 1) & mask;
         }
     }
+}
+
+// int32 words of lidog_coords_compact's scan_ws: rank [n] + the scan's block sums.  (The header used to say 2048 words
+// more than n, which is one word short from n = 2 096 129 rows on: ceil(n / 1024) + 1 > 2048.)
+extern "C" int64_t lidog_coords_compact_ws(int64_t n) {
+    if (n < 0) n = 0;
+    return n + scan_sums_ints(n);
+}
+// int32 words of lidog_coords_stride's ws: slot_of [n_in] + rank [n_in] + the scan's block sums
+extern "C" int64_t lidog_coords_stride_ws(int64_t n_in) {
+    if (n_in < 0) n_in = 0;
+    return 2 * n_in + scan_sums_ints(n_in);
 }
 
 extern "C" int lidog_coords_compact(const int32_t *first_row, int64_t n, const uint64_t *keys, int32_t *vals,

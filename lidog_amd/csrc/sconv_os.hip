@@ -82,7 +82,7 @@ __global__ __launch_bounds__(256) void k_os_wave_masks(const uint32_t *__restric
 // of the digit-major [RS_BINS][chunks] table, one wavefront per digit, (3) scatter -- the chunk is walked 64 elements at a time in
 // order; the lanes holding the same digit find each other with RS_BITS ballots, rank = popcount of the lower peers, the
 // lowest peer advances the digit's cursor: equal keys keep their input order (what the numpy restatement in
-// tests/test_gpu_sconv_os.py calls a stable argsort).  Replaces the CUB-compatibility wrapper the file used in round 4
+// tests/maps_ref.py calls a stable argsort).  Replaces the CUB-compatibility wrapper the file used in round 4
 // (~10 launches of rocPRIM's merge-sort fallback per sort; here 3 per pass).
 #define RS_BITS 9
 #define RS_BINS (1 << RS_BITS)

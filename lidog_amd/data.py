@@ -52,7 +52,7 @@ def quantize_rows(rows, features=None, labels=None, ignore_label=-100, return_in
     call("lidog_coords_insert", ptr(rows), n, ptr(keys), ptr(vals), cap, ptr(first), ptr(sizes[:1]), ptr(sizes[1:]))
     uniq = torch.empty(n, dtype=torch.int32, device=dev)
     inv = torch.empty(n, dtype=torch.int32, device=dev)
-    ws = torch.empty(n + 2048, dtype=torch.int32, device=dev)
+    ws = torch.empty(_lib.load().lidog_coords_compact_ws(n), dtype=torch.int32, device=dev)
     call("lidog_coords_compact", ptr(first), n, ptr(keys), ptr(vals), cap, ptr(rows), ptr(uniq), ptr(inv), ptr(ws))
     m, bad = sizes.cpu().tolist()
     if bad:

@@ -438,7 +438,7 @@ class CoordinateManager:
             m = int(stats[0])
             uniq_full = torch.empty(n, dtype=torch.int32, device=self.device)
             inv = torch.empty(n, dtype=torch.int32, device=self.device)
-            ws = torch.empty(n + 2048, dtype=torch.int32, device=self.device)
+            ws = torch.empty(_lib.load().lidog_coords_compact_ws(n), dtype=torch.int32, device=self.device)
             call("lidog_coords_compact", ptr(first), n, ptr(keys), ptr(vals), cap, ptr(coords), ptr(uniq_full),
                  ptr(inv), ptr(ws))
             uniq = uniq_full[:m]
@@ -458,7 +458,7 @@ class CoordinateManager:
         p2c = torch.empty(n, dtype=torch.int32, device=self.device)
         out = self._own(torch.empty((n, 4), dtype=torch.int32, device=self.device))
         n_out = torch.zeros(1, dtype=torch.int64, device=self.device)
-        ws = torch.empty(2 * n + 2048, dtype=torch.int32, device=self.device)
+        ws = torch.empty(_lib.load().lidog_coords_stride_ws(n), dtype=torch.int32, device=self.device)
         call("lidog_coords_stride", ptr(src.coords), n, int(s_out), ptr(keys), ptr(vals), cap, ptr(p2c), ptr(out),
              ptr(n_out), ptr(ws), ptr(self.err))
         m = int(n_out.item())

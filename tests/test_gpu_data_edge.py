@@ -52,7 +52,7 @@ def _raw_quantize(rows, pad=64):
     call("lidog_coords_insert", ptr(rows), n, ptr(keys), ptr(vals), cap, ptr(first), ptr(sizes[:1]), ptr(sizes[1:]))
     uniq = torch.full((n + pad,), SENTINEL, dtype=torch.int32, device="cuda")
     inv = torch.full((n + pad,), SENTINEL, dtype=torch.int32, device="cuda")
-    ws = torch.empty(n + 2048, dtype=torch.int32, device="cuda")
+    ws = torch.empty(load().lidog_coords_compact_ws(n), dtype=torch.int32, device="cuda")
     call("lidog_coords_compact", ptr(first), n, ptr(keys), ptr(vals), cap, ptr(rows), ptr(uniq), ptr(inv), ptr(ws))
     m, bad = sizes.cpu().tolist()
     return m, bad, uniq, inv

@@ -1,12 +1,13 @@
 """Output-stationary 3^3 convolution (csrc/sconv_os.hip: rows sorted by neighbour mask, no product rows) through the C
 ABI: bit-identical to the two-pass path (gathered GEMM -> product rows -> per-row reduction) and to the CPU oracle's
 fmaf chains, forward and data gradient, with bias / addend, on small scenes and on a bench-size map; the statistics
-forms against the two-pass forms; the sorted-row tables themselves against a numpy restatement.
+forms against the two-pass forms; the sorted-row tables themselves against their numpy restatement (tests/maps_ref.py).
 Reference semantics: MinkowskiConvolution(kernel_size=3, stride=1), utils/models/minkunet_bev.py:425-439."""
 import numpy as np
 import pytest
 import torch
 
+import maps_ref
 from helpers import small_batch
 
 pytestmark = pytest.mark.gpu
@@ -36,27 +37,14 @@ def test_sorted_rows_tables_match_their_definition():
     m = cm.kernel_map(1, 1, 3)
     perm, wm, order = _sorted(m)
     n = m.n_out
-    nbr = m.nbr.cpu().numpy()
-    mask = np.zeros(n, np.int64)
-    for k in range(27):
-        mask |= (nbr[k] >= 0).astype(np.int64) << k
-    counts = (nbr >= 0).sum(1)
-    # bit position of offset k in the key: number of offsets that occur more often (ties: lower k first)
-    pos = [sum(1 for j in range(27) if counts[j] > counts[k] or (counts[j] == counts[k] and j < k)) for k in range(27)]
-    key = np.zeros(n, np.int64)
-    for k in range(27):
-        key |= ((mask >> k) & 1) << pos[k]
-    want = np.argsort(key, kind="stable")
+    # the definition lives in tests/maps_ref.py (sorted_tables), shared with tests/test_gpu_map_primitives.py: the rows in
+    # stable ascending key order, -1 behind row n; the OR of every 32 sorted rows' masks; the tiles in stable ascending
+    # order of 127 - blocks (heaviest first, ties by tile id) -- all three exact
+    want_perm, want_masks, want_order = maps_ref.sorted_tables(m.nbr.cpu().numpy(), m.k_off.cpu().numpy())
     p = perm.cpu().numpy()
-    assert np.array_equal(p[:n], want) and (p[n:] == -1).all()
-    pad = p.shape[0]
-    mm = np.concatenate([mask[want], np.zeros(pad - n, np.int64)]).reshape(-1, 32)
-    assert np.array_equal(wm.cpu().numpy().astype(np.int64) & 0xFFFFFFFF, np.bitwise_or.reduce(mm, axis=1))
-    wo = np.bitwise_or.reduce(mm, axis=1)                      # per 32 sorted rows
-    w = np.array([sum(bin(int(v)).count("1") for v in wo[4 * t:4 * t + 4]) for t in range(pad // 128)])
-    o = order.cpu().numpy()
-    assert sorted(o.tolist()) == list(range(pad // 128))
-    assert all(w[o[i]] >= w[o[i + 1]] for i in range(len(o) - 1))      # heaviest tiles first
+    assert p.shape == want_perm.shape and np.array_equal(p, want_perm) and (p[n:] == -1).all()
+    assert np.array_equal(wm.cpu().numpy().view(np.uint32), want_masks)
+    assert np.array_equal(order.cpu().numpy(), want_order)
 
 
 @pytest.mark.parametrize("Cin,Cout", [(32, 32), (96, 96), (128, 96), (64, 128)])

@@ -87,4 +87,4 @@ def test_instance_norm_entries_in_header_binding_and_exports():
             "lidog_in_reduce_ws"} <= mine
     for name in mine:
         assert hasattr(lib, name) and name in _lib.SIGNATURES
-    assert lib.lidog_abi_version() == _lib.ABI_VERSION == 8
+    assert lib.lidog_abi_version() == _lib.ABI_VERSION == 9

@@ -110,7 +110,7 @@ def test_mix_symbols_are_declared_bound_and_exported():
         assert name in _lib.SIGNATURES, name
         assert hasattr(lib, name), name
     assert "mix.hip" in build.SOURCES
-    assert _lib.ABI_VERSION == 8 and lib.lidog_abi_version() == 8
+    assert _lib.ABI_VERSION == 9 and lib.lidog_abi_version() == 9
 
 
 # ------------------------------------------------------------------ per-item draws

@@ -223,7 +223,7 @@ def test_point_symbols_exported_and_bound():
     header = open(os.path.join(REPO, "include", "lidog_amd.h")).read()
     for name in POINT_SYMBOLS:
         assert hasattr(lib, name) and name in _lib.SIGNATURES and f"{name}(" in header
-    assert _lib.ABI_VERSION == 8 and lib.lidog_abi_version() == 8          # additive entries: the version stays
+    assert _lib.ABI_VERSION == 9 and lib.lidog_abi_version() == 9          # additive entries: the version stays
     assert "pointlabels.hip" in build.SOURCES
     # one definition of the radius test and the label look-up for the loader and the point path
     for f in ("scanload.hip", "pointlabels.hip"):

@@ -167,5 +167,5 @@ def test_iw_entries_in_header_binding_and_exports():
     assert mine == {"lidog_iw_ws", "lidog_iw_fwd", "lidog_iw_bwd"}
     for name in mine:
         assert hasattr(lib, name) and name in _lib.SIGNATURES
-    assert lib.lidog_abi_version() == _lib.ABI_VERSION == 8
+    assert lib.lidog_abi_version() == _lib.ABI_VERSION == 9
     assert "iwloss.hip" in build.SOURCES

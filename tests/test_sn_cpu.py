@@ -265,7 +265,7 @@ def test_sn_symbols_are_declared_bound_and_exported():
         assert name in _lib.SIGNATURES, name
         assert hasattr(lib, name), name
     assert "cluster.hip" in build.SOURCES
-    assert _lib.ABI_VERSION == 8 and lib.lidog_abi_version() == 8
+    assert _lib.ABI_VERSION == 9 and lib.lidog_abi_version() == 9
     assert _lib._RESTYPES["lidog_dbscan_ws"] is _lib._i64
 
 

@@ -655,9 +655,9 @@ int lidog_trunk_work_read(double *out /*[6]*/);
 
 /* bytes of workspace lidog_in_segments needs for a map of n rows */
 int64_t lidog_in_segments_ws(int64_t n);
-/* The segments of a coordinate map (minkunet_ibn.py:26): perm [n] = the rows in stable batch order (radix sort of the
- * batch column), seg_off [B + 1] = where each batch index starts in perm (empty scans: empty ranges), bid [n] = the batch
- * index of every row.  B = largest batch index + 1 (<= 4096).  Rows may be in any order; build once per map. */
+/* The segments of a coordinate map (minkunet_ibn.py:26): perm [n] = the rows in stable batch order (the radix sort
+ * of csrc/prims.hip on the batch column), seg_off [B + 1] = where each batch index starts in perm (empty scans: empty
+ * ranges), bid [n] = the batch index of every row.  B = largest batch index + 1 (<= 4096).  Rows may be in any order; build once per map. */
 int lidog_in_segments(const int32_t *coords, int64_t n, int32_t B, int32_t *perm, int32_t *seg_off, int32_t *bid,
                       void *ws, int64_t ws_bytes, void *stream);
 /* doubles of workspace the per-(b, c) reductions below need (minkunet_ibn.py:26,38-40) */
@@ -798,7 +798,8 @@ int lidog_sn_scale_coords(const int32_t *coords, int64_t n, float voxel_size, fl
  * (utils/datasets/semantickitti_bev.py:209-238, synth4d.py:141-162): the sub-sample gather (dataset.py:58-72),
  * RandomRotation / RandomScale (utils/common/augmentation.py:7-44) under numpy's dtype rules, the bounds filter
  * (semantickitti_bev.py:155-172) and the voxel floor of ME.utils.sparse_quantize in the point's own dtype.  The host
- * makes the draws.  Positions of the kept rows come from lidog_mix_split: the same bytes on every run. */
+ * makes the draws.  Positions of the kept rows come from the ordered compaction of csrc/prims.hip (lidog_mix_split's
+ * kernels with one slot): the same bytes on every run. */
 /* 1 when the list holds a rotation: the points leave as float64 (`coords @ R`, R float64), else 0 (float32) */
 int32_t lidog_augment_is_f64(const int32_t *op_kinds_host, int32_t n_ops);
 /* int32 workspace of lidog_augment_points for k sampled rows (read only with use_bounds) */
@@ -862,7 +863,8 @@ int lidog_train_confusion(const float *const *logits, const int64_t *const *labe
  * (utils/datasets/semantickitti.py:100-131,190-197, nuscenes.py:144-178,238-248, synth4d.py:106-137) and in
  * get_dataset_stats (semantickitti.py:199-213): unpack the records, map the labels, apply the radius mask, compact the
  * kept rows in order, count the labels per class.  The host uploads the files' bytes unmodified.  Positions come from
- * lidog_mix_split and the statistics are integer counts: the same bytes on every run.  No allocation, synchronisation or
+ * the ordered compaction of csrc/prims.hip and the statistics are integer counts: the same bytes on every run.  No
+ * allocation, synchronisation or
  * blocking copy inside. */
 /* int32 workspace of lidog_scan_load for a file of n rows */
 int64_t lidog_scan_load_ws(int64_t n);
@@ -887,7 +889,8 @@ int lidog_scan_load(const float *points_raw, int32_t point_stride, const void *l
 /* ------------------------------------------------------------------ one label per point of a scan file (csrc/pointlabels.hip)
  * What the SemanticKITTI and nuScenes-lidarseg benchmarks score: a class for every record of the file, in file order.
  * The voxel logits go back to the points through the row every record has in lidog_scan_load's output (keep_row) and
- * the voxel every kept row fell into (inverse_map).  Positions come from lidog_mix_split and the counts are integers:
+ * the voxel every kept row fell into (inverse_map).  Positions come from the ordered compaction of csrc/prims.hip and the
+ * counts are integers:
  * the same bytes on every run.  No allocation, synchronisation or blocking copy inside. */
 /* int32 workspace of lidog_scan_keep_rows for a file of n rows */
 int64_t lidog_scan_keep_rows_ws(int64_t n);
@@ -1014,7 +1017,8 @@ int lidog_pool_global_bwd(const float *gy, const int32_t *arg, int64_t n, int32_
  * 1 a bad batch column, 2 a NaN or infinite spatial column.  A finite value beyond the coordinate range sets no bit: such
  * a point simply has no neighbours. */
 int lidog_field_floor(const float *points, int64_t n, int32_t stride, int32_t *rows, int32_t *err, void *stream);
-/* Per-row lists of an index table (a stable counting sort): inv [n] names a row in [0, m) per entry (any other value:
+/* Per-row lists of an index table (the stable radix sort of csrc/prims.hip): inv [n] names a row in [0, m) per entry
+ * (any other value:
  * the entry is in no list).  row_ptr [m + 1], row_list [n]: the entries j with inv[j] == v are
  * row_list[row_ptr[v] .. row_ptr[v + 1]) in ASCENDING j; row_ptr[m] entries are listed, what lies behind them in
  * row_list is unspecified.  Serves a field (inv = point -> voxel row) and the interpolation gradient (inv = the neighbour

@@ -3,9 +3,10 @@
 // (utils/common/augmentation.py:7-44) with numpy's dtype rules, the bounds filter with the ego box
 // (utils/datasets/semantickitti_bev.py:155-172), the voxel floor of ME.utils.sparse_quantize in the point's own dtype,
 // and the stable compaction of the kept rows.  The host makes the draws; the rotation matrix and the scales travel by
-// value in the launch arguments.  The kept rows take their positions from lidog_mix_split (mix.hip: per-block counts,
+// value in the launch arguments.  The kept rows take their positions from lidog_compact_rows (prims.hip: per-block counts,
 // one scan, in-wave ballot ranks), never from an atomic: the same rows in the same order on every run.
 #include "aug_ops.h"
+#include "prims.h"
 
 #define AUG_THREADS 256
 
@@ -29,16 +30,14 @@ __device__ __forceinline__ int64_t aug_source_row(const int32_t *__restrict__ sa
     return i;
 }
 
-// keys[j] = 0 for a sampled row inside the bounds, -1 otherwise; table[0] = 0: the one-slot table of lidog_mix_split
+// keep[j] = 1 for a sampled row inside the bounds, 0 otherwise: the flags of lidog_compact_rows
 __global__ __launch_bounds__(AUG_THREADS) void k_aug_flag(const float *__restrict__ pts, int64_t n,
                                                           const int32_t *__restrict__ sampled_idx, int64_t k, AugOps ops,
-                                                          int32_t *__restrict__ keys, int32_t *__restrict__ table,
-                                                          int32_t *info) {
+                                                          int32_t *__restrict__ keep, int32_t *info) {
     const int64_t j = (int64_t)blockIdx.x * AUG_THREADS + threadIdx.x;
-    if (j == 0) table[0] = 0;
     if (j >= k) return;
     const int64_t i = aug_source_row(sampled_idx, j, n, info);
-    keys[j] = aug_in_bounds(aug_transform(pts, i, ops)) ? 0 : -1;
+    keep[j] = aug_in_bounds(aug_transform(pts, i, ops)) ? 1 : 0;
 }
 
 // output row r: sampled row kept[r] (kept == NULL: r itself), r < count (count_dev == NULL: k).  The transform is
@@ -81,8 +80,8 @@ extern "C" int32_t lidog_augment_is_f64(const int32_t *op_kinds_host, int32_t n_
 }
 
 extern "C" int64_t lidog_augment_ws(int64_t k) {
-    const int64_t kk = k > 0 ? k : 0;   // keys [k], kept [k], table [1], slot_start [2], the split's own workspace
-    return 2 * kk + 3 + lidog_mix_split_ws(kk, 1);
+    const int64_t kk = k > 0 ? k : 0;   // keep [k], kept [k], a spare word (ABI 9 fixes the size), the compaction's own
+    return 2 * kk + 1 + lidog_compact_ws_ints(kk);
 }
 
 extern "C" int lidog_augment_points(const float *points, int64_t n, const int32_t *sampled_idx, int64_t k,
@@ -116,12 +115,11 @@ extern "C" int lidog_augment_points(const float *points, int64_t n, const int32_
     const unsigned grid = (unsigned)cdiv64(k, AUG_THREADS);
     const int32_t *kept = nullptr, *count = nullptr;
     if (use_bounds) {
-        int32_t *keys = ws, *kept_w = ws + k, *table = ws + 2 * k, *slot_start = table + 1, *split_ws = table + 3;
-        k_aug_flag<<<grid, AUG_THREADS, 0, st>>>(points, n, sampled_idx, k, ops, keys, table, info);
+        int32_t *keep = ws, *kept_w = ws + k, *compact_ws = ws + 2 * k + 1;
+        k_aug_flag<<<grid, AUG_THREADS, 0, st>>>(points, n, sampled_idx, k, ops, keep, info);
         LIDOG_LAUNCH_CHECK();
-        if (lidog_mix_split(keys, k, table, 1, 1, kept_w, slot_start, split_ws, stream)) return 1;
+        if (lidog_compact_rows(keep, k, kept_w, compact_ws, &count, st)) return 1;
         kept = kept_w;
-        count = slot_start + 1;
     }
     k_aug_emit<<<grid, AUG_THREADS, 0, st>>>(points, n, sampled_idx, k, ops, kept, count, qx, qy, qz, batch, labels,
                                              (int4 *)rows, xyz, src, labels_out, info);

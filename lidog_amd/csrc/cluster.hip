@@ -23,10 +23,11 @@
 #include <limits.h>
 
 #include "common.h"
+#include "prims.h"
 
 #define CL_THREADS 256
 #define CL_WAVES (CL_THREADS / 64)
-#define CL_SORT_PASSES 4        // 4 x 9 bits cover the 32-bit cell key; an even count: the sorted pairs end in (ka, va)
+#define CL_MAX_KEY 0xffffffffll // the cell key has 32 bits
 #define CL_BOX_BINS 256         // clusters per LDS pass of the box kernel
 #define CL_MAX_COORD 65535      // the coordinate hash's documented range (common.h:lidog_pack)
 #define CL_ERR_RANGE 1
@@ -117,17 +118,6 @@ __global__ __launch_bounds__(CL_THREADS) void k_cl_gather(const int32_t *__restr
     parent[j] = (int32_t)j;
 }
 
-// first position whose key is >= k
-__device__ __forceinline__ int64_t cl_lower(const uint32_t *__restrict__ keys, int64_t n, uint64_t k) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if ((uint64_t)keys[mid] < k) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 struct ClSpace {
     const uint32_t *keys;   // sorted cell keys
     const int4 *sorted;     // (x, y, z, input row) in the same order
@@ -157,7 +147,8 @@ __device__ __forceinline__ void cl_neighbours(const ClSpace &s, int4 me, int lan
             const int ny = cy + ay;
             if (ny < 0 || ny >= dy) continue;
             const uint64_t base = ((uint64_t)nx * dy + ny) * dz;     // the cells (nx, ny, z0..z1) are consecutive keys
-            const int64_t lo = cl_lower(s.keys, s.n, base + z0), hi = cl_lower(s.keys, s.n, base + z1 + 1);
+            const int64_t lo = key_lower_bound(s.keys, s.n, base + z0);
+            const int64_t hi = key_lower_bound(s.keys, s.n, base + z1 + 1);
             for (int64_t j0 = lo; j0 < hi; j0 += 64) {
                 const int64_t j2 = j0 + lane;
                 const bool active = j2 < hi;
@@ -290,45 +281,11 @@ __global__ __launch_bounds__(CL_THREADS) void k_cl_union(ClSpace s, const int32_
 __global__ __launch_bounds__(CL_THREADS) void k_cl_number(const int32_t *__restrict__ core_o,
                                                           const int32_t *__restrict__ parent, int64_t n,
                                                           int32_t *__restrict__ number, int32_t *info) {
-    __shared__ int32_t wsum[CL_WAVES];
-    __shared__ int32_t carry_s;
     if (info[0]) return;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (threadIdx.x == 0) carry_s = 0;
-    __syncthreads();
-    for (int64_t c0 = 0; c0 < n; c0 += 4 * CL_THREADS) {
-        const int64_t b = c0 + 4 * threadIdx.x;
-        int v[4], t = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            v[q] = (b + q < n) ? (core_o[b + q] && parent[b + q] == (int32_t)(b + q)) : 0;
-            t += v[q];
-        }
-        int x = t;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int y = __shfl_up(x, d);
-            if (lane >= d) x += y;
-        }
-        if (lane == 63) wsum[w] = x;
-        __syncthreads();
-        int off = carry_s, tot = 0;
-#pragma unroll
-        for (int i = 0; i < CL_WAVES; ++i) {
-            if (i < w) off += wsum[i];
-            tot += wsum[i];
-        }
-        int e = off + x - t;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (b + q < n) number[b + q] = e;
-            e += v[q];
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) carry_s += tot;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) info[1] = carry_s;
+    const int tot = block_scan_chunks<CL_THREADS, 4>(
+        n, [&](int64_t i) { return (int)(core_o[i] && parent[i] == (int32_t)i); },
+        [&](int64_t i, int e) { number[i] = e; });
+    if (threadIdx.x == 0) info[1] = tot;
 }
 
 __global__ __launch_bounds__(CL_THREADS) void k_cl_label(ClSpace s, const int32_t *__restrict__ info,
@@ -353,12 +310,10 @@ __global__ __launch_bounds__(CL_THREADS) void k_cl_label(ClSpace s, const int32_
     if (lane == 0) labels[me.w] = best == INT_MAX ? -1 : best;
 }
 
-static int64_t cl_align(int64_t bytes) { return (bytes + 255) / 256 * 256; }
-
 extern "C" int64_t lidog_dbscan_ws(int64_t n) {
     if (n <= 0) return 256;
-    return cl_align(4 * CL_GRID_INTS) + 8 * cl_align(4 * n) + cl_align(16 * n) +
-           cl_align(4 * lidog_radix_sort_hist_ints(n, CL_SORT_PASSES));
+    return lidog_align256(4 * CL_GRID_INTS) + 8 * lidog_align256(4 * n) + lidog_align256(16 * n) +
+           lidog_align256(4 * lidog_radix_sort_hist_ints(n, lidog_radix_passes(CL_MAX_KEY)));
 }
 
 extern "C" int lidog_dbscan(const int32_t *coords, int64_t n, float voxel_size, double eps, int32_t min_samples,
@@ -385,16 +340,16 @@ extern "C" int lidog_dbscan(const int32_t *coords, int64_t n, float voxel_size, 
     if (cell < 1) cell = 1;
 
     char *p = (char *)ws;
-    int32_t *grid = (int32_t *)p;     p += cl_align(4 * CL_GRID_INTS);
-    uint32_t *ka = (uint32_t *)p;     p += cl_align(4 * n);
-    uint32_t *kb = (uint32_t *)p;     p += cl_align(4 * n);
-    int32_t *va = (int32_t *)p;       p += cl_align(4 * n);
-    int32_t *vb = (int32_t *)p;       p += cl_align(4 * n);
-    int32_t *core_s = (int32_t *)p;   p += cl_align(4 * n);
-    int32_t *core_o = (int32_t *)p;   p += cl_align(4 * n);
-    int32_t *parent = (int32_t *)p;   p += cl_align(4 * n);
-    int32_t *number = (int32_t *)p;   p += cl_align(4 * n);
-    int4 *sorted = (int4 *)p;         p += cl_align(16 * n);
+    int32_t *grid = (int32_t *)p;     p += lidog_align256(4 * CL_GRID_INTS);
+    uint32_t *ka = (uint32_t *)p;     p += lidog_align256(4 * n);
+    uint32_t *kb = (uint32_t *)p;     p += lidog_align256(4 * n);
+    int32_t *va = (int32_t *)p;       p += lidog_align256(4 * n);
+    int32_t *vb = (int32_t *)p;       p += lidog_align256(4 * n);
+    int32_t *core_s = (int32_t *)p;   p += lidog_align256(4 * n);
+    int32_t *core_o = (int32_t *)p;   p += lidog_align256(4 * n);
+    int32_t *parent = (int32_t *)p;   p += lidog_align256(4 * n);
+    int32_t *number = (int32_t *)p;   p += lidog_align256(4 * n);
+    int4 *sorted = (int4 *)p;         p += lidog_align256(16 * n);
     int32_t *hist = (int32_t *)p;
 
     const unsigned blocks = (unsigned)cdiv64(n, CL_THREADS);
@@ -403,9 +358,11 @@ extern "C" int lidog_dbscan(const int32_t *coords, int64_t n, float voxel_size, 
     k_cl_grid<<<1, 64, 0, st>>>(grid, cell, info);
     k_cl_keys<<<blocks, CL_THREADS, 0, st>>>(coords, n, grid, cell, info, ka, va);
     LIDOG_LAUNCH_CHECK();
-    if (lidog_radix_sort_pairs(ka, va, kb, vb, n, CL_SORT_PASSES, hist, st)) return 1;
-    k_cl_gather<<<blocks, CL_THREADS, 0, st>>>(coords, va, n, sorted, parent);
-    ClSpace s = {ka, sorted, grid, n, cell, voxel_size, eps * eps};
+    const int passes = lidog_radix_passes(CL_MAX_KEY);
+    if (lidog_radix_sort_pairs(ka, va, kb, vb, n, passes, hist, st)) return 1;
+    // an odd count of passes leaves the sorted pairs in (kb, vb)
+    k_cl_gather<<<blocks, CL_THREADS, 0, st>>>(coords, (passes & 1) ? vb : va, n, sorted, parent);
+    ClSpace s = {(passes & 1) ? kb : ka, sorted, grid, n, cell, voxel_size, eps * eps};
     const unsigned wblocks = (unsigned)cdiv64(n, CL_WAVES);      // one wave per point
     k_cl_count<<<wblocks, CL_THREADS, 0, st>>>(s, min_samples, info, core_s, core_o);
     k_cl_hook<<<wblocks, CL_THREADS, 0, st>>>(s, info, core_s, parent);

@@ -47,12 +47,6 @@ static inline int lidog_require_one_relu_source(const char *who, const float *re
 int lidog_launch_sums_finish(const double *partial, int nb, int C, double *sums, double count, BnFinish fin,
                              hipStream_t st);
 
-// stable LSD radix sort of (key, val) pairs on `st` (sconv_os.hip): RS_BITS = 9 key bits per pass, result in (ka, va)
-// after an even number of passes, in (kb, vb) after an odd one; hist: lidog_radix_sort_hist_ints(n, passes) int32
-int64_t lidog_radix_sort_hist_ints(int64_t n, int passes);
-int lidog_radix_sort_pairs(uint32_t *ka, int32_t *va, uint32_t *kb, int32_t *vb, int64_t n, int passes, int32_t *hist,
-                           hipStream_t st);
-
 // 63-bit packed coordinate key: batch 12 bits, x/y/z 17 bits each (biased by 65536).
 #define LIDOG_EMPTY_KEY 0xFFFFFFFFFFFFFFFFull
 

@@ -6,6 +6,7 @@
 #include <stdarg.h>
 
 #include "common.h"
+#include "prims.h"
 
 static thread_local char g_err[512] = "";
 void lidog_set_error(const char *fmt, ...) {
@@ -24,92 +25,6 @@ extern "C" int64_t lidog_hash_capacity(int64_t n) {
     int64_t cap = 1024;
     while (cap < 2 * n) cap <<= 1;
     return cap;
-}
-
-// ------------------------------------------------------------------ block-level scans
-__device__ __forceinline__ int block_excl_scan_256(int v, int *total) {
-    __shared__ int wsum[4];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        int y = __shfl_up(x, d);
-        if (lane >= d) x += y;
-    }
-    __syncthreads();  // protect wsum reuse across calls
-    if (lane == 63) wsum[w] = x;
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if (i < w) off += wsum[i];
-        tot += wsum[i];
-    }
-    *total = tot;
-    return off + x - v;
-}
-
-// exclusive scan of int32 data[n] in place; sums[nb+1] scratch (nb = ceil(n/1024)); sums[nb] = total
-__global__ __launch_bounds__(256) void scan_block_sums(const int32_t *__restrict__ data, int64_t n,
-                                                       int32_t *__restrict__ sums) {
-    int64_t base = (int64_t)blockIdx.x * 1024 + threadIdx.x * 4;
-    int v = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (base + j < n) v += data[base + j];
-    int tot;
-    block_excl_scan_256(v, &tot);
-    if (threadIdx.x == 0) sums[blockIdx.x] = tot;
-}
-
-__global__ __launch_bounds__(256) void scan_block_offsets(int32_t *__restrict__ sums, int64_t nb) {
-    // single block; chunked with carry
-    __shared__ int carry_s;
-    if (threadIdx.x == 0) carry_s = 0;
-    __syncthreads();
-    for (int64_t c = 0; c < nb; c += 256) {
-        int64_t i = c + threadIdx.x;
-        int v = (i < nb) ? sums[i] : 0;
-        int tot;
-        int ex = block_excl_scan_256(v, &tot);
-        int carry = carry_s;
-        if (i < nb) sums[i] = carry + ex;
-        __syncthreads();
-        if (threadIdx.x == 0) carry_s = carry + tot;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) sums[nb] = carry_s;
-}
-
-__global__ __launch_bounds__(256) void scan_apply(int32_t *__restrict__ data, int64_t n,
-                                                  const int32_t *__restrict__ sums) {
-    int64_t base = (int64_t)blockIdx.x * 1024 + threadIdx.x * 4;
-    int v[4], s = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        v[j] = (base + j < n) ? data[base + j] : 0;
-        s += v[j];
-    }
-    int tot;
-    int ex = block_excl_scan_256(s, &tot) + sums[blockIdx.x];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        if (base + j < n) data[base + j] = ex;
-        ex += v[j];
-    }
-}
-
-// ints of `sums` the scan of n entries writes: one per 1024-entry block and the total behind them
-static int64_t scan_sums_ints(int64_t n) { return cdiv64(n, 1024) + 1; }
-
-static int device_exclusive_scan(int32_t *data, int64_t n, int32_t *sums, hipStream_t st) {
-    int64_t nb = cdiv64(n, 1024);
-    if (nb == 0) return 0;
-    scan_block_sums<<<dim3((unsigned)nb), 256, 0, st>>>(data, n, sums);
-    scan_block_offsets<<<1, 256, 0, st>>>(sums, nb);
-    scan_apply<<<dim3((unsigned)nb), 256, 0, st>>>(data, n, sums);
-    LIDOG_LAUNCH_CHECK();
-    return 0;
 }
 
 // ------------------------------------------------------------------ insert
@@ -292,12 +207,12 @@ __global__ __launch_bounds__(256) void k_compact_rows(const int32_t *__restrict_
 // more than n, which is one word short from n = 2 096 129 rows on: ceil(n / 1024) + 1 > 2048.)
 extern "C" int64_t lidog_coords_compact_ws(int64_t n) {
     if (n < 0) n = 0;
-    return n + scan_sums_ints(n);
+    return n + lidog_scan_sums_ints(n);
 }
 // int32 words of lidog_coords_stride's ws: slot_of [n_in] + rank [n_in] + the scan's block sums
 extern "C" int64_t lidog_coords_stride_ws(int64_t n_in) {
     if (n_in < 0) n_in = 0;
-    return 2 * n_in + scan_sums_ints(n_in);
+    return 2 * n_in + lidog_scan_sums_ints(n_in);
 }
 
 extern "C" int lidog_coords_compact(const int32_t *first_row, int64_t n, const uint64_t *keys, int32_t *vals,
@@ -308,7 +223,7 @@ extern "C" int lidog_coords_compact(const int32_t *first_row, int64_t n, const u
     unsigned nb = (unsigned)cdiv64(n, 256);
     int32_t *rank = scan_ws, *sums = scan_ws + n;
     k_flag_first<<<nb, 256, 0, st>>>(first_row, n, rank);
-    if (device_exclusive_scan(rank, n, sums, st)) return 1;
+    if (lidog_exclusive_scan(rank, n, sums, st)) return 1;
     // vals still hold first rows while every thread reads rank[first_row]; the rewrite of vals only
     // touches slots no other thread reads in this kernel
     k_compact_rows<<<nb, 256, 0, st>>>(first_row, n, rank, (const int4 *)coords, keys, vals, (uint64_t)(cap - 1),
@@ -378,7 +293,7 @@ extern "C" int lidog_coords_stride(const int32_t *coords_in, int64_t n_in, int32
     k_insert<<<nb, 256, 0, st>>>((const int4 *)coords_in, n_in, new_stride, keys, vals, (uint64_t)(cap - 1), slot_of,
                                  err_flag);
     k_stride_flag<<<nb, 256, 0, st>>>(slot_of, n_in, vals, rank);
-    if (device_exclusive_scan(rank, n_in, sums, st)) return 1;
+    if (lidog_exclusive_scan(rank, n_in, sums, st)) return 1;
     k_stride_emit<<<nb, 256, 0, st>>>((const int4 *)coords_in, n_in, new_stride, slot_of, vals, rank,
                                       (int4 *)coords_out, parent2child, n_out_dev);
     k_stride_rewrite<<<nb, 256, 0, st>>>(n_in, slot_of, vals, rank, parent2child);
@@ -613,21 +528,8 @@ __global__ __launch_bounds__(256) void k_pairs_count(const int32_t *__restrict__
 __global__ __launch_bounds__(256) void k_pairs_scan(int32_t *__restrict__ cnt, int nbp, int32_t *__restrict__ totals) {
     const int k = blockIdx.x;
     int32_t *c = cnt + (int64_t)k * nbp;
-    __shared__ int carry_s;
-    if (threadIdx.x == 0) carry_s = 0;
-    __syncthreads();
-    for (int b0 = 0; b0 < nbp; b0 += 256) {
-        const int b = b0 + threadIdx.x;
-        const int v = b < nbp ? c[b] : 0;
-        int tot;
-        const int ex = block_excl_scan_256(v, &tot);
-        const int carry = carry_s;
-        if (b < nbp) c[b] = carry + ex;
-        __syncthreads();
-        if (threadIdx.x == 0) carry_s = carry + tot;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) totals[k] = carry_s;
+    const int tot = block_scan_chunks<256, 1>(nbp, [&](int64_t b) { return c[b]; }, [&](int64_t b, int e) { c[b] = e; });
+    if (threadIdx.x == 0) totals[k] = tot;
 }
 
 __global__ __launch_bounds__(128) void k_pairs_koff(const int32_t *__restrict__ totals, int K, int64_t *__restrict__ k_off) {
@@ -676,7 +578,7 @@ __global__ __launch_bounds__(256) void k_pairs_emit(const int32_t *__restrict__ 
         if (o < n_out) {
             int32_t p = -1;
             if (nb_[j] >= 0) {
-                int rank = before + __popcll(masks[j] & ((1ull << lane) - 1ull));
+                int rank = before + wave_rank_below(masks[j]);
                 p = (int32_t)(base + rank);
                 pair_in[p] = nb_[j];
                 pair_out[p] = (int32_t)o;
@@ -744,7 +646,7 @@ extern "C" int lidog_kernel_map_rows(const int32_t *pos, int64_t n, int32_t K, i
     hipStream_t st = (hipStream_t)stream;
     LIDOG_REQUIRE(n >= 0 && K >= 1 && n < ((int64_t)1 << 31) - 2, "kernel_map_rows: bad sizes");
     k_rows_count<<<(unsigned)cdiv64(n + 1, 256), 256, 0, st>>>(pos, n, K, row_ptr);
-    if (device_exclusive_scan(row_ptr, n + 1, ws, st)) return 1;
+    if (lidog_exclusive_scan(row_ptr, n + 1, ws, st)) return 1;
     if (n) k_rows_fill<<<(unsigned)cdiv64(n, 256), 256, 0, st>>>(pos, n, K, mark_k, row_ptr, row_list);
     LIDOG_LAUNCH_CHECK();
     return 0;

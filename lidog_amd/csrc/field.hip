@@ -3,7 +3,7 @@
 // Contract: include/lidog_amd.h.
 //
 // Every result is a gather written with plain stores, in an order the contract names: no atomics, the same bits on
-// every call.  The lists a gradient walks come from ONE stable sort (lidog_radix_sort_pairs of sconv_os.hip, as
+// every call.  The lists a gradient walks come from ONE stable sort (lidog_group_by_key of prims.hip, as
 // lidog_in_segments uses it): entry j of an index table goes to the list of the row it names, ascending j inside a list.
 // For a field that table is the inverse map (point -> voxel); for the interpolation gradient it is the neighbour table
 // nbr [8][Q] itself, whose flat index j = k * Q + q ascends in k and then in q -- the order the contract gives the sum.
@@ -11,6 +11,7 @@
 // Row kernels follow pool.hip: thread idx = row idx / CG, column group idx % CG (float4 groups when C % 4 == 0), so the
 // lanes of a row read consecutive 16-byte pieces of one gathered row; loads go out in unconditional batches of 4.
 #include "common.h"
+#include "prims.h"
 
 namespace {
 
@@ -57,28 +58,6 @@ __global__ __launch_bounds__(256) void k_field_keys(const int32_t *__restrict__ 
     const int32_t v = inv[j];
     keys[j] = ((uint32_t)v < (uint32_t)m) ? (uint32_t)v : (uint32_t)m;   // names no row: behind every list
     vals[j] = (int32_t)j;
-}
-
-// row_ptr[v] = first sorted position whose key is >= v (v = 0 .. m): rows nobody names get empty lists
-__global__ __launch_bounds__(256) void k_field_row_ptr(const uint32_t *__restrict__ sorted, int64_t n, int64_t m,
-                                                       int32_t *__restrict__ row_ptr) {
-    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (v > m) return;
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (sorted[mid] < (uint32_t)v) lo = mid + 1;
-        else hi = mid;
-    }
-    row_ptr[v] = (int32_t)lo;
-}
-
-int64_t fl_align(int64_t bytes) { return (bytes + 255) / 256 * 256; }
-
-int fl_passes(int64_t m) {   // keys 0 .. m
-    int bits = 1;
-    while (((int64_t)1 << bits) <= m) ++bits;
-    return (bits + 8) / 9;   // 9 key bits per pass (RS_BITS of sconv_os.hip)
 }
 
 // ---------------------------------------------------------------- ordered segment sum / mean
@@ -280,7 +259,7 @@ extern "C" int lidog_field_floor(const float *points, int64_t n, int32_t stride,
 
 extern "C" int64_t lidog_field_lists_ws(int64_t n, int64_t m) {
     if (n <= 0 || m < 0) return 256;
-    return 3 * fl_align(4 * n) + fl_align(4 * lidog_radix_sort_hist_ints(n, fl_passes(m)));
+    return lidog_group_ws(n, lidog_radix_passes(m));
 }
 
 extern "C" int lidog_field_lists(const int32_t *inv, int64_t n, int64_t m, int32_t *row_ptr, int32_t *row_list, void *ws,
@@ -294,19 +273,12 @@ extern "C" int lidog_field_lists(const int32_t *inv, int64_t n, int64_t m, int32
     }
     LIDOG_REQUIRE(inv && row_list && ws, "field_lists: inv, row_list and the workspace are required");
     LIDOG_REQUIRE(ws_bytes >= lidog_field_lists_ws(n, m), "field_lists: workspace too small");
-    char *p = (char *)ws;
-    uint32_t *ka = (uint32_t *)p;  p += fl_align(4 * n);
-    uint32_t *kb = (uint32_t *)p;  p += fl_align(4 * n);
-    int32_t *tmp = (int32_t *)p;   p += fl_align(4 * n);
-    int32_t *hist = (int32_t *)p;
-    const int passes = fl_passes(m);
-    int32_t *va = (passes & 1) ? tmp : row_list, *vb = (passes & 1) ? row_list : tmp;   // the entries end in row_list
-    k_field_keys<<<(unsigned)cdiv64(n, 256), 256, 0, st>>>(inv, n, (int32_t)m, ka, va);
+    // row_ptr[v] = first sorted position whose key is >= v (v = 0 .. m): rows nobody names get empty lists
+    const int passes = lidog_radix_passes(m);   // keys 0 .. m
+    const LidogGroupBufs g = lidog_group_bufs(ws, n, passes, row_list);
+    k_field_keys<<<(unsigned)cdiv64(n, 256), 256, 0, st>>>(inv, n, (int32_t)m, g.ka, g.va);
     LIDOG_LAUNCH_CHECK();
-    if (lidog_radix_sort_pairs(ka, va, kb, vb, n, passes, hist, st)) return 1;
-    k_field_row_ptr<<<(unsigned)cdiv64(m + 1, 256), 256, 0, st>>>((passes & 1) ? kb : ka, n, m, row_ptr);
-    LIDOG_LAUNCH_CHECK();
-    return 0;
+    return lidog_group_by_key(g, n, passes, m, row_ptr, st);
 }
 
 extern "C" int lidog_field_reduce(const float *x, int64_t n_x, const int32_t *row_ptr, const int32_t *row_list,

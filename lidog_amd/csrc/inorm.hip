@@ -6,7 +6,7 @@
 //   mean[b, c] = sum_{rows of b} x / n_b,  var[b, c] = sum (x - mean)^2 / n_b (biased),
 //   y = (x - mean[b, c]) * (var + eps)^-1/2 * w[c] + bias[c].
 // The statistics are segmented sums keyed on the batch column of the coordinate map:
-//   segments   a stable ordering of the map's rows by batch id (the radix sort of sconv_os.hip) + seg_off[B + 1];
+//   segments   a stable ordering of the map's rows by batch id (lidog_group_by_key of prims.hip) + seg_off[B + 1];
 //              built once per coordinate map by the caller and kept with it
 //   reduce     per-(b, c) sums in double over each segment; workgroup w owns a contiguous range of SORTED rows and
 //              writes one partial row of 2 B C columns (zeros for the scans it does not touch); the two-level
@@ -21,11 +21,11 @@
 // public; no performance target there).
 #include "bn_math.h"
 #include "common.h"
+#include "prims.h"
 #include "stats_tail.h"
 
 #define IN_MAX_BLOCKS 256       // workgroups (= partial rows) of a segmented reduction
 #define IN_LDS_DOUBLES 4096     // LDS of a reduction workgroup: the row reduction, then the final per-(b, c) sums
-#define IN_RS_BITS 9            // key bits per radix pass (RS_BITS of sconv_os.hip)
 
 // the float4 path: C4 <= 256 lanes per row, and the final 2 B C sums of the backward reduction fit in LDS
 static bool in_vector_path(int C, int B) { return C % 4 == 0 && C / 4 <= 256 && 2 * (int64_t)B * C <= IN_LDS_DOUBLES; }
@@ -41,25 +41,10 @@ __global__ __launch_bounds__(256) void k_in_keys(const int32_t *__restrict__ coo
     rows[r] = (int32_t)r;
 }
 
-// seg_off[b] = first sorted position whose batch id is >= b (b = 0 .. B): empty scans get empty ranges
-__global__ __launch_bounds__(256) void k_in_seg_off(const uint32_t *__restrict__ sorted, int64_t n, int B,
-                                                    int32_t *__restrict__ seg_off) {
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b > B) return;
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (sorted[mid] < (uint32_t)b) lo = mid + 1;
-        else hi = mid;
-    }
-    seg_off[b] = (int32_t)lo;
-}
-
-static int64_t in_align(int64_t bytes) { return (bytes + 255) / 256 * 256; }
-
+// batch ids are below 4096: at most the passes of a 12-bit key, which size the workspace
 extern "C" int64_t lidog_in_segments_ws(int64_t n) {
     if (n <= 0) return 256;
-    return 3 * in_align(4 * n) + in_align(4 * lidog_radix_sort_hist_ints(n, 2));
+    return lidog_group_ws(n, lidog_radix_passes(4095));
 }
 
 extern "C" int lidog_in_segments(const int32_t *coords, int64_t n, int32_t B, int32_t *perm, int32_t *seg_off,
@@ -73,19 +58,11 @@ extern "C" int lidog_in_segments(const int32_t *coords, int64_t n, int32_t B, in
     }
     LIDOG_REQUIRE(coords && perm && bid && ws, "in_segments: coords, perm, bid and the workspace are required");
     LIDOG_REQUIRE(ws_bytes >= lidog_in_segments_ws(n), "in_segments: workspace too small");
-    char *p = (char *)ws;
-    uint32_t *ka = (uint32_t *)p;  p += in_align(4 * n);
-    uint32_t *kb = (uint32_t *)p;  p += in_align(4 * n);
-    int32_t *tmp = (int32_t *)p;   p += in_align(4 * n);
-    int32_t *hist = (int32_t *)p;
-    // batch ids < 4096 are 12 bits: two passes of 9; one when every id fits in the first digit
-    const int passes = B <= (1 << IN_RS_BITS) ? 1 : 2;
-    int32_t *va = (passes & 1) ? tmp : perm, *vb = (passes & 1) ? perm : tmp;   // the row ids end in perm
-    k_in_keys<<<(unsigned)cdiv64(n, 256), 256, 0, st>>>(coords, n, bid, ka, va);
-    if (lidog_radix_sort_pairs(ka, va, kb, vb, n, passes, hist, st)) return 1;
-    k_in_seg_off<<<(unsigned)cdiv64(B + 1, 256), 256, 0, st>>>((passes & 1) ? kb : ka, n, B, seg_off);
-    LIDOG_LAUNCH_CHECK();
-    return 0;
+    // seg_off[b] = first sorted position whose batch id is >= b (b = 0 .. B): empty scans get empty ranges
+    const int passes = lidog_radix_passes(B - 1);   // the ids of B scans
+    const LidogGroupBufs g = lidog_group_bufs(ws, n, passes, perm);
+    k_in_keys<<<(unsigned)cdiv64(n, 256), 256, 0, st>>>(coords, n, bid, g.ka, g.va);
+    return lidog_group_by_key(g, n, passes, B, seg_off, st);
 }
 
 // ------------------------------------------------------------------ segmented reductions

@@ -5,13 +5,11 @@
 // one gather.  The two quantisations reuse lidog_voxel_floor / lidog_coords_insert / lidog_coords_compact (data.py).
 // No position comes from an atomic: the result is the same on every run.
 #include "aug_ops.h"
+#include "prims.h"
 
 #define MIX_THREADS 256
-#define MIX_WAVES (MIX_THREADS / 64)
 #define MIX_HIST_BINS 4096      // LDS bins per pass of the histogram; more bins take more passes over the keys
-#define MIX_MAX_SLOTS 256
-#define MIX_SPLIT_ITERS 4       // rows per split block: MIX_THREADS * MIX_SPLIT_ITERS
-#define MIX_SPLIT_TILE (MIX_THREADS * MIX_SPLIT_ITERS)
+#define MIX_MAX_SLOTS LIDOG_SPLIT_MAX_SLOTS
 #define MIX_MAX_COLS 6
 
 // ------------------------------------------------------------------ histogram
@@ -49,153 +47,12 @@ extern "C" int lidog_mix_histogram(const int32_t *keys, int64_t n, int32_t nbins
 }
 
 // ------------------------------------------------------------------ stable multi-way split
-__device__ __forceinline__ int mix_slot(const int32_t *__restrict__ keys, int64_t i, int64_t n,
-                                        const int32_t *__restrict__ slot_of_key, int32_t n_keys, int32_t S) {
-    if (i >= n) return -1;
-    const int32_t k = keys[i];
-    if (k < 0 || k >= n_keys) return -1;
-    const int32_t s = slot_of_key[k];
-    return (s >= 0 && s < S) ? s : -1;
-}
-
-// taken rows per (slot, block): cnt[s * nblocks + b]
-__global__ __launch_bounds__(MIX_THREADS) void k_mix_split_count(const int32_t *__restrict__ keys, int64_t n,
-                                                                 const int32_t *__restrict__ slot_of_key,
-                                                                 int32_t n_keys, int32_t S, int64_t nblocks,
-                                                                 int32_t *__restrict__ cnt) {
-    __shared__ int32_t c[MIX_MAX_SLOTS];
-    for (int s = threadIdx.x; s < S; s += MIX_THREADS) c[s] = 0;
-    __syncthreads();
-    const int64_t base = (int64_t)blockIdx.x * MIX_SPLIT_TILE;
-#pragma unroll
-    for (int it = 0; it < MIX_SPLIT_ITERS; ++it) {
-        const int s = mix_slot(keys, base + it * MIX_THREADS + threadIdx.x, n, slot_of_key, n_keys, S);
-        if (s >= 0) atomicAdd(&c[s], 1);   // a count: the order of the adds does not matter
-    }
-    __syncthreads();
-    for (int s = threadIdx.x; s < S; s += MIX_THREADS) cnt[(int64_t)s * nblocks + blockIdx.x] = c[s];
-}
-
-// exclusive scan of cnt[len] in place (one block, chunks of 1024 with a carry); slot_start[s] = cnt[s * nblocks] after
-// the scan, slot_start[S] = the total
-__global__ __launch_bounds__(MIX_THREADS) void k_mix_split_scan(int32_t *cnt, int64_t len, int64_t nblocks, int32_t S,
-                                                                int32_t *__restrict__ slot_start) {
-    __shared__ int32_t wsum[MIX_WAVES];
-    __shared__ int32_t carry_s;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (threadIdx.x == 0) carry_s = 0;
-    __syncthreads();
-    for (int64_t c0 = 0; c0 < len; c0 += 4 * MIX_THREADS) {
-        const int64_t b = c0 + 4 * threadIdx.x;
-        int v[4], t = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            v[j] = (b + j < len) ? cnt[b + j] : 0;
-            t += v[j];
-        }
-        int x = t;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int y = __shfl_up(x, d);
-            if (lane >= d) x += y;
-        }
-        if (lane == 63) wsum[w] = x;
-        __syncthreads();
-        int off = carry_s, tot = 0;
-#pragma unroll
-        for (int i = 0; i < MIX_WAVES; ++i) {
-            if (i < w) off += wsum[i];
-            tot += wsum[i];
-        }
-        int e = off + x - t;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (b + j < len) cnt[b + j] = e;
-            e += v[j];
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) carry_s += tot;
-        __syncthreads();
-    }
-    for (int s = threadIdx.x; s < S; s += MIX_THREADS) slot_start[s] = cnt[(int64_t)s * nblocks];
-    if (threadIdx.x == 0) slot_start[S] = carry_s;
-}
-
-// position of a taken row = start of its (slot, block) + taken rows of its slot in earlier chunks of the block + in
-// earlier waves of the chunk + its rank among the lanes of its wave holding the same slot (ballot, popcount of the lower
-// lanes).  Each pass of the loop below resolves the lanes of one slot, so a wave runs (distinct slots in it) passes.
-__global__ __launch_bounds__(MIX_THREADS) void k_mix_split_scatter(const int32_t *__restrict__ keys, int64_t n,
-                                                                   const int32_t *__restrict__ slot_of_key,
-                                                                   int32_t n_keys, int32_t S, int64_t nblocks,
-                                                                   const int32_t *__restrict__ start,
-                                                                   int32_t *__restrict__ rows_out) {
-    __shared__ int32_t run[MIX_MAX_SLOTS];
-    __shared__ int32_t wcnt[MIX_WAVES][MIX_MAX_SLOTS];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const uint64_t lower = (1ull << lane) - 1ull;
-    for (int s = threadIdx.x; s < S; s += MIX_THREADS) {
-        run[s] = start[(int64_t)s * nblocks + blockIdx.x];
-#pragma unroll
-        for (int i = 0; i < MIX_WAVES; ++i) wcnt[i][s] = 0;
-    }
-    __syncthreads();
-    const int64_t base = (int64_t)blockIdx.x * MIX_SPLIT_TILE;
-    for (int it = 0; it < MIX_SPLIT_ITERS; ++it) {
-        const int64_t row = base + it * MIX_THREADS + threadIdx.x;
-        const int slot = mix_slot(keys, row, n, slot_of_key, n_keys, S);
-        int rank = 0;
-        uint64_t pending = __ballot(slot >= 0);
-        while (pending) {   // wave-uniform
-            const int leader = __builtin_ctzll(pending);
-            const int s = __shfl(slot, leader);
-            const uint64_t same = __ballot(slot == s);
-            if (slot == s) rank = __popcll(same & lower);
-            if (lane == leader) wcnt[w][s] = __popcll(same);
-            pending &= ~same;
-        }
-        __syncthreads();
-        if (slot >= 0) {
-            int pos = run[slot] + rank;
-            for (int i = 0; i < w; ++i) pos += wcnt[i][slot];
-            rows_out[pos] = (int32_t)row;
-        }
-        __syncthreads();
-        for (int s = threadIdx.x; s < S; s += MIX_THREADS) {
-            int add = 0;
-#pragma unroll
-            for (int i = 0; i < MIX_WAVES; ++i) {
-                add += wcnt[i][s];
-                wcnt[i][s] = 0;
-            }
-            run[s] += add;
-        }
-        __syncthreads();
-    }
-}
-
-extern "C" int64_t lidog_mix_split_ws(int64_t n, int32_t n_slots) {
-    return (int64_t)(n_slots > 0 ? n_slots : 0) * cdiv64(n > 0 ? n : 0, MIX_SPLIT_TILE) + 1;
-}
+// the kernels are the tree's shared split (prims.hip), which the ordered compactions of the other files use with one slot
+extern "C" int64_t lidog_mix_split_ws(int64_t n, int32_t n_slots) { return lidog_split_ws_ints(n, n_slots); }
 
 extern "C" int lidog_mix_split(const int32_t *keys, int64_t n, const int32_t *slot_of_key, int32_t n_keys,
                                int32_t n_slots, int32_t *rows_out, int32_t *slot_start, int32_t *ws, void *stream) {
-    hipStream_t st = (hipStream_t)stream;
-    LIDOG_REQUIRE(n >= 0 && n < (int64_t)INT32_MAX, "lidog_mix_split: n = %lld out of range", (long long)n);
-    LIDOG_REQUIRE(n_slots >= 0 && n_slots <= MIX_MAX_SLOTS, "lidog_mix_split: %d slots (at most %d)", n_slots,
-                  MIX_MAX_SLOTS);
-    LIDOG_REQUIRE(n_keys >= 0, "lidog_mix_split: n_keys = %d", n_keys);
-    const int64_t nblocks = cdiv64(n, MIX_SPLIT_TILE);
-    if (nblocks == 0 || n_slots == 0) {
-        LIDOG_CHECK_HIP(hipMemsetAsync(slot_start, 0, sizeof(int32_t) * (size_t)(n_slots + 1), st));
-        return 0;
-    }
-    LIDOG_REQUIRE(nblocks < (int64_t)UINT32_MAX, "lidog_mix_split: grid too large");
-    k_mix_split_count<<<(unsigned)nblocks, MIX_THREADS, 0, st>>>(keys, n, slot_of_key, n_keys, n_slots, nblocks, ws);
-    k_mix_split_scan<<<1, MIX_THREADS, 0, st>>>(ws, (int64_t)n_slots * nblocks, nblocks, n_slots, slot_start);
-    k_mix_split_scatter<<<(unsigned)nblocks, MIX_THREADS, 0, st>>>(keys, n, slot_of_key, n_keys, n_slots, nblocks,
-                                                                   ws, rows_out);
-    LIDOG_LAUNCH_CHECK();
-    return 0;
+    return lidog_split_rows(keys, n, slot_of_key, n_keys, n_slots, rows_out, slot_start, ws, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------ fused concatenating gather

@@ -1,13 +1,14 @@
 // One label per point of a scan file, in file order (what the SemanticKITTI and nuScenes-lidarseg benchmarks score):
 //   lidog_scan_keep_rows   the row every record of a file has in lidog_scan_load's compacted output, -1 for a record the
-//                          radius mask dropped: the same scan_in_radius, the same lidog_mix_split, the list inverted
+//                          radius mask dropped: the same scan_in_radius, the same lidog_compact_rows, the list inverted
 //   lidog_point_labels     a loader batch: the arg-max once per voxel row (ev_argmax, the voxel-level evaluator's rule),
 //                          then a walk over the file rows: keep_row -> inverse_map -> voxel prediction -> out_lut; with
 //                          the files' raw labels also the per-scan confusion counts over the kept, labelled points
 // Counts are integers in LDS bins, added with one 64-bit integer atomic per non-empty bin and block; positions come from
-// lidog_mix_split, never from an atomic: two runs give the same bytes.  Every value read from an input array is checked
-// before it is used as an index; what fails sets a bit of the error word and leaves the record at `fill`, uncounted.
+// lidog_compact_rows, never from an atomic: two runs give the same bytes.  Every value read from an input array is
+// checked before it is used as an index; what fails sets a bit of the error word and leaves the record at `fill`, uncounted.
 #include "common.h"
+#include "prims.h"
 #include "row_argmax.h"
 #include "scan_ops.h"
 
@@ -25,16 +26,15 @@
 #define PL_ERR_KEEP 8                       // a keep_row entry outside its scan's kept rows
 
 // ------------------------------------------------------------------ keep index of a file
-// keys[i] = 0 for a kept row, -1 otherwise; keep_row[i] = -1; table[0] = 0 (the one-slot table of lidog_mix_split)
+// keep[i] = 1 for a kept row, 0 otherwise (the flags of lidog_compact_rows); keep_row[i] = -1
 __global__ __launch_bounds__(PL_THREADS) void k_keep_flag(const float *__restrict__ pts, int32_t stride, int32_t vec4,
-                                                          int64_t n, float r2, int32_t *__restrict__ keys,
-                                                          int32_t *__restrict__ table, int32_t *__restrict__ keep_row) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) table[0] = 0;
+                                                          int64_t n, float r2, int32_t *__restrict__ keep,
+                                                          int32_t *__restrict__ keep_row) {
     const int64_t step = (int64_t)gridDim.x * PL_THREADS;
     for (int64_t i = (int64_t)blockIdx.x * PL_THREADS + threadIdx.x; i < n; i += step) {
         float x, y, z;
         scan_xyz(pts, stride, vec4 != 0, i, &x, &y, &z);
-        keys[i] = scan_in_radius(x, y, z, r2) ? 0 : -1;
+        keep[i] = scan_in_radius(x, y, z, r2) ? 1 : 0;
         keep_row[i] = -1;
     }
 }
@@ -53,8 +53,8 @@ __global__ __launch_bounds__(PL_THREADS) void k_keep_invert(const int32_t *__res
 }
 
 extern "C" int64_t lidog_scan_keep_rows_ws(int64_t n) {
-    const int64_t nn = n > 0 ? n : 0;   // keys [n], kept [n], table [1], slot_start [2], the split's own
-    return 2 * nn + 3 + lidog_mix_split_ws(nn, 1);
+    const int64_t nn = n > 0 ? n : 0;   // keep [n], kept [n], a spare word (ABI 9 fixes the size), the compaction's own
+    return 2 * nn + 1 + lidog_compact_ws_ints(nn);
 }
 
 extern "C" int lidog_scan_keep_rows(const float *points_raw, int32_t point_stride, int64_t n, int32_t use_radius,
@@ -72,12 +72,11 @@ extern "C" int lidog_scan_keep_rows(const float *points_raw, int32_t point_strid
     const int32_t *kept = nullptr, *count = nullptr;
     if (use_radius) {
         const int32_t vec4 = (point_stride == 4 && ((uintptr_t)points_raw & 15) == 0) ? 1 : 0;
-        int32_t *keys = ws, *kept_w = ws + n, *table = ws + 2 * n, *slot_start = table + 1, *split_ws = table + 3;
-        k_keep_flag<<<grid, PL_THREADS, 0, st>>>(points_raw, point_stride, vec4, n, radius_sq, keys, table, keep_row);
+        int32_t *keep = ws, *kept_w = ws + n, *compact_ws = ws + 2 * n + 1;
+        k_keep_flag<<<grid, PL_THREADS, 0, st>>>(points_raw, point_stride, vec4, n, radius_sq, keep, keep_row);
         LIDOG_LAUNCH_CHECK();
-        if (lidog_mix_split(keys, n, table, 1, 1, kept_w, slot_start, split_ws, stream)) return 1;
+        if (lidog_compact_rows(keep, n, kept_w, compact_ws, &count, st)) return 1;
         kept = kept_w;
-        count = slot_start + 1;
     }
     k_keep_invert<<<grid, PL_THREADS, 0, st>>>(kept, count, n, keep_row, info);
     LIDOG_LAUNCH_CHECK();

@@ -4,19 +4,20 @@
 //
 // The winner of a cell is one 64-bit integer atomicMin on (bits(r2) << 32) | row: r2 > 0, so its float32 bits order as
 // the values do, and equal r2 falls to the smallest row.  An integer minimum does not depend on the order of arrival,
-// and the kept cells take their positions from lidog_mix_split (mix.hip), never from an atomic: the same bytes on every
-// run.  Angles are float64 atan2 of the float32 differences; the positions of snapped points use the host's float64
+// and the kept cells take their positions from lidog_compact_rows (prims.hip), never from an atomic: the same bytes on
+// every run.  Angles are float64 atan2 of the float32 differences; the positions of snapped points use the host's float64
 // tables only (multiplies and a square root, IEEE on both sides).
 #include "common.h"
+#include "prims.h"
 
 #define RC_THREADS 256
 #define RC_MAX_BLOCKS 2048
 #define RC_EMPTY 0xFFFFFFFFFFFFFFFFull
 #define RC_TWO_PI 6.283185307179586
 
-// int32 words in front of the split's own workspace: table [n_cells] uint64, keys [n_cells], kept [n_cells],
-// slot table [1] + pad [1], slot_start [2]
-static inline int64_t rc_ws_head(int64_t n_cells) { return 4 * n_cells + 4; }
+// int32 words in front of the compaction's own workspace: table [n_cells] uint64, occupied [n_cells], kept [n_cells],
+// two spare words (ABI version 9 fixes the size)
+static inline int64_t rc_ws_head(int64_t n_cells) { return 4 * n_cells + 2; }
 
 __global__ __launch_bounds__(RC_THREADS) void k_rc_fill(unsigned long long *__restrict__ table, int64_t n_cells) {
     const int64_t step = (int64_t)gridDim.x * RC_THREADS;
@@ -64,13 +65,12 @@ __global__ __launch_bounds__(RC_THREADS) void k_rc_splat(const float *__restrict
     }
 }
 
-// keys[c] = 0 for an occupied cell, -1 otherwise; slot[0] = 0: the one-slot table of lidog_mix_split
+// occupied[c] = 1 for a cell with a winner, 0 otherwise: the flags of lidog_compact_rows
 __global__ __launch_bounds__(RC_THREADS) void k_rc_flag(const unsigned long long *__restrict__ table, int64_t n_cells,
-                                                        int32_t *__restrict__ keys, int32_t *__restrict__ slot) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) slot[0] = 0;
+                                                        int32_t *__restrict__ occupied) {
     const int64_t step = (int64_t)gridDim.x * RC_THREADS;
     for (int64_t c = (int64_t)blockIdx.x * RC_THREADS + threadIdx.x; c < n_cells; c += step)
-        keys[c] = table[c] != RC_EMPTY ? 0 : -1;
+        occupied[c] = table[c] != RC_EMPTY ? 1 : 0;
 }
 
 // output row r: the winner of cell kept[r], r < *count
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(RC_THREADS) void k_rc_emit(const float *__restrict_
 extern "C" int64_t lidog_raycast_ws(int64_t n, int64_t n_cells) {
     (void)n;
     const int64_t c = n_cells > 0 ? n_cells : 0;
-    return rc_ws_head(c) + lidog_mix_split_ws(c, 1);
+    return rc_ws_head(c) + lidog_compact_ws_ints(c);
 }
 
 extern "C" int lidog_raycast(const float *points, int64_t n, const float *origin, const double *edges, int32_t n_beams,
@@ -139,21 +139,21 @@ extern "C" int lidog_raycast(const float *points, int64_t n, const float *origin
     LIDOG_REQUIRE(!snap || (cos_el && sin_el && cos_az && sin_az), "lidog_raycast: snap without the four tables");
     LIDOG_REQUIRE(((uintptr_t)ws & 7) == 0, "lidog_raycast: the workspace must be 8-byte aligned");
     unsigned long long *table = (unsigned long long *)ws;
-    int32_t *keys = ws + 2 * n_cells, *kept = ws + 3 * n_cells, *slot = ws + 4 * n_cells, *slot_start = slot + 2,
-            *split_ws = ws + rc_ws_head(n_cells);
+    int32_t *occupied = ws + 2 * n_cells, *kept = ws + 3 * n_cells, *compact_ws = ws + rc_ws_head(n_cells);
+    const int32_t *count = nullptr;
     const int64_t cb = cdiv64(n_cells, RC_THREADS), pb = cdiv64(n, RC_THREADS);
     const unsigned cgrid = (unsigned)(cb < RC_MAX_BLOCKS ? cb : RC_MAX_BLOCKS);
     const unsigned pgrid = (unsigned)(pb < RC_MAX_BLOCKS ? pb : RC_MAX_BLOCKS);
     k_rc_fill<<<cgrid, RC_THREADS, 0, st>>>(table, n_cells);
     k_rc_splat<<<pgrid, RC_THREADS, 0, st>>>(points, n, origin, edges, n_beams, n_az, az0, min2, use_max, max2, cell_out,
                                              table);
-    k_rc_flag<<<cgrid, RC_THREADS, 0, st>>>(table, n_cells, keys, slot);
+    k_rc_flag<<<cgrid, RC_THREADS, 0, st>>>(table, n_cells, occupied);
     LIDOG_LAUNCH_CHECK();
-    if (lidog_mix_split(keys, n_cells, slot, 1, 1, kept, slot_start, split_ws, stream)) return 1;
+    if (lidog_compact_rows(occupied, n_cells, kept, compact_ws, &count, st)) return 1;
     const int64_t most = n < n_cells ? n : n_cells;
     const int64_t eb = cdiv64(most, RC_THREADS);
     k_rc_emit<<<(unsigned)(eb < RC_MAX_BLOCKS ? eb : RC_MAX_BLOCKS), RC_THREADS, 0, st>>>(
-        points, n, origin, table, kept, slot_start + 1, n_cells, n_az, snap, cos_el, sin_el, cos_az, sin_az, points_out,
+        points, n, origin, table, kept, count, n_cells, n_az, snap, cos_el, sin_el, cos_az, sin_az, points_out,
         rows_out, m_dev);
     LIDOG_LAUNCH_CHECK();
     return 0;

@@ -2,31 +2,30 @@
 // 238-266, synth4d.py:106-137,203-220), which the reference runs with numpy in DataLoader workers: unpack the point
 // records, mask the raw labels and map them through the learning-map LUT, apply the radius mask, compact the kept rows
 // in order, and count the per-class label statistics.  The host uploads the files' bytes unmodified.  The kept rows take
-// their positions from lidog_mix_split (mix.hip: per-block counts, one scan, in-wave ballot ranks), never from an
+// their positions from lidog_compact_rows (prims.hip: per-block counts, one scan, in-wave ballot ranks), never from an
 // atomic; the statistics are integer counts (LDS bins, one global integer add per non-empty bin and block): the same
 // bytes on every run.
 #include "common.h"
+#include "prims.h"
 #include "scan_ops.h"
 
 #define SCAN_THREADS 256
 #define SCAN_MAX_BLOCKS 1024
 #define SCAN_MAX_CLASSES 256
 
-// mapped[i] = the mapped label of row i; keys[i] = 0 for a kept row, -1 otherwise (use_radius; table[0] = 0: the
-// one-slot table of lidog_mix_split); counts[c] += rows of the file with mapped label c; info[1] += label errors
+// mapped[i] = the mapped label of row i; keep[i] = 1 for a kept row, 0 otherwise (use_radius: the flags of
+// lidog_compact_rows); counts[c] += rows of the file with mapped label c; info[1] += label errors
 __global__ __launch_bounds__(SCAN_THREADS) void k_scan_flag(const float *__restrict__ pts, int32_t stride, int32_t vec4,
                                                             const void *__restrict__ labels_raw, int32_t kind,
                                                             int32_t mask, int64_t n, const int32_t *__restrict__ lut,
                                                             int32_t L, int32_t use_radius, float r2,
-                                                            int32_t *__restrict__ mapped, int32_t *__restrict__ keys,
-                                                            int32_t *__restrict__ table,
+                                                            int32_t *__restrict__ mapped, int32_t *__restrict__ keep,
                                                             unsigned long long *__restrict__ counts, int32_t C,
                                                             int32_t *info) {
     __shared__ int32_t bins[SCAN_MAX_CLASSES];
     __shared__ int32_t s_bad;
     for (int c = threadIdx.x; c < C; c += SCAN_THREADS) bins[c] = 0;
     if (threadIdx.x == 0) s_bad = 0;
-    if (table && blockIdx.x == 0 && threadIdx.x == 0) table[0] = 0;
     __syncthreads();
     const int64_t step = (int64_t)gridDim.x * SCAN_THREADS;
     for (int64_t i = (int64_t)blockIdx.x * SCAN_THREADS + threadIdx.x; i < n; i += step) {
@@ -35,10 +34,10 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan_flag(const float *__restr
         if (bad) atomicAdd(&s_bad, 1);                       // a count
         if (counts && !bad && l >= 0 && l < C) atomicAdd(&bins[l], 1);
         if (mapped) mapped[i] = l;
-        if (keys) {
+        if (keep) {
             float x, y, z;
             scan_xyz(pts, stride, vec4 != 0, i, &x, &y, &z);
-            keys[i] = scan_in_radius(x, y, z, r2) ? 0 : -1;
+            keep[i] = scan_in_radius(x, y, z, r2) ? 1 : 0;
         }
     }
     __syncthreads();
@@ -74,8 +73,8 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan_emit(const float *__restr
 }
 
 extern "C" int64_t lidog_scan_load_ws(int64_t n) {
-    const int64_t nn = n > 0 ? n : 0;   // mapped [n], keys [n], kept [n], table [1], slot_start [2], the split's own
-    return 3 * nn + 3 + lidog_mix_split_ws(nn, 1);
+    const int64_t nn = n > 0 ? n : 0;   // mapped, keep, kept [n], a spare word (ABI 9 fixes the size), the compaction's
+    return 3 * nn + 1 + lidog_compact_ws_ints(nn);
 }
 
 extern "C" int lidog_scan_load(const float *points_raw, int32_t point_stride, const void *labels_raw, int32_t label_kind,
@@ -103,23 +102,21 @@ extern "C" int lidog_scan_load(const float *points_raw, int32_t point_stride, co
     if (!points_raw) {                  // the labels alone: get_dataset_stats
         if (!counts && label_kind == SCAN_LABELS_NONE) return 0;
         k_scan_flag<<<grid, SCAN_THREADS, 0, st>>>(nullptr, 0, 0, labels_raw, label_kind, label_mask, n, lut, lut_len,
-                                                   0, 0.0f, nullptr, nullptr, nullptr, (unsigned long long *)counts,
+                                                   0, 0.0f, nullptr, nullptr, (unsigned long long *)counts,
                                                    counts ? num_classes : 0, info);
         LIDOG_LAUNCH_CHECK();
         return 0;
     }
-    int32_t *mapped = ws, *keys = ws + n, *kept_w = ws + 2 * n, *table = ws + 3 * n, *slot_start = table + 1,
-            *split_ws = table + 3;
+    int32_t *mapped = ws, *keep = ws + n, *kept_w = ws + 2 * n, *compact_ws = ws + 3 * n + 1;
     k_scan_flag<<<grid, SCAN_THREADS, 0, st>>>(points_raw, point_stride, vec4, labels_raw, label_kind, label_mask, n,
                                                lut, lut_len, use_radius, radius_sq, mapped,
-                                               use_radius ? keys : nullptr, use_radius ? table : nullptr,
+                                               use_radius ? keep : nullptr,
                                                (unsigned long long *)counts, counts ? num_classes : 0, info);
     LIDOG_LAUNCH_CHECK();
     const int32_t *kept = nullptr, *count = nullptr;
     if (use_radius) {
-        if (lidog_mix_split(keys, n, table, 1, 1, kept_w, slot_start, split_ws, stream)) return 1;
+        if (lidog_compact_rows(keep, n, kept_w, compact_ws, &count, st)) return 1;
         kept = kept_w;
-        count = slot_start + 1;
     }
     k_scan_emit<<<grid, SCAN_THREADS, 0, st>>>(points_raw, point_stride, vec4, n, mapped, kept, count, points_out,
                                                labels_out, info);

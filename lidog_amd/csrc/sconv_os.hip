@@ -24,6 +24,7 @@
 
 #include "common.h"
 #include "clock_stamp.h"
+#include "prims.h"
 #include "sconv_mfma.h"
 #include "stats_tail.h"
 
@@ -77,113 +78,11 @@ __global__ __launch_bounds__(256) void k_os_wave_masks(const uint32_t *__restric
     if (i < n_pad && (threadIdx.x & 31) == 0) wave_masks[i >> 5] = m;
 }
 
-// ---- stable LSD radix sort of (key, row) pairs, hand-written for wave64: RS_BITS bits per pass.  A workgroup is ONE
-// wavefront that owns RS_CHUNK consecutive elements: (1) per-chunk digit histogram (+ per-digit totals), (2) exclusive scan
-// of the digit-major [RS_BINS][chunks] table, one wavefront per digit, (3) scatter -- the chunk is walked 64 elements at a time in
-// order; the lanes holding the same digit find each other with RS_BITS ballots, rank = popcount of the lower peers, the
-// lowest peer advances the digit's cursor: equal keys keep their input order (what the numpy restatement in
-// tests/maps_ref.py calls a stable argsort).  Replaces the CUB-compatibility wrapper the file used in round 4
-// (~10 launches of rocPRIM's merge-sort fallback per sort; here 3 per pass).
-#define RS_BITS 9
-#define RS_BINS (1 << RS_BITS)
-#define RS_CHUNK 1024
 #define OS_TILE_ORDER_LDS 16384
-
-// hist [RS_BINS][chunks] (digit-major) + totals [RS_BINS] (zeroed by the caller; integer atomics: order-independent)
-__global__ __launch_bounds__(64) void k_rs_hist(const uint32_t *__restrict__ keys, int64_t n, int shift, int chunks,
-                                                int32_t *__restrict__ hist, int32_t *__restrict__ totals) {
-    __shared__ int32_t cnt[RS_BINS];
-    const int lane = threadIdx.x;
-    for (int i = lane; i < RS_BINS; i += 64) cnt[i] = 0;
-    __syncthreads();
-    const int64_t lo = (int64_t)blockIdx.x * RS_CHUNK, hi = lo + RS_CHUNK < n ? lo + RS_CHUNK : n;
-    uint32_t kreg[RS_CHUNK / 64];      // every load of the chunk in flight before the first use
-#pragma unroll
-    for (int r = 0; r < RS_CHUNK / 64; ++r) {
-        const int64_t i = lo + 64 * r + lane;
-        kreg[r] = keys[i < hi ? i : hi - 1];
-    }
-#pragma unroll
-    for (int r = 0; r < RS_CHUNK / 64; ++r)
-        if (lo + 64 * r + lane < hi) atomicAdd(&cnt[(kreg[r] >> shift) & (RS_BINS - 1)], 1);
-    __syncthreads();
-    for (int i = lane; i < RS_BINS; i += 64) {
-        const int32_t c = cnt[i];
-        hist[(int64_t)i * chunks + blockIdx.x] = c;
-        if (c) atomicAdd(&totals[i], c);
-    }
-}
-
-// one wavefront per digit d: hist[d][*] becomes the exclusive scan of the digit's chunk counts, offset by the number of
-// keys with a smaller digit (the sum of totals[0 .. d)) -- the global position of the first key of (digit, chunk)
-__global__ __launch_bounds__(64) void k_rs_scan(int32_t *__restrict__ hist, const int32_t *__restrict__ totals, int chunks) {
-    const int d = blockIdx.x, lane = threadIdx.x;
-    int32_t before = 0;
-    for (int i = lane; i < d; i += 64) before += totals[i];
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) before += __shfl_xor(before, s);
-    int32_t *row = hist + (int64_t)d * chunks;
-    int32_t run = before;
-    for (int c0 = 0; c0 < chunks; c0 += 64) {
-        const int c = c0 + lane;
-        const int32_t v = c < chunks ? row[c] : 0;
-        int32_t inc = v;
-#pragma unroll
-        for (int s = 1; s < 64; s <<= 1) {
-            const int32_t o = __shfl_up(inc, s);
-            if (lane >= s) inc += o;
-        }
-        if (c < chunks) row[c] = run + inc - v;
-        run += __shfl(inc, 63);
-    }
-}
-
-__global__ __launch_bounds__(64) void k_rs_scatter(const uint32_t *__restrict__ keys, const int32_t *__restrict__ vals,
-                                                   int64_t n, int shift, int chunks, const int32_t *__restrict__ hist,
-                                                   uint32_t *__restrict__ keys_out, int32_t *__restrict__ vals_out) {
-    __shared__ int32_t cur[RS_BINS];
-    const int lane = threadIdx.x;
-    for (int i = lane; i < RS_BINS; i += 64) cur[i] = hist[(int64_t)i * chunks + blockIdx.x];
-    __syncthreads();
-    const int64_t lo = (int64_t)blockIdx.x * RS_CHUNK, hi = lo + RS_CHUNK < n ? lo + RS_CHUNK : n;
-    const uint64_t below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-    uint32_t kreg[RS_CHUNK / 64];
-    int32_t vreg[RS_CHUNK / 64];
-#pragma unroll
-    for (int r = 0; r < RS_CHUNK / 64; ++r) {
-        const int64_t i = lo + 64 * r + lane;
-        kreg[r] = keys[i < hi ? i : hi - 1];
-        vreg[r] = vals[i < hi ? i : hi - 1];
-    }
-#pragma unroll
-    for (int r = 0; r < RS_CHUNK / 64; ++r) {
-        const int64_t i = lo + 64 * r + lane;
-        const bool live = i < hi;
-        const uint32_t key = kreg[r];
-        const int32_t val = vreg[r];
-        const uint32_t d = (key >> shift) & (RS_BINS - 1);
-        uint64_t peers = __ballot(live);
-#pragma unroll
-        for (int b = 0; b < RS_BITS; ++b) {
-            const bool bit = (d >> b) & 1u;
-            const uint64_t bal = __ballot(bit);
-            peers &= bit ? bal : ~bal;
-        }
-        const int rank = __popcll(peers & below);
-        const int32_t at = cur[d];
-        __syncthreads();   // every lane has read its cursor before the leaders move them (one wave: costs nothing)
-        if (live && rank == 0) cur[d] = at + __popcll(peers);
-        __syncthreads();
-        if (live) {
-            keys_out[at + rank] = key;
-            vals_out[at + rank] = val;
-        }
-    }
-}
 
 // launch order of the tiles: the ones with the most (wave, offset) blocks to multiply first, so that the grid ends on its
 // shortest workgroups (a tile walks 5 to 27 offsets).  key = 127 - blocks, ascending, ties by tile id: a counting sort by
-// ONE wavefront (a few thousand tiles; the same ballot ranking as k_rs_scatter).
+// ONE wavefront (a few thousand tiles; the same ballot ranking as k_rs_scatter of prims.hip).
 __global__ __launch_bounds__(64) void k_os_tile_order(const uint32_t *__restrict__ wave_masks, int n_tiles,
                                                       int32_t *__restrict__ tile_order) {
     __shared__ int32_t cur[128];
@@ -213,19 +112,12 @@ __global__ __launch_bounds__(64) void k_os_tile_order(const uint32_t *__restrict
         }
     }
     __syncthreads();
-    const uint64_t below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
     for (int t0 = 0; t0 < n_tiles; t0 += 64) {
         const int t = t0 + lane;
         const bool live = t < n_tiles;
         const int d = live ? key_of(t) : 0;
-        uint64_t peers = __ballot(live);
-#pragma unroll
-        for (int b = 0; b < 7; ++b) {
-            const bool bit = (d >> b) & 1;
-            const uint64_t bal = __ballot(bit);
-            peers &= bit ? bal : ~bal;
-        }
-        const int rank = __popcll(peers & below);
+        const uint64_t peers = wave_digit_peers<7>((uint32_t)d, live);
+        const int rank = wave_rank_below(peers);
         const int at = cur[d];
         __syncthreads();
         if (live && rank == 0) cur[d] = at + __popcll(peers);
@@ -236,34 +128,10 @@ __global__ __launch_bounds__(64) void k_os_tile_order(const uint32_t *__restrict
 
 static int64_t os_pad(int64_t n) { return (n + OS_TM - 1) / OS_TM * OS_TM; }
 
-static int64_t rs_chunks(int64_t n) { return cdiv64(n, RS_CHUNK); }
-
-// Stable LSD radix sort of n (key, val) pairs by the low passes * RS_BITS bits of the keys (declared in common.h): the
-// pairs ping-pong between (ka, va) and (kb, vb), so they end in (ka, va) after an even number of passes and in (kb, vb)
-// after an odd one.  hist: lidog_radix_sort_hist_ints(n, passes) int32.
-int64_t lidog_radix_sort_hist_ints(int64_t n, int passes) { return (int64_t)RS_BINS * (rs_chunks(n) + passes); }
-
-int lidog_radix_sort_pairs(uint32_t *ka, int32_t *va, uint32_t *kb, int32_t *vb, int64_t n, int passes, int32_t *hist,
-                           hipStream_t st) {
-    const int chunks = (int)rs_chunks(n);
-    int32_t *totals = hist + (int64_t)RS_BINS * chunks;      // [passes][RS_BINS], one row per pass (zeroed once)
-    LIDOG_CHECK_HIP(hipMemsetAsync(totals, 0, sizeof(int32_t) * RS_BINS * passes, st));
-    for (int pass = 0; pass < passes; ++pass) {
-        const int shift = pass * RS_BITS;
-        int32_t *tot = totals + pass * RS_BINS;
-        k_rs_hist<<<chunks, 64, 0, st>>>(ka, n, shift, chunks, hist, tot);
-        k_rs_scan<<<RS_BINS, 64, 0, st>>>(hist, tot, chunks);
-        k_rs_scatter<<<chunks, 64, 0, st>>>(ka, va, n, shift, chunks, hist, kb, vb);
-        uint32_t *tk = ka; ka = kb; kb = tk;
-        int32_t *tv = va; va = vb; vb = tv;
-    }
-    return 0;
-}
-
 // bytes of workspace lidog_kernel_map_sorted needs for a map of n rows
 extern "C" int64_t lidog_kernel_map_sorted_ws(int64_t n) {
     if (n <= 0) return 256;
-    return 256 + 4 * 4 * n + 4 * RS_BINS * (rs_chunks(n) + 4) + 4096;
+    return 256 + 4 * 4 * n + 4 * lidog_radix_sort_hist_ints(n, 4) + 4096;   // room for four passes; K <= 27 takes three
 }
 
 // perm [pad128(n)] int32: the rows in sorted order (-1 behind the last one); wave_masks [pad128(n) / 32] uint32: the OR
@@ -285,7 +153,7 @@ extern "C" int lidog_kernel_map_sorted(const int32_t *nbr, int64_t n, int32_t K,
     int32_t *rows = (int32_t *)p;                 p += 4 * n;
     uint32_t *masks = (uint32_t *)p;              p += 4 * n;
     int32_t *hist = (int32_t *)p;
-    const int passes = (K + RS_BITS - 1) / RS_BITS;
+    const int passes = lidog_radix_passes(((int64_t)1 << K) - 1);   // the key has one bit per offset
     // the pairs ping-pong between (keys, a) and (keys_out, b); the row ids start where an odd / even number of passes
     // leaves them in `perm`
     int32_t *va = (passes & 1) ? rows : perm, *vb = (passes & 1) ? perm : rows;

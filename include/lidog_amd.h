@@ -1079,6 +1079,20 @@ int lidog_raycast(const float *points, int64_t n, const float *origin, const dou
                   const double *cos_el, const double *sin_el, const double *cos_az, const double *sin_az,
                   int32_t *cell_out, float *points_out, int32_t *rows_out, int32_t *m_dev, int32_t *ws, void *stream);
 
+/* ---- test-time augmentation at the point level (tta.hip): the scores of one view of a loader batch,
+ * gathered per kept point and accumulated.  logits [m, n_classes] float32 (n_classes 1..32, lidog_point_labels' range):
+ * the view's voxel rows; inverse [k] int64: the voxel row of every kept point; acc [k, n_classes] float32.
+ * With r = inverse[p] and s = the softmax of logits[r] (mode 0: the row maximum subtracted in fp32, expf, the sum in
+ * class order, one division per class), logits[r] itself (mode 1) or the one-hot of its arg-max (mode 2: the first
+ * maximal index, the first NaN in a row holding one, lidog_eval_confusion's rule):
+ *   acc[p] = s (first != 0)   or   acc[p] = acc[p] + s (first == 0), one unfused fp32 addition per element.
+ * One thread owns a row of acc and there are no atomics on it: the same bytes on every run.  A NaN or +inf logit makes
+ * row p NaN in mode 0, as torch.softmax; no other row sees it.  An entry of inverse outside [0, m) sets bit 0 of err [1]
+ * int32 (device, never cleared here); that row of acc is neither read nor written, and no address is formed from the
+ * entry.  k == 0 launches nothing.  No allocation, synchronisation or copy inside. */
+int lidog_tta_vote(const float *logits, int64_t m, int32_t n_classes, const int64_t *inverse, int64_t k, int32_t mode,
+                   int32_t first, float *acc, int32_t *err, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -195,6 +195,7 @@ SIGNATURES = {
     "lidog_interp_bwd": [_p, _p, _i64, _p, _p, _i64, _i32, _i32, _p, _p],
     "lidog_raycast_ws": [_i64, _i64],
     "lidog_raycast": [_p, _i64, _p, _p, _i32, _i32, _d, _f, _i32, _f, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
+    "lidog_tta_vote": [_p, _i64, _i32, _p, _i64, _i32, _i32, _p, _p, _p],
 }
 _RESTYPES = {"lidog_hash_capacity": _i64, "lidog_coords_compact_ws": _i64, "lidog_coords_stride_ws": _i64,
              "lidog_sconv_reduce_stats_ws": _i64, "lidog_bn_reduce_ws": _i64,

@@ -24,6 +24,9 @@ of every scan file gets the class of its voxel (lidog_amd.evaluate.point_labels)
 record in file order, for SemanticKITTI as `predictions/<target>/sequences/SS/predictions/NNNNNN.label`.
 --point-interp trilinear: a point takes the class of the logits interpolated at its own position between the voxels
 (lidog_amd.evaluate.point_logits over csrc/field.hip) instead of its voxel's; the default, nearest, changes nothing.
+--tta NAME [NAME ...]: test-time augmentation (lidog_amd.tta): every batch also runs over the named views and a point
+takes the arg-max of the scores accumulated over its views (--tta-mode prob / logit / vote, csrc/tta.hip); the point
+table goes to `<sources>-TO-<targets>-points-tta.csv`, the voxel-level outputs stay those of the unchanged scan.
 """
 import argparse
 import json
@@ -36,7 +39,7 @@ from . import synth
 from .checkpoint import load_lightning_checkpoint
 from .evaluate import (CLASS_NAMES, PointLabelWriter, PointPath, TargetEvaluator, dataset_batches, inverse_lut,
                        load_inverse_label_map, palette, write_ply, write_results_csv)
-from . import scans
+from . import scans, tta
 from .train import SynthScans, bev_image_size, build_model, source_names
 
 MODELS = ("MinkUNet34BEV", "MinkUNet34", "MinkUNet34IBN", "MinkUNet34Robust")
@@ -72,6 +75,15 @@ def parse_args(argv=None):
     ap.add_argument("--point-interp", default="nearest", choices=["nearest", "trilinear"],
                     help="with --point-level / --save-labels: a point takes its voxel's class (nearest) or the class of the "
                          "logits interpolated trilinearly at its own position (missing neighbours add nothing)")
+    ap.add_argument("--tta", nargs="+", default=None, metavar="NAME",
+                    help="with --point-level / --save-labels: test-time augmentation.  Every batch also runs over these "
+                         "views and a point takes the class its views agree on.  A view is a '+'-joined list of "
+                         "rotz<deg>, flipx, flipy, scale<f>; presets rot4 (rotz90 rotz180 rotz270) and flip4 (flipx "
+                         "flipy flipx+flipy); the unchanged scan is always view 0.  The point table then goes to "
+                         "<sources>-TO-<targets>-points-tta.csv")
+    ap.add_argument("--tta-mode", default=None, choices=list(tta.MODES),
+                    help="with --tta: what the views add up per point: softmax probabilities (prob, the default), logits "
+                         "or one vote per view for its arg-max")
     ap.add_argument("--inverse-label-map", nargs="+", default=None, metavar="FILE",
                     help="one per target: a .yaml / .json file with a learning_map_inv (common class -> id to write; "
                          "entry -1: the id of records beyond the radius, default 0).  Default: the class itself")
@@ -88,6 +100,18 @@ def parse_args(argv=None):
                  "file whose order the labels could follow)")
     if a.point_interp != "nearest" and not (a.point_level or a.save_labels):
         ap.error("--point-interp goes with --point-level or --save-labels")
+    if a.tta_mode is not None and a.tta is None:
+        ap.error("--tta-mode goes with --tta")
+    if a.tta is not None:
+        if a.target_files is None or not (a.point_level or a.save_labels):
+            ap.error("--tta goes with --target-files and --point-level or --save-labels (the views are voted per point)")
+        if a.point_interp != "nearest":
+            ap.error("--tta goes with --point-interp nearest (per-view interpolation is not built)")
+        try:
+            tta.parse_views(a.tta)
+        except ValueError as e:
+            ap.error(f"--tta: {e}")
+    a.tta_mode = a.tta_mode or "prob"
     if a.inverse_label_map is not None:
         if len(a.inverse_label_map) != len(a.target_files):
             ap.error("--inverse-label-map needs one file per --target-files entry")
@@ -154,7 +178,8 @@ def main(argv=None):
                 label_writer = PointLabelWriter(os.path.join(save_dir, "predictions"), name, config,
                                                 data.listings[0].files)
             points = PointPath.of(data, device, out_lut=torch.from_numpy(lut).to(device), fill=fill,
-                                  with_labels=a.point_level, on_point_labels=label_writer, interp=a.point_interp)
+                                  with_labels=a.point_level, on_point_labels=label_writer, interp=a.point_interp, tta=a.tta,
+                                  tta_mode=a.tta_mode)
         writer = None
         if a.save_predictions:
             writer = PredictionWriter(os.path.join(save_dir, "predictions"), name, a.model != "MinkUNet34BEV",
@@ -172,13 +197,16 @@ def main(argv=None):
         extra = {}
         if a.point_level:
             out["points_csv"] = write_results_csv(save_dir, sources, name, res["point_rows"], CLASS_NAMES,
-                                                  first_target=t == 0, file_targets=file_targets + "-points")
+                                                  first_target=t == 0, file_targets=file_targets +
+                                                  ("-points-tta" if a.tta is not None else "-points"))
             out["point_per_class_iou"] = [float(x) for x in res["point_per_class"]]
             out["point_mean_iou"] = res["point_mean"]
             extra = {"point_iou_rows": res["point_rows"], "point_counts": res["point_counts"]}
         if a.save_labels:
             out["label_files"] = len(points.on_point_labels.written)
             extra["label_paths"] = list(points.on_point_labels.written)
+        if a.tta is not None:
+            out.update(tta_views=res["tta_views"], tta_mode=res["tta_mode"])
         print(json.dumps(out), flush=True)
         results.append(dict(out, iou_rows=res["rows"], counts=res["counts"], **extra))
     return results

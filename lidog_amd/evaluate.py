@@ -18,6 +18,7 @@ import torch
 
 from . import me as ME
 from . import precision as _precision
+from . import tta as _tta
 
 
 def per_class_iou(preds, labels, num_classes=7, ignore_label=-1):
@@ -407,12 +408,22 @@ class PointPath:
     file's labels); `on_point_labels(first_scan, labels_out, row_off)`: called per batch with the dataset index of its
     first scan, the host copy of its ids (numpy uint32, file order) and the B + 1 row offsets of its scans; asking for it
     costs one device -> host copy per batch.  `interp`: "nearest" (every point takes its voxel's class) or "trilinear" (the
-    class of the logits interpolated at the point's own position between the voxels, point_logits)."""
+    class of the logits interpolated at the point's own position between the voxels, point_logits).  `tta`: a list of
+    view names or tta.View objects (lidog_amd.tta.parse_views; None or empty: nothing changes): the model also runs over
+    every view of a batch and a point takes the arg-max of its accumulated scores, `tta_mode` "prob" (softmax),
+    "logit" or "vote" (one-hot of every view's arg-max); nearest only."""
 
-    def __init__(self, items, out_lut=None, fill=0, with_labels=True, on_point_labels=None, interp="nearest"):
+    def __init__(self, items, out_lut=None, fill=0, with_labels=True, on_point_labels=None, interp="nearest", tta=None,
+                 tta_mode="prob"):
         if interp not in POINT_INTERP:
             raise ValueError(f"PointPath: interp={interp!r} (one of {', '.join(POINT_INTERP)})")
-        self.interp = interp
+        if tta_mode not in _tta.MODES:
+            raise ValueError(f"PointPath: tta_mode={tta_mode!r} (one of {', '.join(_tta.MODES)})")
+        self.interp, self.tta_mode = interp, tta_mode
+        self.tta = _tta.parse_views(tta) if tta is not None and len(tta) else None       # the identity first
+        if self.tta is not None and interp == "trilinear":
+            raise ValueError("PointPath: tta with interp='trilinear' (every view would need its own interpolation; "
+                             "test-time augmentation is nearest only)")
         self.items, self.out_lut, self.fill = items, out_lut, int(fill)
         self.with_labels, self.on_point_labels = bool(with_labels), on_point_labels
 
@@ -506,7 +517,9 @@ class TargetEvaluator:
         `points` (a PointPath; None changes nothing): every batch's logits also go through point_labels; the dict then
         carries point_counts [n_scans, C, C], point_rows / point_per_class / point_mean (iou_rows / mean_iou_rows with
         the same `rows`), and points.on_point_labels sees every batch's ids.  The point counts and their error word
-        cross to the host at the end, with the voxel ones."""
+        cross to the host at the end, with the voxel ones.  With points.tta every batch is also run once per further
+        view and the point level takes the accumulated scores (_vote); the voxel-level counts and `on_predictions` stay
+        view 0's, and the dict gains tta_views (the names, identity first) and tta_mode."""
         import numpy as np
         if rows not in ("batch", "scan"):
             raise ValueError(f"rows={rows!r} (one of 'batch', 'scan')")
@@ -515,7 +528,7 @@ class TargetEvaluator:
         self.kernels = run.kernels
         it = iter(batches)
         cur = next(it, None)
-        counts = err = pcounts = perr = ferr = None
+        counts = err = pcounts = perr = ferr = terr = None
         batch_of_scan = []
         done = 0
         nb = 0
@@ -530,6 +543,7 @@ class TargetEvaluator:
                     pcounts = torch.zeros((int(n_scans), c, c), dtype=torch.int64, device=coords.device)
                     perr = torch.zeros(1, dtype=torch.int32, device=coords.device)
                     ferr = torch.zeros(1, dtype=torch.int32, device=coords.device)
+                    terr = torch.zeros(1, dtype=torch.int32, device=coords.device)
             k = len(ids)
             if done + k > counts.shape[0]:
                 raise ValueError(f"TargetEvaluator: more than n_scans = {n_scans} scans in the batches")
@@ -545,8 +559,12 @@ class TargetEvaluator:
                 items = points.items(ids)
                 pin = point_inputs(items, points.with_labels)
                 plogits, vox_off, inverse = logits, pin["vox_off"], pin["inverse_map"]
-                if points.interp == "trilinear":    # one row of logits per kept point: every kept row is its own "voxel"
-                    plogits, vox_off = point_logits(run.output, items, err=ferr), pin["kept_off"]
+                if points.interp == "trilinear" or points.tta is not None:
+                    # one row of scores per kept point: every kept row is its own "voxel".  Interpolated logits, or the
+                    # scores accumulated over the views (never both: PointPath refuses the pair)
+                    plogits = point_logits(run.output, items, err=ferr) if points.interp == "trilinear" else \
+                        self._vote(run, logits, items, pin, points, terr)
+                    vox_off = pin["kept_off"]
                     inverse = torch.cat([torch.arange(it["kept"], dtype=torch.int64, device=coords.device)
                                          for it in items])
                 ids_out, _ = point_labels(plogits, pin["row_off"], pin["kept_off"], vox_off, pin["keep_row"],
@@ -575,7 +593,25 @@ class TargetEvaluator:
             pr = iou_rows(point_iou_counts(pc), rows, batch_of_scan)
             p_class, p_mean = mean_iou_rows(pr)
             res.update(point_counts=pc, point_rows=pr, point_per_class=p_class, point_mean=p_mean)
+            if points.tta is not None:
+                _tta.check_vote_error(terr, "TargetEvaluator")
+                res.update(tta_views=[v.name for v in points.tta], tta_mode=points.tta_mode)
         return res
+
+    def _vote(self, run, logits, items, pin, points, terr):
+        """float32 [kept, C]: the scores of every kept point of a loader batch accumulated over the views of
+        points.tta (csrc/tta.hip).  View 0 is the regular forward's `logits`; every further view is built by
+        tta.view_batch and goes through _forward on the recorded map trace with a manager of its own, so the
+        Predictor's prefetch of the next loader batch stays untouched.  The views are voted in view order."""
+        dev = logits.device
+        inverse = torch.cat([it["inverse_map"].long() + int(pin["vox_off"][s]) for s, it in enumerate(items)])
+        acc = torch.empty((inverse.shape[0], logits.shape[1]), dtype=torch.float32, device=dev)
+        _tta.vote(logits, inverse, acc, points.tta_mode, first=True, err=terr)
+        for view in points.tta[1:]:
+            coords, feats, inverse = _tta.view_batch(items, view)
+            out = _forward(self.model, coords, feats, None, self.precision, run.kernels)
+            _tta.vote(out.F.contiguous(), inverse, acc, points.tta_mode, first=False, err=terr)
+        return acc
 
 
 # ------------------------------------------------------------------ point clouds of the prediction dump

@@ -19,6 +19,10 @@
  *     row-major [rows, channels]; all index tables are int32.
  *   - coordinate components must lie in [-65536, 65535], batch in [0, 4095]
  *     (63-bit packed hash key); violations set *err_flag (device int32) to 1.
+ *
+ * Grammar.  lidog_amd/_lib.py derives its ctypes binding from the prototypes below and refuses what it cannot read:
+ * scalars are int, int32_t, int64_t, uint32_t, float or double (returns: int, int32_t, int64_t, const char *),
+ * anything else travels as a pointer; every parameter is named; no function-pointer parameters, no macros in types.
  */
 #ifndef LIDOG_AMD_H
 #define LIDOG_AMD_H
@@ -32,6 +36,7 @@ extern "C" {
 const char *lidog_last_error(void);
 /* 9.  Bumped whenever an entry point changes its arguments or their meaning (additive entries leave it alone);
  * 8 -> 9: the workspaces of lidog_coords_compact / lidog_coords_stride are sized by their _ws functions. */
+#define LIDOG_ABI_VERSION 9
 int lidog_abi_version(void);
 
 /* ------------------------------------------------------------------ coordinate maps

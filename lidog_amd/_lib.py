@@ -3,6 +3,7 @@
 There is NO fallback: if the HIP library is missing or a call fails, this raises."""
 import ctypes
 import os
+import re
 
 import torch
 
@@ -12,206 +13,57 @@ SO_PATH = os.environ.get("LIDOG_SO") or os.path.join(_HERE, "_C", "liblidog_amd.
 
 _i32, _i64, _p, _f, _d = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_float, ctypes.c_double
 
-# name -> argtypes (restype is int unless listed in _RESTYPES)
-SIGNATURES = {
-    "lidog_abi_version": [],
-    "lidog_hash_capacity": [_i64],
-    "lidog_coords_insert": [_p, _i64, _p, _p, _i64, _p, _p, _p, _p],
-    "lidog_coords_insert_info": [_p, _i64, _p, _p, _i64, _p, _p, _p, _p],
-    "lidog_coords_compact_ws": [_i64],
-    "lidog_coords_stride_ws": [_i64],
-    "lidog_coords_compact": [_p, _i64, _p, _p, _i64, _p, _p, _p, _p, _p],
-    "lidog_coords_stride": [_p, _i64, _i32, _p, _p, _i64, _p, _p, _p, _p, _p, _p],
-    "lidog_kernel_map": [_p, _i64, _p, _p, _i64, _p, _i32, _p, _p],
-    "lidog_bitmap_words": [_i32, _i32, _i32, _i32, _i64],
-    "lidog_bitmap_set": [_p, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p],
-    "lidog_kernel_map_bits": [_p, _i64, _p, _p, _i64, _p, _i32, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p],
-    "lidog_kernel_map_pairs": [_p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _p],
-    "lidog_sconv_gemm_units": [_i32, _i32],
-    "lidog_sconv_gemm": [_p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _i64, _p],
-    "lidog_sconv_gemm_addend": [_p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p],
-    "lidog_sconv_reduce": [_p, _p, _i64, _i32, _i32, _p, _p, _p, _p],
-    "lidog_sconv_reduce_stats_ws": [_i64, _i32],
-    "lidog_sconv_reduce_stats": [_p, _p, _i64, _i32, _i32, _p, _p, _p, _p, _d, _f, _f, _p, _p, _p, _p, _p],
-    "lidog_kernel_map_rows": [_p, _i64, _i32, _i32, _p, _p, _p, _p],
-    "lidog_sconv_reduce_rows": [_p, _p, _p, _i64, _i32, _p, _p, _p, _p],
-    "lidog_sconv_reduce_rows_bn": [_p, _p, _p, _i64, _i32, _p, _p, _p, _p, _p, _p, _i32, _p, _p],
-    "lidog_sconv_reduce_rows_stats": [_p, _p, _p, _i64, _i32, _p, _p, _p, _p, _d, _f, _f, _p, _p, _p, _p, _p],
-    "lidog_sconv_reduce_rows_bwdstats": [_p, _p, _p, _i64, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _d, _p, _p, _p],
-    "lidog_bn_bwd_reduce_blocks": [_i64, _i32],
-    "lidog_stats_max_blocks": [],
-    "lidog_sconv_cin1": [_p, _p, _p, _p, _i64, _i32, _i32, _p, _p],
-    "lidog_kernel_map_subset": [_p, _i64, _i32, _p, _i32, _p, _p],
-    "lidog_kernel_map_sorted_ws": [_i64],
-    "lidog_kernel_map_sorted": [_p, _i64, _i32, _p, _p, _p, _p, _p, _i64, _p],
-    "lidog_sconv_os": [_p, _p, _i64, _i32, _p, _p, _p, _p, _i32, _p, _p, _i32, _i32, _p, _p],
-    "lidog_sconv_os_stats_ws": [_i64, _i32],
-    "lidog_sconv_os_bn": [_p, _p, _i64, _i32, _p, _p, _p, _p, _p, _i32, _i32, _p, _p, _p, _p, _p, _i32, _p, _p],
-    "lidog_sconv_os_stats": [_p, _p, _i64, _i32, _p, _p, _p, _p, _p, _i32, _i32, _p, _p, _p, _d, _f, _f, _p, _p, _p, _p, _p],
-    "lidog_pack_kernels_bf16": [_p, _p, _p, _i32, _i64, _p],
-    "lidog_sconv_gemm_bf16": [_p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p],
-    "lidog_sconv_os_bn_bf16": [_p, _p, _i64, _i32, _p, _p, _p, _p, _p, _i32, _i32, _p, _p, _p, _p, _p, _i32, _p, _p],
-    "lidog_sconv_wgrad_bf16": [_p, _p, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _p, _p, _p],
-    "lidog_sconv_wgrad_bf16_slabs": [_i32, _i32, _i32],
-    "lidog_sconv_wgrad_bf16_slots": [_i32, _i32],
-    "lidog_sconv_wgrad": [_p, _p, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _p, _p, _p],
-    "lidog_sconv_gemm_in_bn": [_p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _i32, _i64, _p],
-    "lidog_sconv_os_stats_in_bn": [_p, _p, _i64, _i32, _p, _p, _p, _p, _p, _i32, _i32, _p, _p, _p, _d, _f, _f, _p, _p, _p, _p,
-                                   _p, _p, _p, _p, _i32, _p],
-    "lidog_sconv_wgrad_in_bn": [_p, _p, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _i32, _p],
-    "lidog_sconv_wgrad_slabs": [_i32, _i32, _i32],
-    "lidog_sconv_wgrad_slots": [_i32, _i32, _i32],
-    "lidog_set_sparse_core": [_i32],
-    "lidog_get_sparse_core": [],
-    "lidog_transpose_kernel": [_p, _i32, _i32, _i32, _p, _p],
-    "lidog_transpose_batched": [_p, _p, _p, _i32, _i64, _p],
-    "lidog_bn_reduce_ws": [_i32, _i64],
-    "lidog_bn_stats": [_p, _i64, _i32, _i64, _p, _p, _d, _f, _f, _p, _p, _p, _p, _p],
-    "lidog_bn_finalize": [_p, _d, _i32, _f, _f, _p, _p, _p, _p, _p],
-    "lidog_bn_apply": [_p, _i64, _i32, _i64, _p, _p, _p, _p, _p, _i32, _p, _p],
-    "lidog_bn_bwd_reduce": [_p, _p, _p, _i64, _i32, _i64, _p, _p, _p, _p, _d, _p, _p, _p, _p, _p],
-    "lidog_bn_bwd_apply": [_p, _p, _p, _i64, _i32, _i64, _p, _p, _p, _p, _d, _p, _p, _p, _p, _p, _p],
-    "lidog_relu_bits_words": [_i64, _i32],
-    "lidog_bn_apply_bits": [_p, _i64, _i32, _i64, _p, _p, _p, _p, _p, _i32, _p, _p, _p],
-    "lidog_bn_bwd_reduce_bits": [_p, _p, _p, _p, _i64, _i32, _i64, _p, _p, _p, _p, _d, _p, _p, _p, _p, _p],
-    "lidog_bn_bwd_apply_bits": [_p, _p, _p, _p, _i64, _i32, _i64, _p, _p, _p, _p, _d, _p, _p, _p, _p, _p, _p],
-    "lidog_colsum": [_p, _i64, _i32, _p, _p, _p],
-    "lidog_colsum_ws": [_i32],
-    "lidog_bn_eval_invstd": [_p, _f, _i32, _p, _p],
-    "lidog_cat2": [_p, _i32, _p, _i32, _i64, _p, _p],
-    "lidog_split2": [_p, _i32, _i32, _i64, _p, _p, _p],
-    "lidog_relu_fwd": [_p, _i64, _p, _p],
-    "lidog_relu_bwd": [_p, _p, _i64, _p, _p],
-    "lidog_add": [_p, _p, _i64, _p, _p],
-    "lidog_bev_winner": [_p, _i64, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p],
-    "lidog_bev_pool_fwd": [_p, _i32, _p, _p, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p],
-    "lidog_bev_pool_bwd": [_p, _p, _p, _p, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p],
-    "lidog_conv2d_fwd": [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p],
-    "lidog_conv2d_dgrad": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p],
-    "lidog_conv2d_wgrad": [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _i64, _p],
-    "lidog_conv2d_support_ws": [_i32, _i32, _i32, _i32],
-    "lidog_conv2d_support": [_p, _i32, _i32, _i32, _i32, _p, _p],
-    "lidog_conv2d_fwd_sparse": [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p],
-    "lidog_conv2d_dgrad_sparse": [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p],
-    "lidog_conv2d_wgrad_sparse_ws": [_i32, _i32, _i32, _i32, _i32],
-    "lidog_conv2d_wgrad_sparse": [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _i64, _p],
-    "lidog_voxel_floor": [_p, _i64, _f, _f, _f, _i32, _p, _p],
-    "lidog_label_vote": [_p, _p, _p, _i64, _i64, _i32, _p, _p],
-    "lidog_bev_label_raster": [_p, _p, _i64, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p],
-    "lidog_dice_ws": [_i32],
-    "lidog_dice_fwd": [_p, _p, _i64, _i32, _i64, _i32, _f, _i32, _i32, _i32, _f, _p, _p, _p, _p],
-    "lidog_dice_bwd": [_p, _p, _i64, _i32, _i64, _i32, _f, _i32, _i32, _p, _p, _p, _p],
-    "lidog_dice_kitti_fwd": [_p, _p, _i64, _i32, _i64, _i32, _f, _i32, _i32, _f, _p, _p, _p, _p],
-    "lidog_dice_kitti_bwd": [_p, _p, _i64, _i32, _i64, _i32, _f, _i32, _p, _p, _p, _p],
-    "lidog_ce_ws": [_i32],
-    "lidog_ce_fwd": [_p, _p, _i64, _i32, _i64, _i32, _p, _i32, _d, _d, _p, _p, _p, _p],
-    "lidog_ce_bwd": [_p, _p, _i64, _i32, _i64, _i32, _p, _p, _p, _p, _p],
-    "lidog_adam_step": [_p, _p, _p, _p, _i64, _f, _f, _f, _f, _f, _i32, _f, _p],
-    "lidog_sgd_step": [_p, _p, _p, _i64, _f, _f, _f, _i32, _f, _p],
-    "lidog_comm_unique_id_bytes": [],
-    "lidog_comm_unique_id": [_p],
-    "lidog_comm_init_rank": [_p, _i32, _i32, ctypes.POINTER(ctypes.c_void_p)],
-    "lidog_comm_destroy": [_p],
-    "lidog_allreduce_f32": [_p, _i64, _p, _p],
-    "lidog_allreduce_f64": [_p, _i64, _p, _p],
-    "lidog_comm_count": [_p],
-    "lidog_peer_handle_bytes": [],
-    "lidog_peer_mailbox_bytes": [_i32, _i32],
-    "lidog_peer_mailbox_alloc": [_i64, ctypes.POINTER(ctypes.c_void_p), _p],
-    "lidog_peer_mailbox_open": [_p, ctypes.POINTER(ctypes.c_void_p)],
-    "lidog_peer_comm_create": [_i32, _i32, _i32, _p, _p, ctypes.POINTER(ctypes.c_void_p)],
-    "lidog_peer_max_doubles": [_p],
-    "lidog_peer_set_spin_limit": [_p, _i64],
-    "lidog_peer_allreduce_f64": [_p, _p, _i64, _p],
-    "lidog_peer_status": [_p],
-    "lidog_peer_comm_destroy": [_p, _i32],
-    "lidog_peer_rebind_stream": [_p, _p],
-    "lidog_peer_calls": [_p],
-    "lidog_peer_inject_skip_flag": [_p, _i64],
-    "lidog_peer_mailbox_free": [_p],
-    "lidog_peer_mailbox_close": [_p],
-    "lidog_tiles_host": [_p, _i32, _i32, _i32, _p, _i64],
-    "lidog_wgrad_items_host": [_p, _i32, _i64, _i32, _i32, _p, _p, _i64],
-    "lidog_conv2d_support_work": [_p, _i32, _i32, _i32, _i32, _i32, _p, _p],
-    "lidog_bn_apply_sync": [_p, _i64, _i32, _p, _f, _f, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _p],
-    "lidog_trunk_fusions": [_i32],
-    "lidog_trunk_in_bn_readers": [_p, _i32, _p, _i32, _p, _i32, _p, _i32, _p],
-    "lidog_trunk_gemm_timing": [_i32],
-    "lidog_trunk_gemm_timing_read": [_p],
-    "lidog_trunk_work_read": [_p],
-    "lidog_trunk_forward": [_p, _p, _i32, _p, _i32, _p, _i32, _p, _i32, _p, _p, _p, _i64, _p, _i64, _p, _p, _i32, _p, _p, _p],
-    "lidog_trunk_backward": [_p, _p, _i32, _p, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _i64, _p, _i64, _p,
-                             _i64, _p, _p, _i32, _i32, _p, _p, _p],
-    "lidog_in_segments_ws": [_i64],
-    "lidog_in_segments": [_p, _i64, _i32, _p, _p, _p, _p, _i64, _p],
-    "lidog_in_reduce_ws": [_i32, _i32],
-    "lidog_in_stats": [_p, _i64, _i32, _i32, _p, _p, _f, _p, _p, _p, _p],
-    "lidog_in_apply": [_p, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p],
-    "lidog_in_bwd_reduce": [_p, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p],
-    "lidog_in_bwd_apply": [_p, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p],
-    "lidog_ibn_apply": [_p, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
-    "lidog_ibn_bwd_reduce": [_p, _p, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
-    "lidog_ibn_bwd_apply": [_p, _p, _p, _i64, _i32, _i32, _p, _p, _p, _p, _d, _p, _p, _p, _p, _p, _p, _p],
-    "lidog_iw_ws": [],
-    "lidog_iw_fwd": [_p, _p, _p, _p, _i32, _d, _p, _p, _p, _p],
-    "lidog_iw_bwd": [_p, _p, _p, _p, _i32, _d, _p, _p, _p],
-    "lidog_grad_accumulate": [_p, _i32, _p],
-    "lidog_mix_histogram": [_p, _i64, _i32, _p, _p],
-    "lidog_mix_split_ws": [_i64, _i32],
-    "lidog_mix_split": [_p, _i64, _p, _i32, _i32, _p, _p, _p, _p],
-    "lidog_mix_gather": [_p, _i64, _p, _p, _p, _p, _p, _i32, _i64, _f, _p, _i32, _p, _p, _p],
-    "lidog_mix_gather_aug": [_p, _i64, _p, _i64, _p, _p, _p, _p, _i32, _i64, _f, _p, _i32, _p, _i32, _d, _d, _d, _p, _i32,
-                             _p, _p, _p],
-    "lidog_dbscan_ws": [_i64],
-    "lidog_dbscan": [_p, _i64, _f, _d, _i32, _p, _p, _p, _i64, _p],
-    "lidog_cluster_boxes": [_p, _p, _i64, _i32, _p, _p, _p, _p],
-    "lidog_sn_scale_coords": [_p, _i64, _f, _f, _f, _f, _p, _p],
-    "lidog_augment_is_f64": [_p, _i32],
-    "lidog_augment_ws": [_i64],
-    "lidog_augment_points": [_p, _i64, _p, _i64, _p, _p, _i32, _i32, _d, _d, _d, _i32, _p, _p, _p, _p, _p, _p, _p, _p],
-    "lidog_eval_confusion": [_p, _p, _p, _i64, _i32, _i32, _i64, _p, _p, _p, _p],
-    "lidog_eval_pack_ws": [_i64, _i32],
-    "lidog_eval_pack": [_p, _p, _p, _i64, _i32, _i64, _p, _p, _p, _p],
-    "lidog_train_confusion": [_p, _p, _p, _i32, _i32, _i64, _p, _p, _p],
-    "lidog_scan_load_ws": [_i64],
-    "lidog_scan_load": [_p, _i32, _p, _i32, _i32, _i64, _p, _i32, _i32, _f, _p, _p, _p, _i32, _p, _p, _p],
-    "lidog_scan_keep_rows_ws": [_i64],
-    "lidog_scan_keep_rows": [_p, _i32, _i64, _i32, _f, _p, _p, _p, _p],
-    "lidog_point_labels_ws": [_i64],
-    "lidog_point_labels": [_p, _i64, _i32, _i32, _p, _p, _p, _i64, _i64, _p, _p, _p, ctypes.c_uint32, _p, _i32, _i32, _p,
-                           _i32, _i64, _p, _p, _p, _p, _p],
-    "lidog_pool_rows": [_p, _p, _p, _p, _i64, _i32, _i32, _p, _p, _p],
-    "lidog_pool_rows_max": [_p, _p, _p, _p, _i64, _i32, _p, _p, _p],
-    "lidog_pool_rows_max_bwd": [_p, _p, _p, _p, _p, _i64, _i32, _p, _p],
-    "lidog_pool_global_ws": [_i64, _i32, _i32],
-    "lidog_pool_global": [_p, _i64, _i32, _i32, _p, _p, _i32, _p, _p, _p, _i64, _p],
-    "lidog_pool_global_bwd": [_p, _p, _i64, _i32, _i32, _p, _p, _i32, _p, _p],
-    "lidog_field_floor": [_p, _i64, _i32, _p, _p, _p],
-    "lidog_field_lists_ws": [_i64, _i64],
-    "lidog_field_lists": [_p, _i64, _i64, _p, _p, _p, _i64, _p],
-    "lidog_field_reduce": [_p, _i64, _p, _p, _i64, _i32, _i32, _p, _p],
-    "lidog_field_gather": [_p, _p, _i64, _i64, _i32, _p, _p, _p],
-    "lidog_interp_fwd": [_p, _i64, _i32, _p, _p, _i64, _i32, _p, _p],
-    "lidog_interp_bwd": [_p, _p, _i64, _p, _p, _i64, _i32, _i32, _p, _p],
-    "lidog_raycast_ws": [_i64, _i64],
-    "lidog_raycast": [_p, _i64, _p, _p, _i32, _i32, _d, _f, _i32, _f, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
-    "lidog_tta_vote": [_p, _i64, _i32, _p, _i64, _i32, _i32, _p, _p, _p],
-}
-_RESTYPES = {"lidog_hash_capacity": _i64, "lidog_coords_compact_ws": _i64, "lidog_coords_stride_ws": _i64,
-             "lidog_sconv_reduce_stats_ws": _i64, "lidog_bn_reduce_ws": _i64,
-             "lidog_dice_ws": _i64, "lidog_ce_ws": _i64, "lidog_colsum_ws": _i64, "lidog_conv2d_support_ws": _i64, "lidog_conv2d_wgrad_sparse_ws": _i64,
-             "lidog_tiles_host": _i64, "lidog_wgrad_items_host": _i64, "lidog_bitmap_words": _i64,
-             "lidog_bn_bwd_reduce_blocks": _i64, "lidog_relu_bits_words": _i64,
-             "lidog_peer_mailbox_bytes": _i64, "lidog_peer_calls": _i64,
-             "lidog_kernel_map_sorted_ws": _i64, "lidog_sconv_os_stats_ws": _i64, "lidog_in_segments_ws": _i64,
-             "lidog_in_reduce_ws": _i64, "lidog_iw_ws": _i64, "lidog_mix_split_ws": _i64,
-             "lidog_dbscan_ws": _i64, "lidog_augment_ws": _i64, "lidog_eval_pack_ws": _i64,
-             "lidog_scan_load_ws": _i64, "lidog_pool_global_ws": _i64, "lidog_scan_keep_rows_ws": _i64,
-             "lidog_point_labels_ws": _i64, "lidog_field_lists_ws": _i64, "lidog_raycast_ws": _i64}
+HEADER_PATH = os.path.join(_HERE, "..", "include", "lidog_amd.h")
+_SCALARS = {"int": ctypes.c_int, "int32_t": _i32, "int64_t": _i64, "uint32_t": ctypes.c_uint32, "float": _f,
+            "double": _d}
+_POINTEES = set(_SCALARS) | {"void", "char", "uint16_t", "uint64_t"}
+_RETURNS = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": _i64, "const char *": ctypes.c_char_p}
 
-# lidog_abi_version() of the library these signatures were written against: a stale .so (or a header an external caller
-# compiled against long ago) would take mis-sized arguments without any diagnostic
-ABI_VERSION = 9
+
+def parse_header(text):
+    """(argtypes, restypes, abi_version) from the text of include/lidog_amd.h: name -> list of ctypes types, name ->
+    ctypes type, LIDOG_ABI_VERSION.  Strict: anything outside the grammar that the header's opening comment states
+    raises, so a header this cannot read never yields a shorter table."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    abi = re.search(r"^[ \t]*#[ \t]*define[ \t]+LIDOG_ABI_VERSION[ \t]+(\d+)[ \t]*$", text, re.M)
+    if abi is None:
+        raise RuntimeError("lidog_amd.h: no `#define LIDOG_ABI_VERSION <number>`")
+    text = re.sub(r'^[ \t]*#.*$|extern\s+"C"\s*\{|\}', " ", text, flags=re.M)
+    argtypes, restypes = {}, {}
+    for stmt in filter(None, (" ".join(re.findall(r"\w+|\S", s)) for s in text.split(";"))):
+        m = re.fullmatch(r"(.+?) (lidog_[a-z0-9_]+) \( (.*) \)", stmt)
+        if m is None or m.group(1) not in _RETURNS:
+            raise RuntimeError(f"lidog_amd.h: not a prototype the binding can read: `{stmt}`")
+        ret, name, params = m.groups()
+        if name in argtypes:
+            raise RuntimeError(f"lidog_amd.h: {name} is declared twice")
+        if "(" in params:
+            fp = re.search(r"\( \* (\w+)", params)
+            raise RuntimeError(f"lidog_amd.h: {name}: function-pointer parameter `{fp.group(1) if fp else params}`")
+        args = []
+        for param in [] if params == "void" else params.split(" , "):
+            kind, _, pname = param.rpartition(" ")
+            if not kind or not re.fullmatch(r"[A-Za-z_]\w*", pname) or pname in _POINTEES or pname == "const":
+                raise RuntimeError(f"lidog_amd.h: {name}: parameter `{param}` has no name")
+            t = re.fullmatch(r"(?:const )?(\w+)((?: \*(?: const)?)*)", kind)
+            if t is None or t.group(1) not in (_POINTEES if t.group(2) else _SCALARS):
+                raise RuntimeError(f"lidog_amd.h: {name}: parameter `{pname}` has the unknown type `{kind}`")
+            args.append(ctypes.POINTER(_p) if kind == "void * *" else _p if t.group(2) else _SCALARS[kind])
+        argtypes[name], restypes[name] = args, _RETURNS[ret]
+    if len(argtypes) != len(re.findall(r"\blidog_[a-z0-9_]+\s*\(", text)):
+        raise RuntimeError("lidog_amd.h: a lidog_ name is followed by `(` outside a prototype")
+    return argtypes, restypes, int(abi.group(1))
+
+
+# Derived once, at import: hipcc holds every definition in csrc/ to its declaration in the header, and this holds the
+# binding to the same declarations.  SIGNATURES: name -> argtypes of every entry point but lidog_last_error;
+# _RESTYPES: name -> restype.  ABI_VERSION: what load() demands of lidog_abi_version() -- a stale .so would take
+# mis-sized arguments without any diagnostic.
+if not os.path.exists(HEADER_PATH):
+    raise RuntimeError(f"{HEADER_PATH} is missing: the ctypes binding is derived from it")
+with open(HEADER_PATH) as _header:
+    _ARGTYPES, _RESTYPES, ABI_VERSION = parse_header(_header.read())
+SIGNATURES = {name: args for name, args in _ARGTYPES.items() if name != "lidog_last_error"}
 
 _lib = None
 
@@ -224,16 +76,14 @@ def load():
                 f"{SO_PATH} is missing: build it with `python -m lidog_amd.build` (hipcc, gfx950). "
                 "lidog_amd has no CPU or torch fallback.")
         L = ctypes.CDLL(SO_PATH)
-        L.lidog_last_error.restype = ctypes.c_char_p
-        L.lidog_last_error.argtypes = []
         have = L.lidog_abi_version()
         if have != ABI_VERSION:
             raise RuntimeError(f"{SO_PATH} is ABI version {have}, this package expects {ABI_VERSION}: rebuild it with "
                                "`python -m lidog_amd.build --force`")
-        for name, args in SIGNATURES.items():
+        for name, args in _ARGTYPES.items():
             fn = getattr(L, name)
             fn.argtypes = args
-            fn.restype = _RESTYPES.get(name, ctypes.c_int)
+            fn.restype = _RESTYPES[name]
         _lib = L
     return _lib
 

@@ -19,7 +19,7 @@ extern "C" const char *lidog_last_error(void) { return g_err; }
 // bumped whenever an entry point changes its arguments or their meaning (lidog_amd/_lib.py checks it at load time);
 // 4 = round 4: in-kernel statistics finish (workspace sizes), peer all-reduce stream binding / fault hooks
 // 9 = the scan workspaces of lidog_coords_compact / lidog_coords_stride are sized by lidog_coords_compact_ws / _stride_ws
-extern "C" int lidog_abi_version(void) { return 9; }
+extern "C" int lidog_abi_version(void) { return LIDOG_ABI_VERSION; }
 
 extern "C" int64_t lidog_hash_capacity(int64_t n) {
     int64_t cap = 1024;

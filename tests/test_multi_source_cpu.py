@@ -158,5 +158,5 @@ def test_accumulate_symbol_is_exported_and_declared():
     assert hasattr(lib, "lidog_grad_accumulate")
     header = open(os.path.join(REPO, "include", "lidog_amd.h")).read()
     assert re.search(r"int lidog_grad_accumulate\(const int64_t \*segs, int32_t n_segs, void \*stream\);", header)
-    src = open(os.path.join(REPO, "lidog_amd", "_lib.py")).read()
-    assert '"lidog_grad_accumulate": [_p, _i32, _p]' in src
+    assert _lib.SIGNATURES["lidog_grad_accumulate"] == [_lib._p, _lib._i32, _lib._p]
+    assert lib.lidog_grad_accumulate.argtypes == [_lib._p, _lib._i32, _lib._p]

@@ -410,6 +410,30 @@ int lidog_ce_bwd(const float *logits, const int64_t *target, int64_t n, int32_t 
                  int32_t has_ignore, const float *weight, const float *coef, const float *gout, float *glogits,
                  void *stream);
 
+/* ------------------------------------------------------------------ Lovasz-softmax, the auxiliary point criterion
+ * Berman et al., CVPR 2018 (lovasz_softmax_flat, classes='present'); not in the reference.  logits [n, C] float32 (C in
+ * 2..20, n C < 2^31), target [n] int64.  A row is valid when its label is not ignore_label (with has_ignore != 0) and
+ * lies in [0, C), the rule of lidog_ce_fwd; m = the valid rows, p = the fp32 row softmax.  For a class c that a valid
+ * row carries (P of them):  fg_i = [t_i == c], e_i = |fg_i - p_ic|; the valid rows by descending e as float32 values,
+ * ties by ascending row; G = sum fg, cf_j = the fg among the first j (integers); J(0, .) = 0,
+ * J(j, cf) = 1.0 - (double)(G - cf) / (double)(G + j - cf); g_j = J(j, cf_j) - J(j - 1, cf_j - fg_j);
+ * loss_c = sum_j e_j g_j in float64.  loss = sum_c loss_c / P, 0 when P = 0.
+ * fwd: loss [1]; coef [n C + 1] float32: coef[i C + c] = g sign(p_ic - fg_i) with sign(0) = 0, +0 for the invalid rows
+ * and the absent classes, every entry written once (no memset needed), and coef[n C] = 1 / P (0 when P = 0).  err_out:
+ * NULL, or [C, n] float32 that receives the errors e as sorted on, 0 for the invalid rows.  ws: lidog_lovasz_ws(n, C)
+ * BYTES (0 for a shape fwd refuses).  One stable radix sort of the C n pairs and one stable pass on the class; the
+ * number of launches does not depend on n, nothing is read back to the host, no floating-point atomics: the same bytes on
+ * every run.
+ * bwd: g is a constant (as in the published code): glogits_i = gout[0] p_i (q_i - <q_i, p_i>) with q = coef invP[0];
+ * +0 in the invalid rows.  invP: the tail word of coef, or any device float.
+ * Both return 2 before any launch for another C or n C >= 2^31; n == 0: loss 0, coef[0] = 0, return 0. */
+int64_t lidog_lovasz_ws(int64_t n, int32_t C);
+int lidog_lovasz_fwd(const float *logits, const int64_t *target, int64_t n, int32_t C, int64_t ignore_label,
+                     int32_t has_ignore, void *ws, float *loss, float *coef, float *err_out, void *stream);
+int lidog_lovasz_bwd(const float *logits, const int64_t *target, int64_t n, int32_t C, int64_t ignore_label,
+                     int32_t has_ignore, const float *coef, const float *invP, const float *gout, float *glogits,
+                     void *stream);
+
 /* ------------------------------------------------------------------ data path next to the hot path
  * ME.utils.sparse_quantize (utils/datasets/semantickitti_bev.py:232-238) = lidog_voxel_floor +
  * lidog_coords_insert + lidog_coords_compact + lidog_label_vote; PC2ImgConverter.getBEVImageNew

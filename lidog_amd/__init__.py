@@ -4,7 +4,8 @@ Public surface:
   lidog_amd.me            MinkowskiEngine-compatible operator API (HIP kernels via the C ABI)
   lidog_amd.bev           sparse2super + Encoder2D (fused BEV projection, MFMA 2-D head)
   lidog_amd.MinkUNet34 / MinkUNet34BEV / MinkUNet34IBN / MinkUNet34Robust   the reference models wired to those operators
-  lidog_amd.losses        SoftDICELoss / DICELoss / CELoss / FocalLoss on the device; make_criterion picks one by name
+  lidog_amd.losses        SoftDICELoss / DICELoss / CELoss / FocalLoss on the device; make_criterion picks one by name;
+                          LovaszSoftmaxLoss, the auxiliary point criterion (make_aux_criterion)
   lidog_amd.trainer       training step, Adam, RCCL data parallelism
   lidog_amd.trunk         the whole encoder-decoder as one launch sequence per pass (csrc/trunk.hip)
   lidog_amd.cluster       DBSCAN and per-cluster boxes on the device (csrc/cluster.hip; the SN baseline's statistics)
@@ -63,8 +64,8 @@ _safe_mode()
 
 from . import me, bev, losses, trunk  # noqa: E402,F401
 from .minkunet import make_models  # noqa: E402
-from .losses import (CELoss, DICELoss, FocalLoss, SoftDICELoss, make_bev_criterion,  # noqa: E402,F401
-                     make_criterion)
+from .losses import (CELoss, DICELoss, FocalLoss, LovaszSoftmaxLoss, SoftDICELoss,  # noqa: E402,F401
+                     make_aux_criterion, make_bev_criterion, make_criterion)
 
 me.trunk_forward = trunk.trunk_forward   # the models hand their training-mode trunk pass to the executor
 

@@ -6,6 +6,8 @@
   CELoss        utils/losses/losses.py:8-25             (nn.CrossEntropyLoss(weight, ignore_index), mean)
   FocalLoss     utils/losses/losses.py:423-436          (alpha (1 - exp(-ce))^gamma ce on that mean)
   make_criterion / make_bev_criterion                   (init_losses of utils/pipelines/trainer_lighting*.py)
+  LovaszSoftmaxLoss / make_aux_criterion                (not in the reference: Berman et al., CVPR 2018, added to the
+                                                         point criterion of a step; csrc/lovasz.hip)
   IWLoss        utils/losses/losses.py:464-485          (RobustNet's instance-whitening loss, csrc/iwloss.hip)
   CovMatrix_IRW utils/models/cov_settings.py:4-25        (its eye / mask helper)
 Same formulas as the reference, as HIP kernels (csrc/losses.hip; there is no torch formula behind them: CPU tensors and
@@ -199,6 +201,63 @@ def make_bev_criterion(name, ignore_label=-1):
     if name == "CELoss":
         return CELoss(ignore_label=ignore_label, weight=None)
     raise NotImplementedError(f"sem_bev_criterion {name!r}: one of {BEV_CRITERIA}")
+
+
+# ------------------------------------------------------------------ Lovasz-softmax, the auxiliary point criterion
+class _LovaszFn(torch.autograd.Function):
+    """csrc/lovasz.hip: errors, one radix sort of the C n (error, row) pairs, an integer prefix count and the Jaccard
+    gradient g forward; one pass per row backward.  The launches depend on the shape alone: nothing is read back."""
+
+    @staticmethod
+    def forward(ctx, logits, target, ignore_label):
+        logits, target = logits.contiguous(), target.contiguous()
+        if target.dtype != torch.int64:
+            target = target.long()
+        n, C = logits.shape
+        dev = logits.device
+        ws = torch.empty(_lib.load().lidog_lovasz_ws(n, C), dtype=torch.uint8, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        coef = torch.empty(n * C + 1, dtype=torch.float32, device=dev)      # the tail word: 1 / present classes
+        has_ignore = ignore_label is not None
+        cfg = (n, C, int(ignore_label) if has_ignore else 0, 1 if has_ignore else 0)
+        call("lidog_lovasz_fwd", ptr(logits), ptr(target), *cfg, ptr(ws), ptr(loss), ptr(coef), None)
+        ctx.save_for_backward(logits, target, coef)
+        ctx.cfg = cfg
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        logits, target, coef = ctx.saved_tensors
+        g = torch.empty_like(logits)
+        call("lidog_lovasz_bwd", ptr(logits), ptr(target), *ctx.cfg, ptr(coef), ptr(coef[logits.numel():]),
+             ptr(gout.contiguous()), ptr(g))
+        return g, None, None
+
+
+class LovaszSoftmaxLoss(nn.Module):
+    """Lovasz-softmax (Berman et al., CVPR 2018), lovasz_softmax_flat with classes='present': the mean over the classes
+    that a valid row carries of the Lovasz extension of the Jaccard loss on the errors |[t == c] - softmax(x)_c|.  A row
+    is valid when its label is not `ignore_label` (None: no row is ignored) and lies in [0, C), CELoss's rule.  The
+    surrogate of the mIoU; used next to a point criterion (make_aux_criterion), not in place of one."""
+
+    def __init__(self, ignore_label=None):
+        super().__init__()
+        self.ignore_label = ignore_label
+
+    def forward(self, output, target):
+        _check(output)
+        return _LovaszFn.apply(output, target, self.ignore_label)
+
+
+AUX_CRITERIA = ("LovaszSoftmaxLoss",)
+
+
+def make_aux_criterion(name, ignore_label=-1):
+    """the auxiliary point criterion of a training step by name (trainer._Step: sem_aux_criterion): it is ADDED to the
+    step's point criterion, times a weight.  Not in the reference; any other name raises."""
+    if name == "LovaszSoftmaxLoss":
+        return LovaszSoftmaxLoss(ignore_label=ignore_label)
+    raise NotImplementedError(f"sem_aux_criterion {name!r}: one of {AUX_CRITERIA}")
 
 
 # ------------------------------------------------------------------ instance-whitening loss (RobustNet)

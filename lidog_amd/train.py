@@ -45,7 +45,7 @@ from .data import (augment_item, check_augmentations, collate_items, cosmix_merg
                    draw_scaling, draw_source, mix3d_merge, on_merge_stream, pointcutmix_merge, scaling_params, sn_scale)
 from . import precision as _precision
 from .evaluate import CLASS_NAMES, per_class_iou
-from .losses import BEV_CRITERIA, POINT_CRITERIA
+from .losses import AUX_CRITERIA, BEV_CRITERIA, POINT_CRITERIA
 from .metrics import MetricLayout, MetricsWriter, StepMetrics
 from .optim import make_optimizer, make_scheduler, shard_indices
 from .trainer import LiDOGStep, RobustStep, SourceStep, setup_data_parallel
@@ -595,11 +595,14 @@ def build_model(kind="MinkUNet34BEV", bound_2d=50.0, in_channels=1, out_channels
 
 def build_step(model, kind="MinkUNet34BEV", optimizer="Adam", lr=1e-3, scheduler=None, weight_decay=1e-4,
                momentum=0.98, warmup_epochs=0, source_weights=(0.5, 0.5), num_classes=7, ignore_label=-1, num_sources=1,
-               precision=None, sem_criterion="SoftDICELoss", sem_bev_criterion=None):
+               precision=None, sem_criterion="SoftDICELoss", sem_bev_criterion=None, sem_aux_criterion=None,
+               sem_aux_weight=1.0):
     """SyncBN conversion when data-parallel (train_lidog.py:227-231), optimiser + scheduler
     (trainer_lighting_2d.py:349-394), step object (PLTTrainer2D / PLTRobustNet / PLTTrainer, on one or two sources).
     `precision`: the training steps' (trainer._Step).  `sem_criterion` / `sem_bev_criterion`: the point and BEV losses by
     name (losses.make_criterion / make_bev_criterion); the BEV one (None: DICELoss) belongs to MinkUNet34BEV alone.
+    `sem_aux_criterion` (None: none) / `sem_aux_weight`: the auxiliary point loss by name (losses.make_aux_criterion) that
+    every step adds to its point loss, and its weight.
     Returns (model, step, scheduler)."""
     if num_sources not in (1, 2):
         raise NotImplementedError(f"{num_sources} sources (the reference takes one or two)")
@@ -612,7 +615,8 @@ def build_step(model, kind="MinkUNet34BEV", optimizer="Adam", lr=1e-3, scheduler
     opt = make_optimizer(optimizer, model, lr, weight_decay=weight_decay, momentum=momentum)
     sched = make_scheduler(scheduler, opt)
     kw = dict(source_weights=source_weights, ignore_label=ignore_label, num_sources=num_sources, precision=precision,
-              sem_criterion=sem_criterion, num_classes=num_classes)
+              sem_criterion=sem_criterion, num_classes=num_classes, sem_aux_criterion=sem_aux_criterion,
+              sem_aux_weight=sem_aux_weight)
     if kind == "MinkUNet34BEV":
         step = LiDOGStep(model, opt, warmup_epochs=warmup_epochs, sem_bev_criterion=sem_bev_criterion or "DICELoss", **kw)
     elif kind == "MinkUNet34Robust":
@@ -648,9 +652,12 @@ class Fit:
                  momentum=0.98, check_val_every_n_epoch=5, num_sanity_val_steps=2, save_dir=None, seed=1234,
                  train_data=None, val_data=None, shuffle=True, resume=None, auto_resume=False, prefetch=True,
                  device="cuda", log=None, state_dict=None, num_sources=None, log_every_n_steps=0, metric_sources=None,
-                 val_precision=None, precision=None, sem_criterion="SoftDICELoss", sem_bev_criterion=None):
+                 val_precision=None, precision=None, sem_criterion="SoftDICELoss", sem_bev_criterion=None,
+                 sem_aux_criterion=None, sem_aux_weight=1.0):
         """`sem_criterion` / `sem_bev_criterion`: losses.sem_criterion / sem_bev_criterion of the reference's
         configurations, by name (build_step); the validation loss is the point criterion's.
+        `sem_aux_criterion` / `sem_aux_weight`: an auxiliary point loss by name (losses.make_aux_criterion:
+        LovaszSoftmaxLoss) added to the point loss times its weight, in the training steps and in the validation loss.
         `precision`: None / "fp32" (the fp32 step, exactly what runs without it) or "bf16": mixed-precision training
         steps (lidog_amd.precision: bf16 operands in the eligible sparse convolutions' forward, data-gradient and
         weight-gradient kernels, everything else -- master weights, gradients, optimiser state, checkpoints -- fp32; the
@@ -686,7 +693,7 @@ class Fit:
         self.model, self.step, self.sched = build_step(
             model, model_kind, optimizer, lr, scheduler, weight_decay, momentum, warmup_epochs, source_weights,
             num_sources=num_sources, precision=precision, sem_criterion=sem_criterion,
-            sem_bev_criterion=sem_bev_criterion)
+            sem_bev_criterion=sem_bev_criterion, sem_aux_criterion=sem_aux_criterion, sem_aux_weight=sem_aux_weight)
         self.opt = self.step.opt
         self.epoch, self.global_step = 0, 0
         self.history = []
@@ -718,7 +725,7 @@ class Fit:
         out = self.model(st)
         logits = (out[0] if isinstance(out, tuple) else out).F
         labels = batch["source_sem_labels0"].long()
-        loss = self.step.sem_criterion(logits, labels)
+        loss = self.step.point_loss(logits, labels)
         iou = per_class_iou(logits.max(dim=1)[1], labels)      # sklearn jaccard_score(labels=0..C-1), -1 = absent
         self.model.train(was)
         present = iou >= 0
@@ -895,8 +902,17 @@ def parse_args(argv=None):
                     help="the point loss (losses.sem_criterion of the reference's configurations; default SoftDICELoss)")
     ap.add_argument("--sem-bev-criterion", default=argparse.SUPPRESS, choices=list(BEV_CRITERIA),
                     help="the BEV loss of MinkUNet34BEV (losses.sem_bev_criterion; default DICELoss)")
+    ap.add_argument("--sem-aux-criterion", default=argparse.SUPPRESS, choices=list(AUX_CRITERIA),
+                    help="an auxiliary point loss added to --sem-criterion's in every step and in the validation loss "
+                         "(LovaszSoftmaxLoss: the mIoU surrogate of Berman et al., csrc/lovasz.hip; default: none)")
+    ap.add_argument("--sem-aux-weight", type=float, default=argparse.SUPPRESS, metavar="W",
+                    help="weight of --sem-aux-criterion in the point loss (default 1.0)")
     scans.add_file_arguments(ap, "--files", "train on")
     a = ap.parse_args(argv)
+    if hasattr(a, "sem_aux_weight") and not hasattr(a, "sem_aux_criterion"):
+        ap.error("--sem-aux-weight goes with --sem-aux-criterion")
+    if hasattr(a, "sem_aux_weight") and not a.sem_aux_weight > 0:
+        ap.error(f"--sem-aux-weight {a.sem_aux_weight}: the weight is positive")
     if getattr(a, "sem_bev_criterion", None) is not None and a.model != "MinkUNet34BEV":
         ap.error(f"--sem-bev-criterion is the loss of the BEV head: --model MinkUNet34BEV, not {a.model}")
     source_augment = getattr(a, "source_augment", None)
@@ -1008,6 +1024,11 @@ def sem_bev_criterion_of(a):
     return getattr(a, "sem_bev_criterion", "DICELoss" if a.model == "MinkUNet34BEV" else None)
 
 
+def sem_aux_of(a):
+    """(--sem-aux-criterion, --sem-aux-weight) of parsed arguments: (None, 1.0) when they were not given"""
+    return getattr(a, "sem_aux_criterion", None), getattr(a, "sem_aux_weight", 1.0)
+
+
 def main(argv=None):
     a = parse_args(argv)
     fit = _fit_from_args(a)
@@ -1024,12 +1045,14 @@ def _fit_from_args(a):
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))
     train, val = _data_from_args(a)
+    sem_aux_criterion, sem_aux_weight = sem_aux_of(a)
     return Fit(a.model, a.bound, a.batch, a.optimizer, a.lr, a.scheduler, a.epochs, a.warmup_epochs,
                source_weights=tuple(a.source_weights), check_val_every_n_epoch=a.check_val_every_n_epoch,
                save_dir=a.save_dir, seed=a.seed, train_data=train, val_data=val, resume=a.resume,
                auto_resume=a.auto_resume, log_every_n_steps=getattr(a, "log_every_n_steps", 0),
                val_precision=val_precision_of(a), precision=precision_of(a), sem_criterion=sem_criterion_of(a),
-               sem_bev_criterion=sem_bev_criterion_of(a))
+               sem_bev_criterion=sem_bev_criterion_of(a), sem_aux_criterion=sem_aux_criterion,
+               sem_aux_weight=sem_aux_weight)
 
 
 def _data_from_args(a):

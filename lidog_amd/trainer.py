@@ -22,7 +22,7 @@ import torch.distributed as dist
 
 from . import me as ME
 from . import precision as _precision
-from .losses import iw_loss, make_bev_criterion, make_criterion
+from .losses import iw_loss, make_aux_criterion, make_bev_criterion, make_criterion
 from .optim import (FlatAdam, FlatParams, FlatSGD, GradientBuckets, make_optimizer, make_scheduler,  # noqa: F401
                     shard_indices)
 
@@ -45,7 +45,10 @@ class _Step:
     step (its `.launches` count the routes).  One rank only.
     `sem_criterion`: the point loss by name, losses.sem_criterion of the reference's configurations
     (losses.make_criterion: CELoss, DICELoss, SoftDICELoss, FocalLoss); `num_classes` = 19 gives SoftDICELoss the KITTI
-    soft labels."""
+    soft labels.
+    `sem_aux_criterion`: None, or an auxiliary point loss by name (losses.make_aux_criterion: LovaszSoftmaxLoss) that is
+    added to the point loss of every source, times `sem_aux_weight`: the step's `sem_loss` (`sem_loss0` / `sem_loss1`) is
+    that sum, so the loss dictionaries and the logged keys keep their shape.  None launches nothing."""
 
     metrics = None
     bf16 = None                         # the packed tables of precision="bf16"
@@ -55,7 +58,7 @@ class _Step:
     metric_count_ignored = True         # jaccard_score over all rows (the LiDOG trainers filter label == -1 first)
 
     def __init__(self, model, optimizer, num_sources=1, ignore_label=-1, precision=None, sem_criterion="SoftDICELoss",
-                 num_classes=7):
+                 num_classes=7, *, sem_aux_criterion=None, sem_aux_weight=1.0):
         if num_sources not in (1, 2):
             raise NotImplementedError(f"{num_sources} sources (the reference takes one or two)")
         self.model, self.opt, self.num_sources = model, optimizer, num_sources
@@ -64,6 +67,10 @@ class _Step:
             _precision.check_single_rank()
             self.bf16 = _precision.Bf16Training(model)
         self.sem_criterion = make_criterion(sem_criterion, ignore_label, num_classes)
+        self.sem_aux_criterion = None if sem_aux_criterion is None else make_aux_criterion(sem_aux_criterion, ignore_label)
+        self.sem_aux_weight = float(sem_aux_weight)
+        if self.sem_aux_criterion is not None and not self.sem_aux_weight > 0:
+            raise ValueError(f"sem_aux_weight = {sem_aux_weight}: the auxiliary criterion's weight is positive")
         self._prepared = {}
         if num_sources == 2:
             optimizer.buckets.set_uses(2)
@@ -93,8 +100,15 @@ class _Step:
                 coords = batch[key]
                 self._prepared[id(coords)] = (coords, ME.CoordinateManager.prepare(coords, trace, ready))
 
+    def point_loss(self, logits, labels):
+        """the point loss of one source: the criterion, plus the weighted auxiliary criterion when there is one"""
+        loss = self.sem_criterion(logits, labels)
+        if self.sem_aux_criterion is not None:
+            loss = loss + self.sem_aux_weight * self.sem_aux_criterion(logits, labels)
+        return loss
+
     def _sem_losses(self, batch, outs):
-        return [self.sem_criterion(o.F, batch[f"source_sem_labels{s}"].long()) for s, o in enumerate(outs)]
+        return [self.point_loss(o.F, batch[f"source_sem_labels{s}"].long()) for s, o in enumerate(outs)]
 
     def _named(self, **losses):
         """{"sem_loss": l} for one source, {"sem_loss0": l0, "sem_loss1": l1} for two"""
@@ -186,8 +200,10 @@ class LiDOGStep(_Step):
     metric_count_ignored = False
 
     def __init__(self, model, optimizer, source_weights=(0.5, 0.5), warmup_epochs=0, num_classes=7, ignore_label=-1,
-                 num_sources=1, precision=None, sem_criterion="SoftDICELoss", sem_bev_criterion="DICELoss"):
-        super().__init__(model, optimizer, num_sources, ignore_label, precision, sem_criterion, num_classes)
+                 num_sources=1, precision=None, sem_criterion="SoftDICELoss", sem_bev_criterion="DICELoss", *,
+                 sem_aux_criterion=None, sem_aux_weight=1.0):
+        super().__init__(model, optimizer, num_sources, ignore_label, precision, sem_criterion, num_classes,
+                         sem_aux_criterion=sem_aux_criterion, sem_aux_weight=sem_aux_weight)
         self.w, self.warmup, self.nc = source_weights, warmup_epochs, num_classes
         self.bev_criterion = make_bev_criterion(sem_bev_criterion, ignore_label)
 
@@ -228,8 +244,9 @@ class SourceStep(_Step):
     One source: total = sem, the only loss returned; two sources (trainer_lighting.py:92-116): w0 * sem0 + w1 * sem1."""
 
     def __init__(self, model, optimizer, source_weights=(0.5, 0.5), ignore_label=-1, num_sources=1, precision=None,
-                 sem_criterion="SoftDICELoss", num_classes=7):
-        super().__init__(model, optimizer, num_sources, ignore_label, precision, sem_criterion, num_classes)
+                 sem_criterion="SoftDICELoss", num_classes=7, *, sem_aux_criterion=None, sem_aux_weight=1.0):
+        super().__init__(model, optimizer, num_sources, ignore_label, precision, sem_criterion, num_classes,
+                         sem_aux_criterion=sem_aux_criterion, sem_aux_weight=sem_aux_weight)
         self.w = source_weights
 
     def _losses(self, batch, epoch):
@@ -250,8 +267,10 @@ class RobustStep(_Step):
     metric_losses = ("sem_loss", "aux_loss")
 
     def __init__(self, model, optimizer, source_weights=(0.5, 0.5), aux_epoch=5, ignore_label=-1, num_sources=1,
-                 precision=None, sem_criterion="SoftDICELoss", num_classes=7):
-        super().__init__(model, optimizer, num_sources, ignore_label, precision, sem_criterion, num_classes)
+                 precision=None, sem_criterion="SoftDICELoss", num_classes=7, *, sem_aux_criterion=None,
+                 sem_aux_weight=1.0):
+        super().__init__(model, optimizer, num_sources, ignore_label, precision, sem_criterion, num_classes,
+                         sem_aux_criterion=sem_aux_criterion, sem_aux_weight=sem_aux_weight)
         self.w, self.aux_epoch = source_weights, aux_epoch
 
     def _losses(self, batch, epoch):

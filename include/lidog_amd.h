@@ -470,6 +470,25 @@ int lidog_grad_accumulate(const int64_t *segs, int32_t n_segs, void *stream);
 int lidog_sgd_step(float *param, const float *grad, float *momentum_buf, int64_t n, float lr, float momentum,
                    float weight_decay, int32_t nesterov, float grad_scale, void *stream);
 
+/* ------------------------------------------------------------------ weight averaging (csrc/wavg.hip)
+ * The average of a model's weights along the training trajectory, lidog_amd.optim.WeightAverage: the exponential moving
+ * average of the reference's MomentumUpdater (utils/common/momentum.py: mp = tau * mp + (1 - tau) * op; no trainer of the
+ * reference uses it) and the uniform average of torch.optim.swa_utils.AveragedModel.  With p the live element and a the
+ * average, every operation rounded separately and the division IEEE-correct: */
+#define LIDOG_WAVG_COPY 0 /* a = p */
+#define LIDOG_WAVG_EMA 1  /* a = c0 * a + c1 * p        (c0 = tau, c1 = 1 - tau) */
+#define LIDOG_WAVG_SWA 2  /* a = a + (p - a) / c0       (c0 = updates so far + 1) */
+#define LIDOG_WAVG_SWAP 3 /* exchange a and p */
+/* ONE launch of n_blocks workgroups over n_segs segments.  table: DEVICE int64 [3 n_segs + n_segs + 1]: the (live address,
+ * average address, element count) triples of lidog_grad_accumulate, then block0 [n_segs + 1]: the first workgroup of every
+ * segment, non-decreasing from block0[0] = 0 to block0[n_segs] = n_blocks (a segment with elements needs at least one
+ * workgroup; one without may have none).  The two ranges of a segment must not overlap, nor may those of different
+ * segments; the entry point cannot read the table, so whoever builds it checks it (lidog_amd.optim.wavg_table).  float4
+ * where a segment's two addresses share their alignment mod 16, scalar elsewhere.  No atomics, nothing is read back.
+ * n_segs == 0 or n_blocks == 0: nothing is launched.  c0, c1: unused by COPY and SWAP; c1 unused by SWA. */
+int lidog_wavg_apply(const int64_t *table, int32_t n_segs, int64_t n_blocks, int32_t mode, float c0, float c1,
+                     void *stream);
+
 /* ------------------------------------------------------------------ collectives (RCCL over xGMI)
  * The two collectives of the data-parallel path for hosts that do not go through torch.distributed: the gradient
  * all-reduce of Lightning DDP (train_lidog.py:227-231, strategy='ddp'; sum, the caller folds 1/world into the

@@ -27,6 +27,9 @@ record in file order, for SemanticKITTI as `predictions/<target>/sequences/SS/pr
 --tta NAME [NAME ...]: test-time augmentation (lidog_amd.tta): every batch also runs over the named views and a point
 takes the arg-max of the scores accumulated over its views (--tta-mode prob / logit / vote, csrc/tta.hip); the point
 table goes to `<sources>-TO-<targets>-points-tta.csv`, the voxel-level outputs stay those of the unchanged scan.
+--weights averaged: evaluate the trajectory average that a run under train --weight-average stored in the checkpoint
+(`averaged_state_dict`) instead of the weights of its last step; every results file then carries `-avg` before `.csv`
+and predictions and labels go under `predictions-avg/`.  The default, live, writes what it always wrote.
 """
 import argparse
 import json
@@ -87,6 +90,10 @@ def parse_args(argv=None):
     ap.add_argument("--inverse-label-map", nargs="+", default=None, metavar="FILE",
                     help="one per target: a .yaml / .json file with a learning_map_inv (common class -> id to write; "
                          "entry -1: the id of records beyond the radius, default 0).  Default: the class itself")
+    ap.add_argument("--weights", default="live", choices=["live", "averaged"],
+                    help="which weights of the checkpoint to evaluate: those of its last step (live, the default) or the "
+                         "trajectory average a run under train --weight-average stored next to them (averaged: every "
+                         "results file gets -avg before .csv, predictions and labels go under predictions-avg/)")
     a = ap.parse_args(argv)
     if a.checkpoint is None:
         ap.error(NO_CHECKPOINT)
@@ -151,7 +158,13 @@ def main(argv=None):
     torch.manual_seed(a.seed)
     device = "cuda"
     model = build_model(a.model, a.bound, device=device)
-    epoch, _ = load_lightning_checkpoint(model, a.checkpoint)
+    try:
+        epoch, _ = load_lightning_checkpoint(model, a.checkpoint, which=a.weights)
+    except KeyError as e:
+        if a.weights != "averaged":
+            raise
+        raise SystemExit(f"eval_target --weights averaged: {e.args[0]}")
+    avg = "-avg" if a.weights == "averaged" else ""      # the two kinds never share a table or a folder
     model.eval()
     save_dir = save_dir_of(a.checkpoint)
     sources = "".join(source_names(a.sources))                       # test_epoch_end concatenates the names
@@ -175,14 +188,14 @@ def main(argv=None):
                                     len(CLASS_NAMES), 0xFFFF if config == "SemanticKITTI" else 2 ** 31 - 1)
             label_writer = None
             if a.save_labels:
-                label_writer = PointLabelWriter(os.path.join(save_dir, "predictions"), name, config,
+                label_writer = PointLabelWriter(os.path.join(save_dir, "predictions" + avg), name, config,
                                                 data.listings[0].files)
             points = PointPath.of(data, device, out_lut=torch.from_numpy(lut).to(device), fill=fill,
                                   with_labels=a.point_level, on_point_labels=label_writer, interp=a.point_interp, tta=a.tta,
                                   tta_mode=a.tta_mode)
         writer = None
         if a.save_predictions:
-            writer = PredictionWriter(os.path.join(save_dir, "predictions"), name, a.model != "MinkUNet34BEV",
+            writer = PredictionWriter(os.path.join(save_dir, "predictions" + avg), name, a.model != "MinkUNet34BEV",
                                       len(CLASS_NAMES))
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -190,7 +203,7 @@ def main(argv=None):
                      points=points)
         dt = time.perf_counter() - t0                                # run() ends with the host copy of the counts
         path = write_results_csv(save_dir, sources, name, res["rows"], CLASS_NAMES, first_target=t == 0,
-                                 file_targets=file_targets)
+                                 file_targets=file_targets + avg)
         out = {"target": name, "checkpoint_epoch": epoch, "per_class_iou": [float(x) for x in res["per_class"]],
                "mean_iou": res["mean"], "rows": int(res["rows"].shape[0]), "rows_per": a.rows,
                "scans": int(res["scans"]), "scans_per_s": res["scans"] / dt, "csv": path}
@@ -198,7 +211,7 @@ def main(argv=None):
         if a.point_level:
             out["points_csv"] = write_results_csv(save_dir, sources, name, res["point_rows"], CLASS_NAMES,
                                                   first_target=t == 0, file_targets=file_targets +
-                                                  ("-points-tta" if a.tta is not None else "-points"))
+                                                  ("-points-tta" if a.tta is not None else "-points") + avg)
             out["point_per_class_iou"] = [float(x) for x in res["point_per_class"]]
             out["point_mean_iou"] = res["point_mean"]
             extra = {"point_iou_rows": res["point_rows"], "point_counts": res["point_counts"]}

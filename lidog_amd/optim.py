@@ -11,6 +11,7 @@ Restates what the reference configures through pytorch-lightning (python the GPU
 Parameters, gradients and optimiser state live in contiguous fp32 buffers: one fused HIP kernel per step
 (csrc/optim.hip:k_adam, csrc/optim.hip:k_sgd), one RCCL all-reduce per 32 MiB bucket.
 """
+import contextlib
 import math
 
 import numpy as np
@@ -18,7 +19,7 @@ import torch
 import torch.distributed as dist
 
 from . import me as ME
-from ._lib import call, call_on, ptr
+from ._lib import call, call_on, ptr, require_gpu
 
 
 class FlatParams:
@@ -450,6 +451,242 @@ def make_optimizer(name, model, lr, weight_decay=1e-4, momentum=0.98, group=None
     if name == "SGD":
         return FlatSGD(model, lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=True, group=group)
     raise NotImplementedError(name)
+
+
+# ------------------------------------------------------------------ weight averaging (csrc/wavg.hip)
+WAVG_COPY, WAVG_EMA, WAVG_SWA, WAVG_SWAP = range(4)     # LIDOG_WAVG_* of include/lidog_amd.h
+WAVG_BLOCK_ELEMS = 1024      # what one workgroup covers per sweep: 256 threads, one float4 each
+WAVG_MAX_BLOCKS = 2048       # a memory-bound pass: about 8 workgroups per CU, the rest is grid-strided
+
+
+def wavg_table(triples, max_blocks=WAVG_MAX_BLOCKS):
+    """(int64 numpy table, workgroups) of lidog_wavg_apply over `triples` [(live address, average address, elements)]:
+    the triples, then block0 [n + 1], the first workgroup of every segment.  A segment gets workgroups in proportion to
+    its share of all elements, at least one and no more than it has sweeps for; an empty one gets none.  The entry point
+    cannot read a table that lives on the device, so everything it relies on is checked HERE: counts, alignment, and
+    that no two of the 2 n address ranges overlap."""
+    triples = [tuple(int(v) for v in t) for t in triples]
+    spans = []
+    for s, (live, avg, n) in enumerate(triples):
+        if n < 0:
+            raise ValueError(f"wavg_table: segment {s} has {n} elements")
+        if n == 0:
+            continue
+        if live <= 0 or avg <= 0 or live % 4 or avg % 4:
+            raise ValueError(f"wavg_table: segment {s}: addresses {live:#x}, {avg:#x} are not those of float32 arrays")
+        spans += [(live, live + 4 * n, s), (avg, avg + 4 * n, s)]
+    spans.sort()
+    for (_, hi, s0), (lo, _, s1) in zip(spans, spans[1:]):
+        if lo < hi:
+            raise ValueError(f"wavg_table: the ranges of segments {s0} and {s1} overlap")
+    total = sum(n for _, _, n in triples)
+    block0 = [0]
+    for _, _, n in triples:
+        nb = min(-(-n // WAVG_BLOCK_ELEMS), max(1, n * max_blocks // total)) if n else 0
+        block0.append(block0[-1] + nb)
+    table = np.array([v for t in triples for v in t] + block0, dtype=np.int64)
+    return table, block0[-1]
+
+
+class WeightAverage:
+    """The average of a model's weights along its training trajectory, kept next to the live weights and updated by
+    ONE launch per step (csrc/wavg.hip) over the optimiser's flat parameter buffer and every floating-point buffer of
+    the model (the BatchNorm running statistics; integer buffers -- num_batches_tracked -- are not averaged).
+
+    mode "ema": a = tau a + (1 - tau) p, the reference's MomentumUpdater (utils/common/momentum.py) with its cosine
+                schedule tau_s = final - (final - decay) (cos(pi s / total_steps) + 1) / 2 over the updates made so far;
+                `final_decay=None`: tau = decay throughout.
+    mode "swa": a = a + (p - a) / (n + 1) after n updates, torch.optim.swa_utils.AveragedModel's default.
+    The first update copies.  Every rank of a data-parallel run averages its own (identical) weights: no collective.
+
+        avg = WeightAverage(opt, model, "ema", decay=0.996)
+        ...; opt.step(); avg.update()
+        with avg.applied():                      # the model computes with the averaged weights and statistics, in place
+            validate(model)
+        sd = avg.averaged_state_dict()           # CPU clones under the model's own keys; no swap
+
+    applied() exchanges live and averaged values behind autograd's back (no version counter moves), so on entry and on
+    exit it refreshes the optimiser's transposed kernels -- which also advances their generation, the signal the bf16
+    training table re-packs on.  Enter it OUTSIDE precision.scope: a bf16 evaluation packs when its scope opens."""
+    MODES = ("ema", "swa")
+
+    @staticmethod
+    def check_arguments(mode, decay=0.996, final_decay=None, total_steps=None):
+        if mode not in WeightAverage.MODES:
+            raise ValueError(f"weight average mode {mode!r} (one of {WeightAverage.MODES})")
+        if not 0.0 <= decay <= 1.0:
+            raise ValueError(f"decay {decay}: it lies in [0, 1]")
+        if final_decay is not None:
+            if not decay <= final_decay <= 1.0:
+                raise ValueError(f"final_decay {final_decay}: decay ({decay}) <= final_decay <= 1")
+            if mode == "ema" and (total_steps is None or int(total_steps) <= 0):
+                raise ValueError("a cosine schedule of the decay (final_decay) needs total_steps > 0")
+
+    def __init__(self, optimizer, model, mode="ema", decay=0.996, final_decay=None, total_steps=None):
+        self.check_arguments(mode, decay, final_decay, total_steps)
+        self.mode, self.decay = mode, float(decay)
+        self.final_decay = None if final_decay is None else float(final_decay)
+        self.total_steps = None if total_steps is None else int(total_steps)
+        self.num_updates = 0
+        self.optimizer, self.model = optimizer, model
+        self._applied = False
+        flat = optimizer.flat
+        require_gpu(flat.flat, "the parameters of WeightAverage's optimiser")
+        self.params = torch.zeros_like(flat.flat)
+        owned = {id(p) for p in flat.params}
+        stray = [k for k, p in model.named_parameters() if id(p) not in owned]
+        if stray:
+            raise ValueError(f"WeightAverage: {stray[:3]} ... are not parameters of the optimiser's flat buffer")
+        # the live buffers are held: their memory outlives the table that names it
+        persistent = set(model.state_dict(keep_vars=True))
+        self._live = [(k, b) for k, b in model.named_buffers() if k in persistent and b.is_floating_point()]
+        offs, off = [], 0
+        for k, b in self._live:
+            if b.dtype != torch.float32 or not b.is_contiguous() or b.device != flat.flat.device:
+                raise ValueError(f"WeightAverage: buffer {k} must be contiguous float32 on the parameters' device")
+            offs.append(off)
+            off += -(-b.numel() // 4) * 4         # every slice starts on a 16-byte boundary, as torch's allocations do
+        self.buffers = torch.zeros(off, dtype=torch.float32, device=flat.flat.device)
+        self._buffer_views = [self.buffers[o:o + b.numel()].view(b.shape) for o, (_, b) in zip(offs, self._live)]
+        triples = [(flat.flat.data_ptr(), self.params.data_ptr(), flat.total)]
+        triples += [(b.data_ptr(), v.data_ptr(), b.numel()) for (_, b), v in zip(self._live, self._buffer_views)]
+        table, self.n_blocks = wavg_table(triples)
+        self.n_segs = len(triples)
+        self._addresses = [t[0] for t in triples]
+        self.table = torch.from_numpy(table).to(flat.flat.device)
+
+    # ------------------------------------------------------------------ the schedule
+    def tau(self, s):
+        """the decay of the update after `s` earlier ones (update_tau of the reference, in python doubles)"""
+        if self.final_decay is None:
+            return self.decay
+        s = min(s, self.total_steps)
+        return self.final_decay - (self.final_decay - self.decay) * (math.cos(math.pi * s / self.total_steps) + 1) / 2
+
+    def coefficients(self, s):
+        """(kernel mode, c0, c1) of the update after `s` earlier ones"""
+        if s == 0:
+            return WAVG_COPY, 0.0, 0.0
+        if self.mode == "ema":
+            tau = self.tau(s)
+            return WAVG_EMA, float(tau), float(1.0 - tau)
+        return WAVG_SWA, float(s + 1), 0.0
+
+    # ------------------------------------------------------------------ launches
+    def _check_live(self):
+        now = [self.optimizer.flat.flat.data_ptr()] + [b.data_ptr() for _, b in self._live]
+        named = dict(self.model.named_buffers())
+        if now != self._addresses or any(named.get(k) is not b for k, b in self._live):
+            raise RuntimeError("WeightAverage: the model's parameters or buffers moved in memory since it was built "
+                               "(.to(), a new optimiser, a re-registered buffer): build a new WeightAverage")
+
+    def _launch(self, mode, c0=0.0, c1=0.0):
+        with torch.cuda.device(self.table.device):
+            call("lidog_wavg_apply", ptr(self.table), self.n_segs, self.n_blocks, mode, c0, c1)
+
+    def update(self):
+        """fold the live weights into the average: call after optimizer.step().  One launch."""
+        if self._applied:
+            raise RuntimeError("WeightAverage.update() inside applied(): the live weights are swapped out")
+        if self.optimizer.flat.flat.data_ptr() != self._addresses[0]:
+            self._check_live()
+        self._launch(*self.coefficients(self.num_updates))
+        self.num_updates += 1
+
+    @contextlib.contextmanager
+    def applied(self):
+        """inside, the model holds the averaged parameters and running statistics and `self` holds the live ones; on
+        exit every live byte is back.  One SWAP launch each way, and the per-parameter caches are made consistent."""
+        if self._applied:
+            raise RuntimeError("WeightAverage.applied() cannot be nested")
+        if self.num_updates == 0:
+            raise RuntimeError("WeightAverage.applied() before the first update(): there is no average yet")
+        self._check_live()
+        self._applied = True
+        self._swap()
+        try:
+            yield self
+        finally:
+            self._swap()
+            self._applied = False
+
+    def _swap(self):
+        self._launch(WAVG_SWAP)
+        self.optimizer.transposed.refresh()     # the copies follow the weights; bf16 tables compare its generation
+
+    # ------------------------------------------------------------------ state
+    def averaged_state_dict(self):
+        """the averaged model under the model's own state-dict keys, as CPU clones: averaged parameters and floating-point
+        buffers, the live values of everything else (the integer counters, brought up to date by the state-dict hooks)"""
+        self._check_live()
+        live = self.model.state_dict()
+        flat = self.optimizer.flat
+        out = {k: v.detach().cpu().clone() for k, v in live.items()}
+        if self._applied:                       # the exchange is in force: the average sits in the live storage
+            return out
+        index = {id(p): off for p, off in zip(flat.params, flat.offsets)}
+        for k, p in self.model.named_parameters():
+            if k in out:
+                off = index[id(p)]
+                out[k] = self.params[off:off + p.numel()].view(p.shape).cpu().clone()
+        for (k, _), v in zip(self._live, self._buffer_views):
+            out[k] = v.cpu().clone()
+        return out
+
+    def load_averaged_state_dict(self, sd):
+        """inverse of averaged_state_dict (a checkpoint's `averaged_state_dict` without its `model.` prefix)"""
+        if self._applied:
+            raise RuntimeError("WeightAverage.load_averaged_state_dict() inside applied()")
+        flat = self.optimizer.flat
+        index = {id(p): off for p, off in zip(flat.params, flat.offsets)}
+        for k, p in self.model.named_parameters():
+            off = index[id(p)]
+            self.params[off:off + p.numel()].copy_(sd[k].reshape(-1).to(self.params.device, torch.float32))
+        for (k, _), v in zip(self._live, self._buffer_views):
+            v.copy_(sd[k].to(v.device, torch.float32))
+
+    def state_dict(self):
+        return {"mode": self.mode, "decay": self.decay, "final_decay": self.final_decay,
+                "total_steps": self.total_steps, "num_updates": self.num_updates}
+
+    def load_state_dict(self, sd):
+        self.check_arguments(sd["mode"], sd["decay"], sd["final_decay"], sd["total_steps"])
+        self.mode, self.decay, self.final_decay = sd["mode"], float(sd["decay"]), sd["final_decay"]
+        self.total_steps, self.num_updates = sd["total_steps"], int(sd["num_updates"])
+
+    # ------------------------------------------------------------------ SWA's BatchNorm pass
+    def update_bn(self, batches, forward):
+        """re-estimate the running statistics of the AVERAGED model (torch.optim.swa_utils.update_bn): inside applied(),
+        zero mean / unit variance, every BatchNorm's momentum None (the cumulative average, me._training_momentum),
+        `forward(batch)` in training mode without autograd over `batches`; then momenta, counters and mode return.  The
+        live statistics are untouched: the exit swap carries the new ones into the average's storage."""
+        bns = [m for m in self.model.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)
+               and m.track_running_stats and m.running_mean is not None]
+        if not bns:
+            return
+        with self.applied():
+            was_training = self.model.training
+            saved = []
+            for bn in bns:
+                ME._flush_batch_counter(bn)
+                saved.append((bn.momentum, bn.num_batches_tracked.clone(), bn.training))
+                bn.running_mean.zero_()
+                bn.running_var.fill_(1.0)
+                bn.num_batches_tracked.zero_()
+                bn.momentum = None
+            try:
+                self.model.train()
+                with torch.no_grad():
+                    for batch in batches:
+                        forward(batch)
+            finally:
+                for bn, (momentum, count, _) in zip(bns, saved):
+                    ME._flush_batch_counter(bn)
+                    bn.momentum = momentum
+                    bn.num_batches_tracked.copy_(count)
+                self.model.train(was_training)
+                for bn, (_, _, training) in zip(bns, saved):
+                    bn.training = training
 
 
 # ------------------------------------------------------------------ learning-rate schedules (stepped per epoch)

@@ -47,7 +47,7 @@ from . import precision as _precision
 from .evaluate import CLASS_NAMES, per_class_iou
 from .losses import AUX_CRITERIA, BEV_CRITERIA, POINT_CRITERIA
 from .metrics import MetricLayout, MetricsWriter, StepMetrics
-from .optim import make_optimizer, make_scheduler, shard_indices
+from .optim import WeightAverage, make_optimizer, make_scheduler, shard_indices
 from .trainer import LiDOGStep, RobustStep, SourceStep, setup_data_parallel
 
 
@@ -653,8 +653,15 @@ class Fit:
                  train_data=None, val_data=None, shuffle=True, resume=None, auto_resume=False, prefetch=True,
                  device="cuda", log=None, state_dict=None, num_sources=None, log_every_n_steps=0, metric_sources=None,
                  val_precision=None, precision=None, sem_criterion="SoftDICELoss", sem_bev_criterion=None,
-                 sem_aux_criterion=None, sem_aux_weight=1.0):
-        """`sem_criterion` / `sem_bev_criterion`: losses.sem_criterion / sem_bev_criterion of the reference's
+                 sem_aux_criterion=None, sem_aux_weight=1.0, weight_average=None, avg_decay=0.996, avg_decay_final=None,
+                 avg_start_epoch=0):
+        """`weight_average`: None, "ema" or "swa": an optim.WeightAverage of the model's weights and running statistics,
+        updated by one launch after every training step of an epoch >= `avg_start_epoch`.  "ema" decays by `avg_decay`,
+        or from `avg_decay` to `avg_decay_final` on the reference's cosine schedule over the steps that remain from
+        `avg_start_epoch` to `epochs`.  Once it has been updated every validation runs a second time with the averaged
+        model in place (history record `validation_avg`, metrics.jsonl keys `validation_avg/...`) and every checkpoint
+        carries the average (checkpoint.save_lightning_checkpoint).  The live run does not change by a bit.
+        `sem_criterion` / `sem_bev_criterion`: losses.sem_criterion / sem_bev_criterion of the reference's
         configurations, by name (build_step); the validation loss is the point criterion's.
         `sem_aux_criterion` / `sem_aux_weight`: an auxiliary point loss by name (losses.make_aux_criterion:
         LovaszSoftmaxLoss) added to the point loss times its weight, in the training steps and in the validation loss.
@@ -695,6 +702,13 @@ class Fit:
             num_sources=num_sources, precision=precision, sem_criterion=sem_criterion,
             sem_bev_criterion=sem_bev_criterion, sem_aux_criterion=sem_aux_criterion, sem_aux_weight=sem_aux_weight)
         self.opt = self.step.opt
+        self.avg, self.avg_start_epoch = None, int(avg_start_epoch)
+        if weight_average is not None:
+            if not 0 <= self.avg_start_epoch < max(epochs, 1):
+                raise ValueError(f"avg_start_epoch {avg_start_epoch}: an epoch of the run, 0 .. {epochs - 1}")
+            per_epoch = len(self._epoch_batches(self.train_data, 0, False))
+            self.avg = WeightAverage(self.opt, self.model, weight_average, avg_decay, avg_decay_final,
+                                     max(per_epoch * (epochs - self.avg_start_epoch), 1))
         self.epoch, self.global_step = 0, 0
         self.history = []
         self.log_every, self.metrics, self.metrics_writer = int(log_every_n_steps), None, None
@@ -707,9 +721,13 @@ class Fit:
         if auto_resume and save_dir and resume is None:
             resume = last_checkpoint(save_dir)
         if resume:
-            ck = load_training_checkpoint(self.model, resume, self.opt, self.sched, map_location=device)
+            ck = load_training_checkpoint(self.model, resume, self.opt, self.sched, map_location=device,
+                                          weight_average=self.avg)
             self.epoch, self.global_step = ck["epoch"] + 1, ck["global_step"]
             self.log(f"resumed from {resume}: next epoch {self.epoch}, global step {self.global_step}")
+            if self.avg is not None:
+                self.log(f"weight average ({self.avg.mode}): {self.avg.num_updates} updates restored" if self.avg.num_updates
+                         else f"weight average ({self.avg.mode}): {resume} holds none, the average starts afresh")
 
     # ------------------------------------------------------------------ data
     def _epoch_batches(self, data, epoch, shuffle):
@@ -732,14 +750,22 @@ class Fit:
         return {"sem_loss": float(loss), "source_iou": float(iou[present].mean()) if bool(present.any()) else 0.0,
                 "per_class_iou": iou.tolist()}
 
-    def validate(self, epoch, limit=None):
+    def validate(self, epoch, limit=None, tag="validation"):
         if self.val_data is None:
             return None
         if isinstance(self.val_data, dict):    # one validation set per source (validation_step's dataloader_idx)
-            return {name: self._validate(data, epoch, limit, name) for name, data in self.val_data.items()}
-        return self._validate(self.val_data, epoch, limit)
+            return {name: self._validate(data, epoch, limit, name, tag) for name, data in self.val_data.items()}
+        return self._validate(self.val_data, epoch, limit, tag=tag)
 
-    def _validate(self, data, epoch, limit=None, phase=None):
+    def validate_averaged(self, epoch, limit=None):
+        """the same passes with the averaged weights and running statistics in place (None before the first update);
+        applied() is entered outside the precision scope, so a bf16 pass packs the averaged weights"""
+        if self.avg is None or self.avg.num_updates == 0 or self.val_data is None:
+            return None
+        with self.avg.applied():
+            return self.validate(epoch, limit, tag="validation_avg")
+
+    def _validate(self, data, epoch, limit=None, phase=None, tag="validation"):
         res = []
         with _precision.scope(self.model, self.val_precision):     # bf16: one pack per validation pass
             for ids in self._epoch_batches(data, 0, False)[:limit]:
@@ -753,21 +779,21 @@ class Fit:
             dist.all_reduce(t)
             out["sem_loss"], out["source_iou"] = (t / self.world).tolist()
         if self.metrics_writer is not None and epoch >= 0:       # not the sanity steps: Lightning logs none of them
-            self.metrics_writer.write(self._validation_record(out, res, phase))
+            self.metrics_writer.write(self._validation_record(out, res, phase, tag))
         return out
 
-    def _validation_record(self, out, res, phase):
+    def _validation_record(self, out, res, phase, tag="validation"):
         """validation_step's keys (trainer_lighting_2d.py:316-324); a class's IoU is the mean over the batches whose
-        labels hold it (on this rank), filed under its own name"""
+        labels hold it (on this rank), filed under its own name.  `tag`: "validation_avg" for the averaged model's pass"""
         if phase is None:
             phase = training_source_names(self.train_data, 1)[0]
-        rec = {"step": self.global_step, f"validation/{phase}/sem_loss": out["sem_loss"],
-               f"validation/{phase}/source_iou": out["source_iou"]}
+        rec = {"step": self.global_step, f"{tag}/{phase}/sem_loss": out["sem_loss"],
+               f"{tag}/{phase}/source_iou": out["source_iou"]}
         for c, name in enumerate(CLASS_NAMES):
             v = [r["per_class_iou"][c] for r in res if r["per_class_iou"][c] >= 0]
             if v:
-                rec[f"validation/{phase}/{name}_source_iou"] = sum(v) / len(v)
-        rec["validation/epoch"] = out["epoch"]
+                rec[f"{tag}/{phase}/{name}_source_iou"] = sum(v) / len(v)
+        rec[f"{tag}/epoch"] = out["epoch"]
         return rec
 
     # ------------------------------------------------------------------ checkpoints (ModelCheckpoint, :222-225)
@@ -778,7 +804,7 @@ class Fit:
         os.makedirs(d, exist_ok=True)
         path = os.path.join(d, f"epoch={epoch}-step={self.global_step}.ckpt")
         save_lightning_checkpoint(self.model, path, epoch=epoch, global_step=self.global_step, optimizer=self.opt,
-                                  scheduler=self.sched)
+                                  scheduler=self.sched, weight_average=self.avg)
         return path
 
     # ------------------------------------------------------------------ the loop
@@ -800,6 +826,8 @@ class Fit:
                     self.metrics.next_step, self.metrics.epoch = self.global_step + 1, epoch
                 out = self.step.training_step(cur, epoch=epoch, prefetch=nxt if self.prefetch else None)
                 losses.append(out["loss"])
+                if self.avg is not None and epoch >= self.avg_start_epoch:
+                    self.avg.update()
                 self.global_step += 1
                 cur = nxt
             lr_used = self.opt.lr
@@ -812,6 +840,8 @@ class Fit:
                 rec["metrics"] = self.metrics.finish()
             if self.val_data is not None and (epoch + 1) % self.check_val == 0:
                 rec["validation"] = self.validate(epoch)
+                if self.avg is not None and self.avg.num_updates > 0:
+                    rec["validation_avg"] = self.validate_averaged(epoch)
             if dist.is_available() and dist.is_initialized():
                 from .comm import _TRANSPORTS
                 for tr in _TRANSPORTS.values():                 # a statistics message that never arrived invalidates the epoch
@@ -907,8 +937,32 @@ def parse_args(argv=None):
                          "(LovaszSoftmaxLoss: the mIoU surrogate of Berman et al., csrc/lovasz.hip; default: none)")
     ap.add_argument("--sem-aux-weight", type=float, default=argparse.SUPPRESS, metavar="W",
                     help="weight of --sem-aux-criterion in the point loss (default 1.0)")
+    ap.add_argument("--weight-average", default=argparse.SUPPRESS, choices=list(WeightAverage.MODES),
+                    help="average the weights and running statistics along the trajectory, one launch per step "
+                         "(optim.WeightAverage): ema (the reference's MomentumUpdater) or swa (the uniform average); "
+                         "validation then also scores the averaged model and checkpoints carry it "
+                         "(eval_target --weights averaged)")
+    ap.add_argument("--avg-decay", type=float, default=argparse.SUPPRESS, metavar="TAU",
+                    help="ema: the decay, in [0, 1] (default 0.996)")
+    ap.add_argument("--avg-decay-final", type=float, default=argparse.SUPPRESS, metavar="TAU",
+                    help="ema: the decay rises from --avg-decay to this on a cosine over the averaged steps "
+                         "(default: constant)")
+    ap.add_argument("--avg-start-epoch", type=int, default=argparse.SUPPRESS, metavar="E",
+                    help="the first epoch whose steps are averaged (default 0)")
     scans.add_file_arguments(ap, "--files", "train on")
     a = ap.parse_args(argv)
+    if not hasattr(a, "weight_average"):
+        for name in ("avg_decay", "avg_decay_final", "avg_start_epoch"):
+            if hasattr(a, name):
+                ap.error(f"--{name.replace('_', '-')} goes with --weight-average")
+    else:
+        try:
+            WeightAverage.check_arguments(a.weight_average, getattr(a, "avg_decay", 0.996),
+                                          getattr(a, "avg_decay_final", None), 1)
+        except ValueError as e:
+            ap.error(f"--weight-average: {e}")
+        if not 0 <= getattr(a, "avg_start_epoch", 0) < max(a.epochs, 1):
+            ap.error(f"--avg-start-epoch {a.avg_start_epoch}: an epoch of the run, 0 .. {a.epochs - 1}")
     if hasattr(a, "sem_aux_weight") and not hasattr(a, "sem_aux_criterion"):
         ap.error("--sem-aux-weight goes with --sem-aux-criterion")
     if hasattr(a, "sem_aux_weight") and not a.sem_aux_weight > 0:
@@ -1029,6 +1083,12 @@ def sem_aux_of(a):
     return getattr(a, "sem_aux_criterion", None), getattr(a, "sem_aux_weight", 1.0)
 
 
+def weight_average_of(a):
+    """Fit's weight_average / avg_* arguments of parsed arguments (weight_average None when it was not given)"""
+    return dict(weight_average=getattr(a, "weight_average", None), avg_decay=getattr(a, "avg_decay", 0.996),
+                avg_decay_final=getattr(a, "avg_decay_final", None), avg_start_epoch=getattr(a, "avg_start_epoch", 0))
+
+
 def main(argv=None):
     a = parse_args(argv)
     fit = _fit_from_args(a)
@@ -1052,7 +1112,7 @@ def _fit_from_args(a):
                auto_resume=a.auto_resume, log_every_n_steps=getattr(a, "log_every_n_steps", 0),
                val_precision=val_precision_of(a), precision=precision_of(a), sem_criterion=sem_criterion_of(a),
                sem_bev_criterion=sem_bev_criterion_of(a), sem_aux_criterion=sem_aux_criterion,
-               sem_aux_weight=sem_aux_weight)
+               sem_aux_weight=sem_aux_weight, **weight_average_of(a))
 
 
 def _data_from_args(a):

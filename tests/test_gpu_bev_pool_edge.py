@@ -18,6 +18,11 @@ BOUND = 2.0
 POOLS = [(5, 3, 1), (3, 2, 1), (2, 2, 0), (8, 3, 4), (8, 1, 0)]
 
 
+def _dev(t):
+    """every float operand the tests hand to the pooling kernels: the feature rows and the image gradient"""
+    return t.cuda()
+
+
 def _bits_equal(a, b):
     a, b = a.detach().cpu().contiguous(), b.detach().cpu().contiguous()
     return a.shape == b.shape and torch.equal(a.view(torch.int32), b.view(torch.int32))
@@ -76,10 +81,11 @@ def _run(coords, feats, B, pool, gout, rowbits, monkeypatch):
     """(image, feature gradient, the same gradient from a second backward run, row bitmask buffer or None)"""
     from lidog_amd import bev
     monkeypatch.setattr(bev, "SPARSE_CONV1", rowbits)
-    fg = feats.clone().cuda().requires_grad_(True)
+    fg = _dev(feats.clone()).requires_grad_(True)
     out = bev._Sparse2SuperFn.apply(fg, coords.cuda(), B, BOUND, 0.05, pool)
-    g1, = torch.autograd.grad(out, fg, gout.cuda(), retain_graph=True)
-    g2, = torch.autograd.grad(out, fg, gout.cuda())
+    gd = _dev(gout)
+    g1, = torch.autograd.grad(out, fg, gd, retain_graph=True)
+    g2, = torch.autograd.grad(out, fg, gd)
     torch.cuda.synchronize()
     return out.detach(), g1, g2, getattr(out.grad_fn, "_lidog_support", None)
 
@@ -172,10 +178,11 @@ def test_no_row_one_row_last_pixel(n, rowbits, monkeypatch):
     Ho = (H + 2 * pool[2] - pool[0]) // pool[1] + 1
     gout = torch.randn((B, C, Ho, Ho), generator=torch.Generator().manual_seed(3))
     monkeypatch.setattr(bev, "SPARSE_CONV1", rowbits)
-    fg = feats.clone().cuda().requires_grad_(True)
+    fg = _dev(feats.clone()).requires_grad_(True)
     out = bev._Sparse2SuperFn.apply(fg, coords.cuda(), B, bound, 0.05, pool)
-    g1, = torch.autograd.grad(out, fg, gout.cuda(), retain_graph=True)
-    g2, = torch.autograd.grad(out, fg, gout.cuda())
+    gd = _dev(gout)
+    g1, = torch.autograd.grad(out, fg, gd, retain_graph=True)
+    g2, = torch.autograd.grad(out, fg, gd)
     if n == 0:
         assert tuple(out.shape) == (B, C, Ho, Ho) and not bool(out.any()) and tuple(g1.shape) == (0, C)
         return

@@ -38,8 +38,13 @@ def _map(name, kind):
     return _CMS[name].kernel_map(1, stride, ks, dil)
 
 
-def _nan(*shape):
-    return torch.full(shape, NAN, dtype=torch.float32, device="cuda")
+def _nan(*shape, dtype=torch.float32):
+    return torch.full(shape, NAN, dtype=dtype, device="cuda")
+
+
+def _dev(t):
+    """every float operand the tests own"""
+    return t.cuda()
 
 
 def _bf(t):
@@ -49,9 +54,9 @@ def _bf(t):
 
 def _operands(n_in, K, Cin, Cout, seed):
     g = torch.Generator().manual_seed(seed)
-    x = torch.randn(n_in, Cin, generator=g).cuda()
-    W = (torch.randn(K, Cin, Cout, generator=g) * 0.1).cuda()
-    b = torch.randn(Cout, generator=g).cuda()
+    x = _dev(torch.randn(n_in, Cin, generator=g))
+    W = _dev(torch.randn(K, Cin, Cout, generator=g) * 0.1)
+    b = _dev(torch.randn(Cout, generator=g))
     return x, W, b
 
 
@@ -67,7 +72,7 @@ def _pack(*kernels):
         desc.append(((W.data_ptr() - kernels[0].data_ptr()) // 4, off, K, Cin, Cout, tiles))
         off += W.numel()
         tiles += K * (-(-Cin // 32)) * (-(-Cout // 32))
-    buf = torch.full((off,), NAN, dtype=torch.bfloat16, device="cuda")
+    buf = _nan(off, dtype=torch.bfloat16)
     call("lidog_pack_kernels_bf16", ptr(kernels[0]), ptr(buf), ptr(torch.tensor(desc, dtype=torch.int64).cuda()),
          len(kernels), tiles)
     return [buf[d[1]:d[1] + W.numel()].view(W.shape[0], W.shape[2], W.shape[1]) for d, W in zip(desc, kernels)]
@@ -92,7 +97,7 @@ def test_pack_is_bit_equal_to_torch_rounding():
         flat[:len(TIES)] = torch.tensor(TIES)                      # +-0 and the ties of tests/test_bf16_cpu.py
         flat[-len(TIES):] = torch.tensor(TIES) * 2.0 ** -20
         W[K - 1, Cin - 1, :len(TIES)] = torch.tensor(TIES) * 2.0 ** 10
-        kernels.append(W.cuda())
+        kernels.append(_dev(W))
     packed = _pack(*kernels)
     for W, Wp in zip(kernels, packed):
         want = W.transpose(1, 2).contiguous().bfloat16()
@@ -178,9 +183,9 @@ class Os:
         (self.Wp,) = _pack(self.W)
         self.sorted = _sorted(self.m)
         g = torch.Generator().manual_seed(Cin + 7 * Cout)
-        self.bn = tuple(v.cuda() for v in (torch.randn(Cout, generator=g) * 0.3, torch.rand(Cout, generator=g) + 0.5,
-                                           torch.rand(Cout, generator=g) + 0.5, torch.randn(Cout, generator=g) * 0.3))
-        self.res = torch.randn(self.n, Cout, generator=g).cuda()       # mean, invstd, weight, bias; residual
+        self.bn = tuple(_dev(v) for v in (torch.randn(Cout, generator=g) * 0.3, torch.rand(Cout, generator=g) + 0.5,
+                                          torch.rand(Cout, generator=g) + 0.5, torch.randn(Cout, generator=g) * 0.3))
+        self.res = _dev(torch.randn(self.n, Cout, generator=g))      # mean, invstd, weight, bias; residual
 
     def os_bn(self, x, residual, relu):
         from lidog_amd._lib import call, ptr

@@ -32,6 +32,18 @@ KINDS = ["k3", "s2", "tr", "k1"]
 _SCENES = {}
 
 
+def _fill(shape, value, dtype=torch.float32):
+    """every output and workspace the tests own; value None: uninitialised (torch.empty)"""
+    if value is None:
+        return torch.empty(shape, dtype=dtype, device="cuda")
+    return torch.full(shape, value, dtype=dtype, device="cuda")
+
+
+def _dev(t):
+    """every float operand the tests own"""
+    return t.cuda()
+
+
 def _manager(coords):
     import lidog_amd.me as ME
     st = ME.SparseTensor(coordinates=coords.cuda(), features=torch.ones((coords.shape[0], 1), device="cuda"))
@@ -105,8 +117,8 @@ def _wgrad(A, pair_a, G, pair_g, k_off, chunk, Cin, Cout):
     item_off = torch.from_numpy(item_off).cuda()
     slabs = _slabs(Cin, Cout, n_items)
     assert slabs >= n_items
-    partial = torch.full((max(slabs, 1), Cin, Cout), NAN, device="cuda")
-    gW = torch.full((K, Cin, Cout), NAN, device="cuda")
+    partial = _fill((max(slabs, 1), Cin, Cout), NAN)
+    gW = _fill((K, Cin, Cout), NAN)
     call("lidog_sconv_wgrad_bf16", ptr(A), ptr(pair_a), ptr(G), ptr(pair_g), ptr(items), n_items, ptr(item_off), K, Cin,
          Cout, ptr(partial), ptr(gW))
     torch.cuda.synchronize()
@@ -120,8 +132,9 @@ def _bf16(t):
 def _operands(n_a, n_g, Cin, Cout, seed, exact):
     g = torch.Generator().manual_seed(seed)
     if exact:
-        return (R.exact_operands((n_a, Cin), g, -15, 15, 0.5, "cuda"), R.exact_operands((n_g, Cout), g, -15, 15, 0.5, "cuda"))
-    return _bf16(torch.randn((n_a, Cin), generator=g)).cuda(), _bf16(torch.randn((n_g, Cout), generator=g)).cuda()
+        return (_dev(R.exact_operands((n_a, Cin), g, -15, 15, 0.5, "cuda")),
+                _dev(R.exact_operands((n_g, Cout), g, -15, 15, 0.5, "cuda")))
+    return _dev(_bf16(torch.randn((n_a, Cin), generator=g))), _dev(_bf16(torch.randn((n_g, Cout), generator=g)))
 
 
 def _check_all(cm, kind, Cin, Cout, monkeypatch, record_property, tag):
@@ -181,7 +194,7 @@ def test_two_calls_give_the_same_bits(Cin, Cout, monkeypatch):
     cm = _scene("small")
     pair_a, pair_g, k_off, n_a, n_g = _pairs(cm, "k3")
     g = torch.Generator().manual_seed(9)
-    A, G = torch.randn((n_a, Cin), generator=g).cuda(), torch.randn((n_g, Cout), generator=g).cuda()
+    A, G = _dev(torch.randn((n_a, Cin), generator=g)), _dev(torch.randn((n_g, Cout), generator=g))
     lay = _layouts(k_off, Cin, Cout, monkeypatch)
     for name in ("fit1", "short"):
         a, _ = _wgrad(A, pair_a, G, pair_g, k_off, lay[name], Cin, Cout)
@@ -213,7 +226,7 @@ def test_a_nan_and_an_inf_stay_in_their_offset_and_channel(Cin, Cout, scene, kin
     chunk = _short(k_off, Cin, Cout)
     assert chunk == 24
     g = torch.Generator().manual_seed(3)
-    A, G = torch.randn((n_a, Cin), generator=g).cuda(), torch.randn((n_g, Cout), generator=g).cuda()
+    A, G = _dev(torch.randn((n_a, Cin), generator=g)), _dev(torch.randn((n_g, Cout), generator=g))
     assert bool((G != 0).all())
     clean, _ = _wgrad(A, pair_a, G, pair_g, k_off, chunk, Cin, Cout)
     assert bool(torch.isfinite(clean).all())

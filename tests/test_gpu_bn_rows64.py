@@ -49,6 +49,18 @@ CASES = (
 )
 
 
+def _fill(shape, value, dtype=torch.float32):
+    """every output and workspace the tests own; value None: uninitialised (torch.empty)"""
+    if value is None:
+        return torch.empty(shape, dtype=dtype, device="cuda")
+    return torch.full(shape, value, dtype=dtype, device="cuda")
+
+
+def _dev(t):
+    """every float operand the tests own, and the running statistics the kernels update in place"""
+    return t.cuda()
+
+
 def _data(n, C, seed):
     g = torch.Generator().manual_seed(seed)
     x = torch.randn((n, C), generator=g) * 2 + 0.5
@@ -58,7 +70,7 @@ def _data(n, C, seed):
     p = dict(w=torch.rand(C, generator=g) + 0.5, b=torch.randn(C, generator=g),
              rm=torch.randn(C, generator=g), rv=torch.rand(C, generator=g) + 0.5,
              res=torch.randn((n, C), generator=g), dy=torch.randn((n, C), generator=g))
-    return x.cuda(), {k: v.cuda() for k, v in p.items()}
+    return _dev(x), {k: _dev(v) for k, v in p.items()}
 
 
 def _elem_bar(got, ref, scale, what, c=5.05):
@@ -117,9 +129,9 @@ def _bwd(x, dy, y_mask_src, mean, invstd, p, n, C, mode, training=True):
     from lidog_amd._lib import call, ptr
     L = _lib.load()
     y, bits = y_mask_src
-    ws = torch.empty(max(L.lidog_bn_reduce_ws(C, 1), 1), dtype=torch.float64, device="cuda")
-    sums = torch.full((2 * C + 1,), NAN, dtype=torch.float64, device="cuda")
-    dw, db = torch.full((C,), NAN, device="cuda"), torch.full((C,), NAN, device="cuda")
+    ws = _fill((max(L.lidog_bn_reduce_ws(C, 1), 1),), None, torch.float64)
+    sums = _fill((2 * C + 1,), NAN, torch.float64)
+    dw, db = _fill((C,), NAN), _fill((C,), NAN)
     ry = y if mode == "y" else None
     rw, rb = (p["w"], p["b"]) if mode == "x" else (None, None)
     rbits = bits if mode == "bits" else None
@@ -127,7 +139,7 @@ def _bwd(x, dy, y_mask_src, mean, invstd, p, n, C, mode, training=True):
          ptr(ws), float(n), ptr(dw), ptr(db), ptr(rw), ptr(rb))
     if not training:
         sums.zero_()
-    dx, dres = torch.full_like(x, NAN), torch.full_like(x, NAN)
+    dx, dres = _fill(x.shape, NAN), _fill(x.shape, NAN)
     call("lidog_bn_bwd_apply_bits", ptr(dy), ptr(x), ptr(ry), ptr(rbits), n, C, 1, ptr(mean), ptr(invstd), ptr(p["w"]),
          ptr(sums), float(n), ptr(dx), ptr(dres), None, None, ptr(rb))
     torch.cuda.synchronize()
@@ -173,21 +185,21 @@ def test_row_batchnorm_vs_float64(C, n, record_property):
     if n == "bench4":
         n = _bench()["n4"]
     x, p = _data(n, C, C * 7919 + n)
-    ws = torch.empty(max(L.lidog_bn_reduce_ws(C, 1), 1), dtype=torch.float64, device="cuda")
-    sums = torch.full((2 * C + 1,), NAN, dtype=torch.float64, device="cuda")
-    mean, invstd = torch.full((C,), NAN, device="cuda"), torch.full((C,), NAN, device="cuda")
-    rm, rv = p["rm"].clone(), p["rv"].clone()
+    ws = _fill((max(L.lidog_bn_reduce_ws(C, 1), 1),), None, torch.float64)
+    sums = _fill((2 * C + 1,), NAN, torch.float64)
+    mean, invstd = _fill((C,), NAN), _fill((C,), NAN)
+    rm, rv = _dev(p["rm"].clone()), _dev(p["rv"].clone())
     call("lidog_bn_stats", ptr(x), n, C, 1, ptr(sums), ptr(ws), float(n), EPS, MOM, ptr(mean), ptr(invstd), ptr(rm),
          ptr(rv))
     torch.cuda.synchronize()
     worst = {"stats": _check_fwd_stats(sums, mean, invstd, rm, rv, x, p, n, f"C{C} n{n}")}
     c4 = C % 4 == 0
     # forward with residual + ReLU (+ the bit mask where the layout has one), and without residual
-    y = torch.full_like(x, NAN)
-    bits = torch.full((max(L.lidog_relu_bits_words(n, C), 1),), -1, dtype=torch.int32, device="cuda") if c4 else None
+    y = _fill(x.shape, NAN)
+    bits = _fill((max(L.lidog_relu_bits_words(n, C), 1),), -1, torch.int32) if c4 else None
     call("lidog_bn_apply_bits", ptr(x), n, C, 1, ptr(mean), ptr(invstd), ptr(p["w"]), ptr(p["b"]), ptr(p["res"]), 1, ptr(y),
          ptr(bits))
-    y_nr = torch.full_like(x, NAN)
+    y_nr = _fill(x.shape, NAN)
     call("lidog_bn_apply", ptr(x), n, C, 1, ptr(mean), ptr(invstd), ptr(p["w"]), ptr(p["b"]), None, 1, ptr(y_nr))
     torch.cuda.synchronize()
     ref, scale = _y_ref(x, mean, invstd, p, p["res"], True)
@@ -207,9 +219,9 @@ def test_row_batchnorm_vs_float64(C, n, record_property):
         wb = max(wb, _check_bwd(got, x, p["dy"], mask, mean, invstd, p, n, f"C{C} n{n} bwd mask {mode}"))
     worst["bwd"] = wb
     # evaluation mode: running statistics as constants
-    inv_e = torch.full((C,), NAN, device="cuda")
+    inv_e = _fill((C,), NAN)
     call("lidog_bn_eval_invstd", ptr(p["rv"]), EPS, C, ptr(inv_e))
-    ye = torch.full_like(x, NAN)
+    ye = _fill(x.shape, NAN)
     call("lidog_bn_apply", ptr(x), n, C, 1, ptr(p["rm"]), ptr(inv_e), ptr(p["w"]), ptr(p["b"]), None, 0, ptr(ye))
     torch.cuda.synchronize()
     inv64 = 1.0 / torch.sqrt(p["rv"].double() + float(np.float32(EPS)))
@@ -235,17 +247,17 @@ def test_sync_apply_on_one_shard_vs_float64_of_the_whole_batch(C, record_propert
     h = n // 2 + 3
     parts = []
     for lo, hi in ((0, h), (h, n)):
-        s = torch.full((2 * C + 1,), NAN, dtype=torch.float64, device="cuda")
-        ws = torch.empty(L.lidog_bn_reduce_ws(C, 1), dtype=torch.float64, device="cuda")
+        s = _fill((2 * C + 1,), NAN, torch.float64)
+        ws = _fill((L.lidog_bn_reduce_ws(C, 1),), None, torch.float64)
         call("lidog_bn_stats", ptr(x[lo:hi]), hi - lo, C, 1, ptr(s), ptr(ws), float(hi - lo), 0.0, 0.0, None, None, None,
              None)
         parts.append(s)
     sums = parts[0] + parts[1]              # the all-reduce in double; sums[2C] = n
     for shard, rows in (("half", h), ("empty", 0)):
-        mean, invstd = torch.full((C,), NAN, device="cuda"), torch.full((C,), NAN, device="cuda")
-        rm, rv = p["rm"].clone(), p["rv"].clone()
-        y = torch.full((max(rows, 1), C), NAN, device="cuda")
-        bits = torch.full((max(L.lidog_relu_bits_words(rows, C), 1),), -1, dtype=torch.int32, device="cuda")
+        mean, invstd = _fill((C,), NAN), _fill((C,), NAN)
+        rm, rv = _dev(p["rm"].clone()), _dev(p["rv"].clone())
+        y = _fill((max(rows, 1), C), NAN)
+        bits = _fill((max(L.lidog_relu_bits_words(rows, C), 1),), -1, torch.int32)
         call("lidog_bn_apply_sync", ptr(x), rows, C, ptr(sums), EPS, MOM, ptr(mean), ptr(invstd), ptr(rm), ptr(rv),
              ptr(p["w"]), ptr(p["b"]), ptr(p["res"]), 1, ptr(y), ptr(bits))
         torch.cuda.synchronize()
@@ -268,15 +280,15 @@ def test_sync_apply_equals_finalize_then_apply_bit_for_bit(C, rows, residual):
     L = _lib.load()
     n = 141                                  # rows of the whole batch behind the sums; this shard holds `rows` of them
     x, p = _data(n, C, 31 * C + rows)
-    sums = torch.full((2 * C + 1,), NAN, dtype=torch.float64, device="cuda")
-    ws = torch.empty(L.lidog_bn_reduce_ws(C, 1), dtype=torch.float64, device="cuda")
+    sums = _fill((2 * C + 1,), NAN, torch.float64)
+    ws = _fill((L.lidog_bn_reduce_ws(C, 1),), None, torch.float64)
     call("lidog_bn_stats", ptr(x), n, C, 1, ptr(sums), ptr(ws), float(n), 0.0, 0.0, None, None, None, None)
     res = p["res"] if residual else None
     got = {}
     for form in ("sync", "two_pass"):
-        o = dict(mean=torch.full((C,), NAN, device="cuda"), invstd=torch.full((C,), NAN, device="cuda"),
-                 rm=p["rm"].clone(), rv=p["rv"].clone(), y=torch.full((max(rows, 1), C), NAN, device="cuda"),
-                 bits=torch.full((max(L.lidog_relu_bits_words(rows, C), 1),), -1, dtype=torch.int32, device="cuda"))
+        o = dict(mean=_fill((C,), NAN), invstd=_fill((C,), NAN),
+                 rm=_dev(p["rm"].clone()), rv=_dev(p["rv"].clone()), y=_fill((max(rows, 1), C), NAN),
+                 bits=_fill((max(L.lidog_relu_bits_words(rows, C), 1),), -1, torch.int32))
         if form == "sync":
             call("lidog_bn_apply_sync", ptr(x), rows, C, ptr(sums), EPS, MOM, ptr(o["mean"]), ptr(o["invstd"]), ptr(o["rm"]),
                  ptr(o["rv"]), ptr(p["w"]), ptr(p["b"]), ptr(res), 1, ptr(o["y"]), ptr(o["bits"]))
@@ -313,15 +325,15 @@ def test_fused_statistics_epilogues_at_bench_size(C, record_property):
     n = m.n_out
     g = torch.Generator().manual_seed(C)
     _, p = _data(n, C, C + 5)
-    bias = (torch.randn(C, generator=g) + 3.0).cuda()
+    bias = _dev(torch.randn(C, generator=g) + 3.0)
     # reduction of product rows with the statistics in its epilogue
-    T = torch.randn((m.P, C), generator=g).cuda()
+    T = _dev(torch.randn((m.P, C), generator=g))
     rp, rl = m.rows("out")
-    out = torch.full((n, C), NAN, device="cuda")
-    sums = torch.full((2 * C + 1,), NAN, dtype=torch.float64, device="cuda")
-    ws = torch.empty(L.lidog_sconv_reduce_stats_ws(n, C), dtype=torch.float64, device="cuda")
-    mean, invstd = torch.full((C,), NAN, device="cuda"), torch.full((C,), NAN, device="cuda")
-    rm, rv = p["rm"].clone(), p["rv"].clone()
+    out = _fill((n, C), NAN)
+    sums = _fill((2 * C + 1,), NAN, torch.float64)
+    ws = _fill((L.lidog_sconv_reduce_stats_ws(n, C),), None, torch.float64)
+    mean, invstd = _fill((C,), NAN), _fill((C,), NAN)
+    rm, rv = _dev(p["rm"].clone()), _dev(p["rv"].clone())
     call("lidog_sconv_reduce_rows_stats", ptr(T), ptr(rp), ptr(rl), n, C, ptr(bias), ptr(out), ptr(sums), ptr(ws),
          float(n), EPS, MOM, ptr(mean), ptr(invstd), ptr(rm), ptr(rv))
     torch.cuda.synchronize()
@@ -331,13 +343,13 @@ def test_fused_statistics_epilogues_at_bench_size(C, record_property):
     # output-stationary convolution with the statistics in its epilogue
     perm, wm, order = _sorted(m)
     Cin = 32
-    x = torch.randn((n, Cin), generator=g).cuda()
-    W = (torch.randn((27, Cin, C), generator=g) * 0.2).cuda()
-    out2 = torch.full((n, C), NAN, device="cuda")
-    sums2 = torch.full((2 * C + 1,), NAN, dtype=torch.float64, device="cuda")
-    ws2 = torch.empty(L.lidog_sconv_os_stats_ws(n, C), dtype=torch.float64, device="cuda")
-    mean2, invstd2 = torch.full((C,), NAN, device="cuda"), torch.full((C,), NAN, device="cuda")
-    rm2, rv2 = p["rm"].clone(), p["rv"].clone()
+    x = _dev(torch.randn((n, Cin), generator=g))
+    W = _dev(torch.randn((27, Cin, C), generator=g) * 0.2)
+    out2 = _fill((n, C), NAN)
+    sums2 = _fill((2 * C + 1,), NAN, torch.float64)
+    ws2 = _fill((L.lidog_sconv_os_stats_ws(n, C),), None, torch.float64)
+    mean2, invstd2 = _fill((C,), NAN), _fill((C,), NAN)
+    rm2, rv2 = _dev(p["rm"].clone()), _dev(p["rv"].clone())
     call("lidog_sconv_os_stats", ptr(x), ptr(m.nbr), n, 27, ptr(perm), ptr(wm), ptr(order), ptr(W), ptr(bias), Cin, C,
          ptr(out2), ptr(sums2), ptr(ws2), float(n), EPS, MOM, ptr(mean2), ptr(invstd2), ptr(rm2), ptr(rv2))
     torch.cuda.synchronize()
@@ -346,16 +358,16 @@ def test_fused_statistics_epilogues_at_bench_size(C, record_property):
                                                    const_channel=False))
     # data-gradient reduction with the BatchNorm backward sums in its epilogue (pre = the BatchNorm's input rows)
     rpi, rli = m.rows("in")
-    Tg = torch.randn((m.P, C), generator=g).cuda()
+    Tg = _dev(torch.randn((m.P, C), generator=g))
     pre = out
-    y = torch.full_like(pre, NAN)
+    y = _fill(pre.shape, NAN)
     call("lidog_bn_apply", ptr(pre), n, C, 1, ptr(mean), ptr(invstd), ptr(p["w"]), ptr(p["b"]), None, 1, ptr(y))
     worst = 0.0
     for mode in ("y", "x", "none"):
-        gout = torch.full((n, C), NAN, device="cuda")
-        s3 = torch.full((2 * C + 1,), NAN, dtype=torch.float64, device="cuda")
-        ws3 = torch.empty(L.lidog_bn_reduce_ws(C, 1), dtype=torch.float64, device="cuda")
-        dw, db = torch.full((C,), NAN, device="cuda"), torch.full((C,), NAN, device="cuda")
+        gout = _fill((n, C), NAN)
+        s3 = _fill((2 * C + 1,), NAN, torch.float64)
+        ws3 = _fill((L.lidog_bn_reduce_ws(C, 1),), None, torch.float64)
+        dw, db = _fill((C,), NAN), _fill((C,), NAN)
         ry = y if mode == "y" else None
         rw, rb = (p["w"], p["b"]) if mode == "x" else (None, None)
         call("lidog_sconv_reduce_rows_bwdstats", ptr(Tg), ptr(rpi), ptr(rli), n, C, ptr(p["res"]), ptr(gout), ptr(pre),

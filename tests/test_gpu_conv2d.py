@@ -20,6 +20,18 @@ pytestmark = pytest.mark.gpu
 NAN = float("nan")
 
 
+def _fill(shape, value, dtype=torch.float32):
+    """every output and workspace of the kernel tests; value None: uninitialised (torch.empty)"""
+    if value is None:
+        return torch.empty(shape, dtype=dtype, device="cuda")
+    return torch.full(shape, value, dtype=dtype, device="cuda")
+
+
+def _dev(t):
+    """every float operand of the kernel tests"""
+    return t.cuda()
+
+
 def _gen(*key):
     s = 0
     for k in key:
@@ -83,27 +95,27 @@ K3_CASES = [
 @pytest.mark.parametrize("B,Cin,H,W,Cout,ws_slabs", K3_CASES)
 def test_conv2d_k3s2_kernels_vs_float64(B, Cin, H, W, Cout, ws_slabs, kind, record_property):
     g = _gen(B, Cin, H, W, Cout, ws_slabs or 0, kind == "exact")
-    x = _operands(kind, g, (B, Cin, H, W), "x").cuda()
-    w = _operands(kind, g, (Cout, Cin, 3, 3), "w").cuda()
+    x = _dev(_operands(kind, g, (B, Cin, H, W), "x"))
+    w = _dev(_operands(kind, g, (Cout, Cin, 3, 3), "w"))
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-    gy = _operands(kind, g, (B, Cout, Ho, Wo), "gy").cuda()
+    gy = _dev(_operands(kind, g, (B, Cout, Ho, Wo), "gy"))
     x64, w64, gy64 = x.double(), w.double(), gy.double()
 
-    y = torch.full((B, Cout, Ho, Wo), NAN, device="cuda")
+    y = _fill((B, Cout, Ho, Wo), NAN)
     _call("lidog_conv2d_fwd", _p(x), _p(w), None, B, Cin, H, W, Cout, 3, 2, 1, _p(y))
     a, K = R.conv3s2_abs_terms(x64, w64, gy64, "fwd")
     _check(kind, y, R.conv3s2_fwd64(x64, w64), a, K, "fwd", record_property)
 
     if Cout % 32 == 0:
-        gx = torch.full_like(x, NAN)
-        ws = torch.empty(9 * Cin * Cout, device="cuda")
+        gx = _fill(x.shape, NAN)
+        ws = _fill((9 * Cin * Cout,), None)
         _call("lidog_conv2d_dgrad", _p(gy), _p(w), B, Cin, H, W, Cout, 3, 2, 1, _p(gx), _p(ws))
         a, K = R.conv3s2_abs_terms(x64, w64, gy64, "dgrad")
         _check(kind, gx, R.conv3s2_dgrad64(gy64, w64, H, W), a, K, "dgrad", record_property)
 
-    gw = torch.full_like(w, NAN)
+    gw = _fill(w.shape, NAN)
     n_ws = 32 * w.numel() if ws_slabs is None else ws_slabs * w.numel()
-    ws = torch.full((n_ws,), NAN, device="cuda")
+    ws = _fill((n_ws,), NAN)
     _call("lidog_conv2d_wgrad", _p(x), _p(gy), B, Cin, H, W, Cout, 3, 2, 1, _p(gw), None, _p(ws), n_ws)
     a, K = R.conv3s2_abs_terms(x64, w64, gy64, "wgrad")
     _check(kind, gw, R.conv3s2_wgrad64(x64, gy64), a, K, "wgrad", record_property)
@@ -126,26 +138,26 @@ PW_CASES = [
 @pytest.mark.parametrize("B,Cin,H,W,Cout,bias", PW_CASES)
 def test_conv2d_1x1_kernels_vs_float64(B, Cin, H, W, Cout, bias, kind, record_property):
     g = _gen(B, Cin, H, W, Cout, bias, kind == "exact")
-    x = _operands(kind, g, (B, Cin, H, W), "x").cuda()
-    w = _operands(kind, g, (Cout, Cin, 1, 1), "w").cuda()
-    b = _operands(kind, g, (Cout,), "b").cuda() if bias else None
-    gy = _operands(kind, g, (B, Cout, H, W), "gy").cuda()
+    x = _dev(_operands(kind, g, (B, Cin, H, W), "x"))
+    w = _dev(_operands(kind, g, (Cout, Cin, 1, 1), "w"))
+    b = _dev(_operands(kind, g, (Cout,), "b")) if bias else None
+    gy = _dev(_operands(kind, g, (B, Cout, H, W), "gy"))
     x64, w64, gy64 = x.double(), w.double(), gy.double()
     b64 = b.double() if bias else None
 
-    y = torch.full((B, Cout, H, W), NAN, device="cuda")
+    y = _fill((B, Cout, H, W), NAN)
     _call("lidog_conv2d_fwd", _p(x), _p(w), _p(b), B, Cin, H, W, Cout, 1, 1, 0, _p(y))
     a = R.pw_fwd64(x64.abs(), w64.abs(), None if b64 is None else b64.abs())
     _check(kind, y, R.pw_fwd64(x64, w64, b64), a, Cin + (1 if bias else 0), "fwd", record_property)
 
-    gx = torch.full_like(x, NAN)
+    gx = _fill(x.shape, NAN)
     _call("lidog_conv2d_dgrad", _p(gy), _p(w), B, Cin, H, W, Cout, 1, 1, 0, _p(gx), None)
     _check(kind, gx, R.pw_dgrad64(gy64, w64), R.pw_dgrad64(gy64.abs(), w64.abs()), Cout, "dgrad", record_property)
 
-    gw = torch.full_like(w, NAN)
-    gb = torch.full((Cout,), NAN, device="cuda") if bias else None
+    gw = _fill(w.shape, NAN)
+    gb = _fill((Cout,), NAN) if bias else None
     n_ws = 4 * B * (w.numel() + Cout)                      # lidog_amd.bev._Conv2dFn
-    ws = torch.full((n_ws,), NAN, device="cuda")
+    ws = _fill((n_ws,), NAN)
     _call("lidog_conv2d_wgrad", _p(x), _p(gy), B, Cin, H, W, Cout, 1, 1, 0, _p(gw), _p(gb), _p(ws), n_ws)
     rw, rb = R.pw_wgrad64(x64, gy64)
     aw, ab = R.pw_wgrad64(x64.abs(), gy64.abs())
@@ -271,30 +283,30 @@ def test_conv2d_over_support_vs_float64(B, Cin, H, W, Cout, pattern, kind, recor
     g = _gen(B, Cin, H, W, Cout, kind == "exact")
     sup = _support(B, Cin, H, W, pattern, g)
     support = torch.where(sup, torch.randint(0, 1000, sup.shape, generator=g), torch.full(sup.shape, -1)).int().cuda()
-    x = (_operands(kind, g, (B, Cin, H, W), "x") * sup).cuda()
-    w = _operands(kind, g, (Cout, Cin, 3, 3), "w").cuda()
+    x = _dev(_operands(kind, g, (B, Cin, H, W), "x") * sup)
+    w = _dev(_operands(kind, g, (Cout, Cin, 3, 3), "w"))
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-    gy = _operands(kind, g, (B, Cout, Ho, Wo), "gy").cuda()
+    gy = _dev(_operands(kind, g, (B, Cout, Ho, Wo), "gy"))
     x64, w64, gy64 = x.double(), w.double(), gy.double()
     L = load()
-    act = torch.empty(L.lidog_conv2d_support_ws(B, Cin, H, W), dtype=torch.int32, device="cuda")
+    act = _fill((L.lidog_conv2d_support_ws(B, Cin, H, W),), None, torch.int32)
     _call("lidog_conv2d_support", _p(support), B, Cin, H, W, _p(act))
-    ws = torch.empty(9 * Cin * Cout, device="cuda")
+    ws = _fill((9 * Cin * Cout,), None)
 
-    y = torch.full((B, Cout, Ho, Wo), NAN, device="cuda")
+    y = _fill((B, Cout, Ho, Wo), NAN)
     _call("lidog_conv2d_fwd_sparse", _p(x), _p(w), _p(act), B, Cin, H, W, Cout, _p(y), _p(ws))
     a, K = R.conv3s2_abs_terms(x64, w64, gy64, "fwd")
     _check(kind, y, R.conv3s2_fwd64(x64, w64), a, K, "fwd", record_property)
 
-    gx = torch.full_like(x, NAN)
+    gx = _fill(x.shape, NAN)
     _call("lidog_conv2d_dgrad_sparse", _p(gy), _p(w), _p(act), B, Cin, H, W, Cout, _p(gx), _p(ws))
     a, K = R.conv3s2_abs_terms(x64, w64, gy64, "dgrad")
     need = sup.cuda()
     _check(kind, gx, R.conv3s2_dgrad64(gy64, w64, H, W), a, K, "dgrad", record_property, mask=need)
 
     n_ws = L.lidog_conv2d_wgrad_sparse_ws(B, Cin, H, W, Cout)
-    gw = torch.full_like(w, NAN)
-    wsw = torch.full((n_ws,), NAN, device="cuda")
+    gw = _fill(w.shape, NAN)
+    wsw = _fill((n_ws,), NAN)
     _call("lidog_conv2d_wgrad_sparse", _p(x), _p(gy), _p(act), B, Cin, H, W, Cout, _p(gw), _p(wsw), n_ws)
     a, K = R.conv3s2_abs_terms(x64, w64, gy64, "wgrad")
     _check(kind, gw, R.conv3s2_wgrad64(x64, gy64), a, K, "wgrad", record_property)
@@ -307,18 +319,18 @@ def test_conv2d_over_support_of_an_empty_batch(Cin):
     from lidog_amd._lib import load
     H, W, Cout = 9, 70, 128
     L = load()
-    act = torch.zeros(max(1, L.lidog_conv2d_support_ws(0, Cin, H, W)), dtype=torch.int32, device="cuda")
-    x = torch.zeros((0, Cin, H, W), device="cuda")
-    gy = torch.zeros((0, Cout, 5, 35), device="cuda")
-    w = torch.randn((Cout, Cin, 3, 3), device="cuda")
+    act = _fill((max(1, L.lidog_conv2d_support_ws(0, Cin, H, W)),), 0, torch.int32)
+    x = _dev(torch.zeros((0, Cin, H, W), device="cuda"))
+    gy = _dev(torch.zeros((0, Cout, 5, 35), device="cuda"))
+    w = _dev(torch.randn((Cout, Cin, 3, 3), device="cuda"))
     support = torch.zeros((0, Cin, H, W), dtype=torch.int32, device="cuda")
-    ws = torch.empty(9 * Cin * Cout, device="cuda")
+    ws = _fill((9 * Cin * Cout,), None)
     _call("lidog_conv2d_support", _p(support), 0, Cin, H, W, _p(act))
     _call("lidog_conv2d_fwd_sparse", _p(x), _p(w), _p(act), 0, Cin, H, W, Cout, None, _p(ws))
     _call("lidog_conv2d_dgrad_sparse", _p(gy), _p(w), _p(act), 0, Cin, H, W, Cout, None, _p(ws))
-    gw = torch.full_like(w, NAN)
+    gw = _fill(w.shape, NAN)
     n_ws = max(1, L.lidog_conv2d_wgrad_sparse_ws(0, Cin, H, W, Cout))
-    wsw = torch.empty(n_ws, device="cuda")
+    wsw = _fill((n_ws,), None)
     _call("lidog_conv2d_wgrad_sparse", _p(x), _p(gy), _p(act), 0, Cin, H, W, Cout, _p(gw), _p(wsw), n_ws)
     torch.cuda.synchronize()
     assert torch.equal(gw, torch.zeros_like(gw))

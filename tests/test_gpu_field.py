@@ -56,12 +56,22 @@ def _operands(n, what):
     return _OPS[what][:n]
 
 
-def _dev(t, C):
-    return t[:, :C].contiguous().cuda()
+def _dev(t, C=None):
+    """every float operand the C ABI tests own: the first C columns of t, or (C None) t itself"""
+    return (t if C is None else t[:, :C].contiguous()).cuda()
 
 
-def _nan(*shape):
-    return torch.full(shape, NAN, dtype=torch.float32, device="cuda")
+def _nan(*shape, dtype=torch.float32):
+    if dtype == torch.int32:
+        return torch.full(shape, -7, dtype=dtype, device="cuda")
+    return torch.full(shape, NAN, dtype=dtype, device="cuda")
+
+
+def _fill(shape, value, dtype):
+    """the error word and the byte workspace; value None: uninitialised (torch.empty)"""
+    if value is None:
+        return torch.empty(shape, dtype=dtype, device="cuda")
+    return torch.full(shape, value, dtype=dtype, device="cuda")
 
 
 def _exact(got, ref64, what):
@@ -92,8 +102,8 @@ def _queries(coords, s, nq, seed):
 
 def _floor(query, s):
     from lidog_amd._lib import call, ptr
-    rows = torch.full((query.shape[0], 4), -7, dtype=torch.int32, device="cuda")
-    err = torch.zeros(1, dtype=torch.int32, device="cuda")
+    rows = _nan(query.shape[0], 4, dtype=torch.int32)
+    err = _fill((1,), 0, torch.int32)
     call("lidog_field_floor", ptr(query), query.shape[0], s, ptr(rows), ptr(err))
     return rows, int(err.item())
 
@@ -103,10 +113,10 @@ def _lists(inv, m):
     from lidog_amd._lib import call, ptr
     inv = inv.reshape(-1).contiguous()
     n = inv.shape[0]
-    row_ptr = torch.full((m + 1,), -7, dtype=torch.int32, device="cuda")
-    row_list = torch.full((max(n, 1),), -7, dtype=torch.int32, device="cuda")
+    row_ptr = _nan(m + 1, dtype=torch.int32)
+    row_list = _nan(max(n, 1), dtype=torch.int32)
     nbytes = _lib.load().lidog_field_lists_ws(n, m)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    ws = _fill((nbytes,), None, torch.uint8)
     call("lidog_field_lists", ptr(inv), n, m, ptr(row_ptr), ptr(row_list), ptr(ws), nbytes)
     return row_ptr, row_list
 
@@ -151,7 +161,7 @@ def _interp_case(cm, coords, s, query, what, channels=CHANNELS):
     import lidog_amd.me as ME
     m, nq = coords.shape[0], query.shape[0]
     nbr_ref, w = F.neighbours(coords, query, s)
-    qd = query.cuda()
+    qd = _dev(query)
     nbr = ME.interpolation_neighbours(cm, s, qd)
     assert nbr.shape == (8, nq) and nbr.cpu().tolist() == nbr_ref.tolist(), f"{what}: neighbour table"
     lists = _lists(nbr, m)
@@ -183,17 +193,17 @@ def test_floor_against_the_yardstick(s):
     q[:40, 1:] = torch.randint(-40, 40, (40, 3), generator=g).float()        # lattice points, negative ones too
     q[40] = torch.tensor([0., -0.25, -1e-30, 65535.75])
     q[41] = torch.tensor([4095., 3e9, -3e9, 2147483520.])                     # beyond int32 (finite): INT32_MIN, no bit
-    rows, err = _floor(q.cuda(), s)
+    rows, err = _floor(_dev(q), s)
     ref, ref_err = F.floor_rows(q, s)
     assert err == ref_err == 0 and rows.cpu().tolist() == ref.tolist()
     for bad, bit in (([0., NAN, 1., 2.], 2), ([0., 1., -INF, 2.], 2), ([0.5, 1., 1., 1.], 1), ([-1., 1., 1., 1.], 1),
                      ([4096., 1., 1., 1.], 1), ([NAN, 1., INF, 1.], 3)):
         qb = q.clone()
         qb[100] = torch.tensor(bad)
-        rows, err = _floor(qb.cuda(), s)
+        rows, err = _floor(_dev(qb), s)
         ref, ref_err = F.floor_rows(qb, s)
         assert err == ref_err == bit and rows.cpu().tolist() == ref.tolist(), bad
-    assert _floor(torch.zeros((0, 4)).cuda(), s)[1] == 0
+    assert _floor(_dev(torch.zeros((0, 4))), s)[1] == 0
 
 
 # ------------------------------------------------------------------ 2. interpolation through the C ABI

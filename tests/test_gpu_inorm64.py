@@ -28,6 +28,22 @@ def _nan(*shape, dtype=torch.float32):
     return torch.full(shape, NAN, dtype=dtype, device="cuda")
 
 
+def _fill(shape, value, dtype):
+    """the integer outputs and the byte workspace, pre-filled with an impossible value"""
+    return torch.full(shape, value, dtype=dtype, device="cuda")
+
+
+def _dev(t):
+    """every float operand the tests own"""
+    return t.cuda()
+
+
+def _case(lay):
+    """inorm_ref.make_case on the GPU with its float tensors through _dev"""
+    d = IR.make_case(lay, "cuda")
+    return {k: _dev(v) if torch.is_tensor(v) and v.is_floating_point() else v for k, v in d.items()}
+
+
 def _segments(batch, B):
     """lidog_in_segments on coords [n, 4] whose batch column is `batch`; outputs pre-filled with -7"""
     from lidog_amd import _lib
@@ -37,10 +53,10 @@ def _segments(batch, B):
     coords = torch.zeros((max(n, 1), 4), dtype=torch.int32, device="cuda")
     coords[:n, 0] = batch
     coords[:n, 1] = torch.arange(n, device="cuda", dtype=torch.int32)
-    perm, bid = (torch.full((max(n, 1),), -7, dtype=torch.int32, device="cuda") for _ in range(2))
-    seg_off = torch.full((B + 1,), -7, dtype=torch.int32, device="cuda")
+    perm, bid = (_fill((max(n, 1),), -7, torch.int32) for _ in range(2))
+    seg_off = _fill((B + 1,), -7, torch.int32)
     nbytes = L.lidog_in_segments_ws(n)
-    ws = torch.full((nbytes,), 0xA5, dtype=torch.uint8, device="cuda")
+    ws = _fill((nbytes,), 0xA5, torch.uint8)
     call("lidog_in_segments", ptr(coords), n, B, ptr(perm), ptr(seg_off), ptr(bid), ptr(ws), nbytes)
     torch.cuda.synchronize()
     return perm[:n], seg_off, bid[:n]
@@ -83,7 +99,7 @@ def _run_ibn(d, segs, o):
     perm, seg_off, bid = segs
     n, C, B, x, dy2 = d["n"], d["C"], d["B"], d["x"], d["dy2"]
     q = dict(bn_mean=_nan(C), bn_invstd=_nan(C), in_mean=o["mean"], in_invstd=o["invstd"], y_in=o["y"],
-             y=_nan(n, 2 * C), bits=torch.full((L.lidog_relu_bits_words(n, 2 * C),), -1, dtype=torch.int32, device="cuda"),
+             y=_nan(n, 2 * C), bits=_fill((L.lidog_relu_bits_words(n, 2 * C),), -1, torch.int32),
              bn_sums=_nan(2 * C + 1, dtype=torch.float64), bn_dw=_nan(C), bn_db=_nan(C), coef=_nan(2 * B * C),
              in_dw=_nan(C), in_db=_nan(C), dx=_nan(n, C))
     fsums = _nan(2 * C + 1, dtype=torch.float64)
@@ -112,7 +128,7 @@ def _record(record_property, r, prefix=""):
 @pytest.mark.timeout(60)
 @pytest.mark.parametrize("lay", IR.LAYOUTS, ids=[lay["id"] for lay in IR.LAYOUTS])
 def test_instance_norm_and_ibn_entries_vs_float64(lay, record_property):
-    d = IR.make_case(lay, "cuda")
+    d = _case(lay)
     segs = _segments(d["batch"], d["B"])
     _check_segments(*segs, d["batch"], d["B"])
     o = _run_in(d, segs)

@@ -61,6 +61,11 @@ def _nan(*shape, dtype=torch.float32):
     return torch.full(shape, NAN, dtype=dtype, device="cuda")
 
 
+def _fill(shape, value, dtype):
+    """the byte workspace of the global pooling"""
+    return torch.full(shape, value, dtype=dtype, device="cuda")
+
+
 def _side(m, side):
     import lidog_amd.me as ME
     return ME._pool_side(m, side)
@@ -298,7 +303,7 @@ def test_rows_without_pairs_and_all_minus_inf(C):
         else:
             _exact(y, ref, f"doctored lists {mode}")
     # every list of the real map: a window of -inf only returns -inf, at its first entry
-    ninf = torch.full((m.n_in, C), -INF, device="cuda")
+    ninf = _dev(torch.full((m.n_in, C), -INF), C)
     y, arg = _rows_max(ninf, _side(m, "out"))
     _, _, nbr = R.scene_map("line_x129", "k3s1")
     yref, aref = P.pool64(ninf, nbr, "max")
@@ -325,7 +330,7 @@ def _global(x, segs, mode):
     y = _nan(B, C)
     arg = _nan(B, C, dtype=torch.int32) if mode == "max" else None
     nbytes = _lib.load().lidog_pool_global_ws(n, B, C)
-    ws = torch.full((max(nbytes, 1),), 0xFF, dtype=torch.uint8, device="cuda")      # NaN partials until written
+    ws = _fill((max(nbytes, 1),), 0xFF, torch.uint8)      # NaN partials until written
     call("lidog_pool_global", ptr(x), n, C, B, ptr(perm), ptr(seg_off), {"sum": 0, "avg": 1, "max": 2}[mode], ptr(y),
          ptr(arg), ptr(ws), nbytes)
     return y, arg

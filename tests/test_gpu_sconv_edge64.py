@@ -64,12 +64,17 @@ def _map(name, kind):
 
 def _operands(n_in, n_out, K, Cin, Cout, seed):
     g = torch.Generator().manual_seed(seed)
-    x = torch.randn(n_in, Cin, generator=g).cuda()
-    W = (torch.randn(K, Cin, Cout, generator=g) * 0.1).cuda()
-    b = torch.randn(Cout, generator=g).cuda()
-    gy = torch.randn(n_out, Cout, generator=g).cuda()
-    ad = torch.randn(n_in, Cin, generator=g).cuda()
+    x = _dev(torch.randn(n_in, Cin, generator=g))
+    W = _dev(torch.randn(K, Cin, Cout, generator=g) * 0.1)
+    b = _dev(torch.randn(Cout, generator=g))
+    gy = _dev(torch.randn(n_out, Cout, generator=g))
+    ad = _dev(torch.randn(n_in, Cin, generator=g))
     return x, W, b, gy, ad
+
+
+def _dev(t):
+    """every float operand the tests own"""
+    return t.cuda()
 
 
 def _nan(*shape, dtype=torch.float32):
@@ -283,16 +288,16 @@ class Forms:
         self.nbr = R.scene_map(name, "k3s1")[2]
         self.nbr_t = R.transpose_map(self.nbr, self.n)
         self.x, self.W, self.b, self.gy, self.ad = _operands(self.n, self.n, 27, Cin, Cout, Cin * 977 + Cout)
-        self.Wt = self.W.transpose(1, 2).contiguous()
+        self.Wt = _dev(self.W.transpose(1, 2).contiguous())
         self.mfma = Cin % 32 == 0 and Cout % 32 == 0
         self.sorted = _sorted(m) if self.mfma else None
         g = torch.Generator().manual_seed(Cin + 7 * Cout)
         for C, tag in ((Cin, "in"), (Cout, "out")):       # BatchNorm vectors over the input / output channels
-            setattr(self, "bn_" + tag, tuple(v.cuda() for v in (
+            setattr(self, "bn_" + tag, tuple(_dev(v) for v in (
                 torch.randn(C, generator=g) * 0.3, torch.rand(C, generator=g) + 0.5, torch.rand(C, generator=g) + 0.5,
                 torch.randn(C, generator=g) * 0.3)))          # mean, invstd, weight, bias
-        self.res = torch.randn(self.n, Cout, generator=g).cuda()
-        self.pre = (torch.randn(self.n, Cin, generator=g) * 2 + 0.5).cuda()
+        self.res = _dev(torch.randn(self.n, Cout, generator=g))
+        self.pre = _dev(torch.randn(self.n, Cin, generator=g) * 2 + 0.5)
 
     # ---- building blocks
     def product(self, A, gather, B, Cin, Cout, core=1, units=(1, 0)):
@@ -523,7 +528,7 @@ def test_k2_s2_direct_scatter_writes_every_row(name, Cin, Cout, record_property)
     n_f, n_c = fine.shape[0], coarse.shape[0]
     assert (m.n_in, m.n_out, m.P) == (n_f, n_c, n_f)
     x_c, W, b, gy_c, _ = _operands(n_c, n_c, 8, Cin, Cout, Cin + 3 * Cout)
-    Wt = W.transpose(1, 2).contiguous()
+    Wt = _dev(W.transpose(1, 2).contiguous())
     up, down = {}, {}
     for core in (1, 0):
         assert L.lidog_set_sparse_core(core) == 0
@@ -536,7 +541,7 @@ def test_k2_s2_direct_scatter_writes_every_row(name, Cin, Cout, record_property)
     g = _all_equal(down, f"{name} k2 s2 data gradient")
     r2 = _inside(g, R.conv64(gy_c, Wt, None, nbr_t), R.bound(gy_c, Wt, None, nbr_t), f"{name} {Cout}->{Cin} k2 s2 dgrad")
     # k2 s2 forward: product rows, then the coarse rows' reduction in both forms
-    x_f = torch.randn(n_f, Cin, generator=torch.Generator().manual_seed(Cin)).cuda()
+    x_f = _dev(torch.randn(n_f, Cin, generator=torch.Generator().manual_seed(Cin)))
     T = _nan(m.P, Cout)
     ME._gemm(x_f, m.pair_in, W, None, m, Cin, Cout, T, None)
     forms = {"reduce": _nan(n_c, Cout)}
@@ -583,10 +588,10 @@ def test_gemm_addend_in_place(name, record_property):
     worst = 0.0
     for gather, mm, rows in ((m.pair_in, m, m.P), (None, ME._IdentityMap(n, "cuda"), n)):
         K = mm.K
-        ad = torch.randn(rows, Cout, generator=torch.Generator().manual_seed(rows)).cuda()
+        ad = _dev(torch.randn(rows, Cout, generator=torch.Generator().manual_seed(rows)))
         T0 = _nan(rows, Cout)
         ME._gemm(x, gather, W, None, mm, Cin, Cout, T0, None)
-        T = ad.clone()
+        T = _dev(ad.clone())
         call("lidog_sconv_gemm_addend", ptr(x), ptr(gather), ptr(W), ptr(mm.tiles[0]), ptr(mm.tiles[1]), ptr(mm.tiles[2]),
              mm.n_tiles, Cin, Cout, ptr(T), ptr(T), None)
         assert torch.equal(T, ad + T0), f"{name}: in place differs from product, then addend + product"

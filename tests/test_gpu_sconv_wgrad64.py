@@ -50,6 +50,18 @@ def sparse_core(request, monkeypatch):
     L.lidog_set_sparse_core(1)
 
 
+def _fill(shape, value, dtype=torch.float32):
+    """every output and workspace the tests own; value None: uninitialised (torch.empty)"""
+    if value is None:
+        return torch.empty(shape, dtype=dtype, device="cuda")
+    return torch.full(shape, value, dtype=dtype, device="cuda")
+
+
+def _dev(t):
+    """every float operand the tests own"""
+    return t.cuda()
+
+
 def _scene(name):
     """coordinate manager of a scene, cached per module (the bench maps are built once)"""
     if name not in _SCENES:
@@ -119,8 +131,8 @@ def _wgrad(A, pair_a, G, pair_g, k_off, chunk, Cin, Cout):
     items = torch.from_numpy(np.ascontiguousarray(items)).cuda()
     item_off = torch.from_numpy(item_off).cuda()
     slabs = _lib.load().lidog_sconv_wgrad_slabs(Cin, Cout, n_items)
-    partial = torch.full((max(slabs, 1), Cin, Cout), NAN, device="cuda")
-    gW = torch.full((K, Cin, Cout), NAN, device="cuda")
+    partial = _fill((max(slabs, 1), Cin, Cout), NAN)
+    gW = _fill((K, Cin, Cout), NAN)
     call("lidog_sconv_wgrad", ptr(A), ptr(pair_a), ptr(G), ptr(pair_g), ptr(items), n_items, ptr(item_off), K, Cin, Cout,
          ptr(partial), ptr(gW))
     torch.cuda.synchronize()
@@ -133,8 +145,9 @@ def _operands(n_a, n_g, Cin, Cout, seed, exact, P_max):
         # |a|, |g| <= 3 with half of them zero: sum |terms| of the largest offset ~ 0.7 P_k, below 2^24 up to the
         # bs-4 centre offset (~2.1 M pairs); small maps get wider operands
         hi = 3 if P_max > 200000 else 15
-        return (R.exact_operands((n_a, Cin), g, -hi, hi, 0.5, "cuda"), R.exact_operands((n_g, Cout), g, -hi, hi, 0.5, "cuda"))
-    return torch.randn((n_a, Cin), generator=g).cuda(), torch.randn((n_g, Cout), generator=g).cuda()
+        return (_dev(R.exact_operands((n_a, Cin), g, -hi, hi, 0.5, "cuda")),
+                _dev(R.exact_operands((n_g, Cout), g, -hi, hi, 0.5, "cuda")))
+    return _dev(torch.randn((n_a, Cin), generator=g)), _dev(torch.randn((n_g, Cout), generator=g))
 
 
 def _check_all(cm, kind, Cin, Cout, layouts, record_property, tag, s=1, precision=True):
@@ -211,10 +224,10 @@ def test_bias_gradient_colsum_vs_float64(scene, C, record_property):
     n = 5003 if scene == "small" else _scene("bench1").maps[1].n
     g = torch.Generator().manual_seed(C + n)
     for exact in (True, False):
-        x = R.exact_operands((n, C), g, -50, 50, 0.3, "cuda") if exact else torch.randn((n, C), generator=g).cuda()
+        x = _dev(R.exact_operands((n, C), g, -50, 50, 0.3, "cuda") if exact else torch.randn((n, C), generator=g))
         ref, ab = R.colsum64(x.double())
-        ws = torch.empty(_lib.load().lidog_colsum_ws(C), dtype=torch.float64, device="cuda")
-        out = torch.full((C,), NAN, device="cuda")
+        ws = _fill((_lib.load().lidog_colsum_ws(C),), None, torch.float64)
+        out = _fill((C,), NAN)
         call("lidog_colsum", ptr(x), n, C, ptr(out), ptr(ws))
         torch.cuda.synchronize()
         if exact:

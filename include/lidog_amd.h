@@ -816,6 +816,54 @@ int lidog_mix_gather_aug(const int32_t *coords_t, int64_t n_target, const int32_
                          double qy, double qz, int32_t *rows_out, int32_t n_cols, void *const *cols_host,
                          const int32_t *col_words_host, void *stream);
 
+/* ------------------------------------------------------------------ sensor-aware scan mixing (PolarMix, LaserMix)
+ * PolarMix (Xiao et al., NeurIPS 2022) swaps an azimuth sector between two voxelised scans and pastes rotated copies of
+ * the instance classes; LaserMix (Kong et al., CVPR 2023) interleaves the two scans by inclination band.  Neither is in
+ * the reference: the arithmetic below IS the definition (lidog_amd.data.polarmix_merge / lasermix_merge,
+ * tests/sensormix_ref.py).  Geometry is decided on the voxel centre in doubled integer units, X = 2x + 1, Y = 2y + 1,
+ * Z = 2z + 1, the sensor at the origin; azimuth and inclination do not depend on the voxel size.  The device evaluates
+ * no atan2, sqrt, sin or cos: the host passes float64 constants.  Every float64 product, sum and difference named below
+ * is rounded on its own, never fused.  Every position comes from the stable split of csrc/prims.hip: no atomics, the
+ * same bytes on every run. */
+/* One launch over the rows of both scans (coords0 [n0, 3], coords1 [n1, 3] int32; labels0 / labels1 int32 per row, NULL:
+ * no row is an instance row): keys [n0 + n1] int32, scan 0's rows first,
+ *   bit 0      in the sector: sa = ax * Y - ay * X, sb = bx * Y - by * X; wide == 0: sa >= 0 && sb < 0 (the sector from
+ *              direction a counter-clockwise to direction b, narrower than pi); wide != 0: sa >= 0 || sb < 0
+ *   bits 1-3   band = the number of the n_bounds <= 7 ascending inclination boundaries the row is at or above.
+ *              Boundary j is t2_host[j] = tan(theta_j)^2 >= 0 with neg_host[j] = (tan theta_j < 0) (HOST arrays); with
+ *              R = X * X + Y * Y (exact in int64 and in float64) a row is at or above it when
+ *              neg == 0: Z > 0 && double(Z * Z) >= t2 * double(R);  neg != 0: Z > 0 || double(Z * Z) <= t2 * double(R)
+ *   bit 4      0 <= label < 32 and bit `label` of instance_mask is set
+ * Precondition |x|, |y|, |z| < 2^24.  info [1] (device, int32) is zeroed here; a row outside the range sets info[0] = 1
+ * and its key is not written: the caller raises.  n0 + n1 == 0: info zeroed, nothing launched. */
+int lidog_sensormix_keys(const int32_t *coords0, const int32_t *labels0, int64_t n0, const int32_t *coords1,
+                         const int32_t *labels1, int64_t n1, double ax, double ay, double bx, double by, int32_t wide,
+                         const double *t2_host, const int32_t *neg_host, int32_t n_bounds, uint32_t instance_mask,
+                         int32_t *keys, int32_t *info, void *stream);
+/* int32 workspace of lidog_sensormix_select */
+int64_t lidog_sensormix_select_ws(int64_t n_base, int64_t n_donor);
+/* The three row lists of a merge, each ascending (lidog_split_rows with one slot): rows_keep = the base rows i with bit
+ * keys_base[i] of keep_keys set, rows_take / rows_paste = the donor rows with bit keys_donor[i] of take_keys /
+ * paste_keys set (a key outside [0, 32): in no list).  rows_keep has room for n_base, rows_take and rows_paste for
+ * n_donor entries.  sizes [6] (device, int32) = (0, |keep|, 0, |take|, 0, |paste|): the one read-back of a merge.  A
+ * set of keys that is 0 and an empty scan launch nothing for their list. */
+int lidog_sensormix_select(const int32_t *keys_base, int64_t n_base, const int32_t *keys_donor, int64_t n_donor,
+                           uint32_t keep_keys, uint32_t take_keys, uint32_t paste_keys, int32_t *rows_keep,
+                           int32_t *rows_take, int32_t *rows_paste, int32_t *sizes, int32_t *ws, void *stream);
+/* The merged voxel rows in one launch.  rows_out [n_keep + n_take + n_copies * n_paste, 4] int32 = (0, voxel), ready for
+ * lidog_coords_insert (16-byte aligned): base row rows_keep[r] for r < n_keep, then donor row rows_take[j], then for
+ * copy k = 0 .. n_copies - 1 (n_copies <= 8) donor row rows_paste[j] rotated about z by (c, s) = (cs_host[2k],
+ * cs_host[2k + 1]) (HOST, float64: cos and sin of the angle): U = double(x) + 0.5, V = double(y) + 0.5, x' = c * U -
+ * s * V, y' = s * U + c * V, voxel (floor(x'), floor(y'), z).  Base rows, taken rows and a copy with (c, s) == (1, 0)
+ * keep their integer voxel without a float round trip.  A list entry outside its scan (n_base, n_donor rows) is
+ * clamped, nothing outside is read.  Columns as lidog_mix_gather (base, donor, merged pointer triples), copied from the
+ * source row unchanged.  No row at all: nothing launched. */
+int lidog_sensormix_gather(const int32_t *coords_base, int64_t n_base, const int32_t *coords_donor, int64_t n_donor,
+                           const int32_t *rows_keep, int64_t n_keep, const int32_t *rows_take, int64_t n_take,
+                           const int32_t *rows_paste, int64_t n_paste, const double *cs_host, int32_t n_copies,
+                           int32_t *rows_out, int32_t n_cols, void *const *cols_host, const int32_t *col_words_host,
+                           void *stream);
+
 /* ------------------------------------------------------------------ SN car-size scaling: DBSCAN, cluster boxes, scaling
  * The start-up statistics of train_scaling_based.py:35-129 (get_average_dims clusters the car voxels of every drawn
  * scan with sklearn.cluster.DBSCAN) and the per-item scaling of utils/datasets/sn_scaling.py.  Integer atomics whose

@@ -8,6 +8,8 @@ Public surface:
                           LovaszSoftmaxLoss, the auxiliary point criterion (make_aux_criterion)
   lidog_amd.trainer       training step, Adam, RCCL data parallelism
   lidog_amd.trunk         the whole encoder-decoder as one launch sequence per pass (csrc/trunk.hip)
+  lidog_amd.data          voxelisation, collation and the scan mixes on the device: mix3d_merge, pointcutmix_merge,
+                          cosmix_merge, polarmix_merge, lasermix_merge (csrc/mix.hip, csrc/sensormix.hip)
   lidog_amd.cluster       DBSCAN and per-cluster boxes on the device (csrc/cluster.hip; the SN baseline's statistics)
   lidog_amd.evaluate      forward-only inference, the reference's mIoU; TargetEvaluator (csrc/evalstats.hip)
   lidog_amd.eval_target   `python -m lidog_amd.eval_target`: a checkpoint on one or two target domains, CSV + point clouds

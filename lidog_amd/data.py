@@ -10,7 +10,8 @@ The reference runs these in DataLoader worker processes with numpy; at >50 scans
 bottleneck, and both are the same hash / winner-map kernels as the hot path.
 
   pointcutmix_merge, cosmix_merge   PointCutMix / CoSMix scan mixing (utils/datasets/pointcutmix.py, cosmix.py), below
-  average_dims, scaling_params, sn_scale   the SN car-size scaling baseline (train_scaling_based.py:35-129,
+  polarmix_merge, lasermix_merge    the sensor-aware mixes PolarMix / LaserMix, defined in include/lidog_amd.h, below
+  average_dims, scaling_params, sn_scale  the SN car-size scaling baseline (train_scaling_based.py:35-129,
                    utils/datasets/sn_scaling.py)
   draw_augmentation, augment_item   sub_p / augmentation_list of the training datasets (dataset.py:58-72,
                    utils/common/augmentation.py, semantickitti_bev.py:209-252, synth4d.py:141-162), at the end
@@ -290,17 +291,11 @@ def _split(keys, slot_of_key, n_slots):
     return rows, start
 
 
-def _merge(scan0, scan1, sel, voxel_size, rows, start, n_take, subs=None, class_ops=None):
-    """target rows, then the selected source rows (lidog_mix_gather), re-quantised at voxel_size; the reference's dict.
-    class_ops (one op list per slot, as draw_ops returns them; [] when no class was drawn): CoSMix's in-merge
-    augmentation, lidog_mix_gather_aug writes the voxel rows itself."""
-    src, tgt = (scan0, scan1) if sel == 0 else (scan1, scan0)
+def _merge_columns(tgt, src, total):
+    """the merged columns of a gather: ({name: empty [total, ...]}, the (target, source, merged) pointer triples, the
+    32-bit words per row, the contiguous inputs the pointers belong to)"""
     dev = tgt["coordinates"].device
-    nt = tgt["coordinates"].shape[0]
-    total = nt + n_take
-    coords_t = tgt["coordinates"].to(torch.int32).contiguous()
-    coords_s = src["coordinates"].to(torch.int32).contiguous()
-    cols, ptrs, words = {}, [], []
+    cols, ptrs, words, inputs = {}, [], [], []
     for k in _MERGE_COLUMNS:
         if k not in tgt:
             continue
@@ -313,6 +308,21 @@ def _merge(scan0, scan1, sel, voxel_size, rows, start, n_take, subs=None, class_
         cols[k] = torch.empty((total,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev)
         ptrs += [t.data_ptr(), s.data_ptr(), cols[k].data_ptr()]
         words.append(row_bytes // 4)
+        inputs += [t, s]
+    return cols, ptrs, words, inputs
+
+
+def _merge(scan0, scan1, sel, voxel_size, rows, start, n_take, subs=None, class_ops=None):
+    """target rows, then the selected source rows (lidog_mix_gather), re-quantised at voxel_size; the reference's dict.
+    class_ops (one op list per slot, as draw_ops returns them; [] when no class was drawn): CoSMix's in-merge
+    augmentation, lidog_mix_gather_aug writes the voxel rows itself."""
+    src, tgt = (scan0, scan1) if sel == 0 else (scan1, scan0)
+    dev = tgt["coordinates"].device
+    nt = tgt["coordinates"].shape[0]
+    total = nt + n_take
+    coords_t = tgt["coordinates"].to(torch.int32).contiguous()
+    coords_s = src["coordinates"].to(torch.int32).contiguous()
+    cols, ptrs, words, _inputs = _merge_columns(tgt, src, total)
     perm = take = None
     n_slots = 0 if start is None else start.shape[0] - 1
     if subs is not None and n_slots:
@@ -453,6 +463,163 @@ def cosmix_merge(scan0, scan1, voxel_size=0.05, class_weights=None, sub_p=0.8, i
         # with the transforms the gather needs every class's extent: sub_p None passes its identity sub-samples
         return _merge(scan0, scan1, sel, voxel_size, rows, start, n_take,
                       subs if sub_p is not None or class_ops is not None else None, class_ops=class_ops)
+
+    return on_merge_stream(work, dev, [t for s in scans for t in s.values()])
+
+
+# ------------------------------------------------------------------ sensor-aware scan mixing: PolarMix and LaserMix
+# PolarMix (Xiao et al., NeurIPS 2022) and LaserMix (Kong et al., CVPR 2023) are not in the reference; include/lidog_amd.h
+# defines both in exact arithmetic on the voxel centres (X, Y, Z) = (2x + 1, 2y + 1, 2z + 1), the sensor at the origin,
+# and tests/sensormix_ref.py restates that in numpy.  The host makes the draws and the float64 constants (directions,
+# squared tangents, cosines and sines); the device writes one key per row, selects the three row lists (kept base rows,
+# taken donor rows, pasted donor rows) and gathers the merged voxel rows (csrc/sensormix.hip), which quantize_rows then
+# reduces to the first row of every voxel.  One device -> host read of the three sizes, one of quantize_rows.
+
+SENSORMIX_MAX_AREAS = 8         # 3 bits of band: at most 7 interior boundaries
+
+
+def draw_polarmix(rng, swap_prob=0.5, paste_prob=1.0):
+    """PolarMix's host draws, always all six in this order: the donor scan, the sector's start azimuth alpha in
+    [-pi, 0) (the sector is the half-plane alpha .. alpha + pi), the two paste rotations omega1 in [0, 2pi/3) and
+    omega2 in [2pi/3, 4pi/3), whether the sector is swapped, whether the instance classes are pasted"""
+    sel = draw_source(rng)
+    alpha = (rng.random_sample() - 1) * np.pi
+    omega1 = rng.random_sample() * 2 * np.pi / 3
+    omega2 = (rng.random_sample() + 1) * 2 * np.pi / 3
+    swap = bool(rng.random_sample() < swap_prob)
+    paste = bool(rng.random_sample() < paste_prob)
+    return {"source": sel, "alpha": float(alpha), "omega1": float(omega1), "omega2": float(omega2), "swap": swap,
+            "paste": paste}
+
+
+def draw_lasermix(rng, areas=(3, 4, 5, 6)):
+    """LaserMix's host draws: the scan whose odd bands are taken, then the number of inclination bands"""
+    sel = draw_source(rng)
+    return {"source": sel, "n_areas": int(rng.choice(areas))}
+
+
+def band_bounds(pitch, n_areas):
+    """(t2, neg) of the n_areas - 1 interior boundaries of the pitch range (degrees) cut into n_areas equal bands:
+    tan(theta)^2 and tan(theta) < 0, float64 and int32, as lidog_sensormix_keys takes them"""
+    lo, hi = float(pitch[0]), float(pitch[1])
+    if not (-90.0 < lo < hi < 90.0):
+        raise ValueError(f"pitch range {pitch}: -90 < lo < hi < 90 degrees")
+    if not 1 <= int(n_areas) <= SENSORMIX_MAX_AREAS:
+        raise ValueError(f"{n_areas} inclination bands (1 .. {SENSORMIX_MAX_AREAS})")
+    t = np.tan(np.linspace(np.radians(lo), np.radians(hi), int(n_areas) + 1)[1:-1])
+    return t * t, (t < 0).astype(np.int32)
+
+
+def instance_mask(instance_classes):
+    """the uint32 class mask of lidog_sensormix_keys"""
+    mask = 0
+    for c in instance_classes:
+        if not 0 <= int(c) < 32:
+            raise ValueError(f"instance class {c}: 0 .. 31 (label -1 is never pasted)")
+        mask |= 1 << int(c)
+    return mask
+
+
+def _key_set(pred):
+    """the keys k in [0, 32) of lidog_sensormix_keys with pred(sector bit, band, instance bit), as a bit set"""
+    return sum(1 << k for k in range(32) if pred(k & 1, (k >> 1) & 7, (k >> 4) & 1))
+
+
+def _sensor_merge(scan0, scan1, sel, a, b, bounds, mask, keep, take, paste, copies):
+    """base = the scan that is not `sel`: its rows whose key is in `keep`, then the donor's rows with a key in `take`,
+    then for every (c, s) of `copies` the donor's rows with a key in `paste` rotated about z; quantised.  The dict of
+    _merge plus `counts`, the sizes of those segments."""
+    donor, base = (scan0, scan1) if sel == 0 else (scan1, scan0)
+    dev = base["coordinates"].device
+    nb, nd = base["coordinates"].shape[0], donor["coordinates"].shape[0]
+    coords_b = base["coordinates"].to(torch.int32).contiguous()
+    coords_d = donor["coordinates"].to(torch.int32).contiguous()
+    labels_b = base["sem_labels"].to(torch.int32).contiguous() if mask else None
+    labels_d = donor["sem_labels"].to(torch.int32).contiguous() if mask else None
+    t2, neg = bounds
+    t2 = (ctypes.c_double * max(len(t2), 1))(*[float(v) for v in t2])
+    n_bounds = len(neg)
+    neg = (ctypes.c_int32 * max(n_bounds, 1))(*[int(v) for v in neg])
+    keys = torch.empty(max(nb + nd, 1), dtype=torch.int32, device=dev)
+    meta = torch.empty(8, dtype=torch.int32, device=dev)           # the three (start, size) pairs, then the range flag
+    call("lidog_sensormix_keys", ptr(coords_b), ptr(labels_b), nb, ptr(coords_d), ptr(labels_d), nd, float(a[0]),
+         float(a[1]), float(b[0]), float(b[1]), 0, t2, neg, n_bounds, mask, ptr(keys), ptr(meta[6:]))
+    lists = torch.empty(max(nb + 2 * nd, 1), dtype=torch.int32, device=dev)
+    rows_keep, rows_take, rows_paste = lists[:nb], lists[nb:nb + nd], lists[nb + nd:nb + 2 * nd]
+    ws = torch.empty(_lib.load().lidog_sensormix_select_ws(nb, nd), dtype=torch.int32, device=dev)
+    call("lidog_sensormix_select", ptr(keys[:nb]), nb, ptr(keys[nb:nb + nd]), nd, keep, take, paste, ptr(rows_keep),
+         ptr(rows_take), ptr(rows_paste), ptr(meta), ptr(ws))
+    m = meta.cpu().tolist()
+    if m[6]:
+        raise ValueError("voxel coordinates out of the range of the sensor-aware mixes: |x|, |y|, |z| < 2^24")
+    n_keep, n_take, n_paste = m[1], m[3], m[5]
+    n_copies = len(copies) if n_paste else 0
+    total = n_keep + n_take + n_copies * n_paste
+    cols, ptrs, words, _inputs = _merge_columns(base, donor, total)
+    col_ptrs = (ctypes.c_void_p * max(len(ptrs), 1))(*ptrs)
+    col_words = (ctypes.c_int32 * max(len(words), 1))(*words)
+    cs = (ctypes.c_double * max(2 * len(copies), 1))(*[float(v) for c_s in copies for v in c_s])
+    vrows = torch.empty((total, 4), dtype=torch.int32, device=dev)
+    call("lidog_sensormix_gather", ptr(coords_b), nb, ptr(coords_d), nd, ptr(rows_keep), n_keep, ptr(rows_take), n_take,
+         ptr(rows_paste), n_paste, cs, len(copies), ptr(vrows), len(words), col_ptrs, col_words)
+    q, index = quantize_rows(vrows, return_index=True)
+    out = {"coordinates": q}
+    for k in ("xyz", "features", "sem_labels"):
+        if k in cols:
+            out[k] = cols[k][index]
+    if "idx" in scan0:
+        out["idx"] = torch.cat([scan0["idx"].view(1, -1), scan1["idx"].view(1, -1)], dim=0)
+    if "sampled_idx" in cols:
+        out["sampled_idx"] = cols["sampled_idx"][index]
+    out["index"] = index
+    out["source"] = sel
+    out["counts"] = (n_keep, n_take) + (n_paste,) * len(copies)
+    return out
+
+
+def lasermix_merge(scan0, scan1, rng=np.random, pitch=(-25.0, 3.0), areas=(3, 4, 5, 6), draws=None):
+    """LaserMix on the GPU; scans as pointcutmix_merge.  Draws (draw_lasermix; `draws`: a ready dict, nothing is drawn)
+    the scan `source` and n_areas; the pitch range (degrees, the sensor's vertical field of view) is cut into n_areas
+    equal inclination bands, rows below the range counting to band 0 and rows above it to the last one.  Merged rows:
+    the OTHER scan's rows in even bands, ascending, then scan `source`'s rows in odd bands, ascending.  A voxel lies in
+    the same band in both scans, so the union holds no voxel twice; quantize_rows still gives the usual `index`.
+    Returns the dict of the other merges plus `counts` = (base rows kept, rows taken).  The inclination is that of the
+    voxel centre seen from the coordinate origin: the scans must be in their sensor's frame."""
+    scans = _check_scans(scan0, scan1)
+    d = draw_lasermix(rng, areas) if draws is None else draws
+    bounds = band_bounds(pitch, d["n_areas"])
+    dev = scan0["coordinates"].device
+
+    def work():
+        return _sensor_merge(scan0, scan1, d["source"], (1.0, 0.0), (1.0, 0.0), bounds, 0,
+                             _key_set(lambda s, band, i: band % 2 == 0), _key_set(lambda s, band, i: band % 2 == 1), 0,
+                             ())
+
+    return on_merge_stream(work, dev, [t for s in scans for t in s.values()])
+
+
+def polarmix_merge(scan0, scan1, rng=np.random, instance_classes=(0, 1), swap_prob=0.5, paste_prob=1.0, draws=None):
+    """PolarMix on the GPU; scans as pointcutmix_merge.  Draws (draw_polarmix, always all six; `draws`: a ready dict,
+    nothing is drawn) the donor scan `source`, alpha, omega1, omega2, swap and paste.  The sector is the half-plane of
+    azimuths alpha .. alpha + pi.  Merged rows: the other (base) scan's rows, ascending, with `swap` only those outside
+    the sector; with `swap` the donor's rows inside the sector; with `paste` the donor's rows whose label is in
+    instance_classes (the whole donor scan; label -1 never) three times: as they are, rotated about z by omega1 and by
+    omega2.  quantize_rows keeps the first row of every voxel.  features / sem_labels / xyz / sampled_idx are copied
+    from the source row: `xyz` is NOT rotated (as CoSMix's in-merge augmentation leaves it).  Returns the dict of the
+    other merges plus `counts` = (base rows kept, sector rows, then the instance rows once per copy)."""
+    scans = _check_scans(scan0, scan1)
+    mask = instance_mask(instance_classes)
+    d = draw_polarmix(rng, swap_prob, paste_prob) if draws is None else draws
+    a = (float(np.cos(d["alpha"])), float(np.sin(d["alpha"])))
+    copies = ((1.0, 0.0),) + tuple((float(np.cos(d[k])), float(np.sin(d[k]))) for k in ("omega1", "omega2"))
+    dev = scan0["coordinates"].device
+
+    def work():
+        keep = _key_set(lambda s, band, i: not s) if d["swap"] else 0xFFFFFFFF
+        take = _key_set(lambda s, band, i: s) if d["swap"] else 0
+        paste = _key_set(lambda s, band, i: i) if d["paste"] else 0
+        return _sensor_merge(scan0, scan1, d["source"], a, (-a[0], -a[1]), ((), ()), mask if d["paste"] else 0, keep,
+                             take, paste, copies)
 
     return on_merge_stream(work, dev, [t for s in scans for t in s.values()])
 

@@ -12,6 +12,8 @@ What the reference's entry scripts do through pytorch-lightning, as plain argume
     python -m torch.distributed.run --nproc-per-node N -m lidog_amd.train ...        (one process per GPU, RCCL)
     python -m lidog_amd.train --sources kitti120k nusc35k --source-weights 0.5 0.5 ...   (two sources, */multi/*.yaml)
     python -m lidog_amd.train --model MinkUNet34 --mix cosmix ...    (PointCutMix / CoSMix, configs/{pointcutmix,cosmix})
+    python -m lidog_amd.train --model MinkUNet34 --mix polarmix --mix-instance-classes 0 1 ...   (PolarMix)
+    python -m lidog_amd.train --model MinkUNet34 --mix lasermix --mix-pitch -25 3 ...   (LaserMix; neither is in the reference)
     python -m lidog_amd.train --model MinkUNet34 --mix cosmix --source-augment RandomRotation RandomScale ...
                                               (the source datasets' augmentation_list under --mix / --mix3d / --sn-targets)
     python -m lidog_amd.train --model MinkUNet34 --config kitti120k_cars --sn-targets nusc35k_cars ...   (SN, configs/SN)
@@ -41,8 +43,9 @@ from . import me as ME
 from . import scans
 from . import synth
 from .checkpoint import load_training_checkpoint, save_lightning_checkpoint
-from .data import (augment_item, check_augmentations, collate_items, cosmix_merge, draw_augmentation,
-                   draw_scaling, draw_source, mix3d_merge, on_merge_stream, pointcutmix_merge, scaling_params, sn_scale)
+from .data import (augment_item, band_bounds, check_augmentations, collate_items, cosmix_merge, draw_augmentation,
+                   draw_lasermix, draw_polarmix, draw_scaling, draw_source, instance_mask, lasermix_merge, mix3d_merge,
+                   on_merge_stream, pointcutmix_merge, polarmix_merge, scaling_params, sn_scale)
 from . import precision as _precision
 from .evaluate import CLASS_NAMES, per_class_iou
 from .losses import AUX_CRITERIA, BEV_CRITERIA, POINT_CRITERIA
@@ -150,16 +153,22 @@ class MixedSynthScans:
     on data.merge_stream, and the batch is handed to the caller's stream with an event: the merges' read-backs do not
     wait for a training step queued earlier.  CoSMix's class weights are the per-class label counts over each source's
     training scans (get_dataset_stats, synth4d.py:203-220; FileScans.class_counts over files); the voxel size is source
-    0's, as the reference's."""
+    0's, as the reference's.  SENSOR_METHODS (polarmix, lasermix) are the two sensor-aware mixes, which the reference
+    does not have: `instance_classes` are the classes PolarMix pastes, `pitch` (degrees) and `areas` the vertical field
+    of view and the band counts LaserMix draws from."""
 
     num_sources = 1
     METHODS = ("pointcutmix", "cosmix")
     ALL_METHODS = ("mix3d",) + METHODS
+    # PolarMix / LaserMix (lidog_amd.data.polarmix_merge / lasermix_merge): not in the reference.  Their draws need no
+    # device counts, so plan(i)["merge"] holds all of them.
+    SENSOR_METHODS = ("polarmix", "lasermix")
 
     def __init__(self, n0, n1, configs=("kitti120k", "kitti120k"), method="cosmix", sub_p=0.8, seed=1234, first=0,
-                 num_classes=7, items=None):
-        if method not in self.ALL_METHODS:
-            raise NotImplementedError(f"mixing method {method!r} (one of {self.ALL_METHODS})")
+                 num_classes=7, items=None, pitch=(-25.0, 3.0), instance_classes=(0, 1), areas=(3, 4, 5, 6)):
+        if method not in self.ALL_METHODS + self.SENSOR_METHODS:
+            raise NotImplementedError(f"mixing method {method!r} (one of {self.ALL_METHODS + self.SENSOR_METHODS})")
+        self.pitch, self.instance_classes, self.areas = tuple(pitch), tuple(instance_classes), tuple(areas)
         self.items = PlainSynthItems(configs, first) if items is None else items
         self.pairs = MultiSynthScans(n0, n1, configs, seed=seed, first=first)
         self.configs, self.method, self.seed, self.first = tuple(configs), method, int(seed), first
@@ -172,6 +181,13 @@ class MixedSynthScans:
             self.merge = lambda s0, s1, rng: mix3d_merge(s0, s1, voxel_size=self.voxel)
         elif method == "pointcutmix":
             self.merge = functools.partial(pointcutmix_merge, voxel_size=self.voxel)
+        elif method == "polarmix":
+            instance_mask(self.instance_classes)      # ValueError for a class outside 0 .. 31
+            self.merge = functools.partial(polarmix_merge, instance_classes=self.instance_classes)
+        elif method == "lasermix":
+            for n_areas in self.areas:
+                band_bounds(self.pitch, n_areas)      # ValueError for a bad pitch range or band count
+            self.merge = functools.partial(lasermix_merge, pitch=self.pitch, areas=self.areas)
         else:
             self.class_weights = tuple(self.items.class_weights((int(n0), int(n1)), num_classes))
             self.merge = functools.partial(cosmix_merge, voxel_size=self.voxel, class_weights=self.class_weights,
@@ -196,11 +212,17 @@ class MixedSynthScans:
         """the host side of item i in the current epoch: {'scans': (j0, j1), 'items': [draws of source 0's item, of
         source 1's] (None: an item that draws nothing), 'merge': {'source': the merge's first draw} (mix3d: {})}.  The
         merge's later draws (cells, classes, sub-samples, per-class transforms) follow from the same generator but
-        depend on counts the device makes from the two items.  Synthetic providers need no device; a FileScans
+        depend on counts the device makes from the two items; polarmix / lasermix need no counts, and 'merge' is the
+        whole dict of draw_polarmix / draw_lasermix.  Synthetic providers need no device; a FileScans
         provider reads the scan's point count from the loaded file."""
         js, draws, rng = self._draws(i, device)
-        return {"scans": tuple(js), "items": draws, "merge": {} if self.method == "mix3d" else
-                {"source": draw_source(rng)}}
+        if self.method == "polarmix":
+            merge = draw_polarmix(rng)
+        elif self.method == "lasermix":
+            merge = draw_lasermix(rng, self.areas)
+        else:
+            merge = {} if self.method == "mix3d" else {"source": draw_source(rng)}
+        return {"scans": tuple(js), "items": draws, "merge": merge}
 
     def _scan(self, s, j, device):
         return self.items.make_item(s, j, None, device)
@@ -879,9 +901,11 @@ def parse_args(argv=None):
                          "MultiBEVSourceDataset; each source is validated on its own")
     ap.add_argument("--source-weights", nargs=2, type=float, default=(0.5, 0.5))
     ap.add_argument("--mix3d", action="store_true")
-    ap.add_argument("--mix", default=None, choices=MixedSynthScans.METHODS,
+    ap.add_argument("--mix", default=None, choices=MixedSynthScans.METHODS + MixedSynthScans.SENSOR_METHODS,
                     help="PointCutMix / CoSMix (train_aug_based.py, pipeline.method): each item one scan mixed from a "
-                         "pair of the two --sources (default: --config twice), trained as one source with SoftDICE")
+                         "pair of the two --sources (default: --config twice), trained as one source with SoftDICE; "
+                         "polarmix / lasermix: the sensor-aware mixes (an azimuth sector swapped and instance classes "
+                         "pasted rotated; the scans interleaved by inclination band), used the same way")
     ap.add_argument("--sub-p", type=float, default=0.8, help="CoSMix: share of each drawn class's rows mixed in; "
                                                              "--augment: the datasets' sub_p, the share of a scan's "
                                                              "points every item draws")
@@ -917,6 +941,11 @@ def parse_args(argv=None):
                     help="SN over --files: the target datasets (their validation listings give the target car sizes)")
     ap.add_argument("--sn-target-label-maps", nargs="+", default=argparse.SUPPRESS, metavar="FILE",
                     help="one label map per --sn-target-files entry")
+    ap.add_argument("--mix-pitch", nargs=2, type=float, default=argparse.SUPPRESS, metavar=("LO", "HI"),
+                    help="--mix lasermix: the sensor's vertical field of view in degrees, cut into the inclination bands "
+                         "(default -25 3)")
+    ap.add_argument("--mix-instance-classes", nargs="+", type=int, default=argparse.SUPPRESS, metavar="C",
+                    help="--mix polarmix: the classes whose rows are pasted rotated (default 0 1: vehicle, person)")
     ap.add_argument("--log-every-n-steps", type=int, default=argparse.SUPPRESS, metavar="N",
                     help="record per-class IoU, class counts, losses and lr of every N-th training step on the GPU and "
                          "append them to <save-dir>/metrics.jsonl (the reference's entry scripts: 50; default 0: off)")
@@ -1023,6 +1052,16 @@ def parse_args(argv=None):
             ap.error("--mix and --mix3d are two different methods (pipeline.method): pass one of them")
         if a.sources is None and a.files is None:
             a.sources = [a.config, a.config]    # the single configs list one dataset twice
+    for name, method in (("mix_pitch", "lasermix"), ("mix_instance_classes", "polarmix")):
+        if hasattr(a, name) and a.mix != method:
+            ap.error(f"--{name.replace('_', '-')} goes with --mix {method}")
+    try:
+        if hasattr(a, "mix_pitch"):
+            band_bounds(a.mix_pitch, 1)
+        if hasattr(a, "mix_instance_classes"):
+            instance_mask(a.mix_instance_classes)
+    except ValueError as e:
+        ap.error(f"--mix {a.mix}: {e}")
     if sn:
         flag = "--sn-targets" if a.sn_targets is not None else "--sn-target-files"
         if a.model in ("MinkUNet34BEV", "MinkUNet34Robust"):   # train_scaling_based.py:142-155, PLTTrainer: SoftDICE only
@@ -1055,6 +1094,16 @@ def mix_method_of(a):
         return a.mix
     merged = getattr(a, "source_augment", None) is not None or getattr(a, "files", None) is not None
     return "mix3d" if getattr(a, "mix3d", False) and merged else None
+
+
+def mix_options_of(a):
+    """MixedSynthScans' pitch / instance_classes of parsed arguments (its defaults when the flags were not given)"""
+    kw = {}
+    if getattr(a, "mix_pitch", None) is not None:
+        kw["pitch"] = tuple(a.mix_pitch)
+    if getattr(a, "mix_instance_classes", None) is not None:
+        kw["instance_classes"] = tuple(a.mix_instance_classes)
+    return kw
 
 
 def val_precision_of(a):
@@ -1129,7 +1178,8 @@ def _data_from_args(a):
         train, val = _file_data(a, bev)
     elif src_aug is not None and mix_method is not None:
         items = AugmentedSynthScans(a.scans, a.sources, src_aug, sub_p=a.sub_p, seed=a.seed)
-        train = MixedSynthScans(a.scans, a.scans, a.sources, method=mix_method, seed=a.seed, items=items)
+        train = MixedSynthScans(a.scans, a.scans, a.sources, method=mix_method, seed=a.seed, items=items,
+                                **mix_options_of(a))
         val = per_source_val()
     elif src_aug is not None:               # --sn-targets
         configs = a.sources or [a.config]
@@ -1156,7 +1206,8 @@ def _data_from_args(a):
         else:
             val = SynthScans(a.val_scans, a.config, first=10 ** 6, bev_size=bev) if a.val_scans else None
     elif getattr(a, "mix", None):
-        train = MixedSynthScans(a.scans, a.scans, a.sources, method=a.mix, sub_p=a.sub_p, seed=a.seed)
+        train = MixedSynthScans(a.scans, a.scans, a.sources, method=a.mix, sub_p=a.sub_p, seed=a.seed,
+                                **mix_options_of(a))
         val = {name: SynthScans(a.val_scans, c, first=10 ** 6 + i * synth.SOURCE1_SEED, bev_size=bev)
                for i, (name, c) in enumerate(zip(source_names(a.sources), a.sources))} if a.val_scans else None
     elif a.sources:
@@ -1182,7 +1233,7 @@ def _file_data(a, bev):
         names = [n for n, _ in a.files]
         if mix_method is not None:
             train = MixedSynthScans(len(listings[0]), len(listings[1]), names, method=mix_method, seed=a.seed,
-                                    items=items)
+                                    items=items, **mix_options_of(a))
         else:
             faces = []
             for (n, p), lut in zip(sn_files, scans.luts_from_files(a.sn_target_label_maps)):

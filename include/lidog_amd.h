@@ -489,6 +489,41 @@ int lidog_sgd_step(float *param, const float *grad, float *momentum_buf, int64_t
 int lidog_wavg_apply(const int64_t *table, int32_t n_segs, int64_t n_blocks, int32_t mode, float c0, float c1,
                      void *stream);
 
+/* ------------------------------------------------------------------ gradient norm, clipping, SAM (csrc/sam.hip)
+ * The global gradient norm over the optimiser's flat gradient buffer and its two users, lidog_amd.optim: torch's
+ * clip_grad_norm_ (Lightning's gradient_clip_val) and the ascent step of sharpness-aware minimisation (SAM, Foret et al.,
+ * ICLR 2021; adaptive: ASAM, Kwon et al., ICML 2021, in its common form e = rho w^2 g / || |w| g ||).  Nothing in the
+ * reference uses either.  The norm stays a double in DEVICE memory: the two users read it there, nothing is read back.
+ * Every fp32 operation below is rounded on its own (no contraction into a fused multiply-add), sqrt and the divisions in
+ * double are the IEEE operations, so a numpy restatement gives the same bits (tests/sam_ref.py).  Every kernel walks at
+ * most LIDOG_FLAT_MAX_BLOCKS workgroups of 256 threads, one float4 per thread and sweep, grid-strided beyond: float4
+ * where the buffers of a call share their alignment mod 16 (a scalar head up to the first 16-byte boundary, a scalar
+ * tail), scalar elsewhere.  No atomics, no state kept between launches. */
+#define LIDOG_FLAT_MAX_BLOCKS 2048
+#define LIDOG_SQNORM_PLAIN 0    /* t = g */
+#define LIDOG_SQNORM_ADAPTIVE 1 /* t = |w| * g, rounded to fp32 */
+/* out[0] = sum over i < n of (double)t_i * (double)t_i (the product of two fp32 values is exact in fp64), summed in
+ * fp64 in a FIXED order: a thread sums its elements in index order into four lanes that are added pairwise, a workgroup
+ * adds its threads in a fixed tree and stores one partial sum into `ws`; a second launch of one workgroup adds the
+ * partial sums in the same way and stores out[0].  The same call gives the same bytes every time; the order (not the
+ * value beyond n 2^-53 relative) depends on n and on the alignment of g.  w: NULL in plain mode.  n == 0: out[0] = 0.
+ * ws: lidog_flat_sqnorm_ws(n) bytes of device memory, 8-byte aligned, written before it is read. */
+int64_t lidog_flat_sqnorm_ws(int64_t n);
+int lidog_flat_sqnorm(const float *g, const float *w, int64_t n, int32_t mode, void *ws, double *out, void *stream);
+/* SAM's ascent step in one launch: backup[i] = w[i], then w[i] = w[i] + e[i] with
+ *   coef = (float)((double)rho / (sqrt(*sqnorm) + 1e-12))           (every thread computes it from the device word)
+ *   plain:    e = coef * g            adaptive:    e = ((w * w) * g) * coef
+ * An element whose gradient is +-0 (a parameter that received none: FlatParams.zero_grad clears the buffer) is not
+ * added to: w[i] keeps its bits, a -0.0 included, whatever coef is.  Restoring is a copy of backup into w (hipMemcpyAsync, or lidog_wavg_apply's COPY), never w - e.  The three
+ * ranges must not overlap. */
+int lidog_sam_perturb(float *w, const float *g, float *backup, int64_t n, const double *sqnorm, float rho,
+                      int32_t adaptive, void *stream);
+/* torch.nn.utils.clip_grad_norm_(max_norm, norm_type=2) on the flat gradient: norm = grad_scale * sqrt(*sqnorm) in
+ * double (grad_scale: the 1 / world the optimiser kernels fold into the gradient; 1 on one rank),
+ *   coef = min(1.0f, (float)((double)max_norm / (norm + 1e-6))),    g[i] = g[i] * coef for every i
+ * so coef = 1 leaves every byte (x * 1.0f is x). */
+int lidog_flat_clip(float *g, int64_t n, const double *sqnorm, float max_norm, float grad_scale, void *stream);
+
 /* ------------------------------------------------------------------ collectives (RCCL over xGMI)
  * The two collectives of the data-parallel path for hosts that do not go through torch.distributed: the gradient
  * all-reduce of Lightning DDP (train_lidog.py:227-231, strategy='ddp'; sum, the caller folds 1/world into the

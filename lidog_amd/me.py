@@ -20,6 +20,7 @@ Mirrors the surface of MinkowskiEngine 0.5.4 that LiDOG's models and pipelines u
 is no CPU path (tensors on the CPU raise).  The pooling operators are HIP gathers over the rule book's per-row lists
 and over the scans of a map (csrc/pool.hip): no weights, no atomics, the same bits on every call.
 """
+import contextlib
 import ctypes
 import enum
 import math
@@ -1220,9 +1221,29 @@ def _count_batch(bn):
         bn.register_load_state_dict_pre_hook(lambda module, *_: setattr(module, "_nbt_pending", 0))
 
 
+_FROZEN_RUNNING_STATS = [False]
+
+
+@contextlib.contextmanager
+def frozen_running_stats():
+    """Inside, a training-mode forward pass normalises with its batch statistics as always but leaves every BatchNorm's
+    running statistics and batch counter alone: _training_momentum yields 0 and counts nothing, on the operator path and
+    in the trunk executor (both read it once per pass).  SAM's second pass over a batch runs under it
+    (trainer._Step): the statistics of a step are those of its first pass, at the live weights."""
+    prev = _FROZEN_RUNNING_STATS[0]
+    _FROZEN_RUNNING_STATS[0] = True
+    try:
+        yield
+    finally:
+        _FROZEN_RUNNING_STATS[0] = prev
+
+
 def _training_momentum(bn):
     """running-statistics update factor of ONE training-mode forward pass, counting the batch as torch does:
-    bn.momentum, or 1 / num_batches_tracked (cumulative moving average) when bn.momentum is None"""
+    bn.momentum, or 1 / num_batches_tracked (cumulative moving average) when bn.momentum is None; 0, and no batch
+    counted, under frozen_running_stats()"""
+    if _FROZEN_RUNNING_STATS[0]:
+        return 0.0
     if not (bn.track_running_stats and bn.num_batches_tracked is not None):
         return 0.0 if bn.momentum is None else float(bn.momentum)
     if bn.momentum is None:   # the factor depends on the counter: read it (one host synchronisation; no LiDOG config

@@ -10,6 +10,9 @@ Restates what the reference configures through pytorch-lightning (python the GPU
 
 Parameters, gradients and optimiser state live in contiguous fp32 buffers: one fused HIP kernel per step
 (csrc/optim.hip:k_adam, csrc/optim.hip:k_sgd), one RCCL all-reduce per 32 MiB bucket.
+
+Beyond the reference, on the same flat buffers: WeightAverage (EMA / SWA, csrc/wavg.hip), and the global gradient norm
+with its two users, clip_grad_norm (Lightning's gradient_clip_val) and SAM (sharpness-aware minimisation), csrc/sam.hip.
 """
 import contextlib
 import math
@@ -19,7 +22,7 @@ import torch
 import torch.distributed as dist
 
 from . import me as ME
-from ._lib import call, call_on, ptr, require_gpu
+from ._lib import call, call_on, load, ptr, require_gpu
 
 
 class FlatParams:
@@ -301,7 +304,10 @@ class _FlatOptimizer:
         if self.buckets.world > 1:
             self.flat.broadcast(group)     # DDP's start-up broadcast of rank 0's parameters
         self.strays = 0
+        self._strays_early = 0
         self.transposed = TransposedKernels(self.flat)
+        self.sqnorm = None    # device double: the squared gradient norm of the last grad_norm / clip_grad_norm
+        self._sqnorm_ws = None
 
     @property
     def steps(self):
@@ -330,9 +336,53 @@ class _FlatOptimizer:
         lane = ME.wgrad_lane(self.flat.grad.device) if self.flat.grad.is_cuda else None
         if lane is not None:   # normally joined already by the engine callback at the end of backward()
             lane.join()
-        self.strays = self.flat.gather_strays()
+        self.strays = self.flat.gather_strays() + self._strays_early   # those a norm taken before this step gathered
+        self._strays_early = 0
         self.buckets.finish()
         return 1.0 / self.buckets.world
+
+    # ---- the global gradient norm (csrc/sam.hip)
+    def _complete_gradients(self):
+        """what step() does before its kernel -- the weight-gradient lane joined, stray gradients gathered, the buckets
+        finished -- without counting a step: the whole gradient is in the flat buffer, on the current stream.  step()
+        repeats it and finds nothing left to do; `strays` keeps this call's count.  Returns the gradient scale."""
+        scale = self._prepare()
+        self._strays_early = self.strays
+        return scale
+
+    def _launch_sqnorm(self, out, adaptive=False):
+        """out[0] (a device double) = sum (t g)^2 over the flat gradient, t = |w| if `adaptive` else 1: two launches, a
+        fixed summation order, nothing read back"""
+        f = self.flat
+        require_gpu(f.grad, "the gradients of the norm's optimiser")
+        if self._sqnorm_ws is None:
+            self._sqnorm_ws = torch.empty(load().lidog_flat_sqnorm_ws(f.total) // 8, dtype=torch.float64,
+                                          device=f.grad.device)
+        call("lidog_flat_sqnorm", ptr(f.grad), ptr(f.flat) if adaptive else None, f.total,
+             SQNORM_ADAPTIVE if adaptive else SQNORM_PLAIN, ptr(self._sqnorm_ws), ptr(out))
+
+    def _own_sqnorm(self):
+        if self.sqnorm is None:
+            self.sqnorm = torch.zeros(1, dtype=torch.float64, device=self.flat.grad.device)
+        return self.sqnorm
+
+    def grad_norm(self):
+        """the 2-norm of the whole gradient as a 0-dim float64 tensor on the device (torch's `total_norm`), taken now:
+        call it between backward() and step().  The host is not synchronised; `.item()` is the caller's to pay."""
+        check_single_rank("grad_norm()")
+        scale = self._complete_gradients()
+        self._launch_sqnorm(self._own_sqnorm())
+        return (self.sqnorm.sqrt() * scale).reshape(())
+
+    def clip_grad_norm(self, max_norm):
+        """torch.nn.utils.clip_grad_norm_(parameters, max_norm) on the flat gradient, between backward() and step(): the
+        norm (two launches) and ONE scaling launch that reads it on the device (include/lidog_amd.h:lidog_flat_clip).
+        The squared norm from before the clipping stays in `self.sqnorm`."""
+        check_clip_argument(max_norm)
+        check_single_rank("clip_grad_norm()")
+        scale = self._complete_gradients()
+        self._launch_sqnorm(self._own_sqnorm())
+        call("lidog_flat_clip", ptr(self.flat.grad), self.flat.total, ptr(self.sqnorm), float(max_norm), float(scale))
 
     def state_dict(self):
         sd = {"lr": self.lr, "base_lr": self.base_lr, "param_steps": list(self.param_steps), "kind": type(self).__name__}
@@ -687,6 +737,93 @@ class WeightAverage:
                 self.model.train(was_training)
                 for bn, (_, _, training) in zip(bns, saved):
                     bn.training = training
+
+
+# ------------------------------------------------------------------ gradient norm, clipping, SAM (csrc/sam.hip)
+SQNORM_PLAIN, SQNORM_ADAPTIVE = 0, 1     # LIDOG_SQNORM_* of include/lidog_amd.h
+FLAT_MAX_BLOCKS = 2048                   # LIDOG_FLAT_MAX_BLOCKS: workgroups of 1024 elements per sweep
+
+
+def check_single_rank(what):
+    """the global gradient norm is taken over one rank's flat buffer; where it stands relative to the bucket
+    all-reduces of a data-parallel run has not been verified on more than one GPU"""
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        raise NotImplementedError(f"{what} with {dist.get_world_size()} ranks: sharpness-aware minimisation and "
+                                  "gradient clipping are one-rank features (the norm is not reduced across ranks)")
+
+
+def check_clip_argument(max_norm):
+    if not (isinstance(max_norm, (int, float)) and max_norm > 0):      # a NaN fails the comparison
+        raise ValueError(f"grad_clip_norm {max_norm}: the largest gradient norm is positive")
+
+
+def check_sam_arguments(sam_rho=None, sam_adaptive=False, grad_clip_norm=None):
+    """the checks of build_step / Fit / the command line for sam_rho, sam_adaptive and grad_clip_norm"""
+    if sam_rho is not None:
+        SAM.check_arguments(sam_rho, sam_adaptive)
+    elif sam_adaptive:
+        raise ValueError("sam_adaptive goes with sam_rho: the adaptive form scales SAM's neighbourhood")
+    if grad_clip_norm is not None:
+        check_clip_argument(grad_clip_norm)
+
+
+class SAM:
+    """Sharpness-aware minimisation (Foret et al., ICLR 2021) around a FlatAdam / FlatSGD: the gradient that the
+    optimiser steps along is taken at w + e, the worst point of a rho-neighbourhood of the weights to first order,
+
+        e = rho g / ||g||                                  adaptive (ASAM, Kwon et al.): e = rho w^2 g / || |w| g ||
+
+        loss(model(batch)).backward();  sam.first_step()        # w -> w + e, the weights saved
+        opt.zero_grad(); loss(model(batch)).backward()          # the same batch, BatchNorm statistics frozen
+        sam.second_step();  opt.step()                          # w back, bit for bit; the step uses the new gradient
+
+    first_step is the norm (two launches, a device double) and ONE launch over the flat buffers that saves and moves
+    the weights (include/lidog_amd.h:lidog_sam_perturb); second_step is a device copy of the saved weights.  Both end
+    with TransposedKernels.refresh(): the [K, Cout, Cin] copies follow the weights and the generation that bf16 tables
+    compare advances (a precision="bf16" step re-packs after each, trainer._Step).  Parameters without a gradient are
+    not moved.  No state: nothing goes into a checkpoint.  One rank."""
+
+    @staticmethod
+    def check_arguments(rho, adaptive=False):
+        if not (isinstance(rho, (int, float)) and rho > 0 and math.isfinite(rho)):
+            raise ValueError(f"sam_rho {rho}: the neighbourhood's radius is positive and finite")
+
+    def __init__(self, optimizer, rho=0.05, adaptive=False):
+        self.check_arguments(rho, adaptive)
+        check_single_rank("SAM")
+        if optimizer.buckets.world > 1:
+            raise NotImplementedError(f"SAM over a data-parallel optimiser ({optimizer.buckets.world} ranks)")
+        self.optimizer, self.rho, self.adaptive = optimizer, float(rho), bool(adaptive)
+        flat = optimizer.flat
+        require_gpu(flat.flat, "the parameters of SAM's optimiser")
+        self.backup = torch.empty_like(flat.flat)       # allocated once
+        self.sqnorm = torch.zeros(1, dtype=torch.float64, device=flat.flat.device)   # of the last first_step
+        self.perturbed = False
+
+    def first_step(self):
+        """after backward(): w -> w + e from the gradient in the flat buffer; no optimiser step is counted"""
+        if self.perturbed:
+            raise RuntimeError("SAM.first_step() twice: second_step() restores the weights first")
+        opt, f = self.optimizer, self.optimizer.flat
+        opt._complete_gradients()      # the weight-gradient lane is joined: no gradient is still being written
+        opt._strays_early = 0           # this pass's gradient is thrown away; step() reports the second pass's strays
+        opt._launch_sqnorm(self.sqnorm, self.adaptive)
+        call("lidog_sam_perturb", ptr(f.flat), ptr(f.grad), ptr(self.backup), f.total, ptr(self.sqnorm), self.rho,
+             1 if self.adaptive else 0)
+        self.perturbed = True
+        opt.transposed.refresh()
+
+    def second_step(self):
+        """after the second backward(): every byte of the weights is back (a copy, never w - e); then optimizer.step()"""
+        if not self.perturbed:
+            raise RuntimeError("SAM.second_step() without first_step()")
+        self.optimizer.flat.flat.copy_(self.backup)
+        self.perturbed = False
+        self.optimizer.transposed.refresh()
+
+    def grad_norm(self):
+        """the norm first_step divided by (|| g ||, adaptive: || |w| g ||), a 0-dim float64 tensor on the device"""
+        return self.sqnorm.sqrt().reshape(())
 
 
 # ------------------------------------------------------------------ learning-rate schedules (stepped per epoch)

@@ -50,7 +50,8 @@ from . import precision as _precision
 from .evaluate import CLASS_NAMES, per_class_iou
 from .losses import AUX_CRITERIA, BEV_CRITERIA, POINT_CRITERIA
 from .metrics import MetricLayout, MetricsWriter, StepMetrics
-from .optim import WeightAverage, make_optimizer, make_scheduler, shard_indices
+from . import optim as _optim
+from .optim import SAM, WeightAverage, check_sam_arguments, make_optimizer, make_scheduler, shard_indices
 from .trainer import LiDOGStep, RobustStep, SourceStep, setup_data_parallel
 
 
@@ -618,13 +619,15 @@ def build_model(kind="MinkUNet34BEV", bound_2d=50.0, in_channels=1, out_channels
 def build_step(model, kind="MinkUNet34BEV", optimizer="Adam", lr=1e-3, scheduler=None, weight_decay=1e-4,
                momentum=0.98, warmup_epochs=0, source_weights=(0.5, 0.5), num_classes=7, ignore_label=-1, num_sources=1,
                precision=None, sem_criterion="SoftDICELoss", sem_bev_criterion=None, sem_aux_criterion=None,
-               sem_aux_weight=1.0):
+               sem_aux_weight=1.0, sam_rho=None, sam_adaptive=False, grad_clip_norm=None):
     """SyncBN conversion when data-parallel (train_lidog.py:227-231), optimiser + scheduler
     (trainer_lighting_2d.py:349-394), step object (PLTTrainer2D / PLTRobustNet / PLTTrainer, on one or two sources).
     `precision`: the training steps' (trainer._Step).  `sem_criterion` / `sem_bev_criterion`: the point and BEV losses by
     name (losses.make_criterion / make_bev_criterion); the BEV one (None: DICELoss) belongs to MinkUNet34BEV alone.
     `sem_aux_criterion` (None: none) / `sem_aux_weight`: the auxiliary point loss by name (losses.make_aux_criterion) that
     every step adds to its point loss, and its weight.
+    `sam_rho` (None: off) / `sam_adaptive`: sharpness-aware minimisation around the optimiser (optim.SAM: radius, the
+    adaptive form); `grad_clip_norm` (None: off): the largest 2-norm of the whole gradient (trainer._Step).  One rank.
     Returns (model, step, scheduler)."""
     if num_sources not in (1, 2):
         raise NotImplementedError(f"{num_sources} sources (the reference takes one or two)")
@@ -632,6 +635,9 @@ def build_step(model, kind="MinkUNet34BEV", optimizer="Adam", lr=1e-3, scheduler
         raise ValueError(f"sem_bev_criterion={sem_bev_criterion!r}: {kind} has no BEV head")
     if _precision.resolve(precision):
         _precision.check_single_rank()
+    check_sam_arguments(sam_rho, sam_adaptive, grad_clip_norm)
+    if sam_rho is not None or grad_clip_norm is not None:
+        _optim.check_single_rank("sam_rho / grad_clip_norm")
     model = setup_data_parallel(model)
     model.train()
     opt = make_optimizer(optimizer, model, lr, weight_decay=weight_decay, momentum=momentum)
@@ -639,6 +645,10 @@ def build_step(model, kind="MinkUNet34BEV", optimizer="Adam", lr=1e-3, scheduler
     kw = dict(source_weights=source_weights, ignore_label=ignore_label, num_sources=num_sources, precision=precision,
               sem_criterion=sem_criterion, num_classes=num_classes, sem_aux_criterion=sem_aux_criterion,
               sem_aux_weight=sem_aux_weight)
+    if sam_rho is not None:
+        kw["sam"] = SAM(opt, sam_rho, sam_adaptive)
+    if grad_clip_norm is not None:
+        kw["grad_clip_norm"] = grad_clip_norm
     if kind == "MinkUNet34BEV":
         step = LiDOGStep(model, opt, warmup_epochs=warmup_epochs, sem_bev_criterion=sem_bev_criterion or "DICELoss", **kw)
     elif kind == "MinkUNet34Robust":
@@ -676,8 +686,10 @@ class Fit:
                  device="cuda", log=None, state_dict=None, num_sources=None, log_every_n_steps=0, metric_sources=None,
                  val_precision=None, precision=None, sem_criterion="SoftDICELoss", sem_bev_criterion=None,
                  sem_aux_criterion=None, sem_aux_weight=1.0, weight_average=None, avg_decay=0.996, avg_decay_final=None,
-                 avg_start_epoch=0):
-        """`weight_average`: None, "ema" or "swa": an optim.WeightAverage of the model's weights and running statistics,
+                 avg_start_epoch=0, sam_rho=None, sam_adaptive=False, grad_clip_norm=None):
+        """`sam_rho` / `sam_adaptive` / `grad_clip_norm`: build_step's (optim.SAM around the optimiser; the global
+        gradient-norm clip).  SAM keeps no state: a resumed run passes the arguments again.
+        `weight_average`: None, "ema" or "swa": an optim.WeightAverage of the model's weights and running statistics,
         updated by one launch after every training step of an epoch >= `avg_start_epoch`.  "ema" decays by `avg_decay`,
         or from `avg_decay` to `avg_decay_final` on the reference's cosine schedule over the steps that remain from
         `avg_start_epoch` to `epochs`.  Once it has been updated every validation runs a second time with the averaged
@@ -703,6 +715,9 @@ class Fit:
         results.  0: off.  `metric_sources`: the source names of the keys (default: training_source_names)"""
         if _precision.resolve(precision):       # before anything is built
             _precision.check_single_rank("Fit(precision='bf16')")
+        check_sam_arguments(sam_rho, sam_adaptive, grad_clip_norm)
+        if sam_rho is not None or grad_clip_norm is not None:
+            _optim.check_single_rank("Fit(sam_rho / grad_clip_norm)")
         self.rank, self.world = _rank_world()
         _precision.resolve(val_precision)
         self.val_precision, self.precision = val_precision, precision
@@ -722,7 +737,8 @@ class Fit:
         self.model, self.step, self.sched = build_step(
             model, model_kind, optimizer, lr, scheduler, weight_decay, momentum, warmup_epochs, source_weights,
             num_sources=num_sources, precision=precision, sem_criterion=sem_criterion,
-            sem_bev_criterion=sem_bev_criterion, sem_aux_criterion=sem_aux_criterion, sem_aux_weight=sem_aux_weight)
+            sem_bev_criterion=sem_bev_criterion, sem_aux_criterion=sem_aux_criterion, sem_aux_weight=sem_aux_weight,
+            sam_rho=sam_rho, sam_adaptive=sam_adaptive, grad_clip_norm=grad_clip_norm)
         self.opt = self.step.opt
         self.avg, self.avg_start_epoch = None, int(avg_start_epoch)
         if weight_average is not None:
@@ -978,8 +994,21 @@ def parse_args(argv=None):
                          "(default: constant)")
     ap.add_argument("--avg-start-epoch", type=int, default=argparse.SUPPRESS, metavar="E",
                     help="the first epoch whose steps are averaged (default 0)")
+    ap.add_argument("--sam-rho", type=float, default=argparse.SUPPRESS, metavar="R",
+                    help="sharpness-aware minimisation (optim.SAM): every step takes its gradient at the worst point of a "
+                         "neighbourhood of radius R of the weights, at the cost of a second forward and backward pass "
+                         "(usual: 0.05; with --sam-adaptive 0.5 to 2; one GPU; default: off)")
+    ap.add_argument("--sam-adaptive", action="store_true", default=argparse.SUPPRESS,
+                    help="--sam-rho's adaptive form (ASAM): the neighbourhood scales with every weight's magnitude")
+    ap.add_argument("--grad-clip-norm", type=float, default=argparse.SUPPRESS, metavar="X",
+                    help="scale the gradient so that its global 2-norm is at most X (torch's clip_grad_norm_, Lightning's "
+                         "gradient_clip_val; one GPU; default: off)")
     scans.add_file_arguments(ap, "--files", "train on")
     a = ap.parse_args(argv)
+    try:
+        check_sam_arguments(**sam_of(a))
+    except ValueError as e:
+        ap.error(str(e))
     if not hasattr(a, "weight_average"):
         for name in ("avg_decay", "avg_decay_final", "avg_start_epoch"):
             if hasattr(a, name):
@@ -1132,6 +1161,12 @@ def sem_aux_of(a):
     return getattr(a, "sem_aux_criterion", None), getattr(a, "sem_aux_weight", 1.0)
 
 
+def sam_of(a):
+    """build_step's sam_rho / sam_adaptive / grad_clip_norm of parsed arguments (off when they were not given)"""
+    return dict(sam_rho=getattr(a, "sam_rho", None), sam_adaptive=getattr(a, "sam_adaptive", False),
+                grad_clip_norm=getattr(a, "grad_clip_norm", None))
+
+
 def weight_average_of(a):
     """Fit's weight_average / avg_* arguments of parsed arguments (weight_average None when it was not given)"""
     return dict(weight_average=getattr(a, "weight_average", None), avg_decay=getattr(a, "avg_decay", 0.996),
@@ -1161,7 +1196,7 @@ def _fit_from_args(a):
                auto_resume=a.auto_resume, log_every_n_steps=getattr(a, "log_every_n_steps", 0),
                val_precision=val_precision_of(a), precision=precision_of(a), sem_criterion=sem_criterion_of(a),
                sem_bev_criterion=sem_bev_criterion_of(a), sem_aux_criterion=sem_aux_criterion,
-               sem_aux_weight=sem_aux_weight, **weight_average_of(a))
+               sem_aux_weight=sem_aux_weight, **weight_average_of(a), **sam_of(a))
 
 
 def _data_from_args(a):

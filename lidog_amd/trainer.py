@@ -21,6 +21,7 @@ import torch
 import torch.distributed as dist
 
 from . import me as ME
+from . import optim as _optim
 from . import precision as _precision
 from .losses import iw_loss, make_aux_criterion, make_bev_criterion, make_criterion
 from .optim import (FlatAdam, FlatParams, FlatSGD, GradientBuckets, make_optimizer, make_scheduler,  # noqa: F401
@@ -48,7 +49,13 @@ class _Step:
     soft labels.
     `sem_aux_criterion`: None, or an auxiliary point loss by name (losses.make_aux_criterion: LovaszSoftmaxLoss) that is
     added to the point loss of every source, times `sem_aux_weight`: the step's `sem_loss` (`sem_loss0` / `sem_loss1`) is
-    that sum, so the loss dictionaries and the logged keys keep their shape.  None launches nothing."""
+    that sum, so the loss dictionaries and the logged keys keep their shape.  None launches nothing.
+    `sam`: None, or an optim.SAM over the step's optimiser: every training step takes its gradient at the perturbed
+    weights, at the cost of a second forward and backward pass over the batch (_sam_second_pass); losses and metrics are
+    the first pass's, at the live weights.  `grad_clip_norm`: None, or the largest 2-norm of the whole gradient
+    (torch's clip_grad_norm_, Lightning's gradient_clip_val): the norm and one scaling launch between backward and the
+    optimiser step; with `sam` it is the second pass's gradient that is clipped.  Both: one rank only; None launches
+    nothing."""
 
     metrics = None
     bf16 = None                         # the packed tables of precision="bf16"
@@ -58,7 +65,7 @@ class _Step:
     metric_count_ignored = True         # jaccard_score over all rows (the LiDOG trainers filter label == -1 first)
 
     def __init__(self, model, optimizer, num_sources=1, ignore_label=-1, precision=None, sem_criterion="SoftDICELoss",
-                 num_classes=7, *, sem_aux_criterion=None, sem_aux_weight=1.0):
+                 num_classes=7, *, sam=None, grad_clip_norm=None, sem_aux_criterion=None, sem_aux_weight=1.0):
         if num_sources not in (1, 2):
             raise NotImplementedError(f"{num_sources} sources (the reference takes one or two)")
         self.model, self.opt, self.num_sources = model, optimizer, num_sources
@@ -74,12 +81,22 @@ class _Step:
         self._prepared = {}
         if num_sources == 2:
             optimizer.buckets.set_uses(2)
+        if sam is not None or grad_clip_norm is not None:
+            _optim.check_single_rank("sam / grad_clip_norm")
+            if sam is not None and sam.optimizer is not optimizer:
+                raise ValueError("sam wraps another optimiser than the step's")
+            if grad_clip_norm is not None:
+                _optim.check_clip_argument(grad_clip_norm)
+        self.sam, self.grad_clip_norm = sam, grad_clip_norm
+        self._managers, self._replay = {}, None     # sam: the first pass's coordinate managers, by source
 
     def sparse_input(self, batch, s=0):
         """the SparseTensor of source `s`, on the coordinate manager prefetch_maps prepared for it if there is one"""
         key = "coords_int1" if s else "coords_int"
         coords = batch[key] if key in batch else batch[f"source_coordinates{s}"].int()
         feats = batch[f"source_features{s}"]
+        if self._replay is not None:    # sam's second pass: the maps of the first, nothing is built again
+            return ME.SparseTensor(features=feats, coordinates=coords, coordinate_manager=self._replay[s])
         hit = self._prepared.pop(id(coords), None)
         if hit is not None and hit[0] is coords:
             st = ME.SparseTensor(features=feats, coordinates=coords, coordinate_manager=hit[1])
@@ -87,6 +104,8 @@ class _Step:
             st = ME.SparseTensor(coordinates=coords, features=feats)
         if s == 0:
             self._last_manager = st.coordinate_manager
+        if self.sam is not None:
+            self._managers[s] = st.coordinate_manager
         return st
 
     def prefetch_maps(self, batch, ready=None):
@@ -150,6 +169,10 @@ class _Step:
             ready = self.metrics.mark() if self.metrics is not None else None
             self.opt.zero_grad()
             total.backward()
+            if self.sam is not None:
+                self._sam_second_pass(batch, epoch)
+            if self.grad_clip_norm is not None:     # the gradient the optimiser steps along: with sam, the second pass's
+                self.opt.clip_grad_norm(self.grad_clip_norm)
             self.opt.step()
             if self.bf16 is not None:   # behind the step's TransposedKernels.refresh(): the dgrad table reads that copy
                 self.bf16.refresh()
@@ -158,6 +181,34 @@ class _Step:
             self.prefetch_maps(prefetch, prefetch_ready)     # inside the scope: work items cut for the bf16 kernel
         _check_transport(self)
         return {k: (v.detach() if torch.is_tensor(v) else v) for k, v in {"loss": total, **losses}.items()}
+
+    def _sam_second_pass(self, batch, epoch):
+        """between the first backward pass and the optimiser step of a step with `sam`: the weights move to w + e
+        (SAM.first_step), the SAME batch goes forward and backward again -- on the first pass's coordinate managers (no
+        map is built twice, their traces keep the first pass's length), with the BatchNorm running statistics frozen
+        (ME.frozen_running_stats) and into a new generation of the flat gradient buffer -- and the weights return
+        (SAM.second_step).  Every cache of the weights follows both moves: the transposed kernels inside the SAM calls,
+        the bf16 tables here.  What the step returns, logs and records stays the first pass's."""
+        self.sam.first_step()
+        if self.bf16 is not None:
+            self.bf16.refresh()
+        bev_outs = getattr(self, "_bev_outs", None)
+        traces = {s: len(cm.trace) for s, cm in self._managers.items()}
+        self._replay = self._managers
+        try:
+            with ME.frozen_running_stats():
+                total, _, _ = self._forward(batch, epoch)
+        finally:
+            self._replay = None
+            for s, cm in self._managers.items():
+                del cm.trace[traces[s]:]
+            self._bev_outs = bev_outs
+        self.opt.zero_grad()
+        total.backward()
+        self.sam.second_step()
+        if self.bf16 is not None:
+            self.bf16.refresh()
+        self._managers = {}
 
     def _metric_pairs(self, batch, s, out):
         """the (logits, labels) of source s that the metrics count, in the order of MetricLayout.segments"""
@@ -201,9 +252,10 @@ class LiDOGStep(_Step):
 
     def __init__(self, model, optimizer, source_weights=(0.5, 0.5), warmup_epochs=0, num_classes=7, ignore_label=-1,
                  num_sources=1, precision=None, sem_criterion="SoftDICELoss", sem_bev_criterion="DICELoss", *,
-                 sem_aux_criterion=None, sem_aux_weight=1.0):
+                 sam=None, grad_clip_norm=None, sem_aux_criterion=None, sem_aux_weight=1.0):
         super().__init__(model, optimizer, num_sources, ignore_label, precision, sem_criterion, num_classes,
-                         sem_aux_criterion=sem_aux_criterion, sem_aux_weight=sem_aux_weight)
+                         sem_aux_criterion=sem_aux_criterion, sem_aux_weight=sem_aux_weight, sam=sam,
+                         grad_clip_norm=grad_clip_norm)
         self.w, self.warmup, self.nc = source_weights, warmup_epochs, num_classes
         self.bev_criterion = make_bev_criterion(sem_bev_criterion, ignore_label)
 
@@ -244,9 +296,11 @@ class SourceStep(_Step):
     One source: total = sem, the only loss returned; two sources (trainer_lighting.py:92-116): w0 * sem0 + w1 * sem1."""
 
     def __init__(self, model, optimizer, source_weights=(0.5, 0.5), ignore_label=-1, num_sources=1, precision=None,
-                 sem_criterion="SoftDICELoss", num_classes=7, *, sem_aux_criterion=None, sem_aux_weight=1.0):
+                 sem_criterion="SoftDICELoss", num_classes=7, *, sam=None, grad_clip_norm=None, sem_aux_criterion=None,
+                 sem_aux_weight=1.0):
         super().__init__(model, optimizer, num_sources, ignore_label, precision, sem_criterion, num_classes,
-                         sem_aux_criterion=sem_aux_criterion, sem_aux_weight=sem_aux_weight)
+                         sem_aux_criterion=sem_aux_criterion, sem_aux_weight=sem_aux_weight, sam=sam,
+                         grad_clip_norm=grad_clip_norm)
         self.w = source_weights
 
     def _losses(self, batch, epoch):
@@ -267,10 +321,11 @@ class RobustStep(_Step):
     metric_losses = ("sem_loss", "aux_loss")
 
     def __init__(self, model, optimizer, source_weights=(0.5, 0.5), aux_epoch=5, ignore_label=-1, num_sources=1,
-                 precision=None, sem_criterion="SoftDICELoss", num_classes=7, *, sem_aux_criterion=None,
-                 sem_aux_weight=1.0):
+                 precision=None, sem_criterion="SoftDICELoss", num_classes=7, *, sam=None, grad_clip_norm=None,
+                 sem_aux_criterion=None, sem_aux_weight=1.0):
         super().__init__(model, optimizer, num_sources, ignore_label, precision, sem_criterion, num_classes,
-                         sem_aux_criterion=sem_aux_criterion, sem_aux_weight=sem_aux_weight)
+                         sem_aux_criterion=sem_aux_criterion, sem_aux_weight=sem_aux_weight, sam=sam,
+                         grad_clip_norm=grad_clip_norm)
         self.w, self.aux_epoch = source_weights, aux_epoch
 
     def _losses(self, batch, epoch):

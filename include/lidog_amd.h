@@ -434,6 +434,30 @@ int lidog_lovasz_bwd(const float *logits, const int64_t *target, int64_t n, int3
                      int32_t has_ignore, const float *coef, const float *invP, const float *gout, float *glogits,
                      void *stream);
 
+/* ------------------------------------------------------------------ entropy, the criterion of test-time adaptation
+ * csrc/entropy.hip; TENT (Wang et al., ICLR 2021) minimises it on unlabelled target batches (lidog_amd.adapt); not in the
+ * reference.  logits [n, C] float32 (C in 2..20); mask [n] uint8 or NULL; row_h [n] float32.  Per row r:
+ *   m = max_c x_c,  s = sum_c exp(x_c - m),  lse = m + log s,  p_c = exp(x_c - lse),  H = lse - sum_c p_c x_c
+ * and row_h[r] = (float)H is written for EVERY row, whether the row takes part or not.  The kernels evaluate this in
+ * double on the shifted logits x_c - m (lse - x_c = log s - (x_c - m), H = log s - sum_c p_c (x_c - m)), so a value is
+ * rounded to float once, at its store.  A row takes part when both hold:
+ *   mask == NULL || mask[r] != 0,    margin <= 0 || row_h[r] < margin   (compared as float32)
+ * the second being the reliable-sample filter of EATA / SAR, whose usual margin is 0.4 ln C.
+ * fwd, with k the number of rows that take part: loss[0] = sum over them of H / k, summed in double (0 when k == 0);
+ * coef[0] = (float)(1.0 / k) (0 when k == 0); coef[1] = (float)k.  ws: lidog_entropy_ws(C) doubles (per-workgroup
+ * partials, added in a fixed order).
+ * bwd decides participation again from mask, row_h and margin (it never recomputes H for that decision):
+ *   glogits[r][j] = gout[0] * coef[0] * p_j * ((lse - x_j) - H)  in the rows that take part, +0 in every other row;
+ * every entry is written exactly once.  A row with one logit far above the rest (1e4, say) has H == 0 and a zero gradient
+ * row: no NaN, no infinity.  No floating-point atomics, nothing read back: the same call gives the same bytes every time.
+ * Both return 2 for another C before any launch; n == 0: fwd gives loss 0 and coef (0, 0), bwd launches nothing, both
+ * return 0. */
+int64_t lidog_entropy_ws(int32_t C);
+int lidog_entropy_fwd(const float *logits, const uint8_t *mask, int64_t n, int32_t C, float margin, double *ws,
+                      float *loss, float *coef, float *row_h, void *stream);
+int lidog_entropy_bwd(const float *logits, const uint8_t *mask, const float *row_h, int64_t n, int32_t C, float margin,
+                      const float *coef, const float *gout, float *glogits, void *stream);
+
 /* ------------------------------------------------------------------ data path next to the hot path
  * ME.utils.sparse_quantize (utils/datasets/semantickitti_bev.py:232-238) = lidog_voxel_floor +
  * lidog_coords_insert + lidog_coords_compact + lidog_label_vote; PC2ImgConverter.getBEVImageNew

@@ -5,7 +5,8 @@ Public surface:
   lidog_amd.bev           sparse2super + Encoder2D (fused BEV projection, MFMA 2-D head)
   lidog_amd.MinkUNet34 / MinkUNet34BEV / MinkUNet34IBN / MinkUNet34Robust   the reference models wired to those operators
   lidog_amd.losses        SoftDICELoss / DICELoss / CELoss / FocalLoss on the device; make_criterion picks one by name;
-                          LovaszSoftmaxLoss, the auxiliary point criterion (make_aux_criterion)
+                          LovaszSoftmaxLoss, the auxiliary point criterion (make_aux_criterion); EntropyLoss
+  lidog_amd.adapt         test-time adaptation at evaluation: TestTimeAdapter (bn, adabn, tent; csrc/entropy.hip)
   lidog_amd.trainer       training step, Adam, RCCL data parallelism
   lidog_amd.trunk         the whole encoder-decoder as one launch sequence per pass (csrc/trunk.hip)
   lidog_amd.data          voxelisation, collation and the scan mixes on the device: mix3d_merge, pointcutmix_merge,
@@ -66,8 +67,9 @@ _safe_mode()
 
 from . import me, bev, losses, trunk  # noqa: E402,F401
 from .minkunet import make_models  # noqa: E402
-from .losses import (CELoss, DICELoss, FocalLoss, LovaszSoftmaxLoss, SoftDICELoss,  # noqa: E402,F401
+from .losses import (CELoss, DICELoss, EntropyLoss, FocalLoss, LovaszSoftmaxLoss, SoftDICELoss,  # noqa: E402,F401
                      make_aux_criterion, make_bev_criterion, make_criterion)
+from .adapt import TestTimeAdapter  # noqa: E402,F401
 
 me.trunk_forward = trunk.trunk_forward   # the models hand their training-mode trunk pass to the executor
 

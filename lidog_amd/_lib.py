@@ -16,7 +16,7 @@ _i32, _i64, _p, _f, _d = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes
 HEADER_PATH = os.path.join(_HERE, "..", "include", "lidog_amd.h")
 _SCALARS = {"int": ctypes.c_int, "int32_t": _i32, "int64_t": _i64, "uint32_t": ctypes.c_uint32, "float": _f,
             "double": _d}
-_POINTEES = set(_SCALARS) | {"void", "char", "uint16_t", "uint64_t"}
+_POINTEES = set(_SCALARS) | {"void", "char", "uint8_t", "uint16_t", "uint64_t"}
 _RETURNS = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": _i64, "const char *": ctypes.c_char_p}
 
 

@@ -30,6 +30,10 @@ table goes to `<sources>-TO-<targets>-points-tta.csv`, the voxel-level outputs s
 --weights averaged: evaluate the trajectory average that a run under train --weight-average stored in the checkpoint
 (`averaged_state_dict`) instead of the weights of its last step; every results file then carries `-avg` before `.csv`
 and predictions and labels go under `predictions-avg/`.  The default, live, writes what it always wrote.
+--adapt bn / adabn / tent: test-time adaptation on the unlabelled target (lidog_amd.adapt; --adapt-lr, --adapt-optimizer,
+--adapt-steps and --adapt-margin belong to tent).  The model returns to the checkpoint before every target; every results
+file carries `-adapt-<mode>` before `.csv` (after `-avg`, `-points`), predictions and labels go under
+`predictions<-avg>-adapt-<mode>/`.  fp32 only, one rank, not together with --tta.  The default, none, builds no adapter.
 """
 import argparse
 import json
@@ -42,7 +46,7 @@ from . import synth
 from .checkpoint import load_lightning_checkpoint
 from .evaluate import (CLASS_NAMES, PointLabelWriter, PointPath, TargetEvaluator, dataset_batches, inverse_lut,
                        load_inverse_label_map, palette, write_ply, write_results_csv)
-from . import scans, tta
+from . import adapt, scans, tta
 from .train import SynthScans, bev_image_size, build_model, source_names
 
 MODELS = ("MinkUNet34BEV", "MinkUNet34", "MinkUNet34IBN", "MinkUNet34Robust")
@@ -94,9 +98,35 @@ def parse_args(argv=None):
                     help="which weights of the checkpoint to evaluate: those of its last step (live, the default) or the "
                          "trajectory average a run under train --weight-average stored next to them (averaged: every "
                          "results file gets -avg before .csv, predictions and labels go under predictions-avg/)")
+    ap.add_argument("--adapt", default="none", choices=["none"] + list(adapt.MODES),
+                    help="test-time adaptation on the unlabelled target (lidog_amd.adapt): bn normalises every batch with "
+                         "its own statistics, adabn re-estimates the BatchNorm running statistics over the target's "
+                         "batches before the scored pass, tent also takes gradient steps on the norm layers' affine "
+                         "parameters that lower the entropy of every batch's predictions.  The model returns to the "
+                         "checkpoint before every target; every results file gets -adapt-<mode> before .csv")
+    ap.add_argument("--adapt-lr", type=float, default=None, help="with --adapt tent: the learning rate (default 1e-3)")
+    ap.add_argument("--adapt-optimizer", default=None, choices=["Adam", "SGD"], help="with --adapt tent (default Adam)")
+    ap.add_argument("--adapt-steps", type=int, default=None,
+                    help="with --adapt tent: gradient steps per batch (default 1)")
+    ap.add_argument("--adapt-margin", type=float, default=None, metavar="F",
+                    help="with --adapt tent: only voxels whose entropy lies below F ln C enter the loss (EATA / SAR use "
+                         "0.4; default: every voxel)")
     a = ap.parse_args(argv)
     if a.checkpoint is None:
         ap.error(NO_CHECKPOINT)
+    if a.adapt != "tent" and any(v is not None for v in (a.adapt_lr, a.adapt_optimizer, a.adapt_steps, a.adapt_margin)):
+        ap.error("--adapt-lr, --adapt-optimizer, --adapt-steps and --adapt-margin go with --adapt tent")
+    if a.adapt != "none":
+        if a.precision == "bf16":
+            ap.error("--adapt goes with --precision fp32 (test-time adaptation is fp32 only)")
+        if a.tta is not None:
+            ap.error("--adapt and --tta exclude each other (the views of a scan would not be adapted)")
+    if a.adapt == "tent":
+        a.adapt_lr = 1e-3 if a.adapt_lr is None else a.adapt_lr
+        a.adapt_optimizer = a.adapt_optimizer or "Adam"
+        a.adapt_steps = 1 if a.adapt_steps is None else a.adapt_steps
+        if a.adapt_steps < 1 or not a.adapt_lr >= 0 or (a.adapt_margin is not None and not a.adapt_margin > 0):
+            ap.error("--adapt-steps must be positive, --adapt-lr non-negative and --adapt-margin positive")
     if a.target_files is not None:
         a.target_files = scans.check_file_arguments(ap, a.target_files, a, "--target-files")
         a.targets = [n for n, _ in a.target_files]               # the CSV's target names
@@ -165,13 +195,23 @@ def main(argv=None):
             raise
         raise SystemExit(f"eval_target --weights averaged: {e.args[0]}")
     avg = "-avg" if a.weights == "averaged" else ""      # the two kinds never share a table or a folder
+    adapter = None
+    if a.adapt != "none":                                # an adapted run never shares a table or a folder either
+        avg += f"-adapt-{a.adapt}"
     model.eval()
+    if a.adapt == "tent":
+        import math
+        adapter = adapt.TestTimeAdapter(model, "tent", lr=a.adapt_lr, optimizer=a.adapt_optimizer, steps=a.adapt_steps,
+                                        margin=None if a.adapt_margin is None else
+                                        a.adapt_margin * math.log(len(CLASS_NAMES)))
+    elif a.adapt != "none":
+        adapter = adapt.TestTimeAdapter(model, a.adapt)
     save_dir = save_dir_of(a.checkpoint)
     sources = "".join(source_names(a.sources))                       # test_epoch_end concatenates the names
     targets = source_names(a.targets)
     file_targets = "".join(targets)
     bev = bev_image_size(a.bound)
-    ev = TargetEvaluator(model, num_classes=len(CLASS_NAMES), precision=a.precision)
+    ev = TargetEvaluator(model, num_classes=len(CLASS_NAMES), precision=a.precision, adapter=adapter)
     results = []
     luts = None
     if a.target_files is not None:
@@ -197,8 +237,12 @@ def main(argv=None):
         if a.save_predictions:
             writer = PredictionWriter(os.path.join(save_dir, "predictions" + avg), name, a.model != "MinkUNet34BEV",
                                       len(CLASS_NAMES))
+        if adapter is not None:
+            adapter.reset()                              # no target sees what another one left in the model
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+        if a.adapt == "adabn":                           # part of the target's time: the scans go through twice
+            adapter.estimate(dataset_batches(data, a.batch, device))
         res = ev.run(dataset_batches(data, a.batch, device), len(data), rows=a.rows, on_predictions=writer,
                      points=points)
         dt = time.perf_counter() - t0                                # run() ends with the host copy of the counts
@@ -220,6 +264,8 @@ def main(argv=None):
             extra["label_paths"] = list(points.on_point_labels.written)
         if a.tta is not None:
             out.update(tta_views=res["tta_views"], tta_mode=res["tta_mode"])
+        if adapter is not None:
+            out.update(adapt=a.adapt, adapt_lr=a.adapt_lr, adapt_steps=a.adapt_steps)
         print(json.dumps(out), flush=True)
         results.append(dict(out, iou_rows=res["rows"], counts=res["counts"], **extra))
     return results

@@ -503,12 +503,16 @@ class TargetEvaluator:
     `on_predictions(index, records)`: called per scan with its [k, 5] int32 records (x, y, z, prediction, label) of the
     labelled voxels; asking for it costs one device -> host copy per batch."""
 
-    def __init__(self, model, num_classes=7, ignore_label=-1, precision=None):
+    def __init__(self, model, num_classes=7, ignore_label=-1, precision=None, adapter=None):
         """`precision`: None / "fp32" / "bf16" as predict(); with "bf16" every run() packs the weights once (`kernels`
-        holds the last run's table)"""
+        holds the last run's table).  `adapter`: a lidog_amd.adapt.TestTimeAdapter of `model` that run() calls in place
+        of its Predictor (test-time adaptation: fp32 only, and no test-time augmentation next to it); None changes
+        nothing."""
+        if adapter is not None and _precision.resolve(precision):
+            raise ValueError("TargetEvaluator: precision='bf16' with an adapter (test-time adaptation is fp32 only)")
         _precision.resolve(precision)
         self.model, self.num_classes, self.ignore_label = model, int(num_classes), int(ignore_label)
-        self.precision, self.kernels = precision, None
+        self.precision, self.kernels, self.adapter = precision, None, adapter
 
     @torch.no_grad()
     def run(self, batches, n_scans, rows="batch", on_predictions=None, points=None):
@@ -524,7 +528,9 @@ class TargetEvaluator:
         if rows not in ("batch", "scan"):
             raise ValueError(f"rows={rows!r} (one of 'batch', 'scan')")
         c = self.num_classes
-        run = Predictor(self.model, self.precision)
+        if self.adapter is not None and points is not None and points.tta is not None:
+            raise ValueError("TargetEvaluator: an adapter with points.tta (the further views would not be adapted)")
+        run = self.adapter if self.adapter is not None else Predictor(self.model, self.precision)
         self.kernels = run.kernels
         it = iter(batches)
         cur = next(it, None)

@@ -260,6 +260,62 @@ def make_aux_criterion(name, ignore_label=-1):
     raise NotImplementedError(f"sem_aux_criterion {name!r}: one of {AUX_CRITERIA}")
 
 
+# ------------------------------------------------------------------ entropy, the criterion of test-time adaptation
+class _EntropyFn(torch.autograd.Function):
+    """csrc/entropy.hip: every row's entropy and the sum over the rows that take part in one pass, the gradient in one
+    pass.  Returns (loss, row_h, taken); only the loss carries a gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, mask, margin):
+        logits = logits.contiguous()
+        n, C = logits.shape
+        dev = logits.device
+        ws = torch.empty(_lib.load().lidog_entropy_ws(C), dtype=torch.float64, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        coef = torch.empty(2, dtype=torch.float32, device=dev)
+        row_h = torch.empty(n, dtype=torch.float32, device=dev)
+        call("lidog_entropy_fwd", ptr(logits), ptr(mask), n, C, margin, ptr(ws), ptr(loss), ptr(coef), ptr(row_h))
+        ctx.save_for_backward(logits, coef, row_h)
+        ctx.mask, ctx.margin = mask, margin
+        taken = coef[1]
+        ctx.mark_non_differentiable(row_h, taken)
+        return loss, row_h, taken
+
+    @staticmethod
+    def backward(ctx, gout, _row_h, _taken):
+        logits, coef, row_h = ctx.saved_tensors
+        n, C = logits.shape
+        g = torch.empty_like(logits)
+        call("lidog_entropy_bwd", ptr(logits), ptr(ctx.mask), ptr(row_h), n, C, ctx.margin, ptr(coef),
+             ptr(gout.contiguous()), ptr(g))
+        return g, None, None
+
+
+class EntropyLoss(nn.Module):
+    """The mean Shannon entropy of softmax(logits) over the rows that take part: what TENT (Wang et al., ICLR 2021)
+    minimises on unlabelled batches (lidog_amd.adapt.TestTimeAdapter); it takes no labels and is no --sem-criterion.
+    `mask` ([n] bool or uint8, None: every row) and `margin` (None or <= 0: off; else only rows whose entropy lies below
+    it take part, the reliable-sample filter of EATA / SAR, usually 0.4 ln C) choose the rows; with none the loss is 0.
+    After a call `row_entropy` holds every row's entropy ([n] float32, rows that take no part included) and `taken` the
+    number of rows that took part (a 0-dim float tensor on the device: nothing is read back)."""
+
+    def __init__(self, margin=None):
+        super().__init__()
+        self.margin = 0.0 if margin is None else float(margin)
+        self.row_entropy = self.taken = None
+
+    def forward(self, logits, mask=None):
+        _check(logits)
+        if mask is not None:
+            _lib.require_gpu(mask, "mask")
+            if mask.shape != (logits.shape[0],) or mask.dtype not in (torch.bool, torch.uint8):
+                raise ValueError(f"EntropyLoss: mask must be bool or uint8 [{logits.shape[0]}], got {mask.dtype} "
+                                 f"{tuple(mask.shape)}")
+            mask = mask.contiguous().view(torch.uint8)
+        loss, self.row_entropy, self.taken = _EntropyFn.apply(logits, mask, self.margin)
+        return loss
+
+
 # ------------------------------------------------------------------ instance-whitening loss (RobustNet)
 # IWLoss views a map [n, C] as [n, C, 1]: its "covariance" is one C x C outer product per ROW, over all rows of all scans
 # together, masked to the strict upper triangle, |.|-summed and divided by n (n - 1) (csrc/iwloss.hip has the closed

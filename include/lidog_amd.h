@@ -809,6 +809,45 @@ int lidog_ibn_bwd_apply(const float *dy, const uint32_t *relu_bits, const float 
                         double bn_count, const int32_t *bid, const float *in_mean, const float *in_invstd,
                         const float *in_w, const float *in_coef, float *dx, void *stream);
 
+/* ------------------------------------------------------------------ MixStyle (csrc/mixstyle.hip)
+ * MixStyle (Zhou et al., ICLR 2021): during training, every scan's per-channel feature statistics are interpolated with
+ * those of another scan of the batch.  Not in the reference repository; this comment is the definition, restated in
+ * float64 in tests/mixstyle_ref.py.
+ * x [n, C] float32 are the rows of a sparse tensor, scan b has the n_b rows of batch index b (B scans, the segments of
+ * lidog_in_segments).  lam [B] float32, partner [B] int32 and eps (a float, widened to double) come from the caller.
+ * Per (b, c), all in double from double sums added in a fixed order (no float atomics, the same bytes on every run):
+ *   mu  = sum x / n_b                                            (0 for a scan without rows)
+ *   var = max(0, (sum x^2 - (sum x)^2 / n_b) / (n_b - 1))        the UNBIASED variance (0 for n_b < 2)
+ *   sig = sqrt(var + eps)
+ *   mu_mix = lam_b mu_b + (1 - lam_b) mu_p,  sig_mix = lam_b sig_b + (1 - lam_b) sig_p,  p = partner[b]
+ * Three float32 tables [B, C], each rounded once from double: sub = mu_b, scale = sig_mix / sig_b, add = mu_mix.
+ *   forward   y = fmaf(x - sub[b], scale[b], add[b]) in float32
+ *   backward  dx = dy * scale[b], one float32 product: the statistics are constants to autograd (the paper's code
+ *             detaches them)
+ * IDENTITY SCANS.  n_b < 2, n_p < 2, partner[b] == b or lam_b == 1 make b an identity scan: its table rows are
+ * (sub, scale, add) = (0, 1, 0) exactly (add carries the sign bit: fmaf(x, 1, -0) keeps the sign of a zero), so y == x and
+ * dx == dy bit for bit.  A scan without rows is an identity scan.  partner need not be a permutation.
+ * [rows, C] with C % 4 == 0, 4 <= C <= 1024 and 2 B C <= 4096 take float4 kernels and ONE launch for the statistics;
+ * any other shape plain scalar kernels (two launches; no performance target). */
+
+/* doubles of workspace lidog_mixstyle_stats needs: lidog_in_reduce_ws(B, C) and B more for lam / partner */
+int64_t lidog_mixstyle_ws(int32_t B, int32_t C);
+/* mean, sig [B, C] (float32 of mu and sig, for tests and benches) and the tables sub, scale, add [B, C].  perm / seg_off
+ * from lidog_in_segments.  lam and partner are HOST arrays [B]: an entry of partner outside [0, B) is an error (return
+ * code, lidog_last_error) with nothing queued; both are then copied to the end of the workspace by hipMemcpyAsync on
+ * `stream`.  From pinned memory that copy does not wait for the device, and the arrays must stay unchanged until it
+ * has run.  The last workgroup of the reduction finishes mean / sig of every (b, c) and, behind a workgroup barrier,
+ * writes the tables: no host wait. */
+int lidog_mixstyle_stats(const float *x, int64_t n, int32_t C, int32_t B, const int32_t *perm, const int32_t *seg_off,
+                         const float *lam, const int32_t *partner, float eps, float *mean, float *sig, float *sub,
+                         float *scale, float *add, double *ws, void *stream);
+/* y [n, C] = fmaf(x - sub[b], scale[b], add[b]), b = bid[row] (lidog_in_segments' bid, every entry in [0, B)) */
+int lidog_mixstyle_apply(const float *x, int64_t n, int32_t C, int32_t B, const int32_t *bid, const float *sub,
+                         const float *scale, const float *add, float *y, void *stream);
+/* dx [n, C] = dy * scale[bid[row]] */
+int lidog_mixstyle_bwd(const float *dy, int64_t n, int32_t C, int32_t B, const int32_t *bid, const float *scale,
+                       float *dx, void *stream);
+
 /* ------------------------------------------------------------------ instance-whitening loss (RobustNet)
  * IWLoss (utils/losses/losses.py:464-485) of PLTRobustNet.training_step (trainer_lighting_robustnet.py) in closed form.
  * For a map x [n, C] (float32, row-major; n >= 2): S = sum_i sum_k |x_ik| P_ik with P_ik = sum_{j<k} |x_ij|, and the

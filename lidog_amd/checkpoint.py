@@ -40,7 +40,7 @@ def _cpu(v):
 
 
 def save_lightning_checkpoint(model, path, epoch=0, global_step=0, optimizer=None, scheduler=None,
-                              weight_average=None):
+                              weight_average=None, mixstyle=None):
     """writes the keys eval_target.py / --auto_resume of the reference read back (`epoch`, `global_step`,
     `state_dict` with the `model.` prefix) plus Lightning's `optimizer_states` / `lr_schedulers` lists
     (trainer.fit(ckpt_path=...), train_lidog.py:298-301).  `optimizer_states[0]` is in torch.optim's own layout
@@ -49,7 +49,8 @@ def save_lightning_checkpoint(model, path, epoch=0, global_step=0, optimizer=Non
     carries `last_epoch` (the only field both sides need).
     `weight_average` (an optim.WeightAverage that has been updated) adds two top-level keys, which Lightning and the
     reference ignore: `averaged_state_dict` (the averaged model, `model.` prefix like `state_dict`) and `weight_average`
-    (its mode, decay schedule and update count)."""
+    (its mode, decay schedule and update count).  `mixstyle` (a dict: layers, p, alpha of a run trained with MixStyle)
+    is recorded as it is under the top-level key `mixstyle`; the modules have no state."""
     ckpt = {"epoch": epoch, "global_step": global_step,
             "state_dict": {"model." + k: v.detach().cpu() for k, v in model.state_dict().items()}}
     if optimizer is not None:
@@ -60,6 +61,8 @@ def save_lightning_checkpoint(model, path, epoch=0, global_step=0, optimizer=Non
     if weight_average is not None and weight_average.num_updates > 0:
         ckpt[AVERAGED_KEY] = {"model." + k: v for k, v in weight_average.averaged_state_dict().items()}
         ckpt[AVERAGE_STATE_KEY] = weight_average.state_dict()
+    if mixstyle is not None:
+        ckpt["mixstyle"] = dict(mixstyle)
     tmp = path + ".tmp"
     torch.save(ckpt, tmp)
     import os

@@ -21,6 +21,7 @@
 // public; no performance target there).
 #include "bn_math.h"
 #include "common.h"
+#include "mixstyle.h"
 #include "prims.h"
 #include "stats_tail.h"
 
@@ -67,13 +68,15 @@ extern "C" int lidog_in_segments(const int32_t *coords, int64_t n, int32_t B, in
 
 // ------------------------------------------------------------------ segmented reductions
 // What the last workgroup does with the per-(b, c) sums.  MODE 0 (x, x^2): mean / invstd.  MODE 1 (dy, dy * xhat):
-// coef [2][B][C] = (sum dy / n_b, sum dy xhat / n_b) and dw / db [C] = sums over b, ascending.
+// coef [2][B][C] = (sum dy / n_b, sum dy xhat / n_b) and dw / db [C] = sums over b, ascending.  MODE 2 (x, x^2, the
+// terms of MODE 0): MixStyle's mean / sig and, behind a barrier, its three mixed tables (mixstyle.h).
 struct InFinish {
     const int32_t *seg_off;
     int B, C;
     float eps;
     float *mean, *invstd;    // MODE 0
     float *coef, *dw, *db;   // MODE 1
+    MsMix mix;               // MODE 2 (with mean)
 };
 
 __device__ __forceinline__ void in_finalize(int mode, const InFinish &f, int j, double s0, double s1) {
@@ -93,6 +96,17 @@ __device__ __forceinline__ void in_finalize(int mode, const InFinish &f, int j, 
         f.coef[j] = cnt > 0 ? (float)(s0 / cnt) : 0.f;
         f.coef[BC + j] = cnt > 0 ? (float)(s1 / cnt) : 0.f;
     }
+}
+
+// MODE 2, phase one: the moments of (b, c) = j in double into mom [2][B C], rounded once into mean / sig
+__device__ __forceinline__ void in_finalize_ms(const InFinish &f, int j, double s0, double s1, double *mom) {
+    const int b = j / f.C;
+    double mu, sig;
+    ms_moments(s0, s1, (double)(f.seg_off[b + 1] - f.seg_off[b]), (double)f.eps, mu, sig);
+    mom[j] = mu;
+    mom[f.B * f.C + j] = sig;
+    f.mean[j] = (float)mu;
+    f.mix.sig[j] = (float)sig;
 }
 
 // largest b in [0, B) with seg_off[b] <= v (the scan that holds sorted row v)
@@ -154,7 +168,7 @@ __global__ __launch_bounds__(256) void k_in_reduce4(const float4 *__restrict__ x
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     if (row0 + u * RB >= e) continue;
-                    bn_red_terms4<MODE>(v[u], g[u], g[u], false, bn_f4(m), bn_f4(is), a);   // g is masked already
+                    bn_red_terms4<MODE == 1>(v[u], g[u], g[u], false, bn_f4(m), bn_f4(is), a);   // g is masked already
                 }
             }
         }
@@ -172,8 +186,13 @@ __global__ __launch_bounds__(256) void k_in_reduce4(const float4 *__restrict__ x
         for (int j = tid; j < BC; j += 256) {
             const double s0 = lidog_rows_sum_sc1(grows, 0, ng, 2 * BC, j);
             const double s1 = lidog_rows_sum_sc1(grows, 0, ng, 2 * BC, BC + j);
-            in_finalize(MODE, fin, j, s0, s1);
+            if (MODE == 2) in_finalize_ms(fin, j, s0, s1, red);
+            else in_finalize(MODE, fin, j, s0, s1);
             if (MODE == 1) { red[j] = s0; red[BC + j] = s1; }
+        }
+        if (MODE == 2) {   // every scan's moments are in LDS before any scan reads its partner's
+            __syncthreads();
+            for (int j = tid; j < BC; j += 256) ms_tables(fin.mix, seg_off, red, B, C, j);
         }
         if (MODE == 1) {
             __syncthreads();
@@ -197,11 +216,11 @@ __global__ __launch_bounds__(256) void k_in_reduce_scalar(const float *__restric
     __shared__ double s_red[2][4];
     const int j = blockIdx.x, b = j / C, c = j % C;
     const int64_t s = fin.seg_off[b], e = fin.seg_off[b + 1];
-    const float m = MODE ? mean[j] : 0.f, is = MODE ? invstd[j] : 1.f;
+    const float m = MODE == 1 ? mean[j] : 0.f, is = MODE == 1 ? invstd[j] : 1.f;
     double t0 = 0, t1 = 0;
     for (int64_t i = s + threadIdx.x; i < e; i += 256) {
         const int64_t pr = perm[i];
-        bn_red_terms<MODE>(x[pr * C + c], MODE ? dy[pr * C + c] : 0.f, 1.f, false, m, is, t0, t1);
+        bn_red_terms<MODE == 1>(x[pr * C + c], MODE == 1 ? dy[pr * C + c] : 0.f, 1.f, false, m, is, t0, t1);
     }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
@@ -213,9 +232,16 @@ __global__ __launch_bounds__(256) void k_in_reduce_scalar(const float *__restric
     if (threadIdx.x == 0) {
         const double s0 = s_red[0][0] + s_red[0][1] + s_red[0][2] + s_red[0][3];
         const double s1 = s_red[1][0] + s_red[1][1] + s_red[1][2] + s_red[1][3];
-        in_finalize(MODE, fin, j, s0, s1);
+        if (MODE == 2) in_finalize_ms(fin, j, s0, s1, sums);
+        else in_finalize(MODE, fin, j, s0, s1);
         if (MODE == 1) { sums[j] = s0; sums[(int64_t)fin.B * C + j] = s1; }
     }
+}
+
+// MODE 2 on the scalar path, phase two: the moments of every (b, c) are in `mom` (the launch in front of this one)
+__global__ __launch_bounds__(256) void k_in_ms_tables(const double *__restrict__ mom, InFinish fin) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j < fin.B * fin.C) ms_tables(fin.mix, fin.seg_off, mom, fin.B, fin.C, j);
 }
 
 __global__ void k_in_param_grads(const double *__restrict__ sums, int B, int C, float *__restrict__ dw,
@@ -258,10 +284,11 @@ static int in_reduce(const float *x, const float *dy, int dy_s4, const uint32_t 
                                                           bits_o4, n, C4, perm, mean, invstd, per, tail, fin);
         if (hipPeekAtLastError() != hipSuccess) lidog_stats_tickets_reset(st);
     } else {
-        LIDOG_REQUIRE(bits == nullptr && (MODE == 0 || dy_s4 == C / 4 || C % 4 != 0),
+        LIDOG_REQUIRE(bits == nullptr && (MODE != 1 || dy_s4 == C / 4 || C % 4 != 0),
                       "instance norm reduce: strided / masked dy only on the float4 path");
         k_in_reduce_scalar<MODE><<<(unsigned)(B * C), 256, 0, st>>>(x, dy, C, perm, mean, invstd, ws, fin);
         if (MODE == 1) k_in_param_grads<<<(C + 127) / 128, 128, 0, st>>>(ws, B, C, fin.dw, fin.db);
+        if (MODE == 2) k_in_ms_tables<<<(unsigned)cdiv64((int64_t)B * C, 256), 256, 0, st>>>(ws, fin);
     }
     LIDOG_LAUNCH_CHECK();
     return 0;
@@ -280,6 +307,12 @@ extern "C" int lidog_in_bwd_reduce(const float *dy, const float *x, int64_t n, i
     LIDOG_REQUIRE(coef && dw && db, "in_bwd_reduce: coef [2, B, C], dw [C] and db [C] required");
     InFinish fin{seg_off, B, C, 0.f, nullptr, nullptr, coef, dw, db};
     return in_reduce<1>(x, dy, C / 4, nullptr, 0, 0, n, C, B, perm, mean, invstd, ws, fin, (hipStream_t)stream);
+}
+
+int lidog_in_reduce_mixstyle(const float *x, int64_t n, int C, int B, const int32_t *perm, const int32_t *seg_off,
+                             float eps, float *mean, const MsMix &mix, double *ws, hipStream_t st) {
+    InFinish fin{seg_off, B, C, eps, mean, nullptr, nullptr, nullptr, nullptr, mix};
+    return in_reduce<2>(x, nullptr, 0, nullptr, 0, 0, n, C, B, perm, nullptr, nullptr, ws, fin, st);
 }
 
 // ------------------------------------------------------------------ elementwise passes

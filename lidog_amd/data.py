@@ -956,3 +956,34 @@ def collate_items(items, with_bev):
         if with_bev:
             batch[f"source_bev_labels{s}"] = {"block8": torch.stack(bev)}
     return batch
+
+
+# ------------------------------------------------------------------ MixStyle (include/lidog_amd.h, csrc/mixstyle.hip)
+MIXSTYLE_STAGES = ("block1", "block2", "block3", "block4")
+MIXSTYLE_DEFAULT_STAGES = ("block1", "block2")
+
+
+def check_mixstyle_arguments(layers, p=0.5, alpha=0.1):
+    """the checks of the models, build_step / Fit and the command line; returns the stage names as a tuple"""
+    layers = tuple(layers)
+    for name in layers:
+        if name not in MIXSTYLE_STAGES:
+            raise ValueError(f"mixstyle stage {name!r}: one of {', '.join(MIXSTYLE_STAGES)}")
+    if len(set(layers)) != len(layers):
+        raise ValueError(f"mixstyle stages {list(layers)}: every stage once")
+    if not (isinstance(p, (int, float)) and 0 <= p <= 1):           # a NaN fails the comparison
+        raise ValueError(f"mixstyle_p {p}: a probability, 0 <= p <= 1")
+    if not (isinstance(alpha, (int, float)) and 0 < alpha < float("inf")):
+        raise ValueError(f"mixstyle_alpha {alpha}: the Beta distribution's parameter is positive and finite")
+    return layers
+
+
+def draw_mixstyle(rng, B, p=0.5, alpha=0.1):
+    """The draws of one MixStyle call on a batch of B scans (rng: a legacy RandomState), in a fixed order:
+    `random_sample()` -- the gate: a value >= p returns None and nothing more is drawn --, then `beta(alpha, alpha, B)`,
+    then `permutation(B)`.  Returns (lam float32 [B], partner int32 [B]): scan b is mixed with scan partner[b]."""
+    if rng.random_sample() >= p:
+        return None
+    lam = rng.beta(alpha, alpha, int(B))
+    partner = rng.permutation(int(B))
+    return np.asarray(lam, dtype=np.float32), np.asarray(partner, dtype=np.int32)

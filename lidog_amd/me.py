@@ -14,9 +14,10 @@ Mirrors the surface of MinkowskiEngine 0.5.4 that LiDOG's models and pipelines u
   MinkowskiFunctional.relu                           utils/models/resunet.py:4,39
   utils.kaiming_normal_                              minkunet_bev.py:404
   modules.resnet_block.BasicBlock                    minkunet_bev.py:4,425-439
+  MinkowskiMixStyle                                  NOT an ME name (MixStyle, csrc/mixstyle.hip)
 
 `install_as_minkowski_engine()` registers this module as `MinkowskiEngine` so the reference's
-`import MinkowskiEngine as ME` resolves to it.  Everything runs on the GPU through the C ABI; there
+`import MinkowskiEngine as ME` resolves to it (MinkowskiMixStyle rides along under that alias).  Everything runs on the GPU through the C ABI; there
 is no CPU path (tensors on the CPU raise).  The pooling operators are HIP gathers over the rule book's per-row lists
 and over the scans of a map (csrc/pool.hip): no weights, no atomics, the same bits on every call.
 """
@@ -1524,6 +1525,102 @@ class MinkowskiInstanceNorm(nn.Module):
 
     def extra_repr(self):
         return f"{self.num_features}"
+
+
+# ------------------------------------------------------------------ MixStyle
+# Not a MinkowskiEngine name: MixStyle (Zhou et al., ICLR 2021) is neither in ME nor in the reference.  It lives here
+# because it is an operator on SparseTensors over the segments of a coordinate map; include/lidog_amd.h defines it.
+MIXSTYLE_EPS = 1e-6
+
+
+class _MixStyleFn(torch.autograd.Function):
+    """y = (x - mu_b) sig_mix / sig_b + mu_mix per scan over the segments of a coordinate map (csrc/mixstyle.hip): one
+    launch for the statistics and the mixed tables, one for the rows; the statistics are constants to autograd, so
+    backward is dx = dy * scale[b].  lam / partner: pinned host tensors [B] (the entry point checks partner and copies
+    both in stream order)."""
+
+    @staticmethod
+    def forward(ctx, x, segs, lam, partner, eps):
+        x = x.contiguous()
+        n, C = x.shape
+        perm, seg_off, bid, B = segs
+        dev = x.device
+        tabs = torch.empty((5, B * C), dtype=torch.float32, device=dev)     # mean, sig, sub, scale, add
+        ws = torch.empty(_lib.load().lidog_mixstyle_ws(B, C), dtype=torch.float64, device=dev)
+        call("lidog_mixstyle_stats", ptr(x), n, C, B, ptr(perm), ptr(seg_off), ptr(lam), ptr(partner), float(eps),
+             ptr(tabs[0]), ptr(tabs[1]), ptr(tabs[2]), ptr(tabs[3]), ptr(tabs[4]), ptr(ws))
+        y = torch.empty_like(x)
+        call("lidog_mixstyle_apply", ptr(x), n, C, B, ptr(bid), ptr(tabs[2]), ptr(tabs[3]), ptr(tabs[4]), ptr(y))
+        ctx.scale, ctx.bid, ctx.B = tabs[3], bid, B
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = dy.contiguous()
+        n, C = dy.shape
+        dx = torch.empty_like(dy)
+        call("lidog_mixstyle_bwd", ptr(dy), n, C, ctx.B, ptr(ctx.bid), ptr(ctx.scale), ptr(dx))
+        return dx, None, None, None, None
+
+
+class MinkowskiMixStyle(nn.Module):
+    """MixStyle on a SparseTensor (NOT a MinkowskiEngine name; include/lidog_amd.h states the definition): in training
+    mode, with probability `p`, every scan's per-channel mean and standard deviation are interpolated with those of a
+    partner scan, lam ~ Beta(alpha, alpha) per scan, the partners a random permutation of the batch
+    (lidog_amd.data.draw_mixstyle on the module's OWN RandomState, seeded with `seed`: nobody else's random sequence is
+    consumed).  In eval mode, or when the gate fails, forward returns `x` itself and launches nothing.
+    `forward(x, draws=(lam, partner))` takes the draws as given ([B] each) and draws nothing.  No parameters, no
+    buffers."""
+
+    def __init__(self, p=0.5, alpha=0.1, eps=MIXSTYLE_EPS, seed=0):
+        super().__init__()
+        from .data import check_mixstyle_arguments
+        check_mixstyle_arguments((), p, alpha)
+        self.p, self.alpha, self.eps, self.seed = p, alpha, eps, seed
+        self.rng = np.random.RandomState(seed)
+        self._stage = None      # (pinned lam, pinned partner, event behind the last launch that copies them)
+
+    def __getstate__(self):     # copies and pickles take the random state along, not the pinned staging buffers
+        state = dict(self.__dict__)
+        state["_stage"] = None
+        return state
+
+    def _upload(self, lam, partner, B):
+        """lam / partner in pinned memory: the entry point's copy does not wait for the device.  The buffers are
+        reused from call to call; the event tells when the previous call's copy has run (long ago, in a training loop)"""
+        lam = np.ascontiguousarray(lam, dtype=np.float32).reshape(-1)
+        partner = np.ascontiguousarray(partner, dtype=np.int32).reshape(-1)
+        if lam.shape[0] != B or partner.shape[0] != B:
+            raise ValueError(f"MinkowskiMixStyle: lam [{lam.shape[0]}] / partner [{partner.shape[0]}] for {B} scans")
+        if self._stage is None or self._stage[0].shape[0] != B:
+            self._stage = (torch.empty(B, dtype=torch.float32).pin_memory(),
+                           torch.empty(B, dtype=torch.int32).pin_memory(), None)
+        h_lam, h_partner, event = self._stage
+        if event is not None:
+            event.synchronize()
+        h_lam.numpy()[:] = lam
+        h_partner.numpy()[:] = partner
+        return h_lam, h_partner
+
+    def forward(self, x, draws=None):
+        if draws is None:
+            if not self.training:
+                return x
+            from .data import draw_mixstyle
+            B = int(x.coordinate_manager.batch_size or 0)
+            draws = draw_mixstyle(self.rng, B, self.p, self.alpha)
+            if draws is None:
+                return x
+        segs = x.coordinate_manager.segments(x.coordinate_map_key)
+        h_lam, h_partner = self._upload(draws[0], draws[1], segs[3])
+        y = _MixStyleFn.apply(x.F, segs, h_lam, h_partner, self.eps)
+        event = torch.cuda.Event()
+        event.record()
+        self._stage = (h_lam, h_partner, event)
+        return x._like(y)
+
+    def extra_repr(self):
+        return f"p={self.p}, alpha={self.alpha}, eps={self.eps}, seed={self.seed}"
 
 
 class _IBNReluFn(torch.autograd.Function):

@@ -136,6 +136,26 @@ def make_models(ME, Encoder2D=None, sparse2super=None):
             self.relu = ME.MinkowskiReLU(inplace=True)
             self.dropout = ME.MinkowskiDropout(p=0.5)  # constructed, never called (minkunet_bev.py:126)
 
+        def _build_mixstyle(self, layers, p, alpha, seed):
+            """MixStyle (ME.MinkowskiMixStyle, include/lidog_amd.h) behind the named encoder stages: weightless modules,
+            registered last and only when asked for, so state_dict keys and their order never change.  Every module
+            draws from its own RandomState, seeded with (seed, stage number)."""
+            layers = tuple(layers)
+            stages = [f"block{i}" for i, _ in _ENC]
+            if any(name not in stages for name in layers) or len(set(layers)) != len(layers):
+                raise ValueError(f"mixstyle_layers {list(layers)}: distinct stages among {', '.join(stages)}")
+            if layers:
+                self.mixstyle = nn.ModuleDict({name: ME.MinkowskiMixStyle(p=p, alpha=alpha, seed=[seed, int(name[5:])])
+                                               for name in sorted(layers)})
+
+        def _mixstyle_training(self):
+            """MixStyle may act in this forward pass: the operator path runs it (the executor knows BasicBlocks only)"""
+            return self.training and "mixstyle" in self._modules
+
+        def _mix(self, stage, x):
+            mods = self._modules.get("mixstyle")
+            return mods[stage](x) if mods is not None and stage in mods else x
+
         def _make_layer(self, planes, blocks, block):
             downsample = None
             if self.inplanes != planes:
@@ -167,7 +187,7 @@ def make_models(ME, Encoder2D=None, sparse2super=None):
 
         def _trunk_forward(self, x):
             """returns (out_block8, out_bottle, {level: tensor}, classifier output or None = not computed yet)"""
-            if _trunk_exec is not None and self.EXECUTOR:
+            if _trunk_exec is not None and self.EXECUTOR and not self._mixstyle_training():
                 done = _trunk_exec(self, x)
                 if done is not None:
                     return done
@@ -175,7 +195,7 @@ def make_models(ME, Encoder2D=None, sparse2super=None):
             skips = [out]
             for i, s in _ENC:
                 out = self._conv_bn_relu(getattr(self, f"conv{i}p{s}s2"), getattr(self, f"bn{i}"), out)
-                out = getattr(self, f"block{i}")(out)
+                out = self._mix(f"block{i}", getattr(self, f"block{i}")(out))
                 skips.append(out)
             bottle = skips.pop()
             levels = {}
@@ -188,10 +208,12 @@ def make_models(ME, Encoder2D=None, sparse2super=None):
             return out, bottle, levels, None
 
     class MinkUNet34(_Trunk):
-        def __init__(self, in_channels, out_channels, D=3, initial_kernel_size=5):
+        def __init__(self, in_channels, out_channels, D=3, initial_kernel_size=5, mixstyle_layers=(), mixstyle_p=0.5,
+                     mixstyle_alpha=0.1, mixstyle_seed=0):
             super().__init__()
             self._build_trunk(in_channels, out_channels, D, initial_kernel_size)
             self.weight_initialization()
+            self._build_mixstyle(mixstyle_layers, mixstyle_p, mixstyle_alpha, mixstyle_seed)
 
         def forward(self, x, is_seg=True):
             out, _, _, seg = self._trunk_forward(x)
@@ -201,7 +223,8 @@ def make_models(ME, Encoder2D=None, sparse2super=None):
     class MinkUNet34BEV(_Trunk):
         def __init__(self, in_channels, out_channels, D, initial_kernel_size=5, dynamic_mapping=False,
                      decoder_2d_level=("block8",), bottle_img_dim=None, bottle_out_img_dim=None,
-                     mapping_bound_2d=50.0, scaling_factors=None, binary_seg_layer=False):
+                     mapping_bound_2d=50.0, scaling_factors=None, binary_seg_layer=False, mixstyle_layers=(),
+                     mixstyle_p=0.5, mixstyle_alpha=0.1, mixstyle_seed=0):
             super().__init__()
             assert not binary_seg_layer, "binary_seg_layer is off in every LiDOG config"
             self.mapping_bound_2d = mapping_bound_2d
@@ -211,6 +234,7 @@ def make_models(ME, Encoder2D=None, sparse2super=None):
             self.encoders2d = nn.ModuleDict({k: Encoder2D(BEV_LEVEL_CHANNELS[k], n_classes=out_channels)
                                              for k in self.decoder_2d_level})
             self.weight_initialization()
+            self._build_mixstyle(mixstyle_layers, mixstyle_p, mixstyle_alpha, mixstyle_seed)
 
         def forward(self, x, is_seg=True, is_train=False):
             out, bottle, levels, seg = self._trunk_forward(x)
@@ -232,10 +256,12 @@ def make_models(ME, Encoder2D=None, sparse2super=None):
         conv0p1s1 is always 5^3 (resnet_old.py via minkunet_ibn.py:68-69)."""
         EXECUTOR = False
 
-        def __init__(self, in_channels, out_channels, D=3, initial_kernel_size=5):
+        def __init__(self, in_channels, out_channels, D=3, initial_kernel_size=5, mixstyle_layers=(), mixstyle_p=0.5,
+                     mixstyle_alpha=0.1, mixstyle_seed=0):
             super().__init__()
             self._build_trunk(in_channels, out_channels, D, 5)
             self.weight_initialization()
+            self._build_mixstyle(mixstyle_layers, mixstyle_p, mixstyle_alpha, mixstyle_seed)
 
         def _stage_block(self, stage):
             return IBNBlock if stage <= 3 else BasicBlock
@@ -256,7 +282,8 @@ def make_models(ME, Encoder2D=None, sparse2super=None):
         therefore stays un-ReLU'd (the [ME-mem] convention next to lidog_amd.me.IN_EPS)."""
         EXECUTOR = False
 
-        def __init__(self, in_channels, out_channels, D=3, initial_kernel_size=5):
+        def __init__(self, in_channels, out_channels, D=3, initial_kernel_size=5, mixstyle_layers=(), mixstyle_p=0.5,
+                     mixstyle_alpha=0.1, mixstyle_seed=0):
             super().__init__()
             self.D = D
             # minkunet_robustnet.py:68-158, in registration order (state_dict keys)
@@ -284,6 +311,7 @@ def make_models(ME, Encoder2D=None, sparse2super=None):
             self.relu = ME.MinkowskiReLU(inplace=True)
             self.dropout = ME.MinkowskiDropout(p=0.5)  # constructed, never called
             self.weight_initialization()
+            self._build_mixstyle(mixstyle_layers, mixstyle_p, mixstyle_alpha, mixstyle_seed)
 
         def forward(self, x, is_seg=True):
             # minkunet_robustnet.py:160-224
@@ -296,15 +324,16 @@ def make_models(ME, Encoder2D=None, sparse2super=None):
             # for its backward pass (same values; out_in1 is not ReLU'd either way)
             out = ME.MinkowskiReLU()(out)
             out_in1p2 = self.block1(out)
-            out_b1p2 = self.relu(out_in1p2)
+            # MixStyle acts on what the next stage and the skip read; the maps of the whitening loss stay as they are
+            out_b1p2 = self._mix("block1", self.relu(out_in1p2))
             out = self._conv_bn_relu(self.conv2p2s2, self.bn2, out_b1p2)
             out_in2p4 = self.block2(out)
-            out_b2p4 = self.relu(out_in2p4)
+            out_b2p4 = self._mix("block2", self.relu(out_in2p4))
             out = self._conv_bn_relu(self.conv3p4s2, self.bn3, out_b2p4)
             out_in3p8 = self.block3(out)
-            out_b3p8 = self.relu(out_in3p8)
+            out_b3p8 = self._mix("block3", self.relu(out_in3p8))
             out = self._conv_bn_relu(self.conv4p8s2, self.bn4, out_b3p8)
-            out = self.block4(out)
+            out = self._mix("block4", self.block4(out))
             skips = [out_p1, out_b1p2, out_b2p4, out_b3p8]
             for j, s in _DEC:
                 out = self._conv_bn_relu(getattr(self, f"convtr{j}p{s}s2"), getattr(self, f"bntr{j}"), out)

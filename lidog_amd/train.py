@@ -43,7 +43,8 @@ from . import me as ME
 from . import scans
 from . import synth
 from .checkpoint import load_training_checkpoint, save_lightning_checkpoint
-from .data import (augment_item, band_bounds, check_augmentations, collate_items, cosmix_merge, draw_augmentation,
+from .data import (MIXSTYLE_DEFAULT_STAGES, augment_item, band_bounds, check_augmentations, check_mixstyle_arguments,
+                   collate_items, cosmix_merge, draw_augmentation,
                    draw_lasermix, draw_polarmix, draw_scaling, draw_source, instance_mask, lasermix_merge, mix3d_merge,
                    on_merge_stream, pointcutmix_merge, polarmix_merge, scaling_params, sn_scale)
 from . import precision as _precision
@@ -596,30 +597,66 @@ def bev_image_size(bound_2d, voxel=0.05, pool=(5, 3, 1)):
 
 
 def build_model(kind="MinkUNet34BEV", bound_2d=50.0, in_channels=1, out_channels=7, conv1_kernel_size=5,
-                decoder_2d_levels=("block8",), device="cuda"):
+                decoder_2d_levels=("block8",), device="cuda", mixstyle_layers=(), mixstyle_p=0.5, mixstyle_alpha=0.1,
+                mixstyle_seed=0):
     """get_model of train_lidog.py:42-75 (MinkUNet34BEV) / train_source.py:43-58 (MinkUNet34, MinkUNet34IBN,
-    MinkUNet34Robust)"""
+    MinkUNet34Robust).  `mixstyle_layers`: the encoder stages (block1 .. block4) whose output passes through a
+    MinkowskiMixStyle(mixstyle_p, mixstyle_alpha) in training mode; the default builds exactly the reference's model."""
     import lidog_amd
+    ms = {}
+    if check_mixstyle_arguments(mixstyle_layers, mixstyle_p, mixstyle_alpha):
+        ms = dict(mixstyle_layers=tuple(mixstyle_layers), mixstyle_p=mixstyle_p, mixstyle_alpha=mixstyle_alpha,
+                  mixstyle_seed=mixstyle_seed)
     if kind == "MinkUNet34BEV":
         m = lidog_amd.MinkUNet34BEV(in_channels=in_channels, out_channels=out_channels, D=3,
                                     initial_kernel_size=conv1_kernel_size, decoder_2d_level=list(decoder_2d_levels),
-                                    mapping_bound_2d=bound_2d)
+                                    mapping_bound_2d=bound_2d, **ms)
     elif kind == "MinkUNet34":
         m = lidog_amd.MinkUNet34(in_channels=in_channels, out_channels=out_channels, D=3,
-                                 initial_kernel_size=conv1_kernel_size)
+                                 initial_kernel_size=conv1_kernel_size, **ms)
     elif kind == "MinkUNet34IBN":   # train_source.py:49-53; ResNetBase drops the kernel size: conv0p1s1 is 5^3
-        m = lidog_amd.MinkUNet34IBN(in_channels=in_channels, out_channels=out_channels, D=3)
+        m = lidog_amd.MinkUNet34IBN(in_channels=in_channels, out_channels=out_channels, D=3, **ms)
     elif kind == "MinkUNet34Robust":   # the same: conv0p1s1 is 5^3
-        m = lidog_amd.MinkUNet34Robust(in_channels=in_channels, out_channels=out_channels, D=3)
+        m = lidog_amd.MinkUNet34Robust(in_channels=in_channels, out_channels=out_channels, D=3, **ms)
     else:
         raise NotImplementedError(kind)
     return m.to(device)
 
 
+def mixstyle_stages_of(model):
+    """the stages of `model` that carry a MinkowskiMixStyle, in stage order (() for a plain model)"""
+    mods = getattr(model, "_modules", {}).get("mixstyle")
+    return tuple(mods.keys()) if mods is not None else ()
+
+
+def check_mixstyle(mixstyle, mixstyle_p=0.5, mixstyle_alpha=0.1, precision=None, sam_rho=None, batch_size=None,
+                   what="mixstyle"):
+    """The argument checks of MixStyle training (data.check_mixstyle_arguments) and what is not built: more than one
+    rank, bf16 training steps, SAM (its second pass would need the first pass's draws replayed) and a batch of one scan
+    (nothing to mix with).  `mixstyle`: None (off) or the stage names.  Returns the stages as a tuple."""
+    if mixstyle is None:
+        return ()
+    layers = check_mixstyle_arguments(mixstyle, mixstyle_p, mixstyle_alpha)
+    if not layers:
+        raise ValueError(f"{what}: no stage named (block1 .. block4); leave it out to train without MixStyle")
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        raise NotImplementedError(f"{what} with {dist.get_world_size()} ranks: a MixStyle step leaves the trunk executor "
+                                  "for the operator path and mixes within one rank's batch; data-parallel runs are "
+                                  "not built")
+    if _precision.resolve(precision):
+        raise NotImplementedError(f"{what} with precision='bf16': MixStyle is validated on the fp32 step only")
+    if sam_rho is not None:
+        raise NotImplementedError(f"{what} with sam_rho: SAM's second pass would need the first pass's draws replayed")
+    if batch_size is not None and batch_size < 2:
+        raise ValueError(f"{what} with a batch of {batch_size} scan: a scan is mixed with another scan of its batch")
+    return layers
+
+
 def build_step(model, kind="MinkUNet34BEV", optimizer="Adam", lr=1e-3, scheduler=None, weight_decay=1e-4,
                momentum=0.98, warmup_epochs=0, source_weights=(0.5, 0.5), num_classes=7, ignore_label=-1, num_sources=1,
                precision=None, sem_criterion="SoftDICELoss", sem_bev_criterion=None, sem_aux_criterion=None,
-               sem_aux_weight=1.0, sam_rho=None, sam_adaptive=False, grad_clip_norm=None):
+               sem_aux_weight=1.0, sam_rho=None, sam_adaptive=False, grad_clip_norm=None, mixstyle=None, mixstyle_p=0.5,
+               mixstyle_alpha=0.1):
     """SyncBN conversion when data-parallel (train_lidog.py:227-231), optimiser + scheduler
     (trainer_lighting_2d.py:349-394), step object (PLTTrainer2D / PLTRobustNet / PLTTrainer, on one or two sources).
     `precision`: the training steps' (trainer._Step).  `sem_criterion` / `sem_bev_criterion`: the point and BEV losses by
@@ -628,6 +665,9 @@ def build_step(model, kind="MinkUNet34BEV", optimizer="Adam", lr=1e-3, scheduler
     every step adds to its point loss, and its weight.
     `sam_rho` (None: off) / `sam_adaptive`: sharpness-aware minimisation around the optimiser (optim.SAM: radius, the
     adaptive form); `grad_clip_norm` (None: off): the largest 2-norm of the whole gradient (trainer._Step).  One rank.
+    `mixstyle` (None: the stages `model` was built with, build_model's mixstyle_layers) / `mixstyle_p` /
+    `mixstyle_alpha`: checked against what MixStyle training does not support (check_mixstyle); the modules themselves
+    belong to the model.
     Returns (model, step, scheduler)."""
     if num_sources not in (1, 2):
         raise NotImplementedError(f"{num_sources} sources (the reference takes one or two)")
@@ -638,6 +678,12 @@ def build_step(model, kind="MinkUNet34BEV", optimizer="Adam", lr=1e-3, scheduler
     check_sam_arguments(sam_rho, sam_adaptive, grad_clip_norm)
     if sam_rho is not None or grad_clip_norm is not None:
         _optim.check_single_rank("sam_rho / grad_clip_norm")
+    if mixstyle is None and mixstyle_stages_of(model):
+        mixstyle = mixstyle_stages_of(model)
+    if check_mixstyle(mixstyle, mixstyle_p, mixstyle_alpha, precision, sam_rho) and \
+            set(mixstyle) != set(mixstyle_stages_of(model)):
+        raise ValueError(f"mixstyle={list(mixstyle)}: the model was built with {list(mixstyle_stages_of(model))} "
+                         "(build_model's mixstyle_layers)")
     model = setup_data_parallel(model)
     model.train()
     opt = make_optimizer(optimizer, model, lr, weight_decay=weight_decay, momentum=momentum)
@@ -686,8 +732,15 @@ class Fit:
                  device="cuda", log=None, state_dict=None, num_sources=None, log_every_n_steps=0, metric_sources=None,
                  val_precision=None, precision=None, sem_criterion="SoftDICELoss", sem_bev_criterion=None,
                  sem_aux_criterion=None, sem_aux_weight=1.0, weight_average=None, avg_decay=0.996, avg_decay_final=None,
-                 avg_start_epoch=0, sam_rho=None, sam_adaptive=False, grad_clip_norm=None):
-        """`sam_rho` / `sam_adaptive` / `grad_clip_norm`: build_step's (optim.SAM around the optimiser; the global
+                 avg_start_epoch=0, sam_rho=None, sam_adaptive=False, grad_clip_norm=None, mixstyle=None, mixstyle_p=0.5,
+                 mixstyle_alpha=0.1):
+        """`mixstyle` (None: off; else the encoder stages, e.g. ("block1", "block2")) / `mixstyle_p` / `mixstyle_alpha`:
+        MixStyle (me.MinkowskiMixStyle, include/lidog_amd.h) behind those stages in training mode: per step and stage,
+        with probability p, every scan's feature statistics are mixed with another scan's of the same source's batch.
+        The modules draw from their own random states, seeded from `seed`; the data pipeline's sequence is untouched.
+        Validation and eval_target see the plain model; checkpoints record the three values under `mixstyle`.  One
+        rank, fp32 steps, no SAM, at least two scans per batch (check_mixstyle).
+        `sam_rho` / `sam_adaptive` / `grad_clip_norm`: build_step's (optim.SAM around the optimiser; the global
         gradient-norm clip).  SAM keeps no state: a resumed run passes the arguments again.
         `weight_average`: None, "ema" or "swa": an optim.WeightAverage of the model's weights and running statistics,
         updated by one launch after every training step of an epoch >= `avg_start_epoch`.  "ema" decays by `avg_decay`,
@@ -718,6 +771,9 @@ class Fit:
         check_sam_arguments(sam_rho, sam_adaptive, grad_clip_norm)
         if sam_rho is not None or grad_clip_norm is not None:
             _optim.check_single_rank("Fit(sam_rho / grad_clip_norm)")
+        self.mixstyle = check_mixstyle(mixstyle, mixstyle_p, mixstyle_alpha, precision, sam_rho, batch_size,
+                                       "Fit(mixstyle)")
+        self.mixstyle_p, self.mixstyle_alpha = mixstyle_p, mixstyle_alpha
         self.rank, self.world = _rank_world()
         _precision.resolve(val_precision)
         self.val_precision, self.precision = val_precision, precision
@@ -729,7 +785,8 @@ class Fit:
         self.device = device
         self.log = log if log is not None else (print if self.rank == 0 else (lambda *_: None))
         torch.manual_seed(seed)                         # pipeline.seed (semantickitti.yaml:32)
-        model = build_model(model_kind, bound_2d, device=device)
+        model = build_model(model_kind, bound_2d, device=device, mixstyle_layers=self.mixstyle, mixstyle_p=mixstyle_p,
+                            mixstyle_alpha=mixstyle_alpha, mixstyle_seed=seed)
         if state_dict is not None:
             model.load_state_dict(state_dict)
         if num_sources is None:
@@ -738,7 +795,8 @@ class Fit:
             model, model_kind, optimizer, lr, scheduler, weight_decay, momentum, warmup_epochs, source_weights,
             num_sources=num_sources, precision=precision, sem_criterion=sem_criterion,
             sem_bev_criterion=sem_bev_criterion, sem_aux_criterion=sem_aux_criterion, sem_aux_weight=sem_aux_weight,
-            sam_rho=sam_rho, sam_adaptive=sam_adaptive, grad_clip_norm=grad_clip_norm)
+            sam_rho=sam_rho, sam_adaptive=sam_adaptive, grad_clip_norm=grad_clip_norm,
+            mixstyle=self.mixstyle or None, mixstyle_p=mixstyle_p, mixstyle_alpha=mixstyle_alpha)
         self.opt = self.step.opt
         self.avg, self.avg_start_epoch = None, int(avg_start_epoch)
         if weight_average is not None:
@@ -842,7 +900,9 @@ class Fit:
         os.makedirs(d, exist_ok=True)
         path = os.path.join(d, f"epoch={epoch}-step={self.global_step}.ckpt")
         save_lightning_checkpoint(self.model, path, epoch=epoch, global_step=self.global_step, optimizer=self.opt,
-                                  scheduler=self.sched, weight_average=self.avg)
+                                  scheduler=self.sched, weight_average=self.avg,
+                                  mixstyle={"layers": list(self.mixstyle), "p": self.mixstyle_p,
+                                            "alpha": self.mixstyle_alpha} if self.mixstyle else None)
         return path
 
     # ------------------------------------------------------------------ the loop
@@ -1003,8 +1063,29 @@ def parse_args(argv=None):
     ap.add_argument("--grad-clip-norm", type=float, default=argparse.SUPPRESS, metavar="X",
                     help="scale the gradient so that its global 2-norm is at most X (torch's clip_grad_norm_, Lightning's "
                          "gradient_clip_val; one GPU; default: off)")
+    ap.add_argument("--mixstyle", nargs="*", default=argparse.SUPPRESS, metavar="STAGE",
+                    help="MixStyle (Zhou et al., ICLR 2021; csrc/mixstyle.hip): in training, every scan's per-channel "
+                         "feature mean and standard deviation behind these encoder stages (block1 .. block4; the bare "
+                         "flag: block1 block2) are interpolated with another scan's of the batch; validation and "
+                         "evaluation see the plain model (one GPU, fp32, not with --sam-rho, --batch >= 2; default: off)")
+    ap.add_argument("--mixstyle-p", type=float, default=argparse.SUPPRESS, metavar="P",
+                    help="--mixstyle: the probability that a stage mixes in a step (default 0.5)")
+    ap.add_argument("--mixstyle-alpha", type=float, default=argparse.SUPPRESS, metavar="A",
+                    help="--mixstyle: the mixing weights are drawn from Beta(A, A) per scan (default 0.1)")
     scans.add_file_arguments(ap, "--files", "train on")
     a = ap.parse_args(argv)
+    if hasattr(a, "mixstyle"):
+        if not a.mixstyle:
+            a.mixstyle = list(MIXSTYLE_DEFAULT_STAGES)
+        try:
+            check_mixstyle(a.mixstyle, getattr(a, "mixstyle_p", 0.5), getattr(a, "mixstyle_alpha", 0.1),
+                           getattr(a, "precision", None), getattr(a, "sam_rho", None), a.batch, "--mixstyle")
+        except (ValueError, NotImplementedError) as e:
+            ap.error(str(e))
+    else:
+        for name in ("mixstyle_p", "mixstyle_alpha"):
+            if hasattr(a, name):
+                ap.error(f"--{name.replace('_', '-')} goes with --mixstyle")
     try:
         check_sam_arguments(**sam_of(a))
     except ValueError as e:
@@ -1167,6 +1248,12 @@ def sam_of(a):
                 grad_clip_norm=getattr(a, "grad_clip_norm", None))
 
 
+def mixstyle_of(a):
+    """Fit's mixstyle / mixstyle_p / mixstyle_alpha of parsed arguments (mixstyle None when the flag was not given)"""
+    return dict(mixstyle=getattr(a, "mixstyle", None), mixstyle_p=getattr(a, "mixstyle_p", 0.5),
+                mixstyle_alpha=getattr(a, "mixstyle_alpha", 0.1))
+
+
 def weight_average_of(a):
     """Fit's weight_average / avg_* arguments of parsed arguments (weight_average None when it was not given)"""
     return dict(weight_average=getattr(a, "weight_average", None), avg_decay=getattr(a, "avg_decay", 0.996),
@@ -1196,7 +1283,7 @@ def _fit_from_args(a):
                auto_resume=a.auto_resume, log_every_n_steps=getattr(a, "log_every_n_steps", 0),
                val_precision=val_precision_of(a), precision=precision_of(a), sem_criterion=sem_criterion_of(a),
                sem_bev_criterion=sem_bev_criterion_of(a), sem_aux_criterion=sem_aux_criterion,
-               sem_aux_weight=sem_aux_weight, **weight_average_of(a), **sam_of(a))
+               sem_aux_weight=sem_aux_weight, **weight_average_of(a), **sam_of(a), **mixstyle_of(a))
 
 
 def _data_from_args(a):

@@ -458,6 +458,74 @@ int lidog_entropy_fwd(const float *logits, const uint8_t *mask, int64_t n, int32
 int lidog_entropy_bwd(const float *logits, const uint8_t *mask, const float *row_h, int64_t n, int32_t C, float margin,
                       const float *coef, const float *gout, float *glogits, void *stream);
 
+/* ------------------------------------------------------------------ calibration of the row softmax
+ * csrc/calib.hip (lidog_amd.calibration; eval_target --calibration); not in the reference, whose metrics are IoU only.
+ * logits [n, C] float32, C in 2..32; labels [n] int64.  A row is LABELLED iff 0 <= label < C and label != ignore_label
+ * (lidog_eval_confusion's rule); every other row is not read and adds nothing.  beta: a DEVICE double, the inverse
+ * temperature 1 / T > 0, or NULL for 1.0 (a device 1.0 gives the same bytes as NULL).  Per labelled row, in double:
+ *   m = max_c x_c,  z_c = beta ((double)x_c - (double)m),  s = sum_c exp(z_c) in class order,  p_c = exp(z_c) / s,
+ *   pred = the first maximal class (so lidog_eval_confusion's, for any beta > 0),  conf = 1 / s,
+ *   nll = log s - z_label,  brier = sum_c (p_c - [c == label])^2 in class order,
+ *   bin = min(B - 1, (int)floor(conf B))                       B = n_bins in 1..64, equal-width bins of [0, 1]
+ * lidog_calib_stats ADDS a batch into accumulators the caller keeps (and zeroes before the first call):
+ *   table [B, 3] int64: (count, correct = rows with pred == label, conf_q += llrint(conf 2^32)) per bin
+ *   totals [2] int64:   (rows, brier_q += llrint(brier 2^32))
+ *   nll_sum [1] double
+ * The bounded quantities are fixed-point integers on purpose: integer addition is associative, so table and totals do
+ * not depend on the order of rows, the grid or the cut of a dataset into calls (one call over n rows and calls over its
+ * slices give the same bytes).  They hold 2^30 rows.  nll_sum is unbounded and stays a double: per-workgroup partial
+ * sums in ws (compensated: every addition keeps its rounding error, Knuth's two-sum, so a batch's sum is the rounded
+ * sum of its rows whatever their spread), added in a fixed order by the last workgroup to arrive (an integer ticket),
+ * then added to nll_sum once;
+ * the same sequence of calls gives the same bytes, another cut into calls another rounding.  No floating-point atomic.
+ * A labelled row with a NaN or infinite logit (or whose conf is no positive number: a beta that is not positive and
+ * finite) is left out of everything and sets bit 1 (value 2) of *err (device int32, the caller zeroes it).
+ * ws: lidog_calib_ws(n) doubles, 8-byte aligned; ws[0] is the ticket and must be 8 zero bytes before the FIRST call that
+ * uses this workspace; every call leaves it zero.  One workspace serves one stream at a time.
+ * n == 0 launches nothing and returns 0; C outside 2..32, n_bins outside 1..64 or n C >= 2^31 return 2 before any launch.
+ *
+ * Temperature scaling minimises NLL(beta) = (1 / N) sum_rows [log sum_c exp(beta x_c) - beta x_label] over the N labelled
+ * rows (finite logits) of a calibration set: convex in beta, gradient g = (1 / N) sum (E_p[x] - x_label), curvature
+ * h = (1 / N) sum Var_p[x] >= 0, so g is non-decreasing.  state [8] double (device), trace [3] double (device):
+ *   state = (beta, lo, hi, last nll, last g, last h, iterations done, labelled rows of the last launch)
+ * lidog_calib_fit_init: state = (min(max(1, beta_min), beta_max), beta_min, beta_max, 0, 0, 0, 0, 0).
+ * lidog_calib_fit_step, ONE launch: reads beta = state[0]; sums over the rows, in double on z_c = x_c - m (the shift
+ * cancels in g and h), e_c = exp(beta z_c), s = sum e_c, E = (sum e_c z_c) / s:
+ *   L += log s - beta z_label,   G += E - z_label,   H += (sum_c e_c (z_c - E)^2) / s,   N += 1
+ * (fixed-order partials, as nll_sum); then its last workgroup writes trace = (beta, L / N, G / N) and updates
+ *   g > 0: hi = beta;  g < 0: lo = beta;  g == 0: lo = hi = beta
+ *   cand = beta - g / h  (h > 0; else -inf, +inf or beta by the sign of g)
+ *   next = beta                      if cand == beta (the step is below beta's spacing: converged)
+ *        = cand                      else if lo < cand < hi (false for a NaN)
+ *        = beta_max                  else if g < 0, cand >= hi, hi == beta_max and beta != beta_max
+ *        = beta_min                  else if g > 0, cand <= lo, lo == beta_min and beta != beta_min
+ *        = lo + (hi - lo) / 2        else
+ *   next = min(max(next, beta_min), beta_max)
+ * The first line keeps a converged iterate: beta is then an end of the bracket, the step is not strictly inside, and the
+ * midpoint would throw the iterate away and bisect back from the far end.  The two bound lines look at the interval's own
+ * bound once the step leaves through it, so a set on which g has one sign over [beta_min, beta_max] ends AT that bound
+ * (lo == hi == the bound) instead of halving towards it for ever.
+ * N == 0 (no labelled row, or n == 0: the launch still happens): beta, lo, hi stay, nll = g = h = 0.  No NaN either way.
+ * `iters` launches are queued back to back; nothing is read back in between.  err, ws: as lidog_calib_stats.
+ * Returns 2 before any launch for another C, n C >= 2^31 or bounds that are not 0 < beta_min <= beta_max < inf. */
+#define LIDOG_CALIB_STATE 8
+#define LIDOG_CALIB_BETA 0
+#define LIDOG_CALIB_LO 1
+#define LIDOG_CALIB_HI 2
+#define LIDOG_CALIB_NLL 3
+#define LIDOG_CALIB_G 4
+#define LIDOG_CALIB_H 5
+#define LIDOG_CALIB_ITER 6
+#define LIDOG_CALIB_ROWS 7
+int64_t lidog_calib_ws(int64_t n);
+int lidog_calib_stats(const float *logits, const int64_t *labels, int64_t n, int32_t C, int64_t ignore_label,
+                      const double *beta, int32_t n_bins, int64_t *table, int64_t *totals, double *nll_sum, int32_t *err,
+                      double *ws, void *stream);
+int lidog_calib_fit_init(double *state, double beta_min, double beta_max, void *stream);
+int lidog_calib_fit_step(const float *logits, const int64_t *labels, int64_t n, int32_t C, int64_t ignore_label,
+                         double beta_min, double beta_max, double *state, double *trace, int32_t *err, double *ws,
+                         void *stream);
+
 /* ------------------------------------------------------------------ data path next to the hot path
  * ME.utils.sparse_quantize (utils/datasets/semantickitti_bev.py:232-238) = lidog_voxel_floor +
  * lidog_coords_insert + lidog_coords_compact + lidog_label_vote; PC2ImgConverter.getBEVImageNew

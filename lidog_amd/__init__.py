@@ -7,6 +7,8 @@ Public surface:
   lidog_amd.losses        SoftDICELoss / DICELoss / CELoss / FocalLoss on the device; make_criterion picks one by name;
                           LovaszSoftmaxLoss, the auxiliary point criterion (make_aux_criterion); EntropyLoss
   lidog_amd.adapt         test-time adaptation at evaluation: TestTimeAdapter (bn, adabn, tent; csrc/entropy.hip)
+  lidog_amd.calibration   ECE / MCE / NLL / Brier and temperature scaling: CalibrationTable, fit_temperature
+                          (csrc/calib.hip)
   lidog_amd.trainer       training step, Adam, RCCL data parallelism
   lidog_amd.trunk         the whole encoder-decoder as one launch sequence per pass (csrc/trunk.hip)
   lidog_amd.data          voxelisation, collation and the scan mixes on the device: mix3d_merge, pointcutmix_merge,
@@ -70,6 +72,8 @@ from .minkunet import make_models  # noqa: E402
 from .losses import (CELoss, DICELoss, EntropyLoss, FocalLoss, LovaszSoftmaxLoss, SoftDICELoss,  # noqa: E402,F401
                      make_aux_criterion, make_bev_criterion, make_criterion)
 from .adapt import TestTimeAdapter  # noqa: E402,F401
+from .calibration import (CalibrationTable, collect_logits, fit_temperature,  # noqa: E402,F401
+                          metrics_from_table)
 
 me.trunk_forward = trunk.trunk_forward   # the models hand their training-mode trunk pass to the executor
 

@@ -6,6 +6,7 @@
     python -m lidog_amd.eval_target --checkpoint ... --target-files SemanticKITTI=/data/SemanticKITTI --label-maps semantickitti2common.yaml
     python -m lidog_amd.eval_target --checkpoint ... --target-files ... --label-maps ... --point-level
     python -m lidog_amd.eval_target --checkpoint ... --target-files ... --label-maps ... --save-labels --inverse-label-map common2semantickitti.yaml
+    python -m lidog_amd.eval_target --checkpoint ... --calibration --temperature fit --calibrate-on kitti120k
 
 What the reference does through pytorch-lightning's trainer.test, as plain arguments:
   get_model / get_target_domains / loaders with batch_size * 2, shuffle=False        eval_target.py:46-89,119-167
@@ -34,6 +35,14 @@ and predictions and labels go under `predictions-avg/`.  The default, live, writ
 --adapt-steps and --adapt-margin belong to tent).  The model returns to the checkpoint before every target; every results
 file carries `-adapt-<mode>` before `.csv` (after `-avg`, `-points`), predictions and labels go under
 `predictions<-avg>-adapt-<mode>/`.  fp32 only, one rank, not together with --tta.  The default, none, builds no adapter.
+--calibration: how far the voxel softmax can be trusted (lidog_amd.calibration over csrc/calib.hip): ECE, MCE, NLL, Brier
+score, accuracy and mean confidence over --calib-bins equal-width confidence bins into
+`<sources>-TO-<targets>-calibration<suffix>.csv`, the per-bin table into `<sources>-TO-<targets>-reliability<suffix>.csv`
+(the suffixes of --weights averaged and --adapt, as above).  --temperature VALUE scores T = 1 and T = VALUE; --temperature
+fit first fits T (temperature scaling) with the checkpoint under evaluation on a labelled calibration set, the validation
+scans of --calibrate-on CONFIG (synthetic, --calibrate-scans of them) or of --calibrate-files NAME=PATH with
+--calibrate-label-maps, before any target runs; under --adapt the adapter runs over that set and is reset afterwards.  A
+temperature moves no arg-max: every other output stays byte for byte what it is.  Voxel level only.
 """
 import argparse
 import json
@@ -44,8 +53,8 @@ import torch
 
 from . import synth
 from .checkpoint import load_lightning_checkpoint
-from .evaluate import (CLASS_NAMES, PointLabelWriter, PointPath, TargetEvaluator, dataset_batches, inverse_lut,
-                       load_inverse_label_map, palette, write_ply, write_results_csv)
+from .evaluate import (CLASS_NAMES, PointLabelWriter, PointPath, Predictor, TargetEvaluator, dataset_batches,
+                       inverse_lut, load_inverse_label_map, palette, write_ply, write_results_csv)
 from . import adapt, scans, tta
 from .train import SynthScans, bev_image_size, build_model, source_names
 
@@ -111,9 +120,28 @@ def parse_args(argv=None):
     ap.add_argument("--adapt-margin", type=float, default=None, metavar="F",
                     help="with --adapt tent: only voxels whose entropy lies below F ln C enter the loss (EATA / SAR use "
                          "0.4; default: every voxel)")
+    ap.add_argument("--calibration", action="store_true",
+                    help="also report the calibration of the voxel softmax (ECE, MCE, NLL, Brier, accuracy, mean "
+                         "confidence) into <sources>-TO-<targets>-calibration.csv and the per-bin table into "
+                         "<sources>-TO-<targets>-reliability.csv")
+    ap.add_argument("--calib-bins", type=int, default=None, metavar="B",
+                    help="with --calibration: equal-width confidence bins, 1..64 (default 15)")
+    ap.add_argument("--temperature", default=None, metavar="VALUE|fit",
+                    help="with --calibration: also score softmax(logits / T); a value in 0.01..100, or `fit`: temperature "
+                         "scaling fitted on the calibration set (--calibrate-on or --calibrate-files) before any target runs")
+    ap.add_argument("--calibrate-on", default=None, choices=sorted(synth.CONFIGS), metavar="CONFIG",
+                    help="with --temperature fit: fit on the synthetic validation scans of this configuration")
+    ap.add_argument("--calibrate-scans", type=int, default=None, metavar="N",
+                    help="with --temperature fit: scans of the calibration set (default 16; the first N files of "
+                         "--calibrate-files)")
+    ap.add_argument("--calibrate-files", default=None, metavar="NAME=PATH",
+                    help="with --temperature fit: fit on the validation scans of this dataset (names as --target-files)")
+    ap.add_argument("--calibrate-label-maps", default=None, metavar="FILE",
+                    help="the label map of --calibrate-files")
     a = ap.parse_args(argv)
     if a.checkpoint is None:
         ap.error(NO_CHECKPOINT)
+    check_calibration_arguments(ap, a)
     if a.adapt != "tent" and any(v is not None for v in (a.adapt_lr, a.adapt_optimizer, a.adapt_steps, a.adapt_margin)):
         ap.error("--adapt-lr, --adapt-optimizer, --adapt-steps and --adapt-margin go with --adapt tent")
     if a.adapt != "none":
@@ -130,7 +158,8 @@ def parse_args(argv=None):
     if a.target_files is not None:
         a.target_files = scans.check_file_arguments(ap, a.target_files, a, "--target-files")
         a.targets = [n for n, _ in a.target_files]               # the CSV's target names
-    elif a.label_maps is not None or a.synth4d_splits is not None or a.limit_files is not None:
+    elif a.label_maps is not None or (a.synth4d_splits is not None and a.calibrate_files is None) or \
+            a.limit_files is not None:
         ap.error("--label-maps, --synth4d-splits and --limit-files go with --target-files")
     if (a.point_level or a.save_labels or a.inverse_label_map is not None) and a.target_files is None:
         ap.error("--point-level, --save-labels and --inverse-label-map go with --target-files (a synthetic target has no "
@@ -157,6 +186,85 @@ def parse_args(argv=None):
     if a.scans < 1 or a.batch < 1:
         ap.error("--scans and --batch must be positive")
     return a
+
+
+T_MIN, T_MAX = 0.01, 100.0
+
+
+def check_calibration_arguments(ap, a):
+    """the refusals of --calibration and what goes with it; a.temperature becomes None, "fit" or a float, the defaults
+    of --calib-bins and --calibrate-scans are filled in, a.calibrate_files becomes (name, path)"""
+    sets = (a.calibrate_on is not None) + (a.calibrate_files is not None)
+    if not a.calibration:
+        if a.calib_bins is not None or a.temperature is not None or sets or a.calibrate_scans is not None or \
+                a.calibrate_label_maps is not None:
+            ap.error("--calib-bins, --temperature, --calibrate-on, --calibrate-scans, --calibrate-files and "
+                     "--calibrate-label-maps go with --calibration")
+        return
+    a.calib_bins = 15 if a.calib_bins is None else a.calib_bins
+    if not 1 <= a.calib_bins <= 64:
+        ap.error("--calib-bins must lie in 1..64")
+    if a.temperature is not None and a.temperature != "fit":
+        try:
+            a.temperature = float(a.temperature)
+        except ValueError:
+            ap.error(f"--temperature: {a.temperature!r} is neither a number nor `fit`")
+        if not a.temperature > 0:
+            ap.error("--temperature must be positive")
+        if not T_MIN <= a.temperature <= T_MAX:
+            ap.error(f"--temperature must lie in {T_MIN}..{T_MAX:g}")
+    if a.temperature == "fit":
+        if sets != 1:
+            ap.error("--temperature fit needs exactly one calibration set: --calibrate-on CONFIG or --calibrate-files "
+                     "NAME=PATH")
+    elif sets or a.calibrate_scans is not None or a.calibrate_label_maps is not None:
+        ap.error("--calibrate-on, --calibrate-scans, --calibrate-files and --calibrate-label-maps go with --temperature fit")
+    if a.temperature == "fit":
+        a.calibrate_scans = 16 if a.calibrate_scans is None else a.calibrate_scans
+        if a.calibrate_scans < 1:
+            ap.error("--calibrate-scans must be positive")
+        if (a.calibrate_files is None) != (a.calibrate_label_maps is None):
+            ap.error("--calibrate-files and --calibrate-label-maps go together")
+        if a.calibrate_files is not None:
+            try:
+                files = scans.parse_files([a.calibrate_files])
+            except ValueError as e:
+                ap.error(f"--calibrate-files: {e}")
+            if "Synth4D" in files[0][0] and a.synth4d_splits is None:
+                ap.error("--calibrate-files: a Synth4D entry needs --synth4d-splits")
+            a.calibrate_files = files[0]
+
+
+def calibration_set(a, bev):
+    """the labelled scans --temperature fit fits on: validation scans, as train draws them for its first source"""
+    if a.calibrate_files is not None:
+        name, path = a.calibrate_files
+        return scans.FileScans(scans.listing(name, path, "validation", version=a.version,
+                                             synth4d_splits=a.synth4d_splits, limit=a.calibrate_scans),
+                               scans.luts_from_files([a.calibrate_label_maps])[0])
+    return SynthScans(a.calibrate_scans, a.calibrate_on, first=10 ** 6, bev_size=bev)
+
+
+def fit_on_calibration_set(a, model, adapter, bev, device):
+    """(Temperature, its calibration metrics at T = 1 and at the fitted T) of the checkpoint on calibration_set(a): the
+    logits are those a target would be scored on (--precision, --adapt; the adapter is reset before and after)"""
+    from . import calibration
+    data = calibration_set(a, bev)
+    if adapter is not None:
+        adapter.reset()
+        if a.adapt == "adabn":
+            adapter.estimate(dataset_batches(data, a.batch, device))
+    run = adapter if adapter is not None else Predictor(model, a.precision)
+    logits, labels = calibration.collect_logits(run, dataset_batches(data, a.batch, device))
+    if adapter is not None:
+        adapter.reset()
+    fit = calibration.fit_temperature(logits, labels, beta_min=1.0 / T_MAX, beta_max=1.0 / T_MIN)
+    own = {}
+    for name, beta in (("raw", None), ("scaled", fit.beta)):
+        own[name] = calibration.CalibrationTable(a.calib_bins, logits.device).add(logits, labels, beta=beta).result()
+    if fit.summary()["rows"] == 0:
+        raise SystemExit("eval_target --temperature fit: the calibration set has no labelled voxel")
+    return fit, own
 
 
 def save_dir_of(checkpoint):
@@ -213,6 +321,17 @@ def main(argv=None):
     bev = bev_image_size(a.bound)
     ev = TargetEvaluator(model, num_classes=len(CLASS_NAMES), precision=a.precision, adapter=adapter)
     results = []
+    calib = fit = None                                   # [(name, beta)] of TargetEvaluator.run, and their temperatures
+    if a.calibration:
+        from . import calibration
+        calib, temps = [("raw", None)], [1.0]
+        if a.temperature == "fit":
+            fit, fit_own = fit_on_calibration_set(a, model, adapter, bev, device)
+            calib.append(("scaled", fit.beta))
+            temps.append(fit.temperature())
+        elif a.temperature is not None:
+            calib.append(("scaled", torch.tensor([1.0 / a.temperature], dtype=torch.float64, device=device)))
+            temps.append(a.temperature)
     luts = None
     if a.target_files is not None:
         luts = scans.luts_from_files(a.label_maps)
@@ -244,7 +363,7 @@ def main(argv=None):
         if a.adapt == "adabn":                           # part of the target's time: the scans go through twice
             adapter.estimate(dataset_batches(data, a.batch, device))
         res = ev.run(dataset_batches(data, a.batch, device), len(data), rows=a.rows, on_predictions=writer,
-                     points=points)
+                     points=points, calibration=calib, calib_bins=a.calib_bins or 15)
         dt = time.perf_counter() - t0                                # run() ends with the host copy of the counts
         path = write_results_csv(save_dir, sources, name, res["rows"], CLASS_NAMES, first_target=t == 0,
                                  file_targets=file_targets + avg)
@@ -266,6 +385,21 @@ def main(argv=None):
             out.update(tta_views=res["tta_views"], tta_mode=res["tta_mode"])
         if adapter is not None:
             out.update(adapt=a.adapt, adapt_lr=a.adapt_lr, adapt_steps=a.adapt_steps)
+        if calib is not None:
+            entries = [(temp, res["calibration"][n]) for temp, (n, _) in zip(temps, calib)]
+            out["calibration_csv"] = calibration.write_calibration_csv(
+                save_dir, sources, name, entries, first_target=t == 0, file_targets=file_targets + "-calibration" + avg)
+            out["reliability_csv"] = calibration.write_reliability_csv(
+                save_dir, sources, name, entries, first_target=t == 0, file_targets=file_targets + "-reliability" + avg)
+            out["calibration"] = {n: {k: m[k] for k in calibration.METRICS + ("rows",)}
+                                  for n, m in res["calibration"].items()}
+            extra["calibration_tables"] = res["calibration"]
+            if len(temps) > 1:
+                out["temperature"] = temps[1]
+            if fit is not None:
+                out["temperature_fit"] = {"on": a.calibrate_on or a.calibrate_files[0], "scans": a.calibrate_scans,
+                                          "nll_raw": fit_own["raw"]["nll"], "nll_scaled": fit_own["scaled"]["nll"],
+                                          "rows": fit_own["raw"]["rows"]}
         print(json.dumps(out), flush=True)
         results.append(dict(out, iou_rows=res["rows"], counts=res["counts"], **extra))
     return results

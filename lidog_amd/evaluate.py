@@ -19,6 +19,7 @@ import torch
 from . import me as ME
 from . import precision as _precision
 from . import tta as _tta
+from . import calibration as _calibration
 
 
 def per_class_iou(preds, labels, num_classes=7, ignore_label=-1):
@@ -515,7 +516,7 @@ class TargetEvaluator:
         self.precision, self.kernels, self.adapter = precision, None, adapter
 
     @torch.no_grad()
-    def run(self, batches, n_scans, rows="batch", on_predictions=None, points=None):
+    def run(self, batches, n_scans, rows="batch", on_predictions=None, points=None, calibration=None, calib_bins=15):
         """`batches`: iterable of (batch dict, scan indices); `n_scans`: scans of all batches together.  Returns a dict:
         counts [n_scans, C + 1, C] (numpy), batch_of_scan, rows (IoU rows), per_class (percent), mean, scans.
         `points` (a PointPath; None changes nothing): every batch's logits also go through point_labels; the dict then
@@ -523,7 +524,12 @@ class TargetEvaluator:
         the same `rows`), and points.on_point_labels sees every batch's ids.  The point counts and their error word
         cross to the host at the end, with the voxel ones.  With points.tta every batch is also run once per further
         view and the point level takes the accumulated scores (_vote); the voxel-level counts and `on_predictions` stay
-        view 0's, and the dict gains tta_views (the names, identity first) and tta_mode."""
+        view 0's, and the dict gains tta_views (the names, identity first) and tta_mode.
+        `calibration` (None builds nothing and launches nothing): a list of (name, beta) entries, beta None for the raw
+        softmax or an inverse temperature as calibration.CalibrationTable.add takes it; every batch's voxel logits (an
+        adapter's: those it returns for the batch) go into one CalibrationTable of `calib_bins` bins per entry, one
+        launch each, and the dict gains calibration = {name: calibration.metrics_from_table(...)}.  The tables cross to
+        the host at the end, with the counts."""
         import numpy as np
         if rows not in ("batch", "scan"):
             raise ValueError(f"rows={rows!r} (one of 'batch', 'scan')")
@@ -535,6 +541,11 @@ class TargetEvaluator:
         it = iter(batches)
         cur = next(it, None)
         counts = err = pcounts = perr = ferr = terr = None
+        tables = None
+        if calibration is not None:
+            calibration = [(str(name), beta) for name, beta in calibration]
+            if len({name for name, _ in calibration}) != len(calibration):
+                raise ValueError("TargetEvaluator: two calibration entries share a name")
         batch_of_scan = []
         done = 0
         nb = 0
@@ -550,6 +561,8 @@ class TargetEvaluator:
                     perr = torch.zeros(1, dtype=torch.int32, device=coords.device)
                     ferr = torch.zeros(1, dtype=torch.int32, device=coords.device)
                     terr = torch.zeros(1, dtype=torch.int32, device=coords.device)
+                if calibration is not None:
+                    tables = [_calibration.CalibrationTable(calib_bins, coords.device) for _ in calibration]
             k = len(ids)
             if done + k > counts.shape[0]:
                 raise ValueError(f"TargetEvaluator: more than n_scans = {n_scans} scans in the batches")
@@ -557,6 +570,9 @@ class TargetEvaluator:
             labels = b["source_sem_labels0"]
             preds, _ = confusion(logits, labels, coords, k, out=counts[done:done + k], ignore_label=self.ignore_label,
                                  err=err)
+            if tables is not None:
+                for table, (_, beta) in zip(tables, calibration):
+                    table.add(logits, labels, beta=beta, ignore_label=self.ignore_label)
             if on_predictions is not None:
                 buf = pack_predictions(coords, preds, labels, k, self.ignore_label, err=err)
                 for idx, rec in zip(ids, unpack_predictions(buf, k)):
@@ -591,6 +607,8 @@ class TargetEvaluator:
         per_class, mean = mean_iou_rows(r)
         res = {"counts": counts, "batch_of_scan": batch_of_scan, "rows": r, "per_class": per_class, "mean": mean,
                "scans": done}
+        if tables is not None:
+            res["calibration"] = {name: table.result() for (name, _), table in zip(calibration, tables)}
         if points is not None:
             check_point_error(perr, "TargetEvaluator")
             if points.interp == "trilinear":
